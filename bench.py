@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the batched ring step loop (BASELINE.json configs[1], "C2").
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one Env.step of ALL replicas on every rank (controllers -> fail-safes ->
 integration -> headways -> crash check -> observation + reward + done written to HBM).
@@ -14,11 +14,14 @@ region.  For N > 1 each rank owns its own replicas (no data-path collective insi
 a step); the only exchange is one RCCL all-gather of the fragment's final
 observation/reward/done to the learner per fragment.
 
-Prints ONE JSON line (rank 0).  `value` / `ms_per_step` describe exactly the --steps given.  Whatever --steps is,
+Prints ONE JSON line (rank 0).  `value` / `ms_per_step` describe exactly the --steps given.  A plain run does only
+that: set up, warm up, time the --steps, print.  `--dump-outputs DIR` then writes what the last timed step returned
+(rank 0's observation, reward and done) as DIR/{obs,reward,done}.npy in float32; the inputs are seeded, so two builds
+can be compared output for output.  Everything else needs `--full`: whatever --steps is,
 `roofline` (dominant kernel, per-launch HIP events) and `parity` (deviation of the reported dtype from the float64
 oracle after a 1500-step episode) come from >= 5 full 1500-step launches made in the same process.  Extra keys at
-N = 1: `rollout_1500` (the same for mixed / f32 / f64), `cpu_baseline` (oracle C port on the host cores, bounded
-sample), `step_api` (one launch per env step), `ring_default_speed_mode` (the reference's ring experiment with its
+N = 1 (`--full` without `--no-extras`): `rollout_1500` (the same for mixed / f32 / f64), `cpu_baseline` (oracle C
+port on the host cores, bounded sample), `step_api` (one launch per env step), `ring_default_speed_mode` (the reference's ring experiment with its
 default speed mode: generic kernel), `c3_*` / `c4_bottleneck` / `c5_merge` (the other BASELINE configs, informational).
 `--gpus N` without a launcher starts its N ranks itself.
 """
@@ -72,6 +75,7 @@ class Runner:
         self.sim.reset_dev(self.obs0)
         self.events = []
         self.launches = 0
+        self.last_row = None            # row of obs / rew / done that holds the last step stepped
         # (HIP events for the per-launch times, made here: creating them inside the timed region cost a short run --
         # the driver's --steps 20 is ONE launch -- tens of microseconds of host time per launch)
         self._event_pool = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(64)]
@@ -90,6 +94,7 @@ class Runner:
         while left > 0:
             k = min(self.fragment, left, self.horizon - self.t_in_episode)
             self.sim.rollout_dev(k, self.obs, self.rew, self.done, obs_every_step=True)
+            self.last_row = k - 1
             n_full += 1 if k == self.fragment else 0
             if record:
                 self.launches += 1
@@ -766,6 +771,24 @@ def generic_kernel_leg(device, R=4096, K=1500):
             "median_launch_ms": t * 1e3, "note": "C2 on the generic step kernel (FLOWSIM_FORCE_GENERIC=1)"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, runner):
+    """--dump-outputs: the observation, reward and done the last timed step returned, as float32 .npy files.  Above
+    DUMP_MAX_BYTES in all, a fixed seeded sample of replicas (sorted, the same rows in every file) is written instead."""
+    k = runner.last_row
+    arrays = {"obs": runner.obs[k], "reward": runner.rew[k], "done": runner.done[k]}
+    arrays = {name: a.float().cpu().numpy() for name, a in arrays.items()}
+    row_bytes = sum(a[0].nbytes for a in arrays.values())
+    if runner.R * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(runner.R, DUMP_MAX_BYTES // row_bytes, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks as child processes (nothing in THIS
     process has touched the GPU), fail loudly when the node has fewer devices, exit with the worst child code."""
@@ -802,8 +825,16 @@ def main():
     ap.add_argument("--precision", default="mixed", choices=["f32", "f64", "mixed"],
                     help="mixed (default): float64 state, float32 controller -- the precision that holds the 1e-4 "
                          "trajectory bar; f32: the float32 bit-twin; f64: the reference's arithmetic")
-    ap.add_argument("--no-extras", action="store_true", help="skip every leg but the headline and its roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the observation, reward and done of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the roofline and parity of its dtype (50 full-fragment launches) and, "
+                         "at one GPU, every other leg and the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip every leg but the headline and its roofline")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)
@@ -913,7 +944,8 @@ def main():
                             "note": "value = replicas x steps / wall time of exactly --steps env steps (barrier + "
                                     "synchronize on both sides); a region shorter than one 1500-step fragment is "
                                     "dominated by launch + synchronize latency -- the kernel's own rate is in "
-                                    "`roofline` / `rollout_1500`, measured over >= 5 full fragments in this process"}}
+                                    "`roofline` / `rollout_1500` of a --full run, measured over >= 5 full fragments in "
+                                    "that process"}}
 
     # the latency floor of a fragment: a launch is a chain of `fragment` dependent steps per wave, and 4096 replicas are
     # about one wave per SIMD already -- fewer replicas per GPU (strong scaling of BASELINE's "4096 replicas, whole node")
@@ -930,16 +962,19 @@ def main():
                     "shorten it, adding replicas per GPU (weak scaling) is what scales"
                     % (runner.fragment, R, R / 4.0 / 1024.0)}
 
-    # ---- roofline of the dominant kernel: ALWAYS from >= 5 full 1500-step launches of this process (HIP events
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, runner)
+
+    # ---- --full: roofline of the dominant kernel, from >= 5 full 1500-step launches of this process (HIP events
     # on the kernel's stream), whatever --steps was; plus the parity figure of the reported dtype
     legs = {}
-    if rank == 0:
+    if args.full and rank == 0:
         legs[args.precision] = rollout_1500_leg(device, args.precision, R, check_parity=True)
         out["roofline"] = legs[args.precision]["roofline"]
         out["parity"] = legs[args.precision]["parity"]
     runner.sim.close()
 
-    if world == 1 and rank == 0 and not args.no_extras:
+    if args.full and world == 1 and rank == 0 and not args.no_extras:
         for other in ("mixed", "f32", "f64"):
             if other not in legs:
                 legs[other] = rollout_1500_leg(device, other, R, check_parity=True)

@@ -1,6 +1,7 @@
 #!/bin/bash
 # A/B timings of the rollout kernels in ONE gpurun call (boxes differ by up to ~25 %: never compare across calls).
-#   scripts/ab_bench.sh "VAR=val python bench.py args" ...   each argument is one command line
+#   scripts/ab_bench.sh "VAR=val python bench.py --full args" ...   each argument is one command line (--full: the
+#   roofline this script prints)
 for cmd in "$@"; do
   out=$(bash -c "$cmd" 2>/dev/null | tail -1)
   python3 - "$cmd" "$out" <<'PY'

@@ -7,7 +7,7 @@ set -e
 TAG=${1:-r02}
 PREC=${2:-mixed}
 OUT=gpurun_out/prof_${TAG}_${PREC}
-ARGS="--steps 7500 --warmup 1500 --no-extras --precision $PREC"
+ARGS="--steps 7500 --warmup 1500 --full --no-extras --precision $PREC"
 mkdir -p $OUT
 cd /tmp 2>/dev/null && export TMPDIR=/tmp && cd - >/dev/null
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py $ARGS > $OUT/bench_trace.json 2> $OUT/trace.err

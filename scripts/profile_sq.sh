@@ -5,7 +5,7 @@ set -e
 TAG=${1:-r02}
 shift || true
 OUT=gpurun_out/prof_$TAG
-ARGS="--steps 6000 --warmup 1500 --no-extras $*"
+ARGS="--steps 6000 --warmup 1500 --full --no-extras $*"
 mkdir -p $OUT
 cd /tmp 2>/dev/null && export TMPDIR=/tmp && cd - >/dev/null
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY --output-format csv -d $OUT/pmc_sq -- python3 bench.py $ARGS > $OUT/bench_sq.json 2> $OUT/sq.err
