@@ -175,8 +175,9 @@ def user_header(body):
 
 def build_user(body, verbose=False):
     """A copy of the library whose FS_CTRL_USER slots run the user's controller: flow_amd/_user/<hash>/libflowsim.so.
-    Every part that holds generic step kernels is recompiled with -DFS_USER_CONTROLLER_HEADER (in parallel; the stock
-    objects of the C ABI and the queue kernels are reused); cached by the hash of the body and of the sources."""
+    Every part but the queue kernels' is recompiled with -DFS_USER_CONTROLLER_HEADER (in parallel; the C ABI object too:
+    its Sim::launch_steps refuses FS_CTRL_USER slots without the header); cached by the hash of the body and of the
+    sources."""
     text = user_header(body)
     tag = hashlib.sha256((text + _stamp([])).encode()).hexdigest()[:16]
     out_dir = os.path.join(USER_DIR, tag)
@@ -198,7 +199,7 @@ def build_user(body, verbose=False):
         f.write(text)
     objs, todo = [], []
     for name, src, extra in parts():
-        if name == "main" or name.startswith("queue"):
+        if name.startswith("queue"):
             objs.append(os.path.join(OBJ, name + ".o"))
             continue
         out = os.path.join(out_dir, name + ".o")

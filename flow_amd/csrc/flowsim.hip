@@ -277,30 +277,15 @@ int create_typed(const fs_config* cfg, fs_handle* out) {
     return fail(FS_ERR_HIP, std::string("fs_create: no usable HIP device: ") + hipGetErrorString(e));
   }
   s->stream = s->own_stream;
-  {
-    const char* fg = std::getenv("FLOWSIM_FORCE_GENERIC");
-    s->force_generic = fg && fg[0] == '1';
-    const char* nf = std::getenv("FLOWSIM_NO_FASTDIV");
-    s->no_fastdiv = nf && nf[0] == '1';
-    const char* nl = std::getenv("FLOWSIM_NO_LOOP_KERNEL");
-    s->no_loop_kernel = nl && nl[0] == '1';
-    const char* nlf = std::getenv("FLOWSIM_NO_LOOP_FULL");
-    s->no_loop_full = nlf && nlf[0] == '1';
-    const char* nrr = std::getenv("FLOWSIM_NO_RING_RL");
-    s->no_ring_rl = nrr && nrr[0] == '1';
-    const char* nq = std::getenv("FLOWSIM_NO_QUEUE");
-    s->no_queue = nq && nq[0] == '1';
-    const char* np = std::getenv("FLOWSIM_NO_PAIR");
-    s->no_pair = np && np[0] == '1';
-    const char* pb = std::getenv("FLOWSIM_PAIR_BLOCK");
-    if (pb) {
-      const int v = std::atoi(pb);
-      if (v >= 64 && v <= 256 && v % 64 == 0) s->pair_block = v;
-    }
-    const char* rb = std::getenv("FLOWSIM_ROLLOUT_BLOCK");
-    if (rb) {
-      const int v = std::atoi(rb);
-      if (v >= 64 && v <= 1024 && v % 64 == 0) s->rollout_block = v;
+  {   // development switches (tests): FLOWSIM_<NAME>=1 keeps a specialised kernel out of the choice
+    const std::pair<const char*, bool SimBase::*> switches[] = {
+        {"FLOWSIM_FORCE_GENERIC", &SimBase::force_generic}, {"FLOWSIM_NO_FASTDIV", &SimBase::no_fastdiv},
+        {"FLOWSIM_NO_LOOP_KERNEL", &SimBase::no_loop_kernel}, {"FLOWSIM_NO_LOOP_FULL", &SimBase::no_loop_full},
+        {"FLOWSIM_NO_RING_RL", &SimBase::no_ring_rl}, {"FLOWSIM_NO_QUEUE", &SimBase::no_queue},
+        {"FLOWSIM_NO_PAIR", &SimBase::no_pair}};
+    for (const auto& sw : switches) {
+      const char* v = std::getenv(sw.first);
+      s->*sw.second = v && v[0] == '1';
     }
   }
   int rc = s->init();

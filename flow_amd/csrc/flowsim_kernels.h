@@ -1490,7 +1490,7 @@ __global__ __launch_bounds__(1024) void k_rollout_idm(DevView<T> s, int num_step
   // CU.  Measured at R = 4096 (2048 waves, 1500 steps): 64 threads 0.657 ms, 256: 0.626, 512: 0.621,
   // 768: 0.737, 1024: 0.909 -- packing 4 waves per SIMD onto half the CUs is SLOWER, i.e. the loop is
   // bound by VALU issue (~4 cycles per instruction of this mix), not by exposed latency; 512 keeps every
-  // CU busy with 2 waves per SIMD (Sim::rollout_block, profiles/r01_sweep_block.log).
+  // CU busy with 2 waves per SIMD (Sim::launch_idm, profiles/r01_sweep_block.log).
   constexpr int RPW = 64 / SEG;
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;

@@ -889,7 +889,7 @@ __global__ __launch_bounds__(256) void k_rollout_pair(DevView<T> s, int num_step
 
 // observation of the current state of a FS_MIXED handle (Env.reset): the mixed head's own form (reciprocal
 // multiplication in float64, then the rounding to float32)
-template <typename T>     // (T = float is never launched: it keeps launch_seg<float> well-formed)
+template <typename T>     // (T = double only: Sim::launch_obs_mixed)
 __global__ void k_obs_mixed(DevView<T> s, float* __restrict__ obs) {
   if constexpr (std::is_same<T, double>::value) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;

@@ -7,19 +7,27 @@
 
 namespace fsim {
 #if defined(FS_PART_QUEUE)
-template int Sim<FS_PART_T>::launch_queue(int, const float*, size_t, float*, float*, uint8_t*, int);
-template int Sim<FS_PART_T>::launch_dropq(int, const float*, size_t, float*, float*, uint8_t*, int);
+template int Sim<FS_PART_T>::launch_queue(const StepArgs&);
+template int Sim<FS_PART_T>::launch_dropq(const StepArgs&);
 #elif defined(FS_PART_WIDE)
-template int Sim<FS_PART_T>::launch_wide<FS_PART_WIDE>(int, const uint8_t*, const float*, size_t, float*, float*, uint8_t*, int);
+template int Sim<FS_PART_T>::launch_wide<FS_PART_WIDE>(const StepArgs&);
 #elif defined(FS_PART_SEG)
-template int Sim<FS_PART_T>::launch_seg<FS_PART_SEG>(int, const uint8_t*, const float*, size_t, float*, float*, uint8_t*, int);
+template int Sim<FS_PART_T>::launch_open<FS_PART_SEG>(const StepArgs&);
+template int Sim<FS_PART_T>::launch_ml<FS_PART_SEG>(const StepArgs&);
+template int Sim<FS_PART_T>::launch_ring<FS_PART_SEG>(const StepArgs&);
+template int Sim<FS_PART_T>::launch_pair<FS_PART_SEG>(const StepArgs&);
+template int Sim<FS_PART_T>::launch_idm<FS_PART_SEG>(const StepArgs&);
+template int Sim<FS_PART_T>::launch_k_steps<FS_PART_SEG>(const StepArgs&);
 #if FS_PART_SEG == 16
-template int Sim<FS_PART_T>::launch_policy_loop16(const fs_policy*, int, int, const float*, float*, float*, float*, float*,
-                                                  uint8_t*);
+template int Sim<FS_PART_T>::launch_loop(const StepArgs&);
+template int Sim<FS_PART_T>::launch_policy_loop16(const fs::PolicyView&, int, int, float*, float*, float*, float*, uint8_t*);
 #endif
 #if FS_PART_SEG == 32
-template int Sim<FS_PART_T>::launch_policy_row16(const fs_policy*, int, int, const float*, float*, float*, float*, float*,
-                                                 uint8_t*);
+template int Sim<FS_PART_T>::launch_policy_act(const fs::PolicyView&, const float*, float*, float*);
+template int Sim<FS_PART_T>::launch_policy_row16(const fs::PolicyView&, int, int, float*, float*, float*, float*, uint8_t*);
+#endif
+#if FS_PART_SEG == 64
+template int Sim<FS_PART_T>::launch_obs_mixed(const StepArgs&);     // (one object: the kernel does not depend on the width)
 #endif
 #else
 #error "flowsim_part.hip: define FS_PART_T and FS_PART_SEG or FS_PART_WIDE"

@@ -1,8 +1,8 @@
 // flowsim_sim.h -- host side of libflowsim.so shared by its translation units: the handle (SimBase / Sim<T>),
-// allocation, table upload, kernel choice.  The library is compiled as several objects (flow_amd/build.py): flowsim.hip
-// holds the C ABI, validation and everything but the step launches; flowsim_part.hip is compiled once per
-// (precision, lanes-per-replica) pair and holds Sim<T>::launch_seg<SEG> / launch_wide<W> with the step kernels they
-// instantiate (defined in flowsim_launch.h, which only the parts include).
+// allocation, table upload, kernel choice (Sim<T>::launch_steps).  The library is compiled as several objects
+// (flow_amd/build.py): flowsim.hip holds the C ABI, validation and everything but the kernel launches; flowsim_part.hip
+// is compiled once per (precision, lanes-per-replica) pair and holds the Sim<T>::launch_* of that width with the step
+// kernels they instantiate (defined in flowsim_launch.h, which only the parts include).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -46,6 +46,27 @@ inline int fail(int code, const std::string& msg) {
       return fail(FS_ERR_HIP, std::string(#expr) + " failed: " + hipGetErrorString(e_));   \
   } while (0)
 
+// the arguments of one step launch, as every launch_* takes them
+struct StepArgs {
+  int num_steps;
+  const uint8_t* mask;
+  const float* actions;
+  size_t act_stride;
+  float* obs;
+  float* rew;
+  uint8_t* done;
+  int obs_every_step;
+};
+
+template <int N>
+using Int = std::integral_constant<int, N>;
+
+// a run-time switch as a template argument: f(std::true_type()) if b, else f(std::false_type())
+template <typename F>
+auto pick(bool b, F&& f) {
+  return b ? f(std::true_type()) : f(std::false_type());
+}
+
 struct SimBase {
   virtual ~SimBase() {}
   fs_config cfg{};
@@ -71,7 +92,6 @@ struct SimBase {
   int after_reset = 0;          // open networks: the next zero-step launch follows a reset (update(reset=True))
   bool force_generic = false;   // FLOWSIM_FORCE_GENERIC=1: never take the specialised kernels (tests)
   bool no_fastdiv = false;      // FLOWSIM_NO_FASTDIV=1: keep the IEEE division sequence in k_rollout_idm
-  int rollout_block = 512;      // threads per block of k_rollout_idm (FLOWSIM_ROLLOUT_BLOCK overrides; sweep: docs/HISTORY.md)
   bool f16s = false;            // FS_F16S: the state between launches is kept as halves (DevView::st16)
   bool mixed = false;           // FS_MIXED: float64 state, float32 controller arithmetic (k_rollout_pair<double>)
   bool no_pair = false;         // FLOWSIM_NO_PAIR=1: keep k_rollout_idm (one vehicle per lane) for the float rollout
@@ -94,8 +114,12 @@ struct SimBase {
     return FS_OK;
   }
   bool has_user_ctrl = false;   // a FS_CTRL_USER slot: only a library built with the user's controller may launch it
-  int pair_block = 256;         // threads per block of k_rollout_pair (FLOWSIM_PAIR_BLOCK overrides)
   const char* last_kernel = "";  // family of the step kernel the last launch_steps call chose (fs_last_kernel)
+  // after a kernel launch: its launch error, if any
+  int launched() {
+    HIP_TRY(hipGetLastError());
+    return FS_OK;
+  }
 
   virtual int launch_steps(int num_steps, const uint8_t* mask, const float* actions, size_t act_stride,
                            float* obs, float* rew, uint8_t* done, int obs_every_step) = 0;
@@ -587,55 +611,69 @@ struct Sim : SimBase {
     }
     return true;
   }
-  bool fastdiv_ok() {
-    if ((!std::is_same<T, float>::value && !mixed) || force_generic || no_fastdiv) return false;
-    if (fastdiv_state >= 0) return fastdiv_state == 1;
-    fastdiv_state = 0;
+  // The divisor proofs share this routine: collect(cs) checks the kernel's premises (false: one fails) and gathers its
+  // distinct divisors.  The answer is cached in `state`.
+  template <typename Collect>
+  bool prove_divisors(int& state, Collect collect) {
+    if (state >= 0) return state == 1;
+    state = 0;
     std::vector<float> cs;
-    auto add = [&cs](float c) {
-      for (float e : cs)
-        if (e == c) return;
-      cs.push_back(c);
-    };
-    for (int i = 0; i < dv.N; ++i) {            // per-slot IDM divisors and the s0 >= 1e-3 premise
-      add(float(veh[i].p[0]));
-      add(2.0f * std::sqrt(float(veh[i].p[2]) * float(veh[i].p[3])));
-      if (!(float(veh[i].p[5]) >= 1e-3f) || !(float(veh[i].p[5]) <= 1e6f)) return false;
-      if (speed_mode_any) {                     // sumo_acc_pair's divisors and its minGap >= 1e-3 premise
-        add(float(veh[i].sumo_max_speed));
-        add(2.0f * std::sqrt(float(veh[i].max_accel) * float(veh[i].max_decel)));
-        if (!(float(veh[i].sumo_min_gap) >= 1e-3f) || !(float(veh[i].sumo_min_gap) <= 1e6f)) return false;
-      }
-    }
+    if (!collect(cs)) return false;
+    for (float c : cs)
+      if (!fastdiv_exact_for(c)) return false;
+    state = 1;
+    return true;
+  }
+  static void add_divisor(std::vector<float>& cs, float c) {
+    if (std::find(cs.begin(), cs.end(), c) == cs.end()) cs.push_back(c);
+  }
+  void add_idm_divisors(std::vector<float>& cs, int i) const {     // v0 and 2 sqrt(a b) of slot i's IDM
+    add_divisor(cs, float(veh[i].p[0]));
+    add_divisor(cs, 2.0f * std::sqrt(float(veh[i].p[2]) * float(veh[i].p[3])));
+  }
+  void add_sumo_divisors(std::vector<float>& cs, int i) const {    // SUMO's max speed and 2 sqrt(a b) of slot i
+    add_divisor(cs, float(veh[i].sumo_max_speed));
+    add_divisor(cs, 2.0f * std::sqrt(float(veh[i].max_accel) * float(veh[i].max_decel)));
+  }
+  // the loop length of every replica; more than `limit` distinct divisors are too many to verify cheaply
+  bool add_ring_divisors(std::vector<float>& cs, size_t limit) const {
     for (T b : h_ring_len) {                    // host copy: no HIP call on the launch path
       const float L = float(b) + 4.0f * float(dv.jlen);
       if (!(L >= 1.0f)) return false;        // keeps x = 0 or x >= ulp(L)/2 out of the tiny range
-      add(L);
-      if (cs.size() > 80) return false;      // too many distinct loop lengths to verify cheaply
+      add_divisor(cs, L);
+      if (cs.size() > limit) return false;
     }
-    for (float c : cs)
-      if (!fastdiv_exact_for(c)) return false;
-    fastdiv_state = 1;
     return true;
+  }
+  static bool gap_in(double g, float lo) { return float(g) >= lo && float(g) <= 1e6f; }    // the s0 / minGap premises
+
+  bool fastdiv_ok() {
+    if ((!std::is_same<T, float>::value && !mixed) || force_generic || no_fastdiv) return false;
+    return prove_divisors(fastdiv_state, [&](std::vector<float>& cs) {
+      for (int i = 0; i < dv.N; ++i) {            // per-slot IDM divisors and the s0 >= 1e-3 premise
+        add_idm_divisors(cs, i);
+        if (!gap_in(veh[i].p[5], 1e-3f)) return false;
+        if (speed_mode_any) {                     // sumo_acc_pair's divisors and its minGap >= 1e-3 premise
+          add_sumo_divisors(cs, i);
+          if (!gap_in(veh[i].sumo_min_gap, 1e-3f)) return false;
+        }
+      }
+      return add_ring_divisors(cs, 80);
+    });
   }
 
   // k_rollout_loop<..., FULL>: its controller divisions by launch constants are div_const -- every divisor proven
   int loop_fastc_state = -1;
   bool loop_fastc_ok() {
     if (!(std::is_same<T, float>::value || mixed) || no_fastdiv) return false;
-    if (loop_fastc_state >= 0) return loop_fastc_state == 1;
-    loop_fastc_state = 0;
-    if (!loop_div_ok) return false;               // s0 / minGap in [1e-3, 1e6]: tiny dividends cannot matter
-    for (int i = 0; i < dv.N; ++i) {
-      if (veh[i].controller == FS_CTRL_IDM) {
-        if (!fastdiv_exact_for(float(veh[i].p[0]))) return false;
-        if (!fastdiv_exact_for(2.0f * std::sqrt(float(veh[i].p[2]) * float(veh[i].p[3])))) return false;
+    return prove_divisors(loop_fastc_state, [&](std::vector<float>& cs) {
+      if (!loop_div_ok) return false;               // s0 / minGap in [1e-3, 1e6]: tiny dividends cannot matter
+      for (int i = 0; i < dv.N; ++i) {
+        if (veh[i].controller == FS_CTRL_IDM) add_idm_divisors(cs, i);
+        add_sumo_divisors(cs, i);
       }
-      if (!fastdiv_exact_for(float(veh[i].sumo_max_speed))) return false;
-      if (!fastdiv_exact_for(2.0f * std::sqrt(float(veh[i].max_accel) * float(veh[i].max_decel)))) return false;
-    }
-    loop_fastc_state = 1;
-    return true;
+      return true;
+    });
   }
 
   // k_ring_pair<..., FAST> (flowsim_ringrl.h): exponent 4 and the exact reciprocal divisions -- every divisor proven.
@@ -644,38 +682,19 @@ struct Sim : SimBase {
   // term is exactly zero, gives an acceleration too small to move a speed near v0 -- so an inexact quotient there
   // cannot change a result; from 2^-60 up div_core's operands are inside its proven range (|h| in [1e-3, L]).
   int ringrl_fast_state = -1;
-  bool any_sim = false;                  // some slot is a SimCarFollowingController
   bool ringrl_fast_ok() {
     if (no_fastdiv || force_generic) return false;
-    if (ringrl_fast_state >= 0) return ringrl_fast_state == 1;
-    ringrl_fast_state = 0;
-    std::vector<float> cs;
-    auto add = [&cs](float c) {
-      for (float e : cs)
-        if (e == c) return;
-      cs.push_back(c);
-    };
-    for (int i = 0; i < dv.N; ++i) {
-      if (veh[i].controller == FS_CTRL_IDM) {
-        if (veh[i].p[4] != 4.0) return false;
-        add(float(veh[i].p[0]));
-        add(2.0f * std::sqrt(float(veh[i].p[2]) * float(veh[i].p[3])));
-        if (!(float(veh[i].p[5]) >= 0.0f) || !(float(veh[i].p[5]) <= 1e6f)) return false;
+    return prove_divisors(ringrl_fast_state, [&](std::vector<float>& cs) {
+      for (int i = 0; i < dv.N; ++i) {
+        if (veh[i].controller == FS_CTRL_IDM) {
+          if (veh[i].p[4] != 4.0 || !gap_in(veh[i].p[5], 0.0f)) return false;
+          add_idm_divisors(cs, i);
+        }
+        add_sumo_divisors(cs, i);
+        if (!gap_in(veh[i].sumo_min_gap, 0.0f)) return false;
       }
-      add(float(veh[i].sumo_max_speed));
-      add(2.0f * std::sqrt(float(veh[i].max_accel) * float(veh[i].max_decel)));
-      if (!(float(veh[i].sumo_min_gap) >= 0.0f) || !(float(veh[i].sumo_min_gap) <= 1e6f)) return false;
-    }
-    for (T b : h_ring_len) {
-      const float L = float(b) + 4.0f * float(dv.jlen);
-      if (!(L >= 1.0f)) return false;
-      add(L);
-      if (cs.size() > 96) return false;
-    }
-    for (float c : cs)
-      if (!fastdiv_exact_for(c)) return false;
-    ringrl_fast_state = 1;
-    return true;
+      return add_ring_divisors(cs, 96);
+    });
   }
 
   // the specialisations for the headline configuration (see flowsim_kernels.h)
@@ -683,60 +702,150 @@ struct Sim : SimBase {
   bool loop_div_ok = false, loop_delta4 = false, open_div_ok = false;
   bool sumo_beyond_speed_mode = false;   // FLAG_NEED_SUMO for more than speed-mode bits (Sim / RL slots, junction mode)
   bool speed_mode_any = false;           // some slot carries a speed-mode clamp (bits 0-2)
+  bool any_sim = false;                  // some slot is a SimCarFollowingController
+
+  // ---- the conditions of launch_steps' kernels (each is asked only after those before it in launch_steps failed) ----
   // allow_speed_mode: the caller's kernel evaluates the speed-mode clamps itself (k_rollout_pair<..., SM = true>)
-  bool fast_ok(const uint8_t* mask, int num_steps, bool allow_speed_mode = false, bool allow_noise = false) const {
+  bool fast_ok(const StepArgs& a, bool allow_speed_mode = false, bool allow_noise = false) const {
     const int f = dv.flags;
     const bool sumo_free = !(f & fs::FLAG_NEED_SUMO) || (allow_speed_mode && !sumo_beyond_speed_mode);
     const bool noise_free = !(f & fs::FLAG_HAS_NOISE) || allow_noise;
     return (f & fs::FLAG_ALL_IDM) && !(f & fs::FLAG_HAS_FAILSAFE) && noise_free && sumo_free &&
            dv.env == FS_ENV_ACCEL && !dv.evaluate && dv.sims_per_step == 1 && dv.integrator == FS_EULER &&
-           !dv.junction_mode && !dv.track_aux && mask == nullptr && num_steps > 0 && !force_generic &&
+           !dv.junction_mode && !dv.track_aux && a.mask == nullptr && a.num_steps > 0 && !force_generic &&
            dv.nseg == 0 && !dv.junction_on && !dv.sort_vehicles && dv.obs_perm == nullptr;
   }
 
   // the merge network in queue order (flowsim_queue.h): float32, IDM / RL / Sim slots, the multi-agent head, scheduled
-  // inflows, every replica stepping.  Defined in flowsim_launch.h for the one part that holds the kernel (FS_PART_QUEUE).
-  bool queue_ok(const uint8_t* mask, int num_steps) const {
+  // inflows, every replica stepping
+  bool queue_ok(const StepArgs& a) const {
     if (!std::is_same<T, float>::value || !open_net || cfg.network != FS_NET_MERGE || no_queue || force_generic) return false;
     if (dv.env != FS_ENV_MERGE_MA || !(dv.flags & fs::FLAG_IDM_SET) || !open_div_ok || ov.n_prob > 0) return false;
     if (!(dv.flags & fs::FLAG_DELTA4) || (dv.flags & fs::FLAG_HAS_FAILSAFE) || dv.integrator != FS_EULER || !qc.ok) return false;
-    if (mask != nullptr || num_steps < 1 || dv.N > 64) return false;
+    if (a.mask != nullptr || a.num_steps < 1 || dv.N > 64) return false;
     for (const fs_inflow& f : inflows)
       if (f.route < 0 || f.route > 1) return false;
     return true;
   }
-  int launch_queue(int num_steps, const float* actions, size_t act_stride, float* obs, float* rew, uint8_t* done,
-                   int obs_every_step);
   // the lane-drop network in queue order (flowsim_dropq.h): one wave per entry lane, every vehicle on SUMO's model
-  bool dropq_ok(const uint8_t* mask, int num_steps) const {
+  bool dropq_ok(const StepArgs& a) const {
     if (!std::is_same<T, float>::value || !open_net || cfg.network != FS_NET_BOTTLENECK || no_queue || force_generic) return false;
     if (cfg.num_paths != 4 || ov.lc_enabled || ov.track_followers || ov.n_prob > 0 || !open_div_ok) return false;
     if (!(dv.flags & fs::FLAG_NO_FLOW_CTRL) || dv.integrator != FS_EULER) return false;
     if (dv.env != FS_ENV_BOTTLENECK_DV && dv.env != FS_ENV_BOTTLENECK) return false;
     if (dv.env == FS_ENV_BOTTLENECK && dv.num_rl > 0 && ov.ma_apply_actions) return false;   // per-vehicle RL accelerations (BottleneckAccelEnv)
-    if (mask != nullptr || num_steps < 1 || dv.N > 256 || ov.nseg[0] > 16 || ov.obs_span > 3 || ov.act_span > 2) return false;
+    if (a.mask != nullptr || a.num_steps < 1 || dv.N > 256 || ov.nseg[0] > 16 || ov.obs_span > 3 || ov.act_span > 2) return false;
     for (int i = 0; i < dv.N; ++i)
       if (float(veh[i].length) != float(veh[0].length) || veh[i].type < 0 || veh[i].type > 7) return false;
     for (const fs_inflow& f : inflows)
       if (f.route > 3) return false;
     return true;
   }
-  int launch_dropq(int num_steps, const float* actions, size_t act_stride, float* obs, float* rew, uint8_t* done,
-                   int obs_every_step);
+  // several lanes, or a lane-changing head (flowsim_kernels.h k_steps_ml)
+  bool ml_ok() const {
+    return dv.num_lanes > 1 || dv.env == FS_ENV_LANE_CHANGE_ACCEL || dv.env == FS_ENV_LANE_CHANGE_ACCEL_PO;
+  }
+  // closed loops with a segment table (figure eight) in rows of 16 lanes: the rollout kernel of flowsim_fig8.h
+  // (FS_MIXED handles: its float64-state instantiation; whatever that does not cover -- resets, masks, warm-up, single
+  // vehicles -- steps on the generic float64 kernel, which is the reference's arithmetic)
+  bool loop_ok(const StepArgs& a) const {
+    const int f = dv.flags;
+    const bool ma_loop = std::is_same<T, float>::value && dv.env == FS_ENV_ACCEL_PO_MA;   // MultiAgentAccelPOEnv (multiagent_figure_eight.py)
+    const bool head_ok = (dv.env == FS_ENV_ACCEL && !dv.evaluate) || dv.env == FS_ENV_WAVE_ATTENUATION_PO || ma_loop;
+    return seg == 16 && (std::is_same<T, float>::value || mixed) && dv.nseg > 0 && (f & fs::FLAG_IDM_SET) &&
+           !(f & fs::FLAG_HAS_FAILSAFE) && head_ok && dv.integrator == FS_EULER && dv.sims_per_step == 1 &&
+           a.mask == nullptr && !dv.sort_vehicles && dv.obs_perm == nullptr && a.num_steps > 0 &&
+           (a.obs_every_step || a.num_steps == 1) && dv.N > 1 && loop_div_ok && !force_generic && !no_loop_kernel;
+  }
+  // single-lane rings of IDM and RL vehicles, float32 (noise included) or FS_MIXED (flowsim_ringrl.h): the RL
+  // experiments' populations and heads, masked and zero-step launches included; the all-IDM AccelEnv rollout keeps
+  // k_rollout_pair (pair_ok)
+  bool ring_rl_ok(const StepArgs& a) const {
+    const int f = dv.flags;
+    const bool ma_head = dv.env == FS_ENV_WAVE_ATTENUATION_PO_MA || dv.env == FS_ENV_ACCEL_PO_MA;   // float32 only
+    return (std::is_same<T, float>::value || mixed) && dv.nseg == 0 && !dv.junction_on && (f & fs::FLAG_IDM_SET) &&
+           !any_sim && !(f & fs::FLAG_HAS_FAILSAFE) && dv.sims_per_step == 1 && dv.integrator == FS_EULER &&
+           !dv.junction_mode && !dv.track_aux && !dv.sort_vehicles && dv.obs_perm == nullptr && !dv.evaluate &&
+           (dv.env == FS_ENV_ACCEL || dv.env == FS_ENV_WAVE_ATTENUATION_PO || (ma_head && !mixed)) && dv.N >= 2 &&
+           (dv.N % 2) == 0 && !force_generic && !no_ring_rl && !pair_ok(a);
+  }
+  // two vehicles per lane (flowsim_pair.h): float32 (the noisy form too) or FS_MIXED, even N
+  bool pair_ok(const StepArgs& a) const {
+    return (std::is_same<T, float>::value || mixed) && fast_ok(a, true, std::is_same<T, float>::value) &&
+           (a.obs_every_step || a.num_steps == 1) && dv.N >= 2 && (dv.N % 2) == 0 && a.actions == nullptr && !no_pair &&
+           size_t(dv.R) * 2 * dv.N * sizeof(float) * 16 < (size_t(1) << 32);   // 32-bit offsets in a block
+  }
+  // one vehicle per lane (flowsim_kernels.h k_rollout_idm)
+  bool rollout_idm_ok(const StepArgs& a) const {
+    return fast_ok(a) && a.obs_every_step && dv.N > 1 && a.actions == nullptr &&
+           size_t(dv.R) * 2 * dv.N * sizeof(float) < (size_t(1) << 32);   // 32-bit byte offsets inside one step's block
+  }
 
-  // more than 64 slots per replica (lane-drop network): one workgroup of W waves per replica (flowsim_launch.h)
+  // ---- the launches, one per kernel family: flowsim_launch.h, compiled into the parts (flowsim_part.hip) ----
+  int launch_queue(const StepArgs& a);       // float32 (the queue part)
+  int launch_dropq(const StepArgs& a);       // float32 (the queue part)
   template <int W>
-  int launch_wide(int num_steps, const uint8_t* mask, const float* actions, size_t act_stride, float* obs,
-                  float* rew, uint8_t* done, int obs_every_step);
+  int launch_wide(const StepArgs& a);        // one workgroup of W waves per replica
+  // one wave carries 64 / SEG replicas
+  template <int SEG>
+  int launch_open(const StepArgs& a);
+  template <int SEG>
+  int launch_ml(const StepArgs& a);
+  int launch_loop(const StepArgs& a);        // SEG = 16
+  template <int SEG>
+  int launch_ring(const StepArgs& a);
+  int launch_obs_mixed(const StepArgs& a);   // FS_MIXED
+  template <int SEG>
+  int launch_pair(const StepArgs& a);
+  template <int SEG>
+  int launch_idm(const StepArgs& a);
+  template <int SEG>
+  int launch_k_steps(const StepArgs& a);
+  // f(Int<SEG>()): a family's instantiation for this handle's lanes per replica
+  template <typename F>
+  int per_seg(F&& f) {
+    switch (seg) {
+      case 8: return f(Int<8>());
+      case 16: return f(Int<16>());
+      case 32: return f(Int<32>());
+      default: return f(Int<64>());
+    }
+  }
 
-  // the policy kernels exist for rows of 16 lanes (SEG = 32: 18..32 vehicles); defined in flowsim_launch.h, instantiated
-  // by the SEG = 32 objects
-  int launch_policy_row16(const fs_policy* pol, int num_steps, int reset_done, const float* obs_in, float* obs, float* act,
-                          float* logp, float* rew, uint8_t* done);
-  // the fused policy + step kernel of segment-table loops (the figure eight, flowsim_policy.h k_loop_policy): rows of 16
-  // lanes (up to 16 vehicles); defined in flowsim_launch.h, instantiated by the SEG = 16 objects
-  int launch_policy_loop16(const fs_policy* pol, int num_steps, int reset_done, const float* obs_in, float* obs, float* act,
-                           float* logp, float* rew, uint8_t* done);
+  // The step kernel of a launch, in order of preference.
+  int launch_steps(int num_steps, const uint8_t* mask, const float* actions, size_t act_stride, float* obs,
+                   float* rew, uint8_t* done, int obs_every_step) override {
+    const StepArgs a{num_steps, mask, actions, act_stride, obs, rew, done, obs_every_step};
+    if (has_user_ctrl && !fs::kHasUserController)
+      return fail(FS_ERR_UNSUPPORTED, "FS_CTRL_USER: this library was built without a user controller "
+                                      "(flow_amd.build.build_user / flow_amd.controllers.CompiledController)");
+    if constexpr (std::is_same<T, float>::value) {
+      if (queue_ok(a)) return launch_queue(a);
+      if (dropq_ok(a)) return launch_dropq(a);
+    }
+    if (seg == 128) return launch_wide<2>(a);            // more than 64 slots per replica (lane-drop network)
+    if (seg == 256) return launch_wide<4>(a);
+    if (open_net) return per_seg([&](auto S) { return launch_open<S>(a); });
+    if (ml_ok()) return per_seg([&](auto S) { return launch_ml<S>(a); });
+    if (loop_ok(a)) return launch_loop(a);
+    if (ring_rl_ok(a)) return per_seg([&](auto S) { return launch_ring<S>(a); });
+    if (mixed && num_steps == 0 && dv.nseg == 0) return launch_obs_mixed(a);   // observation of the current state (Env.reset)
+    if (mixed && !pair_ok(a) && dv.nseg == 0)
+      return fail(FS_ERR_UNSUPPORTED, "FS_MIXED: this launch fits neither mixed kernel (k_rollout_pair / k_ring_pair: "
+                                      "single-lane ring, even number of IDM / RL vehicles, AccelEnv or "
+                                      "WaveAttenuationPOEnv, track_aux = 0)");
+    if (pair_ok(a)) return per_seg([&](auto S) { return launch_pair<S>(a); });
+    if (rollout_idm_ok(a)) return per_seg([&](auto S) { return launch_idm<S>(a); });
+    return per_seg([&](auto S) { return launch_k_steps<S>(a); });        // k_steps: FAST / CSET / generic
+  }
+
+  // policy in the loop (flowsim_policy.h; flowsim_launch.h): the eager policy, the fused policy + step kernels of rings
+  // (rows of 16 lanes: 18..32 vehicles) and of segment-table loops (the figure eight: up to 16 vehicles)
+  int launch_policy_act(const fs::PolicyView& pv, const float* obs_in, float* act, float* logp);
+  int launch_policy_row16(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act, float* logp,
+                          float* rew, uint8_t* done);
+  int launch_policy_loop16(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act, float* logp,
+                           float* rew, uint8_t* done);
   int launch_policy(const fs_policy* pol, int num_steps, int reset_done, const float* obs_in, float* obs, float* act,
                     float* logp, float* rew, uint8_t* done) override {
     if (!pol || pol->struct_size != sizeof(fs_policy)) return fail(FS_ERR_INVALID, "fs_policy: struct_size mismatch");
@@ -757,13 +866,6 @@ struct Sim : SimBase {
                (obs != nullptr && reset_done && cfg.warmup_steps != 0))
         why = "configuration (what k_rollout_loop steps: IDM / RL / Sim vehicles, Euler, track_aux = 0; resets inside a "
               "fragment: warmup_steps = 0)";
-      if (why) return fail(FS_ERR_UNSUPPORTED, std::string("fs_policy: not built for this handle: ") + why);
-      if (!d_pol_ctr) {
-        int rc = dev_alloc(&d_pol_ctr, size_t(dv.R));
-        if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(d_pol_ctr, 0, size_t(dv.R) * sizeof(uint32_t), stream));
-      }
-      return launch_policy_loop16(pol, num_steps, reset_done, obs_in, obs, act, logp, rew, done);
     }
     else if (!f32_or_mixed) why = "precision (f32 or mixed)";
     else if (seg != 32) why = "num_vehicles (18..32: a row of 16 lanes per replica)";
@@ -779,24 +881,18 @@ struct Sim : SimBase {
       if (rc) return rc;
       HIP_TRY(hipMemsetAsync(d_pol_ctr, 0, size_t(dv.R) * sizeof(uint32_t), stream));
     }
-    return launch_policy_row16(pol, num_steps, reset_done, obs_in, obs, act, logp, rew, done);
-  }
-
-  // one wave carries 64 / SEG replicas (flowsim_launch.h)
-  template <int SEG>
-  int launch_seg(int num_steps, const uint8_t* mask, const float* actions, size_t act_stride, float* obs,
-                 float* rew, uint8_t* done, int obs_every_step);
-
-  int launch_steps(int num_steps, const uint8_t* mask, const float* actions, size_t act_stride, float* obs,
-                   float* rew, uint8_t* done, int obs_every_step) override {
-    switch (seg) {
-      case 8: return launch_seg<8>(num_steps, mask, actions, act_stride, obs, rew, done, obs_every_step);
-      case 16: return launch_seg<16>(num_steps, mask, actions, act_stride, obs, rew, done, obs_every_step);
-      case 32: return launch_seg<32>(num_steps, mask, actions, act_stride, obs, rew, done, obs_every_step);
-      case 128: return launch_wide<2>(num_steps, mask, actions, act_stride, obs, rew, done, obs_every_step);
-      case 256: return launch_wide<4>(num_steps, mask, actions, act_stride, obs, rew, done, obs_every_step);
-      default: return launch_seg<64>(num_steps, mask, actions, act_stride, obs, rew, done, obs_every_step);
-    }
+    fs::PolicyView pv;
+    pv.w = pol->weights_dev;
+    pv.log_std = pol->log_std_dev;
+    pv.ctr = d_pol_ctr;
+    pv.in_dim = pol->obs_dim;
+    pv.num_hidden = pol->num_hidden;
+    pv.n_out = pol->log_std_dev ? 1 : 2;
+    pv.seed_lo = uint32_t(pol->seed & 0xFFFFFFFFull);
+    pv.seed_hi = uint32_t(pol->seed >> 32);
+    if (obs == nullptr) return launch_policy_act(pv, obs_in, act, logp);      // eager: the policy alone
+    if (loop) return launch_policy_loop16(pv, num_steps, reset_done, obs, act, logp, rew, done);
+    return launch_policy_row16(pv, num_steps, reset_done, obs, act, logp, rew, done);
   }
 
   int launch_reset(const uint8_t* mask) override {

@@ -6,7 +6,7 @@ library refuses such a population loudly."""
 import numpy as np
 import pytest
 
-from helpers import idm_vehicle, ring_spec
+from helpers import bottleneck_spec, idm_vehicle, ring_spec
 from oracle import refsim as S
 
 pytestmark = pytest.mark.gpu
@@ -81,6 +81,13 @@ def test_the_stock_library_refuses_a_user_controller_and_the_class_builds_throug
     with pytest.raises(NotImplementedError, match="FS_CTRL_USER"):
         stock.reset()
     stock.close()
+    # every launch path refuses it: a lane-drop handle of more than 64 slots (k_steps_wide) too
+    spec = bottleneck_spec(R=2, cap_human=80, cap_rl=8)
+    spec["vehicles"][0] = dict(spec["vehicles"][0], controller=S.CTRL_USER)
+    wide = FlowSim(dict(spec, user_controller_source=None), "f32")
+    with pytest.raises(NotImplementedError, match="FS_CTRL_USER"):
+        wide.reset()
+    wide.close()
 
     veh = VehicleParams()
     veh.add("gap", acceleration_controller=(TimeGap, {"t_gap": 1.0}), routing_controller=(ContinuousRouter, {}),
