@@ -143,22 +143,22 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     pi = GaussianPolicy(k_ag if shared_agents else vec.obs_dim, 1 if shared_agents else vec.act_dim).to(dev)
     opt = torch.optim.Adam(pi.parameters(), lr=lr)
     # the rollout: ONE kernel per fragment where the library has the fused policy + step form for this experiment and
-    # model (fs_policy_rollout_dev: rings with one RL vehicle, WaveAttenuationPOEnv, 1..3 hidden layers of 32 tanh units);
-    # otherwise K single steps around the torch policy captured as one HIP graph
+    # model (fs_policy_rollout_dev: rings / the figure eight with one RL vehicle, the multi-agent ring and figure eight
+    # with their agents sharing the policy, 1..3 hidden layers of 32 tanh units); otherwise K single steps around the
+    # torch policy captured as one HIP graph.  (Shared agents: the network's input is one agent's block, k_ag values.)
     fused, graph = None, None
+    shared = "; one policy shared by %d agents per replica" % n_ag if shared_agents else ""
     try:
-        if shared_agents:
-            raise NotImplementedError("one policy shared by %d agents per replica" % n_ag)
         from flow_amd.utils.device_policy import DevicePolicy
         fused = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=pi.log_std, seed=seed)
         vec.reset()
         vec.policy_rollout(fused, 1, reset_done=True)           # (probe: raises NotImplementedError when not built)
         kernel = vec.sim.last_kernel
         vec.reset()
-        log("rollout: fused policy + step kernel (%s)" % kernel)
+        log("rollout: fused policy + step kernel (%s)%s" % (kernel, shared))
     except NotImplementedError as e:
         fused = None
-        log("rollout: HIP graph of %d single steps around the torch policy (%s)" % (fragment, e))
+        log("rollout: HIP graph of %d single steps around the torch policy (%s)%s" % (fragment, e, shared))
         if world > 1:
             torch.manual_seed(seed + 1000 * (rank + 1))       # the graph's torch.randn: another stream per rank
         R_ = hi - lo

@@ -232,10 +232,10 @@ namespace fsim {
   }
 
   template <typename T>
-  int Sim<T>::launch_policy_act(const fs::PolicyView& pv, const float* obs_in, float* act, float* logp) {
+  int Sim<T>::launch_policy_act(const fs::PolicyView& pv, int n_ag, const float* obs_in, float* act, float* logp) {
     last_kernel = "k_policy_act";
-    hipLaunchKernelGGL(fs::k_policy_act<16>, dim3((dv.R * 16 + 255) / 256), dim3(256), 0, stream, pv, dv.R, dv.rep0, obs_in,
-                       act, logp);
+    hipLaunchKernelGGL(fs::k_policy_act<16>, dim3((dv.R * 16 + 255) / 256), dim3(256), 0, stream, pv, dv.R, n_ag, dv.rep0,
+                       obs_in, act, logp);
     return launched();
   }
 
@@ -243,10 +243,19 @@ namespace fsim {
   int Sim<T>::launch_policy_row16(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act,
                                   float* logp, float* rew, uint8_t* done) {
     const bool fast = ringrl_fast_ok();
-    const auto k = pick(dv.flags & fs::FLAG_HAS_NOISE, [&](auto NZ) {
-      return pick(fast, [&](auto FA) { return &fs::k_ring_policy<T, NZ, FA>; });
-    });
+    auto kernel = [&](auto H) {
+      return pick(dv.flags & fs::FLAG_HAS_NOISE, [&](auto NZ) {
+        return pick(fast, [&](auto FA) { return &fs::k_ring_policy<T, H, NZ, FA>; });
+      });
+    };
+    auto k = kernel(Int<1>());                                     // WaveAttenuationPOEnv
     last_kernel = "k_ring_policy";
+    if constexpr (std::is_same<T, float>::value) {
+      if (dv.env == FS_ENV_WAVE_ATTENUATION_PO_MA) {                // MultiAgentWaveAttenuationPOEnv (float32 only)
+        k = kernel(Int<2>());
+        last_kernel = "k_ring_policy<POMA>";
+      }
+    }
     const int waves = (dv.R + 3) / 4;
     hipLaunchKernelGGL(k, dim3((waves + 3) / 4), dim3(256), 0, stream, dv, pv, num_steps, reset_done, cfg.warmup_steps,
                        obs, act, logp, rew, done);
@@ -262,8 +271,9 @@ namespace fsim {
         return fastc ? &fs::k_loop_policy<H, true, true>
                      : loop_delta4 ? &fs::k_loop_policy<H, true, false> : &fs::k_loop_policy<H, false, false>;
       };
-      const auto k = dv.env == FS_ENV_WAVE_ATTENUATION_PO ? kernel(Int<1>()) : kernel(Int<0>());
-      last_kernel = "k_loop_policy";
+      const auto k = dv.env == FS_ENV_WAVE_ATTENUATION_PO ? kernel(Int<1>())
+                     : dv.env == FS_ENV_ACCEL_PO_MA ? kernel(Int<2>()) : kernel(Int<0>());
+      last_kernel = dv.env == FS_ENV_ACCEL_PO_MA ? "k_loop_policy<AccelMA>" : "k_loop_policy";
       const int waves = (dv.R + 3) / 4;
       hipLaunchKernelGGL(k, dim3((waves + 3) / 4), dim3(256), 0, stream, dv, pv, num_steps, reset_done, obs, act, logp, rew,
                          done);

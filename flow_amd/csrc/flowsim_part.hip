@@ -23,7 +23,7 @@ template int Sim<FS_PART_T>::launch_loop(const StepArgs&);
 template int Sim<FS_PART_T>::launch_policy_loop16(const fs::PolicyView&, int, int, float*, float*, float*, float*, uint8_t*);
 #endif
 #if FS_PART_SEG == 32
-template int Sim<FS_PART_T>::launch_policy_act(const fs::PolicyView&, const float*, float*, float*);
+template int Sim<FS_PART_T>::launch_policy_act(const fs::PolicyView&, int, const float*, float*, float*);
 template int Sim<FS_PART_T>::launch_policy_row16(const fs::PolicyView&, int, int, float*, float*, float*, float*, uint8_t*);
 #endif
 #if FS_PART_SEG == 64

@@ -202,55 +202,86 @@ __device__ __forceinline__ void policy_eval(const PolicyView& pv, const PolicyLd
 }
 
 // the action: mean + std * g, g the replica's next standard normal draw (Philox block of four per counter / 4, column
-// 0x40000000 + 0: a stream of its own next to the vehicles' noise); log-probability of a 1-d diagonal Gaussian
+// 0x40000000 + agent: a stream of its own next to the vehicles' noise -- agent 0 is the single-agent stream); log-probability
+// of a 1-d diagonal Gaussian
 __device__ __forceinline__ void policy_sample(const PolicyView& pv, uint32_t replica, uint32_t ctr, float mu, float log_std,
-                                              float& action, float& logp, NoiseBlock<float>* nzb = nullptr) {
+                                              float& action, float& logp, NoiseBlock<float>* nzb = nullptr,
+                                              uint32_t agent = 0u) {
   // (a fragment keeps the four draws of a block over four steps: NoiseBlock::draw is gauss() bit for bit)
-  const float g = nzb ? nzb->draw(pv.seed_lo, pv.seed_hi, replica, 0x40000000u, ctr)
-                      : gauss<float>(pv.seed_lo, pv.seed_hi, replica, 0x40000000u, ctr);
+  const uint32_t col = 0x40000000u + agent;
+  const float g = nzb ? nzb->draw(pv.seed_lo, pv.seed_hi, replica, col, ctr)
+                      : gauss<float>(pv.seed_lo, pv.seed_hi, replica, col, ctr);
   const float sd = __builtin_amdgcn_exp2f(log_std * 1.4426950408889634f);
   action = __builtin_fmaf(sd, g, mu);
   logp = __builtin_fmaf(-0.5f * g, g, -log_std) - 0.9189385332046727f;
 }
 
-// eager form: actions and log-probabilities for the observations obs [R, 3]; advances the sampling counters
+// a fused kernel's draw for agent c of a shared policy: agents 0 and 1 keep their Philox block over four steps (one
+// NoiseBlock each, six registers), agents from 2 on draw with gauss() -- the same bits either way (NoiseBlock::draw is
+// gauss()); a block per agent for every agent would be an array indexed by the run-time agent: scratch memory
+__device__ __forceinline__ void policy_sample_agent(const PolicyView& pv, uint32_t replica, uint32_t ctr, int c, float mu,
+                                                    float log_std, float& action, float& logp, NoiseBlock<float>& nzb0,
+                                                    NoiseBlock<float>& nzb1) {
+  if (c == 0) policy_sample(pv, replica, ctr, mu, log_std, action, logp, &nzb0, 0u);          // (wave-uniform)
+  else if (c == 1) policy_sample(pv, replica, ctr, mu, log_std, action, logp, &nzb1, 1u);
+  else policy_sample(pv, replica, ctr, mu, log_std, action, logp, nullptr, uint32_t(c));
+}
+
+// eager form: actions and log-probabilities for the observations obs [R, n_ag * in_dim] of n_ag agents sharing the policy
+// (n_ag = 1: one RL vehicle); act / logp [R, n_ag].  A row of 16 lanes is one replica and evaluates its agents in turn:
+// agent c draws from column 0x40000000 + c at the replica's counter, which advances by ONE per call.  (One row per
+// (replica, agent) would let a replica's agents straddle two waves, and the row that advances the counter could run
+// before a row that still has to read it.)
 template <int ROW>     // (a template so that every object of the library may include this header)
-__global__ __launch_bounds__(256) void k_policy_act(PolicyView pv, int R, uint32_t rep0, const float* __restrict__ obs,
-                                                    float* __restrict__ act, float* __restrict__ logp) {
+__global__ __launch_bounds__(256) void k_policy_act(PolicyView pv, int R, int n_ag, uint32_t rep0,
+                                                    const float* __restrict__ obs, float* __restrict__ act,
+                                                    float* __restrict__ logp) {
   __shared__ PolicyLds L;
   policy_load(pv, &L, threadIdx.x, blockDim.x);
   const int lane = threadIdx.x & 63, j = lane & 15;
   const int r = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
   const int rr = r < R ? r : R - 1;
-  const float* o = obs + size_t(rr) * pv.in_dim;
-  float mu, ls;
-  if (pv.in_dim > 4) {                                   // (wave-uniform) two values per lane: inputs j and half + j
-    const int half = pv.in_dim >> 1;
-    const float ia = j < half ? o[j] : 0.0f, ib = j < half ? o[half + j] : 0.0f;
-    policy_eval<ROW, true>(pv, &L, j, ia, ib, 0.0f, mu, ls);
-  } else {
-    policy_eval<ROW>(pv, &L, j, o[0], pv.in_dim > 1 ? o[1] : 0.0f, pv.in_dim > 2 ? o[2] : 0.0f, mu, ls);
+  const uint32_t c0 = pv.ctr[rr];
+#pragma unroll 1
+  for (int c = 0; c < n_ag; ++c) {
+    const float* o = obs + (size_t(rr) * n_ag + c) * pv.in_dim;
+    float mu, ls;
+    if (pv.in_dim > 4) {                                   // (wave-uniform) two values per lane: inputs j and half + j
+      const int half = pv.in_dim >> 1;
+      const float ia = j < half ? o[j] : 0.0f, ib = j < half ? o[half + j] : 0.0f;
+      policy_eval<ROW, true>(pv, &L, j, ia, ib, 0.0f, mu, ls);
+    } else {
+      policy_eval<ROW>(pv, &L, j, o[0], pv.in_dim > 1 ? o[1] : 0.0f, pv.in_dim > 2 ? o[2] : 0.0f, mu, ls);
+    }
+    float a, lp;
+    policy_sample(pv, rep0 + uint32_t(rr), c0, mu, ls, a, lp, nullptr, uint32_t(c));
+    if (r < R && j == 0) {
+      act[size_t(r) * n_ag + c] = a;
+      logp[size_t(r) * n_ag + c] = lp;
+    }
   }
-  const uint32_t c = pv.ctr[rr];
-  float a, lp;
-  policy_sample(pv, rep0 + uint32_t(rr), c, mu, ls, a, lp);
-  if (r < R && j == 0) {
-    act[r] = a;
-    logp[r] = lp;
-    pv.ctr[r] = c + 1u;
-  }
+  if (r < R && j == 0) pv.ctr[r] = c0 + 1u;
 }
 
-// K x (policy -> action -> Env.step [-> reset of a finished episode]) for rings of IDM vehicles and ONE RL vehicle with
-// the WaveAttenuationPOEnv head.  obs [K+1, R, 3] (obs[0]: the observation of the state the fragment starts from),
-// act [K, R], logp [K, R], rew [K, R], done [K, R].  The simulator part is k_ring_pair's arithmetic statement by statement.
-template <typename T, bool NOISE, bool FAST>
+// K x (policy -> action -> Env.step [-> reset of a finished episode]) for rings of IDM vehicles and RL vehicles.
+// HEAD 1: WaveAttenuationPOEnv, ONE RL vehicle: obs [K+1, R, 3] (obs[0]: the observation of the state the fragment starts
+// from), act [K, R], logp [K, R], rew [K, R], done [K, R].
+// HEAD 2: MultiAgentWaveAttenuationPOEnv (float32), n_ag = num_rl agents sharing the policy: agent c is the RL vehicle of
+// column c, obs [K+1, R, 3 n_ag] (block c: its three values), act / logp [K, R, n_ag], rew [K, R] (the shared reward); a
+// collision ends nothing (multiagent/base.py:188-190).  Per step the row evaluates the agents in turn (the observation of
+// agent c, the network, the draw of column 0x40000000 + c); each lane keeps the actions of its own slots' columns and of
+// its places in the reward's sum by selects.
+// The simulator part is k_ring_pair's arithmetic statement by statement.
+template <typename T, int HEAD, bool NOISE, bool FAST>
 __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv, int num_steps, int reset_done,
                                                      int warmup_steps, float* __restrict__ obs, float* __restrict__ act,
                                                      float* __restrict__ logp, float* __restrict__ rew,
                                                      uint8_t* __restrict__ done) {
   constexpr int ROW = 16;
   constexpr bool MIXED = sizeof(T) == 8;
+  constexpr bool MA = HEAD == 2;
+  static_assert(HEAD == 1 || HEAD == 2, "k_ring_policy: the PO heads");
+  static_assert(!(MA && MIXED), "the multi-agent head exists in float32 only");
   constexpr int RPW = 64 / ROW;
   __shared__ PolicyLds PL;
   policy_load(pv, &PL, threadIdx.x, blockDim.x);
@@ -399,13 +430,14 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
     }
     return nz;
   };
-  // one step (k_ring_pair's `advance`): `have_act` false = rl_actions None (the warm-up steps of a reset)
-  auto advance = [&](bool live, bool have_act, float a_rl) {
+  // one step (k_ring_pair's `advance`): `have_act` false = rl_actions None (the warm-up steps of a reset); a_rlA / a_rlB:
+  // the commands of the lane's two slots (one RL vehicle: the same value)
+  auto advance = [&](bool live, bool have_act, float a_rlA, float a_rlB) {
     f2 acc = idm_pair<FAST, FAST>(v, vl, h, p, two_sqrt_ab, rc_ab, rc_v0, one);
     if constexpr (NOISE) acc = pk_add(acc, noise_term(live));
-    const float a_cl = clip(a_rl);
-    acc.x = rlA ? a_cl : acc.x;
-    acc.y = rlB ? a_cl : acc.y;
+    const float a_clA = clip(a_rlA), a_clB = clip(a_rlB);
+    acc.x = rlA ? a_clA : acc.x;
+    acc.y = rlB ? a_clB : acc.y;
     const bool cmdA = !rlA || have_act, cmdB = !rlB || have_act;
     const f2 acc_s = sumo_acc_pair<FAST>(v, vl, h, sc, one);
     if (MIXED) {
@@ -502,31 +534,85 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
     }
   };
 
+  // MultiAgentWaveAttenuationPOEnv.get_state of agent c (k_ring_pair<POMA>'s write_obs: [v / 15, (v_lead - v) / 15,
+  // bumper-to-bumper headway / max_length]).  The lane of column c's RL slot -- and whether it is A or B -- is a slot
+  // role, the same in every row of the wave: that lane and its two row neighbours divide one value each (the PO head's
+  // helpers above), store it in block c and hand the three to the row as the policy's input.
+  const int n_ag = MA ? s.num_rl : 1;
+  const int colA = rlA ? s.rl_index[iA] : -1, colB = rlB ? s.rl_index[iB] : -1;
+  const bool redA = MA && valid && iA < s.num_rl, redB = MA && valid && iB < s.num_rl;    // (finish()'s places)
+  const int obs_dim = MA ? 3 * n_ag : 3;
+  auto observe_agent = [&](int c, float* orow) {
+    const unsigned long long m = __ballot(k < LP && (colA == c || colB == c));
+    const int k_c = m ? (__builtin_ctzll(m) & (ROW - 1)) : 0;
+    const bool selB = colB == c;
+    const float v_me = selB ? v.y : v.x, v_ld = selB ? vl.y : vl.x, h_me = selB ? h.y : h.x;
+    const float n1 = dpp<0x120 + 1>(v_ld - v_me), n2 = dpp<0x120 + 2>(h_me);      // row_ror: lane i <- lane i - 1 / i - 2
+    const int pc = (k - k_c) & (ROW - 1);
+    const float n = pc == 0 ? v_me : (pc == 1 ? n1 : n2);
+    const float q = div_via_f64(n, pc == 2 ? pml64 : 15.0, pc == 2 ? rc_pml64 : rc15);
+    if (rvalid && pc < 3) orow[3 * c + pc] = q;
+    row_bcast3(k_c, q, q, q, o0, o1, o2);
+  };
+
   const size_t R = size_t(s.R);
-  NoiseBlock<float> act_draws;
+  NoiseBlock<float> act_draws, act_draws1;
   act_draws.init();
-  observe(obs + size_t(rr) * 3);
+  act_draws1.init();
+  if constexpr (!MA) observe(obs + size_t(rr) * 3);
   for (int step = 0; step < num_steps; ++step) {
     // ---- policy -> action --------------------------------------------------------------------------------------
-    float mu, ls, a, lp;
-    policy_eval<ROW>(pv, &PL, k, o0, o1, o2, mu, ls);
-    policy_sample(pv, s.rep0 + uint32_t(rr), pctr, mu, ls, a, lp, &act_draws);
-    pctr += 1u;
-    if (rvalid && k == 0) {
-      act[size_t(step) * R + rr] = a;
-      logp[size_t(step) * R + rr] = lp;
+    float a, aA, aB, arA = 0.0f, arB = 0.0f;            // arA / arB: the columns summed at the lane's places (MA)
+    if constexpr (MA) {
+      aA = 0.0f;
+      aB = 0.0f;
+      a = 0.0f;
+      float* orow = obs + (size_t(step) * R + rr) * obs_dim;
+#pragma unroll 1
+      for (int c = 0; c < n_ag; ++c) {
+        observe_agent(c, orow);
+        float mu, ls, ac, lp;
+        policy_eval<ROW>(pv, &PL, k, o0, o1, o2, mu, ls);
+        policy_sample_agent(pv, s.rep0 + uint32_t(rr), pctr, c, mu, ls, ac, lp, act_draws, act_draws1);
+        if (rvalid && k == 0) {
+          act[(size_t(step) * R + rr) * n_ag + c] = ac;
+          logp[(size_t(step) * R + rr) * n_ag + c] = lp;
+        }
+        aA = colA == c ? ac : aA;
+        aB = colB == c ? ac : aB;
+        arA = iA == c ? ac : arA;
+        arB = iB == c ? ac : arB;
+      }
+    } else {
+      float mu, ls, lp;
+      policy_eval<ROW>(pv, &PL, k, o0, o1, o2, mu, ls);
+      policy_sample(pv, s.rep0 + uint32_t(rr), pctr, mu, ls, a, lp, &act_draws);
+      if (rvalid && k == 0) {
+        act[size_t(step) * R + rr] = a;
+        logp[size_t(step) * R + rr] = lp;
+      }
+      aA = a;
+      aB = a;
     }
+    pctr += 1u;
     // ---- Env.step ------------------------------------------------------------------------------------------------
-    advance(true, true, a);
+    advance(true, true, aA, aB);
     const f2 hc = pk_sub(h, gap2), vb = pk_sub(v, f2{-100.0f, -100.0f});        // sign masks (k_ring_pair's terms)
     const unsigned fl = ((__builtin_bit_cast(unsigned, hmin(hc.x, hc.y)) >> 31) |
                          ((__builtin_bit_cast(unsigned, hmin(vb.x, vb.y)) >> 31) << 1)) & (valid ? 3u : 0u);
     const unsigned fany = seg_or<ROW>(fl);
-    const bool crashed = (fany & 1u) != 0u;
+    const bool crashed = !MA && (fany & 1u) != 0u;          // (multiagent/base.py:188-190: crash = 0)
     const bool bad = (fany & 2u) != 0u || crashed;
     const float sv = seg_sum<ROW>(valid ? v.x + v.y : 0.0f);
     const float mean_v = div_via_f64(sv, double(N), 1.0 / double(N));
-    const float mean_a = tabs(clip(a));                     // (one column: the sum is the value, / 1)
+    float mean_a;
+    if constexpr (MA) {                                     // k_ring_pair's terms / finish: column i summed where slot i stands
+      const float caA = tabs(clip(arA)), caB = tabs(clip(arB));
+      const float sa = seg_sum<ROW>((redA ? caA : 0.0f) + (redB ? caB : 0.0f));
+      mean_a = div_via_f64(sa, double(s.num_rl), 1.0 / double(s.num_rl));
+    } else {
+      mean_a = tabs(clip(a));                               // (one column: the sum is the value, / 1)
+    }
     float reward = div_via_f64(4.0f * mean_v, 20.0, 1.0 / 20.0);
     if (mean_a > 0.0f) reward = reward + 4.0f * (0.0f - mean_a);
     reward = bad ? 0.0f : reward;
@@ -549,10 +635,15 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
       h = headway();
       vl = f2{v.y, next_a<ROW>(v.x, last, lane)};
 #pragma unroll 1
-      for (int w = 0; w < warmup_steps; ++w) advance(fin, false, 0.0f);
+      for (int w = 0; w < warmup_steps; ++w) advance(fin, false, 0.0f, 0.0f);
       if (fin && valid && kk == 0) const_cast<T*>(s.ring_len)[rr] = s.init_ring_len[rr];
     }
-    observe(obs + (size_t(step + 1) * R + rr) * 3);
+    // (MA: the agents' observations are made at the top of the next step, where the policy takes them)
+    if constexpr (!MA) observe(obs + (size_t(step + 1) * R + rr) * 3);
+  }
+  if constexpr (MA) {
+#pragma unroll 1
+    for (int c = 0; c < n_ag; ++c) observe_agent(c, obs + (size_t(num_steps) * R + rr) * obs_dim);
   }
 
   if (valid) {
@@ -580,6 +671,11 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
 // quotients and reward expressions, so a fragment equals eager stepping (fs_policy_act_dev, fs_step_dev -- which runs
 // k_rollout_loop --, masked fs_reset_dev) bit for bit (tests/test_policy_gpu.py).  Resets inside the fragment: placement only
 // (warmup_steps = 0: Sim::launch_policy refuses anything else).
+// HEAD 2: MultiAgentAccelPOEnv (examples/exp_configs/rl/multiagent/multiagent_figure_eight.py), n_ag = num_rl agents sharing
+// the policy: obs [K+1, R, 6 n_ag], act / logp [K, R, n_ag], the shared desired-velocity reward, no crash
+// (tests/test_policy_ma_gpu.py).  Agent c's six values sit on two lanes -- its RL vehicle's (four) and its follower's (two,
+// k_rollout_loop's flush_obs) -- and are gathered into policy_eval<16, WIDE>'s layout with half = 3 (lane i < 3: inputs i
+// and 3 + i), the layout k_policy_act gives a 6-value block.
 template <int HEAD, bool DELTA4, bool FASTC>
 __global__ __launch_bounds__(256) void k_loop_policy(DevView<float> s, PolicyView pv, int num_steps, int reset_done,
                                                      float* __restrict__ obs, float* __restrict__ act,
@@ -708,13 +804,30 @@ __global__ __launch_bounds__(256) void k_loop_policy(DevView<float> s, PolicyVie
 
   // the observation of the current state: stored, and handed to the row as the policy's input.  PO head: the RL vehicle's
   // three values reach every lane of its row; AccelEnv head: every lane keeps its own two (inputs ii and N + ii)
-  const int obs_dim = HEAD == 1 ? 3 : 2 * N;
+  const int obs_dim = HEAD == 1 ? 3 : (HEAD == 2 ? 6 * num_rl : 2 * N);
   const unsigned long long rl_m = __ballot(valid && rl_lane);
   const int k_rl = rl_m ? (__builtin_ctzll(rl_m) & (SEG - 1)) : 0;
   const int src_rl = (lane - i) + k_rl;
   float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f;
+  // HEAD 2 (k_rollout_loop<AccelMA>'s observation): a lane's four values of its own block and the two of its leader's
+  // (lead_col: the leader's column, -1 if the leader is no RL vehicle); kept for the agents' gather (m3l: the leader's m3)
+  const int own_col = sl.rl_index < 0 ? 0 : sl.rl_index;
+  const int lead_col = HEAD == 2 ? __builtin_bit_cast(int, lead16(__builtin_bit_cast(float, rl_lane ? own_col : -1), wrap_lead)) : -1;
+  const bool fw_lane = HEAD == 2 && valid && lead_col >= 0;
+  float m0 = 0.0f, m1 = 0.0f, m2 = 0.0f, m3l = 0.0f, m5 = 0.0f;
   auto observe = [&](float* orow) {
-    if (HEAD == 1) {
+    if (HEAD == 2) {
+      const T xo = c_fs + c_sl * (x - c_st);
+      const T xol = lead16(xo, wrap_lead);
+      m0 = divc(xo, d_L);                                                          // multiagent/ring/accel.py:163-208
+      m1 = divc(v, d_ms);
+      m2 = divc(vl - v, d_ms);
+      const float m3 = divc((xol - xo) - len_me, d_L);
+      m5 = divc(h, d_L);
+      if (valid && rl_lane) { float* o = orow + 6 * own_col; o[0] = m0; o[1] = m1; o[2] = m2; o[3] = m3; }
+      if (fw_lane) { float* o = orow + 6 * lead_col; o[4] = m2; o[5] = m5; }
+      m3l = lead16(m3, wrap_lead);                     // the follower of an RL vehicle holds that vehicle's fourth value
+    } else if (HEAD == 1) {
       const float po0 = divc(v, d_15), po1 = divc(vl - v, d_15), po2 = divc(d, d_po);      // wave_attenuation.py:248-269
       if (obs_lane) { orow[0] = po0; orow[1] = po1; orow[2] = po2; }
       row_bcast1x3(k_rl, po0, po1, po2, o0, o1, o2);
@@ -728,20 +841,47 @@ __global__ __launch_bounds__(256) void k_loop_policy(DevView<float> s, PolicyVie
   };
 
   const size_t R = size_t(s.R);
-  NoiseBlock<float> act_draws;
+  const int n_ag = HEAD == 2 ? num_rl : 1;
+  NoiseBlock<float> act_draws, act_draws1;
   act_draws.init();
+  act_draws1.init();
   observe(obs + size_t(rr) * obs_dim);
   for (int step = 0; step < num_steps; ++step) {
     // ---- policy -> action --------------------------------------------------------------------------------------
     float mu, ls, a, lp;
-    if (HEAD == 1) policy_eval<SEG>(pv, &PL, i, o0, o1, o2, mu, ls);
-    else policy_eval<SEG, true>(pv, &PL, i, o0, o1, 0.0f, mu, ls);
-    policy_sample(pv, s.rep0 + uint32_t(rr), pctr, mu, ls, a, lp, &act_draws);
-    pctr += 1u;
-    if (rvalid && i == 0) {
-      act[size_t(step) * R + rr] = a;
-      logp[size_t(step) * R + rr] = lp;
+    if constexpr (HEAD == 2) {
+      // agent c: its RL vehicle's lane i_c and the follower's f_c (slot roles: the same in every row) hand their values
+      // to the row, lanes 0..2 keep theirs; the lane of an RL vehicle keeps its own column's action
+      a = 0.0f;
+#pragma unroll 1
+      for (int c = 0; c < n_ag; ++c) {
+        const unsigned long long m = __ballot(i < N && rl_lane && sl.rl_index == c);
+        const int i_c = m ? (__builtin_ctzll(m) & (SEG - 1)) : 0;
+        const int f_c = i_c == 0 ? N - 1 : i_c - 1;
+        float a0, a1, a2, b0, b1, b2;
+        row_bcast1x3(i_c, m0, m1, m2, a0, a1, a2);
+        row_bcast1x3(f_c, m3l, m2, m5, b0, b1, b2);
+        const float ia = i == 0 ? a0 : (i == 1 ? a1 : (i == 2 ? a2 : 0.0f));
+        const float ib = i == 0 ? b0 : (i == 1 ? b1 : (i == 2 ? b2 : 0.0f));
+        float ac;
+        policy_eval<SEG, true>(pv, &PL, i, ia, ib, 0.0f, mu, ls);
+        policy_sample_agent(pv, s.rep0 + uint32_t(rr), pctr, c, mu, ls, ac, lp, act_draws, act_draws1);
+        if (rvalid && i == 0) {
+          act[(size_t(step) * R + rr) * n_ag + c] = ac;
+          logp[(size_t(step) * R + rr) * n_ag + c] = lp;
+        }
+        a = (rl_lane && own_col == c) ? ac : a;
+      }
+    } else {
+      if (HEAD == 1) policy_eval<SEG>(pv, &PL, i, o0, o1, o2, mu, ls);
+      else policy_eval<SEG, true>(pv, &PL, i, o0, o1, 0.0f, mu, ls);
+      policy_sample(pv, s.rep0 + uint32_t(rr), pctr, mu, ls, a, lp, &act_draws);
+      if (rvalid && i == 0) {
+        act[size_t(step) * R + rr] = a;
+        logp[size_t(step) * R + rr] = lp;
+      }
     }
+    pctr += 1u;
     // ---- Env.step: k_rollout_loop's step ---------------------------------------------------------------------------
     bool on_a = false, on_b = false, on_any = false, on_both = false;
     if (junction_on) {
@@ -816,7 +956,8 @@ __global__ __launch_bounds__(256) void k_loop_policy(DevView<float> s, PolicyVie
     f2_ &= valid_bits;
     f2_ = seg_or<SEG>(f2_);
     jf = (f2_ >> 4) & 3u;
-    const bool crashed = ((f2_ | ((f2_ >> 1) & (f2_ >> 2))) & 1u) != 0u;
+    // (the multi-agent head sees no crash: multiagent/base.py:188-190)
+    const bool crashed = HEAD != 2 && ((f2_ | ((f2_ >> 1) & (f2_ >> 2))) & 1u) != 0u;
     const bool bad = (((f2_ >> 3) & 1u) != 0u) || crashed;
     // ---- reward (the block form's transposed_sum is seg_sum's tree) --------------------------------------------------
     T reward;
@@ -829,7 +970,7 @@ __global__ __launch_bounds__(256) void k_loop_policy(DevView<float> s, PolicyVie
       reward = divc(T(4.0) * mean_v, d_20);
       if (mean_a > T(0)) reward = reward + T(4) * (T(0) - mean_a);
       reward = bad ? T(0) : reward;
-    } else {                                                       // rewards.py:6-59
+    } else {                                                       // rewards.py:6-59 (AccelEnv, MultiAgentAccelPOEnv)
       const T dv = valid ? T(v) - target_v : T(0);
       const T cost = tsqrt(seg_sum<SEG>(dv * dv));
       reward = divc(tmax(max_cost - cost, T(0)), d_mc);

@@ -840,8 +840,9 @@ struct Sim : SimBase {
   }
 
   // policy in the loop (flowsim_policy.h; flowsim_launch.h): the eager policy, the fused policy + step kernels of rings
-  // (rows of 16 lanes: 18..32 vehicles) and of segment-table loops (the figure eight: up to 16 vehicles)
-  int launch_policy_act(const fs::PolicyView& pv, const float* obs_in, float* act, float* logp);
+  // (rows of 16 lanes: 18..32 vehicles) and of segment-table loops (the figure eight: up to 16 vehicles); n_ag agents
+  // share the policy on the multi-agent heads (MultiAgentWaveAttenuationPOEnv on rings, MultiAgentAccelPOEnv on loops)
+  int launch_policy_act(const fs::PolicyView& pv, int n_ag, const float* obs_in, float* act, float* logp);
   int launch_policy_row16(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act, float* logp,
                           float* rew, uint8_t* done);
   int launch_policy_loop16(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act, float* logp,
@@ -851,10 +852,35 @@ struct Sim : SimBase {
     if (!pol || pol->struct_size != sizeof(fs_policy)) return fail(FS_ERR_INVALID, "fs_policy: struct_size mismatch");
     const bool f32_or_mixed = mixed || std::is_same<T, float>::value;
     const bool loop = dv.nseg > 0;                       // a segment-table loop (figure eight) or a ring
+    const bool ma = dv.env == FS_ENV_WAVE_ATTENUATION_PO_MA || dv.env == FS_ENV_ACCEL_PO_MA || dv.env == FS_ENV_MERGE_MA;
     const char* why = nullptr;
     if (pol->num_hidden < 1 || pol->num_hidden > 3 || pol->hidden_width != 32 || pol->activation != 0)
       why = "fs_policy model (1..3 hidden layers of 32 tanh units)";
     else if (!pol->weights_dev) why = "fs_policy.weights_dev (NULL)";
+    else if (ma) {                                       // one policy shared by the num_rl agents of a replica
+      if (dv.env == FS_ENV_MERGE_MA)
+        why = "env (FS_ENV_MERGE_MA: the merge's agents enter and leave the network; capture single steps instead)";
+      else if (!std::is_same<T, float>::value || mixed)
+        why = "precision (the multi-agent heads are float32 only: FS_MIXED / FS_F64 handles are not built)";
+      else if (!loop && dv.env != FS_ENV_WAVE_ATTENUATION_PO_MA)
+        why = "env (FS_ENV_ACCEL_PO_MA on a ring: rings take MultiAgentWaveAttenuationPOEnv)";
+      else if (loop && dv.env != FS_ENV_ACCEL_PO_MA)
+        why = "env (FS_ENV_WAVE_ATTENUATION_PO_MA on a segment-table loop: loops take MultiAgentAccelPOEnv)";
+      else if (dv.num_rl < 1 || pol->obs_dim * dv.num_rl != obs_dim)
+        why = "fs_policy.obs_dim (one agent's block: fs_obs_dim / num_rl)";
+      else if (loop && (seg != 16 || dv.N < 2)) why = "num_vehicles (2..16: a row of 16 lanes per replica)";
+      else if (loop && (!(dv.flags & fs::FLAG_IDM_SET) || (dv.flags & fs::FLAG_HAS_FAILSAFE) || dv.sims_per_step != 1 ||
+                        dv.integrator != FS_EULER || dv.track_aux || dv.sort_vehicles || dv.obs_perm != nullptr ||
+                        !loop_div_ok || (obs != nullptr && reset_done && cfg.warmup_steps != 0)))
+        why = "configuration (what k_rollout_loop steps: IDM / RL / Sim vehicles, Euler, track_aux = 0; resets inside a "
+              "fragment: warmup_steps = 0)";
+      else if (!loop && seg != 32) why = "num_vehicles (18..32: a row of 16 lanes per replica)";
+      else if (!loop && (dv.junction_on || dv.num_lanes > 1 || !(dv.flags & fs::FLAG_IDM_SET) || any_sim ||
+                         (dv.flags & fs::FLAG_HAS_FAILSAFE) || dv.sims_per_step != 1 || dv.integrator != FS_EULER ||
+                         dv.junction_mode || dv.track_aux || dv.sort_vehicles || dv.obs_perm != nullptr || dv.evaluate ||
+                         (dv.N % 2) != 0))
+        why = "configuration (what k_ring_pair steps: single-lane ring of IDM / RL vehicles, Euler, track_aux = 0)";
+    }
     else if (loop) {
       const bool po = dv.env == FS_ENV_WAVE_ATTENUATION_PO, accel = dv.env == FS_ENV_ACCEL && !dv.evaluate;
       if (!std::is_same<T, float>::value || mixed) why = "precision (f32 on segment-table loops)";
@@ -890,7 +916,7 @@ struct Sim : SimBase {
     pv.n_out = pol->log_std_dev ? 1 : 2;
     pv.seed_lo = uint32_t(pol->seed & 0xFFFFFFFFull);
     pv.seed_hi = uint32_t(pol->seed >> 32);
-    if (obs == nullptr) return launch_policy_act(pv, obs_in, act, logp);      // eager: the policy alone
+    if (obs == nullptr) return launch_policy_act(pv, ma ? dv.num_rl : 1, obs_in, act, logp);      // eager: the policy alone
     if (loop) return launch_policy_loop16(pv, num_steps, reset_done, obs, act, logp, rew, done);
     return launch_policy_row16(pv, num_steps, reset_done, obs, act, logp, rew, done);
   }

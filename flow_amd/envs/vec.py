@@ -274,7 +274,11 @@ class VecFlowEnv(object):
         (``fs_policy_rollout_dev``; ``policy``: a ``flow_amd.utils.device_policy.DevicePolicy``).  Returns device tensors
         ``obs [K+1, R, obs_dim]`` (obs[0]: the state the fragment starts from), ``actions [K, R]``, ``logp [K, R]``,
         ``rew [K, R]``, ``done [K, R]`` (flag byte: bit 0 horizon, bit 1 collision).  Built for the reference's RL ring
-        experiments (one RL vehicle, WaveAttenuationPOEnv); ``capture`` serves every other environment / model."""
+        and figure-eight experiments: one RL vehicle (WaveAttenuationPOEnv; AccelEnv on the figure eight), or the
+        multi-agent ring (MultiAgentWaveAttenuationPOEnv) and figure eight (MultiAgentAccelPOEnv), whose ``num_rl``
+        agents share ``policy`` (its input: one agent's observation block, ``obs_dim / num_rl``): ``actions`` and
+        ``logp`` are then ``[K, R, num_rl]`` (column c: agent c, the RL vehicle of rl_index c) and ``rew`` is the shared
+        reward.  ``capture`` serves every other environment / model."""
         torch, R, K = self.torch, self.num_envs, int(num_steps)
         self.use_current_stream()
         if reset_done and self._resample and not getattr(self, "_warned_pending_length", False):
@@ -284,10 +288,12 @@ class VecFlowEnv(object):
                           "(flow/envs/ring/wave_attenuation.py:157-210); every reset inside ONE fragment takes the replica's "
                           "pending length (FS_FIELD_INIT_RING_LENGTH) -- call vec.redraw_ring_lengths() between fragments, "
                           "and keep fragments shorter than an episode if each episode must draw its own.", stacklevel=2)
+        n_ag = self.sim.policy_agents
+        per_agent = (K, R) if n_ag == 1 else (K, R, n_ag)
         if out is None:
             out = (torch.empty((K + 1, R, self.obs_dim), dtype=torch.float32, device=self.device),
-                   torch.empty((K, R), dtype=torch.float32, device=self.device),
-                   torch.empty((K, R), dtype=torch.float32, device=self.device),
+                   torch.empty(per_agent, dtype=torch.float32, device=self.device),
+                   torch.empty(per_agent, dtype=torch.float32, device=self.device),
                    torch.empty((K, R), dtype=torch.float32, device=self.device),
                    torch.empty((K, R), dtype=torch.uint8, device=self.device))
         self.sim.policy_rollout_dev(policy.struct, K, out[0], out[1], out[2], out[3], out[4], reset_done=reset_done)

@@ -259,10 +259,20 @@ class FlowSim:
                                         _ptr(obs), _ptr(rew), _ptr(done), int(bool(obs_every_step))), self.lib)
 
     # ------------------------------------------------------------------ policy in the loop (include/flowsim.h fs_policy)
+    @property
+    def policy_agents(self):
+        """Agents sharing one policy per replica: num_rl on the multi-agent heads (observation block c and action column
+        c are agent c's), 1 otherwise.  fs_policy.obs_dim is one agent's block: obs_dim / policy_agents."""
+        env = int(self.spec.get("env", L.FS_ENV_ACCEL))
+        ma = env in (L.FS_ENV_WAVE_ATTENUATION_PO_MA, L.FS_ENV_ACCEL_PO_MA, L.FS_ENV_MERGE_MA)
+        return max(self.num_rl, 1) if ma else 1
+
     def policy_act_dev(self, pol, obs, act, logp):
+        """act / logp [R] (one agent) or [R, policy_agents] for the observations obs [R, obs_dim]."""
         L.check(self.lib.fs_policy_act_dev(self._h, C.byref(pol), _ptr(obs), _ptr(act), _ptr(logp)), self.lib)
 
     def policy_rollout_dev(self, pol, num_steps, obs, act, logp, rew, done, reset_done=False):
+        """obs [K+1, R, obs_dim]; act / logp [K, R] (one agent) or [K, R, policy_agents]; rew / done [K, R]."""
         L.check(self.lib.fs_policy_rollout_dev(self._h, C.byref(pol), int(num_steps), int(bool(reset_done)), _ptr(obs),
                                                _ptr(act), _ptr(logp), _ptr(rew), _ptr(done)), self.lib)
 

@@ -421,6 +421,7 @@ int fs_add_vehicle(fs_handle h, int replica, int slot, int route, double x, doub
 /* Family of the step kernel the handle's last fs_step / fs_rollout / fs_policy_rollout launch chose ("k_rollout_pair" with
  * "+speed_mode" and / or "+noise", "k_rollout_idm", "k_ring_pair<Accel | PO | POMA | AccelMA>", "k_rollout_loop",
  * "k_rollout_loop<FULL>", "k_rollout_loop<AccelMA>", "k_rollout_loop<FULL,AccelMA>", "k_ring_policy", "k_loop_policy",
+ * "k_ring_policy<POMA>", "k_loop_policy<AccelMA>",
  * "k_steps<FAST>", "k_steps<CSET>", "k_steps", "k_steps_ml", "k_steps_open" (also "<mixed>"), "k_steps_wide",
  * "k_merge_queue", "k_drop_queue", "k_obs_mixed"; "" before the first launch).  Diagnostics for tests and bench.py: which
  * configuration class a workload landed in (no reference counterpart).  The string is static.
@@ -444,10 +445,21 @@ const char* fs_last_kernel(fs_handle h);
  * The arithmetic (fma order, hardware exp2 / rcp) is defined by flow_amd/csrc/flowsim_policy.h; fs_policy_act_dev is
  * the SAME evaluation as a call of its own, so fs_policy_rollout_dev equals K x (fs_policy_act_dev, fs_step_dev
  * [, fs_reset_dev(done)]) bit for bit.  Other environments / models: FS_ERR_UNSUPPORTED (capture K single steps
- * around any policy instead: flow_amd.envs.VecFlowEnv.capture). */
+ * around any policy instead: flow_amd.envs.VecFlowEnv.capture).
+ * Shared agents (the reference's multi-agent experiments map every agent to ONE policy): FS_ENV_WAVE_ATTENUATION_PO_MA on
+ * a single-lane ring (multiagent_ring.py; 18..32 vehicles, IDM / RL, Euler, track_aux = 0, warm-up steps inside the
+ * fragment allowed) and FS_ENV_ACCEL_PO_MA on a segment-table loop (multiagent_figure_eight.py; up to 16 vehicles,
+ * warmup_steps = 0 when a fragment resets), float32 handles only.  Agent c is the RL vehicle with rl_index c: its
+ * observation is block c of the observation row, its action column c (the layout of fs_step_dev for these heads);
+ * n_ag = num_rl agents, and obs_dim must be ONE agent's block, fs_obs_dim / num_rl (3 or 6).  fs_policy_act_dev takes
+ * obs [R, n_ag * obs_dim] and writes act / logp [R, n_ag]: agent c of replica r draws from Philox column 0x40000000 + c
+ * at the replica's counter, which advances by one per call (c = 0 is the single-agent stream).  fs_policy_rollout_dev
+ * takes obs [K+1, R, n_ag * obs_dim], act / logp [K, R, n_ag], rew / done [K, R] (the reward all agents share; a
+ * collision ends nothing and zeroes no reward, multiagent/base.py:188-190).  FS_MIXED / FS_F64 with a multi-agent head,
+ * FS_ENV_ACCEL_PO_MA on a ring and FS_ENV_MERGE_MA are refused by name. */
 typedef struct fs_policy {
   uint32_t struct_size;               /* sizeof(fs_policy) */
-  int32_t obs_dim;                    /* must equal fs_obs_dim (3) */
+  int32_t obs_dim;                    /* must equal fs_obs_dim; shared agents: fs_obs_dim / num_rl */
   int32_t num_hidden;                 /* 1..3 hidden layers ... */
   int32_t hidden_width;               /* ... of 32 units each */
   int32_t activation;                 /* 0 = tanh */
@@ -456,12 +468,14 @@ typedef struct fs_policy {
   uint64_t seed;
 } fs_policy;
 
-/* actions [R] and log-probabilities [R] for the observations obs_dev [R, obs_dim]; advances the sampling streams */
+/* actions [R] and log-probabilities [R] for the observations obs_dev [R, obs_dim] ([R, n_ag] for [R, n_ag * obs_dim] with
+ * shared agents); advances the sampling streams */
 int fs_policy_act_dev(fs_handle h, const fs_policy* pol, const float* obs_dev, float* act_dev, float* logp_dev);
 /* K x (policy -> action -> Env.step), with reset_done != 0 followed by Env.reset of the replicas whose episode ended
  * (placement, FS_FIELD_INIT_RING_LENGTH, warm-up steps).  obs_dev [K+1, R, obs_dim]: obs[0] = observation of the state
  * the fragment starts from (written by the call), obs[k+1] = observation after step k (after the reset, if one
- * happened); act_dev [K, R], logp_dev [K, R], rew_dev [K, R], done_dev [K, R] (flags as in fs_rollout_dev). */
+ * happened); act_dev [K, R], logp_dev [K, R] ([K, R, n_ag] with shared agents), rew_dev [K, R], done_dev [K, R] (flags as in
+ * fs_rollout_dev). */
 int fs_policy_rollout_dev(fs_handle h, const fs_policy* pol, int num_steps, int reset_done, float* obs_dev,
                           float* act_dev, float* logp_dev, float* rew_dev, uint8_t* done_dev);
 
