@@ -86,20 +86,31 @@ def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None):
     """One PPO update over `shards` = [(obs [K+1, R, D], act [K, R, A], rew [K, R], done [K, R])]: the shards this
     process holds (one per rank in data-parallel runs, all of them in a single process).  Every quantity that couples the
     shards is a SUM: the advantage statistics and the gradient -- summed over the local shards here, over the ranks by
-    allreduce_sum / allreduce_gradients -- so N ranks with one shard each and one process with N shards agree."""
+    allreduce_sum / allreduce_gradients -- so N ranks with one shard each and one process with N shards agree.
+    A sample whose action is NaN is an agent that was absent (the multi-agent merge's fused rollout: its RL slot held no
+    vehicle): it is left out of the advantage statistics and the loss, and its action is never read."""
     from flow_amd.dist import allreduce_gradients, allreduce_sum
     prepared, stats = [], None
     for obs, act, rew, done in shards:
         K, R = rew.shape
         o, a = obs[:K].reshape(K * R, -1), act.reshape(K * R, -1)
+        present = ~torch.isnan(a).any(-1)
+        if bool(present.all()):
+            present = None                                   # (every sample present: the plain sums)
+        else:
+            a = torch.where(present[:, None], a, torch.zeros_like(a))
         with torch.no_grad():
             logp_old, val = pi.logp_value(o, a)
             last_val = pi.value(obs[K]).squeeze(-1)
             adv, ret = gae(rew, val.view(K, R), done, last_val)
             adv = adv.reshape(-1).double()
-            st = torch.stack([adv.sum(), (adv * adv).sum(), torch.tensor(float(adv.numel()), dtype=torch.float64, device=adv.device)])
+            if present is None:
+                st = torch.stack([adv.sum(), (adv * adv).sum(), torch.tensor(float(adv.numel()), dtype=torch.float64, device=adv.device)])
+            else:
+                m = present.double()
+                st = torch.stack([(adv * m).sum(), (adv * adv * m).sum(), m.sum()])
             stats = st if stats is None else stats + st
-        prepared.append((o, a, logp_old, adv, ret.reshape(-1)))
+        prepared.append((o, a, logp_old, adv, ret.reshape(-1), present))
     stats = allreduce_sum(stats, group)
     n = stats[2]
     mean = stats[0] / n
@@ -107,13 +118,17 @@ def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None):
     params = list(pi.parameters())
     for _ in range(epochs):
         opt.zero_grad()
-        for o, a, logp_old, adv, ret in prepared:
+        for o, a, logp_old, adv, ret, present in prepared:
             adv_n = ((adv - mean) / (std + 1e-8)).float()
             logp, v = pi.logp_value(o, a)
             ratio = (logp - logp_old).exp()
+            pg = torch.min(ratio * adv_n, ratio.clamp(1 - clip, 1 + clip) * adv_n)
+            vf = (v - ret).pow(2)
+            if present is not None:
+                pg = torch.where(present, pg, torch.zeros_like(pg))
+                vf = torch.where(present, vf, torch.zeros_like(vf))
             # the GLOBAL mean as a sum of per-shard sums
-            loss = (-torch.min(ratio * adv_n, ratio.clamp(1 - clip, 1 + clip) * adv_n).sum()
-                    + 0.5 * (v - ret).pow(2).sum()) / float(n)
+            loss = (-pg.sum() + 0.5 * vf.sum()) / float(n)
             loss.backward()                                  # (accumulates over the local shards)
         allreduce_gradients(params, group)
         opt.step()
@@ -143,9 +158,11 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     pi = GaussianPolicy(k_ag if shared_agents else vec.obs_dim, 1 if shared_agents else vec.act_dim).to(dev)
     opt = torch.optim.Adam(pi.parameters(), lr=lr)
     # the rollout: ONE kernel per fragment where the library has the fused policy + step form for this experiment and
-    # model (fs_policy_rollout_dev: rings / the figure eight with one RL vehicle, the multi-agent ring and figure eight
-    # with their agents sharing the policy, 1..3 hidden layers of 32 tanh units); otherwise K single steps around the
-    # torch policy captured as one HIP graph.  (Shared agents: the network's input is one agent's block, k_ag values.)
+    # model (fs_policy_rollout_dev: rings / the figure eight with one RL vehicle, the multi-agent ring, figure eight and
+    # merge -- its actions applied -- with their agents sharing the policy, 1..3 hidden layers of 32 tanh units);
+    # otherwise K single steps around the torch policy captured as one HIP graph.  (Shared agents: the network's input is
+    # one agent's block, k_ag values; on the merge an agent whose RL slot is empty has a NaN action, which ppo_update
+    # leaves out.)
     fused, graph = None, None
     shared = "; one policy shared by %d agents per replica" % n_ag if shared_agents else ""
     try:

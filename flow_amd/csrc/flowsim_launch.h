@@ -17,7 +17,19 @@ namespace fsim {
     const auto k = pick(noise, [&](auto NZ) { return pick(act, [&](auto ACT) { return &fs::k_merge_queue<NZ, ACT>; }); });
     last_kernel = "k_merge_queue";
     hipLaunchKernelGGL(k, dim3(dv.R), dim3(64), 0, stream, dv, ov, qc, a.num_steps, a.actions, a.act_stride, a.obs, a.rew,
-                       a.done, a.obs_every_step);
+                       a.done, a.obs_every_step, fs::PolicyView{}, static_cast<float*>(nullptr), static_cast<float*>(nullptr),
+                       0);
+    return launched();
+  }
+  // the multi-agent merge with its agents sharing the policy: k_merge_queue's POLICY form (one wave per replica)
+  template <typename T>
+  int Sim<T>::launch_policy_queue(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act,
+                                  float* logp, float* rew, uint8_t* done) {
+    const bool noise = (dv.flags & fs::FLAG_HAS_NOISE) != 0;
+    const auto k = pick(noise, [&](auto NZ) { return &fs::k_merge_queue<NZ, true, true>; });
+    last_kernel = "k_merge_policy";
+    hipLaunchKernelGGL(k, dim3(dv.R), dim3(64), 0, stream, dv, ov, qc, num_steps, static_cast<const float*>(nullptr),
+                       size_t(0), obs, rew, done, 1, pv, act, logp, reset_done);
     return launched();
   }
   template <typename T>
@@ -234,8 +246,11 @@ namespace fsim {
   template <typename T>
   int Sim<T>::launch_policy_act(const fs::PolicyView& pv, int n_ag, const float* obs_in, float* act, float* logp) {
     last_kernel = "k_policy_act";
+    const bool merge = dv.env == FS_ENV_MERGE_MA;        // (agents present or not: the handle's current routes)
     hipLaunchKernelGGL(fs::k_policy_act<16>, dim3((dv.R * 16 + 255) / 256), dim3(256), 0, stream, pv, dv.R, n_ag, dv.rep0,
-                       obs_in, act, logp);
+                       obs_in, act, logp, merge ? static_cast<const int*>(dv.lane) : nullptr,
+                       merge ? static_cast<const int*>(dv.ctrl) : nullptr,
+                       merge ? static_cast<const int*>(dv.rl_index) : nullptr, dv.N);
     return launched();
   }
 

@@ -1286,9 +1286,62 @@ __global__ __launch_bounds__(64) void k_steps_open(DevView<T> s, OpenView<T> o, 
   if (bn_env && rvalid && live_replica && i < 20) o.arr_hist[size_t(rr) * 20 + i] = hist_l;
 }
 
-// Env.reset of an open network: the initial vehicles back in their slots, every other slot free, clocks and
-// id counters restarted (restart_instance: SUMO starts again at time 0, envs/base.py:430-470); S13: one step
-// has run when reset returns.
+// Env.reset of an open network for slot i of replica r: the initial vehicle back in its slot or the slot free, and (slot
+// 0) the replica's clocks and id counters restarted (restart_instance: SUMO starts again at time 0, envs/base.py:430-470);
+// S13: one step has run when reset returns.  Shared by k_reset_open and the in-fragment reset of k_merge_queue<POLICY>.
+template <typename T>
+__device__ __forceinline__ void reset_open_slot(const DevView<T>& s, const OpenView<T>& o, int r, int i) {
+  const int N = s.N;
+  const size_t e = size_t(r) * N + i;
+  const uint8_t* al = o.init_alive + size_t(r) * N;
+  const bool a = al[i] != 0;
+  int ids = 0;                                   // id-list place = number of initial vehicles in lower slots
+  for (int j = 0; j < i; ++j) ids += al[j] ? 1 : 0;
+  s.pos[e] = s.init_pos[e];
+  s.vel[e] = s.init_vel[e];
+  s.prev_vel[e] = s.init_vel[e];
+  s.accel[e] = T(0);
+  s.ctrl_state[e] = T(0);
+  s.lane[e] = a ? s.init_lane[e] : -1;
+  o.seq[e] = a ? ids : 0;
+  const int old_origin = o.origin[e];
+  const bool po_keep = s.env == FS_ENV_MERGE_PO;
+  o.origin[e] = a ? -1 - i : -1;
+  o.foll[e] = -1;
+  o.foll_h[e] = T(3.0e38);
+  // MergePOEnv never clears rl_veh (merge.py:223-231 resets only leader / follower): the vehicles it lists at the end
+  // of an episode stay listed into the next one -- an initial vehicle that is placed again keeps its place, every
+  // other entry is a vehicle that no longer exists (a ghost row until additional_command has removed it, subject to
+  // the skipping above).  A slot that an initial vehicle needs cannot also hold such a ghost: that entry is dropped.
+  {
+    const int old_ctl = o.ctl_seq[e];
+    const bool same_vehicle = a && old_origin == -1 - i;
+    o.ctl_seq[e] = (po_keep && old_ctl >= 0 && (same_vehicle || !a)) ? old_ctl : -1;
+  }
+  o.arrived_rl[e] = 0;
+  o.vmax[e] = s.sumo_max_speed[i];
+  s.last_lc[e] = -(1 << 30);
+  o.lead[e] = -1;
+  o.headway[e] = T(1000);
+  if (i < FS_MAX_INFLOWS) {
+    o.emitted[size_t(r) * FS_MAX_INFLOWS + i] = 0;
+    o.generated[size_t(r) * FS_MAX_INFLOWS + i] = 0;
+  }
+  if (i == 0) {
+    int total = 0;
+    for (int j = 0; j < N; ++j) total += al[j] ? 1 : 0;
+    int32_t* cnt = o.counters + size_t(r) * 8;
+    cnt[CNT_SIM_STEPS] = 1;
+    cnt[CNT_SEQ] = total;
+    for (int q = 2; q < 8; ++q)
+      if (!(q == CNT_CTL && s.env == FS_ENV_MERGE_PO)) cnt[q] = 0;      // (the join counter orders rl_veh: it goes on)
+    for (int q = 0; q < 20; ++q) o.arr_hist[size_t(r) * 20 + q] = 0;
+    s.time[r] = 0;
+    o.episode[r] += 1;                           // a new episode draws new entry lanes (the reference re-seeds SUMO)
+  }
+}
+
+// Env.reset of an open network (the replicas of `mask`, every replica without one)
 template <typename T>
 __global__ void k_reset_open(DevView<T> s, OpenView<T> o, const uint8_t* __restrict__ mask) {
   const int N = s.N;
@@ -1296,52 +1349,7 @@ __global__ void k_reset_open(DevView<T> s, OpenView<T> o, const uint8_t* __restr
   for (size_t e = size_t(blockIdx.x) * blockDim.x + threadIdx.x; e < n; e += size_t(gridDim.x) * blockDim.x) {
     const int r = int(e / N), i = int(e % N);
     if (mask != nullptr && mask[r] == 0) continue;
-    const uint8_t* al = o.init_alive + size_t(r) * N;
-    const bool a = al[i] != 0;
-    int ids = 0;                                   // id-list place = number of initial vehicles in lower slots
-    for (int j = 0; j < i; ++j) ids += al[j] ? 1 : 0;
-    s.pos[e] = s.init_pos[e];
-    s.vel[e] = s.init_vel[e];
-    s.prev_vel[e] = s.init_vel[e];
-    s.accel[e] = T(0);
-    s.ctrl_state[e] = T(0);
-    s.lane[e] = a ? s.init_lane[e] : -1;
-    o.seq[e] = a ? ids : 0;
-    const int old_origin = o.origin[e];
-    const bool po_keep = s.env == FS_ENV_MERGE_PO;
-    o.origin[e] = a ? -1 - i : -1;
-    o.foll[e] = -1;
-    o.foll_h[e] = T(3.0e38);
-    // MergePOEnv never clears rl_veh (merge.py:223-231 resets only leader / follower): the vehicles it lists at the end
-    // of an episode stay listed into the next one -- an initial vehicle that is placed again keeps its place, every
-    // other entry is a vehicle that no longer exists (a ghost row until additional_command has removed it, subject to
-    // the skipping above).  A slot that an initial vehicle needs cannot also hold such a ghost: that entry is dropped.
-    {
-      const int old_ctl = o.ctl_seq[e];
-      const bool same_vehicle = a && old_origin == -1 - i;
-      o.ctl_seq[e] = (po_keep && old_ctl >= 0 && (same_vehicle || !a)) ? old_ctl : -1;
-    }
-    o.arrived_rl[e] = 0;
-    o.vmax[e] = s.sumo_max_speed[i];
-    s.last_lc[e] = -(1 << 30);
-    o.lead[e] = -1;
-    o.headway[e] = T(1000);
-    if (i < FS_MAX_INFLOWS) {
-      o.emitted[size_t(r) * FS_MAX_INFLOWS + i] = 0;
-      o.generated[size_t(r) * FS_MAX_INFLOWS + i] = 0;
-    }
-    if (i == 0) {
-      int total = 0;
-      for (int j = 0; j < N; ++j) total += al[j] ? 1 : 0;
-      int32_t* cnt = o.counters + size_t(r) * 8;
-      cnt[CNT_SIM_STEPS] = 1;
-      cnt[CNT_SEQ] = total;
-      for (int q = 2; q < 8; ++q)
-        if (!(q == CNT_CTL && s.env == FS_ENV_MERGE_PO)) cnt[q] = 0;      // (the join counter orders rl_veh: it goes on)
-      for (int q = 0; q < 20; ++q) o.arr_hist[size_t(r) * 20 + q] = 0;
-      s.time[r] = 0;
-      o.episode[r] += 1;                           // a new episode draws new entry lanes (the reference re-seeds SUMO)
-    }
+    reset_open_slot(s, o, r, i);
   }
   // replicas with fewer than FS_MAX_INFLOWS slots: the remaining inflow counters
   if (N < FS_MAX_INFLOWS)

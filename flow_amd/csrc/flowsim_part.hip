@@ -9,6 +9,7 @@ namespace fsim {
 #if defined(FS_PART_QUEUE)
 template int Sim<FS_PART_T>::launch_queue(const StepArgs&);
 template int Sim<FS_PART_T>::launch_dropq(const StepArgs&);
+template int Sim<FS_PART_T>::launch_policy_queue(const fs::PolicyView&, int, int, float*, float*, float*, float*, uint8_t*);
 #elif defined(FS_PART_WIDE)
 template int Sim<FS_PART_T>::launch_wide<FS_PART_WIDE>(const StepArgs&);
 #elif defined(FS_PART_SEG)

@@ -36,8 +36,9 @@ struct alignas(16) PolicyLds {
   // the same LDS banks: a 16-way conflict on every read, measured 1.4 -> 0.9 G)
   float w_hid[2][16][16][4];
   float w_in[32][4];       // layer 1: [unit][input (3, padded)]
-  // layer 1 of a WIDE observation (in_dim = 2 * half <= 32, e.g. AccelEnv's speeds and positions): input i < half is the
-  // first value of lane i, input half + i its second value -- the layout and the summation order of a hidden layer
+  // layer 1 of a WIDE observation (in_dim <= 32, e.g. AccelEnv's speeds and positions; half = ceil(in_dim / 2)): input
+  // i < half is the first value of lane i, input half + i < in_dim its second value -- the layout and the summation order
+  // of a hidden layer (an odd in_dim leaves the second value of lane half - 1 at zero)
   float w_wide[16][16][4];
   float b[3][32];
   float w_out[2][32];
@@ -45,17 +46,20 @@ struct alignas(16) PolicyLds {
   float obs[4][4][4];      // [wave of the block][row][value]: the observation of a replica, handed from its RL lane to the row
 };
 
+// the inputs of a WIDE observation per lane: lane j < half holds inputs j and half + j (the latter if < in_dim)
+__host__ __device__ __forceinline__ int policy_half(int in_dim) { return (in_dim + 1) >> 1; }
+
 __device__ __forceinline__ void policy_load(const PolicyView& pv, PolicyLds* L, int tid, int nthreads) {
   // weights -> LDS (once per launch); layout of pv.w: [W1 32x3][b1 32][W2 32x32][b2][W3 32x32][b3][Wout n_out x 32][bout]
   const float* p = pv.w;
   const bool wide = pv.in_dim > 4;
   for (int e = tid; e < 32 * 4; e += nthreads) L->w_in[e / 4][e % 4] = (!wide && (e % 4) < pv.in_dim) ? p[(e / 4) * pv.in_dim + (e % 4)] : 0.0f;
   {
-    const int half = pv.in_dim >> 1;
+    const int half = policy_half(pv.in_dim);
     for (int e = tid; e < 32 * 32; e += nthreads) {
       const int u = e / 32, ip = e % 32;                       // ip: place of the input in the hidden-layer order
       const int i = ip < 16 ? ip : half + (ip - 16);           // ... and its index in the observation
-      const bool used = wide && (ip & 15) < half;
+      const bool used = wide && (ip & 15) < half && i < pv.in_dim;
       L->w_wide[ip >> 1][u & 15][(ip & 1) * 2 + (u >> 4)] = used ? p[u * pv.in_dim + i] : 0.0f;
     }
   }
@@ -227,28 +231,54 @@ __device__ __forceinline__ void policy_sample_agent(const PolicyView& pv, uint32
   else policy_sample(pv, replica, ctr, mu, log_std, action, logp, nullptr, uint32_t(c));
 }
 
+// an agent without a vehicle (FS_ENV_MERGE_MA: its column's RL slot is empty): no command (fs_step_dev reads NaN as
+// "no action for this vehicle"), log-probability 0
+__device__ __forceinline__ float policy_no_action() { return __builtin_nanf(""); }
+
+// the agents present in the replica's state (FS_ENV_MERGE_MA: agent c is present when the RL slot of column c holds a
+// vehicle), as a mask over the columns; every agent of the other heads (slot_lane == NULL).  The 16 lanes of row j test
+// slots j, j + 16, ...
+template <int ROW>
+__device__ __forceinline__ unsigned long long policy_present(const int* slot_lane, const int* slot_ctrl,
+                                                             const int* slot_rl, int N, int rr, int j) {
+  if (slot_lane == nullptr) return ~0ull;
+  unsigned lo = 0u, hi = 0u;
+  for (int i = j; i < N; i += ROW) {
+    if (slot_ctrl[i] != FS_CTRL_RL || slot_lane[size_t(rr) * N + i] < 0) continue;
+    const int c = slot_rl[i] & 63;
+    lo |= c < 32 ? 1u << c : 0u;
+    hi |= c >= 32 ? 1u << (c - 32) : 0u;
+  }
+  return (static_cast<unsigned long long>(seg_or<ROW>(hi)) << 32) | seg_or<ROW>(lo);
+}
+
 // eager form: actions and log-probabilities for the observations obs [R, n_ag * in_dim] of n_ag agents sharing the policy
 // (n_ag = 1: one RL vehicle); act / logp [R, n_ag].  A row of 16 lanes is one replica and evaluates its agents in turn:
 // agent c draws from column 0x40000000 + c at the replica's counter, which advances by ONE per call.  (One row per
 // (replica, agent) would let a replica's agents straddle two waves, and the row that advances the counter could run
-// before a row that still has to read it.)
+// before a row that still has to read it.)  slot_lane / slot_ctrl / slot_rl (FS_ENV_MERGE_MA, else NULL): the handle's
+// current routes [R, N] and its slots' controllers and columns, which say which agents are present (policy_present);
+// an absent agent gets policy_no_action() and log-probability 0.
 template <int ROW>     // (a template so that every object of the library may include this header)
 __global__ __launch_bounds__(256) void k_policy_act(PolicyView pv, int R, int n_ag, uint32_t rep0,
                                                     const float* __restrict__ obs, float* __restrict__ act,
-                                                    float* __restrict__ logp) {
+                                                    float* __restrict__ logp, const int* __restrict__ slot_lane,
+                                                    const int* __restrict__ slot_ctrl, const int* __restrict__ slot_rl,
+                                                    int N) {
   __shared__ PolicyLds L;
   policy_load(pv, &L, threadIdx.x, blockDim.x);
   const int lane = threadIdx.x & 63, j = lane & 15;
   const int r = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
   const int rr = r < R ? r : R - 1;
   const uint32_t c0 = pv.ctr[rr];
+  const unsigned long long present = policy_present<ROW>(slot_lane, slot_ctrl, slot_rl, N, rr, j);
 #pragma unroll 1
   for (int c = 0; c < n_ag; ++c) {
     const float* o = obs + (size_t(rr) * n_ag + c) * pv.in_dim;
     float mu, ls;
     if (pv.in_dim > 4) {                                   // (wave-uniform) two values per lane: inputs j and half + j
-      const int half = pv.in_dim >> 1;
-      const float ia = j < half ? o[j] : 0.0f, ib = j < half ? o[half + j] : 0.0f;
+      const int half = policy_half(pv.in_dim);
+      const float ia = j < half ? o[j] : 0.0f, ib = (j < half && half + j < pv.in_dim) ? o[half + j] : 0.0f;
       policy_eval<ROW, true>(pv, &L, j, ia, ib, 0.0f, mu, ls);
     } else {
       policy_eval<ROW>(pv, &L, j, o[0], pv.in_dim > 1 ? o[1] : 0.0f, pv.in_dim > 2 ? o[2] : 0.0f, mu, ls);
@@ -256,8 +286,9 @@ __global__ __launch_bounds__(256) void k_policy_act(PolicyView pv, int R, int n_
     float a, lp;
     policy_sample(pv, rep0 + uint32_t(rr), c0, mu, ls, a, lp, nullptr, uint32_t(c));
     if (r < R && j == 0) {
-      act[size_t(r) * n_ag + c] = a;
-      logp[size_t(r) * n_ag + c] = lp;
+      const bool here = ((present >> (c & 63)) & 1ull) != 0ull;
+      act[size_t(r) * n_ag + c] = here ? a : policy_no_action();
+      logp[size_t(r) * n_ag + c] = here ? lp : 0.0f;
     }
   }
   if (r < R && j == 0) pv.ctr[r] = c0 + 1u;

@@ -64,12 +64,26 @@ struct alignas(16) QueueRow {
   int ctrl, speed_mode, rl_index;
 };
 
-template <bool NOISE, bool ACT>
+// POLICY (k_merge_policy: fs_policy_rollout_dev): one policy shared by the agents, in the loop.  Agent c is the RL slot
+// of column c (rl_index c); it is present when that slot holds a vehicle in the state its observation is taken from.
+// Per env step the head's five features of every present agent wait in LDS by column; the present columns, compacted
+// with a ballot, go four to a pass onto the wave's 16-lane rows, and each row runs policy_eval / policy_sample (what
+// k_policy_act runs: agent c draws from column 0x40000000 + c at the replica's counter, which advances by one per step).
+// The sampled actions go to act_out / logp_out [K, R, n_ag] and into the LDS action row the ACT path reads (an absent
+// agent: policy_no_action(), log-probability 0).  obs [K+1, R, 5 n_ag]: obs[0] is the state the launch starts from.
+// reset_done: a replica whose episode ended (the horizon: crash is always 0 here) is reset in place as fs_reset_dev(done)
+// resets it (reset_open_slot, the halves of FS_F16S, update(reset=True)'s follower entries) and set up again from HBM as
+// the next launch would be; obs[k + 1] is then the observation of the new episode.  So a fragment equals
+// K x (fs_policy_act_dev, fs_step_dev, fs_reset_dev(done)) bit for bit (tests/test_policy_merge_gpu.py).
+template <bool NOISE, bool ACT, bool POLICY = false>
 __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<float> o, QueueConsts qc, int num_steps,
                                                     const float* __restrict__ actions, size_t act_stride,
                                                     float* __restrict__ obs, float* __restrict__ rew,
-                                                    uint8_t* __restrict__ done, int obs_every_step) {
+                                                    uint8_t* __restrict__ done, int obs_every_step, PolicyView pv,
+                                                    float* __restrict__ act_out, float* __restrict__ logp_out,
+                                                    int reset_done) {
   using T = float;
+  static_assert(!POLICY || ACT, "k_merge_queue: the policy's actions take the ACT path");
   const T BIGV = 3.0e38f;
   const int lane = threadIdx.x;
   const int r = blockIdx.x;                       // one replica per wave (grid = R)
@@ -82,8 +96,12 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
   __shared__ QueueRow rows[64];
   __shared__ float scr_f[64], scr_g[64], act_row[64];
   __shared__ int scr_i[64], scr_j[64];
+  __shared__ PolicyLds PL;                        // (POLICY) the network
+  __shared__ float feat[5][64], lp_row[64];       // (POLICY) the features by column, the log-probabilities of a step
+  __shared__ int pcol[64];                        // (POLICY) the present columns, compacted
   OpenTabs<T, true> tb;
   tb.load(o, lane, false, &tabs_mem);
+  if constexpr (POLICY) policy_load(pv, &PL, lane, 64);
 
   // ---- the slot tables as LDS rows --------------------------------------------------------------------------
   {
@@ -106,14 +124,10 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
   const int slot_rl_index = s.rl_index[li];
   __syncthreads();
 
-  // ---- replica scalars (one replica per wave: all of them wave-uniform) ------------------------------------
-  int tcount = s.time[r];
-  uint32_t nctr = s.noise_ctr[r];
+  // ---- replica scalars (one replica per wave: all of them wave-uniform; load_state below) -------------------
+  int tcount, sim_steps, seq_ctr, n_arr, n_dep, tot_arr, tot_dep, emit_l;
+  uint32_t nctr;
   int32_t* cnt = o.counters + size_t(r) * 8;
-  int sim_steps = cnt[CNT_SIM_STEPS], seq_ctr = cnt[CNT_SEQ];
-  int n_arr = cnt[CNT_ARRIVED], n_dep = cnt[CNT_DEPARTED], tot_arr = cnt[CNT_TOTAL_ARRIVED],
-      tot_dep = cnt[CNT_TOTAL_DEPARTED];
-  int emit_l = (lane < FS_MAX_INFLOWS) ? o.emitted[size_t(r) * FS_MAX_INFLOWS + lane] : 0;
   const bool my_flow = lane < o.n_inflows;             // lane f keeps inflow f's schedule (M2)
   const double my_per = my_flow ? o.flow_tab_d[lane] : 0.0;
   const double my_begin = my_flow ? o.flow_tab_d[64 + lane] : 0.0, my_end = my_flow ? o.flow_tab_d[128 + lane] : 0.0;
@@ -126,11 +140,11 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
   const int f_typ = o.flow_tab_i[fl], f_route = o.flow_tab_i[64 + fl];
   // inflows that are due but found no room (M3: retried every sub-step): bit f.  The sub-step watches their gap
   // itself -- one test for all of them -- and runs the insertion code only when one of them fits
-  unsigned long long pend_m = 0ull;
+  unsigned long long pend_m;
   int tlA = -1, tlU = -1;                              // lane of the vehicle an insertion on route 0 / 1 is checked against
   // the first sub-step index n (n = sim_steps - 1 of the sub-step's `now = n * sim_step`) at which some inflow is due:
   // the schedule is float64 (M2); the hot loop compares integers
-  int due_n = 0;
+  int due_n;
   const double inv_dt_d = 1.0 / o.dt_d;
   auto due_index = [&](double t) -> int {
     if (!(t > 0.0)) return 0;
@@ -147,30 +161,46 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
     const bool open_me = my_flow && (due_t <= my_end) && (my_number < 0 || k_me < my_number);
     return open_me ? due_index(due_t) : 0x7fffffff;
   };
-  int my_due = my_due_of(emit_l);
+  int my_due;
 
   // ---- the vehicle this lane holds (slot view first: lane i = slot i) ---------------------------------------
-  T x = s.pos[base + li];
-  T v = s.vel[base + li];
-  if (s.st16 != nullptr) state16_load(s, base + li, x, v);
-  int route = slot_ok ? s.lane[base + li] : -1;
-  int lab = lane;
-  int seq = o.seq[base + li];
-  int origin = o.origin[base + li];
-  int foll = o.foll[base + li];
-  T foll_h = o.foll_h[base + li];
-  T prev_v = s.prev_vel[base + li], last_acc = s.accel[base + li];
-  T vmax = o.vmax[base + li];
-  float a_me = 0.0f;                                   // this step's action of my vehicle (ACT)
-  T g0 = 0.0f, g1 = 0.0f, g2 = 0.0f, g3 = 0.0f;        // the four draws of my vehicle's current Philox block (NOISE)
-  int nz_reload = 1;                                   // (wave-uniform) the block must be evaluated before the next draw
+  T x, v, foll_h, prev_v, last_acc, vmax;
+  int route, lab, seq, origin, foll;
+  float a_me;                                          // this step's action of my vehicle (ACT)
+  T g0, g1, g2, g3;                                    // the four draws of my vehicle's current Philox block (NOISE)
+  int nz_reload;                                       // (wave-uniform) the block must be evaluated before the next draw
   int nA = 0, n1 = 0, nD = 0;
-  unsigned long long alive_lab = __ballot(route >= 0);             // bit i: slot i holds a vehicle
-  unsigned long long arr_rl = 0ull;                                 // RL slots that arrived in the last sub-step
-  {
+  unsigned long long alive_lab;                        // bit i: slot i holds a vehicle
+  unsigned long long arr_rl;                           // RL slots that arrived in the last sub-step
+  // the replica's state from HBM: at launch start, and again after a reset inside the launch (POLICY)
+  auto load_state = [&]() {
+    tcount = s.time[r];
+    nctr = s.noise_ctr[r];
+    sim_steps = cnt[CNT_SIM_STEPS]; seq_ctr = cnt[CNT_SEQ];
+    n_arr = cnt[CNT_ARRIVED]; n_dep = cnt[CNT_DEPARTED]; tot_arr = cnt[CNT_TOTAL_ARRIVED]; tot_dep = cnt[CNT_TOTAL_DEPARTED];
+    emit_l = (lane < FS_MAX_INFLOWS) ? o.emitted[size_t(r) * FS_MAX_INFLOWS + lane] : 0;
+    pend_m = 0ull;
+    due_n = 0;
+    my_due = my_due_of(emit_l);
+    x = s.pos[base + li];
+    v = s.vel[base + li];
+    if (s.st16 != nullptr) state16_load(s, base + li, x, v);
+    route = slot_ok ? s.lane[base + li] : -1;
+    lab = lane;
+    seq = o.seq[base + li];
+    origin = o.origin[base + li];
+    foll = o.foll[base + li];
+    foll_h = o.foll_h[base + li];
+    prev_v = s.prev_vel[base + li]; last_acc = s.accel[base + li];
+    vmax = o.vmax[base + li];
+    a_me = 0.0f;
+    g0 = 0.0f; g1 = 0.0f; g2 = 0.0f; g3 = 0.0f;
+    nz_reload = 1;
+    alive_lab = __ballot(route >= 0);
     const int a0 = o.arrived_rl[base + li];
     arr_rl = __ballot(slot_ok && a0 != 0);
-  }
+  };
+  load_state();
 
   // launch constants the sub-step reads: in VGPRs (uniform values the compiler would otherwise keep in SGPRs it does
   // not have: k_steps_open's loop spills ~60 of them to VGPR lanes and reads them back with v_readlane)
@@ -570,17 +600,239 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
     FS_QA(0, q_ev0);
   };
 
+  // ---- get_state / compute_reward / done of the current state: obs_out -> orow (POLICY: and the features to LDS),
+  // rew_out -> rrow / drow ----------------------------------------------------------------------------------------
+  auto head = [&](bool obs_out, bool rew_out) {
+    FS_QT(q_hd0);
+    const bool isA = lane < nA, isU = lane >= 64 - n1, alive = isA | isU, uh = isU && lane == 63;
+    const bool has = ((mHas >> lane) & 1ull) != 0ull, k_rl = ((mKrl >> lane) & 1ull) != 0ull;
+    // the five features of my vehicle (flow/envs/multiagent/merge.py:108-140)
+    // Flow's coordinate of x (O5, route_lookup's arithmetic): both routes' tables are launch constants in registers
+    // -- five compares and selects each, no table walk through LDS (that walk was half of the head's time)
+    T fx;
+    {
+      T fxr[2];
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) {
+        T st = sg_st[rt][0], fs0 = sg_fs[rt][0], sl = sg_sl[rt][0];
+#pragma unroll
+        for (int q = 1; q < 6; ++q) {
+          const bool hit = x >= sg_st[rt][q];
+          st = hit ? sg_st[rt][q] : st;
+          fs0 = hit ? sg_fs[rt][q] : fs0;
+          sl = hit ? sg_sl[rt][q] : sl;
+        }
+        fxr[rt] = fs0 + sl * (x - st);
+      }
+      fx = route == 1 ? fxr[1] : fxr[0];
+    }
+    const T fx_up = dpp<DPP_WAVE_SHR1>(fx), fx_dn = dpp<DPP_WAVE_SHL1>(fx);
+    const T fx_t = read_lane(fx, td);
+    T fx_l = isA ? fx_up : fx_dn;
+    fx_l = uh ? fx_t : fx_l;
+    // ONE exchange hands everything the head needs by SLOT to the slots' lanes (the follower is a slot: which lane
+    // holds it now; the reward's sums run in slot order): four scatters, one wait, the reads, one wait -- a free slot's
+    // entry is stale and masked by `alive_lab` (the first version cleared and waited per value: fourteen LDS round trips)
+    const T dvt = v - s.target_velocity;
+    const bool use = alive && k_rl && has && (v > 0.0f);
+    const T t_headway = tmax(h / (use ? v : 1.0f), 0.0f);
+    const T term = tmin((t_headway - 1.0f) / 1.0f, 0.0f);
+    if (alive) {
+      scr_i[lab & 63] = lane;
+      scr_f[lab & 63] = s.evaluate ? v : dvt * dvt;
+      scr_g[lab & 63] = term;
+      scr_j[lab & 63] = use ? 1 : 0;
+    }
+    q_fence();
+    const bool slot_alive = ((alive_lab >> lane) & 1ull) != 0ull;
+    const int fo = alive ? foll : -1;
+    const int fl_ = scr_i[fo & 63];
+    const T sum_s_ = scr_f[lane], term_s_ = scr_g[lane];
+    const int use_s_ = scr_j[lane];
+    q_fence();
+    FS_QA(11, q_hd0);
+    FS_QT(q_h2);
+    const int fl = (fo >= 0 && ((alive_lab >> (fo & 63)) & 1ull) != 0ull) ? fl_ : -1;
+    const T sum_s = slot_alive ? sum_s_ : 0.0f, term_s = slot_alive ? term_s_ : 0.0f;
+    const int use_s = slot_alive ? use_s_ : 0;
+    T v_f = bperm(v, fl >= 0 ? fl : lane), h_f = bperm(h, fl >= 0 ? fl : lane);
+    if (fo >= 0 && fl < 0) {                          // a recorded follower that has left: its slot's values of record
+      v_f = s.vel[base + size_t(fo)];
+      h_f = 1000.0f;
+    }
+    const bool hl = alive && has;
+    const T this_speed = alive ? v : -1001.0f;
+    const T lead_speed = hl ? vl : s.max_speed;
+    const T lead_head = hl ? fx_l - fx - LEN : o.net_length;
+    const T follow_speed = fo >= 0 ? v_f : 0.0f;
+    const T follow_head = fo >= 0 ? h_f : o.net_length;
+    T f5[5];                                                        // (launch-constant divisors: the exact float64 route)
+    f5[0] = div_via_f64(this_speed, ms64, rc_ms64);
+    f5[1] = div_via_f64(lead_speed - this_speed, ms64, rc_ms64);
+    f5[2] = div_via_f64(lead_head, nl64, rc_nl64);
+    f5[3] = div_via_f64(this_speed - follow_speed, ms64, rc_ms64);
+    f5[4] = div_via_f64(follow_head, nl64, rc_nl64);
+    if (obs_out && alive && k_rl) {
+      const int col = rows[lab & 63].rl_index;
+#pragma unroll
+      for (int q = 0; q < 5; ++q) orow[5 * col + q] = f5[q];
+      if constexpr (POLICY) {                                       // the policy's input, by column
+#pragma unroll
+        for (int q = 0; q < 5; ++q) feat[q][col & 63] = f5[q];
+      }
+    }
+    if (obs_out && slot_is_rl && !((alive_lab >> lane) & 1ull)) {   // (slot view) an RL slot without a vehicle
+#pragma unroll
+      for (int q = 0; q < 5; ++q) orow[5 * slot_rl_index + q] = 0.0f;
+    }
+    FS_QA(12, q_h2);
+    FS_QT(q_h3);
+    if (!rew_out) return;
+    // reward (flow/envs/multiagent/merge.py:142-171 over rewards.desired_velocity), sums in SLOT order
+    const int n_alive = nA + n1;
+    T reward;
+    if (s.evaluate) {
+      const T sum_v = seg_sum<64>(sum_s);
+      reward = n_alive > 0 ? sum_v / T(n_alive) : 0.0f;
+    } else {
+      const T mc_lane = tb.template t_gather<TAB_MAX_COST>(n_alive & 63);
+      const T max_cost = n_alive < 64 ? mc_lane : o.max_cost_full;
+      const T cost = tsqrt(seg_sum<64>(sum_s));
+      T cost1 = tmax(max_cost - cost, 0.0f) / (max_cost + 1.1920928955078125e-07f);
+      const bool bad = (__ballot(alive && (v < -100.0f)) != 0ull) || n_alive == 0;
+      cost1 = bad ? 0.0f : cost1;
+      T cost2 = 0.0f;
+      for (unsigned long long u = __ballot(use_s != 0); u; u &= u - 1ull) cost2 = cost2 + read_lane(term_s, __ffsll((long long)u) - 1);
+      reward = tmax(cost1 + 0.1f * cost2, 0.0f);
+    }
+    FS_QA(13, q_h3);
+    if (lane == 0) {
+      *rrow = reward;
+      *drow = done_flag(tcount >= s.step_limit, false);          // multiagent/base.py:188-190: crash = 0
+    }
+    FS_QA(6, q_hd0);
+  };
+
+  uint32_t pctr = 0u;                                  // (POLICY) the replica's draw counter of the policy's stream
+  // ---- the state back to its slots (the end of a launch) ---------------------------------------------------------
+  auto store_state = [&]() {
+    const bool isA = lane < nA, isU = lane >= 64 - n1, alive = isA | isU, uh = isU && lane == 63;
+    const bool has = ((mHas >> lane) & 1ull) != 0ull;
+    const int lab_up = dpp_i<DPP_WAVE_SHR1>(lab), lab_dn = dpp_i<DPP_WAVE_SHL1>(lab);
+    const int lab_t = read_lane_i(lab, td);
+    int lab_l = isA ? lab_up : lab_dn;
+    lab_l = uh ? lab_t : lab_l;
+    if (alive) {
+      const size_t e = base + size_t(lab & 63);
+      if (s.st16 != nullptr) state16_store(s, e, x, v);
+      else { s.pos[e] = x; s.vel[e] = v; }
+      s.lane[e] = route;
+      s.prev_vel[e] = prev_v;
+      s.accel[e] = last_acc;
+      o.seq[e] = seq;
+      o.origin[e] = origin;
+      o.foll[e] = foll;
+      o.foll_h[e] = foll_h;
+      o.vmax[e] = vmax;
+      o.lead[e] = has ? lab_l : -1;
+      o.headway[e] = h;
+    }
+    if (slot_ok) o.arrived_rl[base + lane] = int((arr_rl >> lane) & 1ull);
+    if (lane == 0) {
+      if (POLICY) pv.ctr[r] = pctr;
+      s.time[r] = tcount;
+      s.noise_ctr[r] = nctr;
+      cnt[CNT_SIM_STEPS] = sim_steps;
+      cnt[CNT_SEQ] = seq_ctr;
+      cnt[CNT_ARRIVED] = n_arr;
+      cnt[CNT_DEPARTED] = n_dep;
+      cnt[CNT_TOTAL_ARRIVED] = tot_arr;
+      cnt[CNT_TOTAL_DEPARTED] = tot_dep;
+    }
+    if (lane < FS_MAX_INFLOWS) o.emitted[size_t(r) * FS_MAX_INFLOWS + lane] = emit_l;
+  };
+  // ---- (POLICY) the end of one launch and the start of the next, inside the launch: `reset` -- the episode ended --
+  // does what fs_reset_dev(done) does (k_reset_open, k_state16_pack, update(reset=True)'s follower entries); otherwise
+  // (FS_F16S) the state goes to its slots -- the halves are the state of record -- and comes back as the next launch loads it
+  auto restart = [&](bool reset) {
+    __threadfence_block();                           // (the stores of retire() land before the slots are written again)
+    if (reset) {
+      if (lane < N) {
+        reset_open_slot(s, o, r, lane);
+        if (s.st16 != nullptr) state16_store(s, base + lane, s.pos[base + lane], s.vel[base + lane]);
+      } else if (lane < FS_MAX_INFLOWS) {
+        o.emitted[size_t(r) * FS_MAX_INFLOWS + lane] = 0;
+        o.generated[size_t(r) * FS_MAX_INFLOWS + lane] = 0;
+      }
+      if (lane == 0) s.noise_ctr[r] = nctr;          // (the reset keeps the noise stream going)
+    } else {
+      store_state();
+    }
+    __threadfence_block();
+    load_state();
+    resort();
+    classes(true);
+    T h_n, vl_n, foll_h_n;
+    int foll_n;
+    snapshot(dpp<DPP_WAVE_SHR1>(x), dpp<DPP_WAVE_SHL1>(x), h_n, vl_n, foll_n, foll_h_n);
+    h = h_n;
+    vl = vl_n;
+    if (reset) {                                     // (a launch start registers no follower; update(reset=True) does)
+      foll = foll_n;
+      foll_h = foll_h_n;
+    }
+  };
+
   asm volatile("" :: "v"(x), "v"(v), "v"(route), "v"(seq), "v"(origin), "v"(foll), "v"(foll_h), "v"(prev_v), "v"(last_acc), "v"(vmax));
 #ifdef FS_QDIAG
   const unsigned long long dg_start = __builtin_readcyclecounter();
 #endif
+  if constexpr (POLICY) {
+    pctr = pv.ctr[r];
+    head(true, false);                                 // obs[0]: the state the fragment starts from
+    orow += step_rows * obs_dim;
+  }
   // (the action row of a step is loaded one step ahead: read where it is used, it was an L2 / HBM round trip at the top of
   // every step; the load itself is unconditional -- a select on its value would wait for it at once)
   const int act_lane = lane < s.num_rl ? lane : 0;
   float a_pref = 0.0f;
-  if (ACT && num_steps > 0) a_pref = actions[size_t(r) * s.num_rl + act_lane];
+  if (ACT && !POLICY && num_steps > 0) a_pref = actions[size_t(r) * s.num_rl + act_lane];
   for (int step = 0; step < num_steps; ++step) {
-    if (ACT) {                                         // the step's action row, by RL column, in LDS
+    if constexpr (POLICY) {
+      // ---- the policy: the present agents' actions, by column, into the action row ------------------------------
+      const int n_ag = s.num_rl;
+      const unsigned long long pm = __ballot(slot_is_rl && ((alive_lab >> lane) & 1ull));   // (slot view) present RL slots
+      const int np = __popcll(pm);
+      if ((pm >> lane) & 1ull) pcol[__popcll(pm & ((1ull << lane) - 1ull))] = slot_rl_index & 63;
+      act_row[lane] = lane < n_ag ? policy_no_action() : 0.0f;
+      lp_row[lane] = 0.0f;
+      q_fence();
+      constexpr int HALF = 3;                          // policy_half(5): lane j < 3 holds inputs j and 3 + j (< 5)
+      const int prow = lane >> 4, j = lane & 15;
+      for (int p0 = 0; p0 < np; p0 += 4) {             // (wave-uniform) four agents per pass, one per 16-lane row
+        const int idx = p0 + prow;
+        const bool rv = idx < np;
+        const int col = pcol[rv ? idx : p0];
+        const float ia = j < HALF ? feat[j < HALF ? j : 0][col] : 0.0f;
+        const float ib = HALF + j < 5 ? feat[HALF + j < 5 ? HALF + j : 0][col] : 0.0f;
+        float mu, ls, a, lp;
+        policy_eval<16, true>(pv, &PL, j, ia, ib, 0.0f, mu, ls);
+        policy_sample(pv, s.rep0 + uint32_t(r), pctr, mu, ls, a, lp, nullptr, uint32_t(col));
+        if (rv && j == 0) {
+          act_row[col] = a;
+          lp_row[col] = lp;
+        }
+      }
+      q_fence();
+      if (lane < n_ag) {
+        const size_t e = (size_t(step) * s.R + r) * n_ag + lane;
+        act_out[e] = act_row[lane];
+        logp_out[e] = lp_row[lane];
+      }
+      pctr += 1u;
+      a_me = act_row[rl_col & 63];
+      q_fence();
+    } else if (ACT) {                                  // the step's action row, by RL column, in LDS
       act_row[lane] = lane < s.num_rl ? a_pref : 0.0f;
       q_fence();
       a_me = act_row[rl_col & 63];
@@ -710,114 +962,23 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
 
     // ---- get_state / compute_reward / done ------------------------------------------------------------------
     const bool emit = obs_every_step || (step == num_steps - 1);
-    FS_QT(q_hd0);
     if (emit) {
-      const bool isA = lane < nA, isU = lane >= 64 - n1, alive = isA | isU, uh = isU && lane == 63;
-      const bool has = ((mHas >> lane) & 1ull) != 0ull, k_rl = ((mKrl >> lane) & 1ull) != 0ull;
-      // the five features of my vehicle (flow/envs/multiagent/merge.py:108-140)
-      // Flow's coordinate of x (O5, route_lookup's arithmetic): both routes' tables are launch constants in registers
-      // -- five compares and selects each, no table walk through LDS (that walk was half of the head's time)
-      T fx;
-      {
-        T fxr[2];
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt) {
-          T st = sg_st[rt][0], fs0 = sg_fs[rt][0], sl = sg_sl[rt][0];
-#pragma unroll
-          for (int q = 1; q < 6; ++q) {
-            const bool hit = x >= sg_st[rt][q];
-            st = hit ? sg_st[rt][q] : st;
-            fs0 = hit ? sg_fs[rt][q] : fs0;
-            sl = hit ? sg_sl[rt][q] : sl;
-          }
-          fxr[rt] = fs0 + sl * (x - st);
+      // (POLICY) the episode ended (the horizon; crash is always 0): reset in place, the observation is the new
+      // episode's.  FS_F16S: eager stepping rounds the state through halves between steps, and fs_reset_dev(done)
+      // observes every replica again from what was stored -- so does the fragment
+      const bool fin = POLICY && reset_done && tcount >= s.step_limit;
+      const bool again = POLICY && (fin || s.st16 != nullptr);
+      head(!again, true);
+      if constexpr (POLICY) {
+        if (again) {
+          restart(fin);
+          head(true, false);
         }
-        fx = route == 1 ? fxr[1] : fxr[0];
-      }
-      const T fx_up = dpp<DPP_WAVE_SHR1>(fx), fx_dn = dpp<DPP_WAVE_SHL1>(fx);
-      const T fx_t = read_lane(fx, td);
-      T fx_l = isA ? fx_up : fx_dn;
-      fx_l = uh ? fx_t : fx_l;
-      // ONE exchange hands everything the head needs by SLOT to the slots' lanes (the follower is a slot: which lane
-      // holds it now; the reward's sums run in slot order): four scatters, one wait, the reads, one wait -- a free slot's
-      // entry is stale and masked by `alive_lab` (the first version cleared and waited per value: fourteen LDS round trips)
-      const T dvt = v - s.target_velocity;
-      const bool use = alive && k_rl && has && (v > 0.0f);
-      const T t_headway = tmax(h / (use ? v : 1.0f), 0.0f);
-      const T term = tmin((t_headway - 1.0f) / 1.0f, 0.0f);
-      if (alive) {
-        scr_i[lab & 63] = lane;
-        scr_f[lab & 63] = s.evaluate ? v : dvt * dvt;
-        scr_g[lab & 63] = term;
-        scr_j[lab & 63] = use ? 1 : 0;
-      }
-      q_fence();
-      const bool slot_alive = ((alive_lab >> lane) & 1ull) != 0ull;
-      const int fo = alive ? foll : -1;
-      const int fl_ = scr_i[fo & 63];
-      const T sum_s_ = scr_f[lane], term_s_ = scr_g[lane];
-      const int use_s_ = scr_j[lane];
-      q_fence();
-      FS_QA(11, q_hd0);
-      FS_QT(q_h2);
-      const int fl = (fo >= 0 && ((alive_lab >> (fo & 63)) & 1ull) != 0ull) ? fl_ : -1;
-      const T sum_s = slot_alive ? sum_s_ : 0.0f, term_s = slot_alive ? term_s_ : 0.0f;
-      const int use_s = slot_alive ? use_s_ : 0;
-      T v_f = bperm(v, fl >= 0 ? fl : lane), h_f = bperm(h, fl >= 0 ? fl : lane);
-      if (fo >= 0 && fl < 0) {                          // a recorded follower that has left: its slot's values of record
-        v_f = s.vel[base + size_t(fo)];
-        h_f = 1000.0f;
-      }
-      const bool hl = alive && has;
-      const T this_speed = alive ? v : -1001.0f;
-      const T lead_speed = hl ? vl : s.max_speed;
-      const T lead_head = hl ? fx_l - fx - LEN : o.net_length;
-      const T follow_speed = fo >= 0 ? v_f : 0.0f;
-      const T follow_head = fo >= 0 ? h_f : o.net_length;
-      T f5[5];                                                        // (launch-constant divisors: the exact float64 route)
-      f5[0] = div_via_f64(this_speed, ms64, rc_ms64);
-      f5[1] = div_via_f64(lead_speed - this_speed, ms64, rc_ms64);
-      f5[2] = div_via_f64(lead_head, nl64, rc_nl64);
-      f5[3] = div_via_f64(this_speed - follow_speed, ms64, rc_ms64);
-      f5[4] = div_via_f64(follow_head, nl64, rc_nl64);
-      if (alive && k_rl) {
-        const int col = rows[lab & 63].rl_index;
-#pragma unroll
-        for (int q = 0; q < 5; ++q) orow[5 * col + q] = f5[q];
-      }
-      if (slot_is_rl && !((alive_lab >> lane) & 1ull)) {              // (slot view) an RL slot without a vehicle
-#pragma unroll
-        for (int q = 0; q < 5; ++q) orow[5 * slot_rl_index + q] = 0.0f;
-      }
-      FS_QA(12, q_h2);
-      FS_QT(q_h3);
-      // reward (flow/envs/multiagent/merge.py:142-171 over rewards.desired_velocity), sums in SLOT order
-      const int n_alive = nA + n1;
-      T reward;
-      if (s.evaluate) {
-        const T sum_v = seg_sum<64>(sum_s);
-        reward = n_alive > 0 ? sum_v / T(n_alive) : 0.0f;
-      } else {
-        const T mc_lane = tb.template t_gather<TAB_MAX_COST>(n_alive & 63);
-        const T max_cost = n_alive < 64 ? mc_lane : o.max_cost_full;
-        const T cost = tsqrt(seg_sum<64>(sum_s));
-        T cost1 = tmax(max_cost - cost, 0.0f) / (max_cost + 1.1920928955078125e-07f);
-        const bool bad = (__ballot(alive && (v < -100.0f)) != 0ull) || n_alive == 0;
-        cost1 = bad ? 0.0f : cost1;
-        T cost2 = 0.0f;
-        for (unsigned long long u = __ballot(use_s != 0); u; u &= u - 1ull) cost2 = cost2 + read_lane(term_s, __ffsll((long long)u) - 1);
-        reward = tmax(cost1 + 0.1f * cost2, 0.0f);
-      }
-      FS_QA(13, q_h3);
-      if (lane == 0) {
-        *rrow = reward;
-        *drow = done_flag(tcount >= s.step_limit, false);          // multiagent/base.py:188-190: crash = 0
       }
       orow += step_rows * obs_dim;
       rrow += step_rows;
       drow += step_rows;
     }
-    FS_QA(6, q_hd0);
   }
 #ifdef FS_QDIAG
   dg_t[7] = __builtin_readcyclecounter() - dg_start;
@@ -831,41 +992,7 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
 
   // ---- the state back to its slots -----------------------------------------------------------------------------
   __threadfence();
-  {
-    const bool isA = lane < nA, isU = lane >= 64 - n1, alive = isA | isU, uh = isU && lane == 63;
-    const bool has = ((mHas >> lane) & 1ull) != 0ull;
-    const int lab_up = dpp_i<DPP_WAVE_SHR1>(lab), lab_dn = dpp_i<DPP_WAVE_SHL1>(lab);
-    const int lab_t = read_lane_i(lab, td);
-    int lab_l = isA ? lab_up : lab_dn;
-    lab_l = uh ? lab_t : lab_l;
-    if (alive) {
-      const size_t e = base + size_t(lab & 63);
-      if (s.st16 != nullptr) state16_store(s, e, x, v);
-      else { s.pos[e] = x; s.vel[e] = v; }
-      s.lane[e] = route;
-      s.prev_vel[e] = prev_v;
-      s.accel[e] = last_acc;
-      o.seq[e] = seq;
-      o.origin[e] = origin;
-      o.foll[e] = foll;
-      o.foll_h[e] = foll_h;
-      o.vmax[e] = vmax;
-      o.lead[e] = has ? lab_l : -1;
-      o.headway[e] = h;
-    }
-    if (slot_ok) o.arrived_rl[base + lane] = int((arr_rl >> lane) & 1ull);
-    if (lane == 0) {
-      s.time[r] = tcount;
-      s.noise_ctr[r] = nctr;
-      cnt[CNT_SIM_STEPS] = sim_steps;
-      cnt[CNT_SEQ] = seq_ctr;
-      cnt[CNT_ARRIVED] = n_arr;
-      cnt[CNT_DEPARTED] = n_dep;
-      cnt[CNT_TOTAL_ARRIVED] = tot_arr;
-      cnt[CNT_TOTAL_DEPARTED] = tot_dep;
-    }
-    if (lane < FS_MAX_INFLOWS) o.emitted[size_t(r) * FS_MAX_INFLOWS + lane] = emit_l;
-  }
+  store_state();
 }
 
 }  // namespace fs

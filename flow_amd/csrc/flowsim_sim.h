@@ -783,6 +783,8 @@ struct Sim : SimBase {
 
   // ---- the launches, one per kernel family: flowsim_launch.h, compiled into the parts (flowsim_part.hip) ----
   int launch_queue(const StepArgs& a);       // float32 (the queue part)
+  int launch_policy_queue(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act, float* logp,
+                          float* rew, uint8_t* done);    // float32 (the queue part): the multi-agent merge's policy
   int launch_dropq(const StepArgs& a);       // float32 (the queue part)
   template <int W>
   int launch_wide(const StepArgs& a);        // one workgroup of W waves per replica
@@ -841,7 +843,8 @@ struct Sim : SimBase {
 
   // policy in the loop (flowsim_policy.h; flowsim_launch.h): the eager policy, the fused policy + step kernels of rings
   // (rows of 16 lanes: 18..32 vehicles) and of segment-table loops (the figure eight: up to 16 vehicles); n_ag agents
-  // share the policy on the multi-agent heads (MultiAgentWaveAttenuationPOEnv on rings, MultiAgentAccelPOEnv on loops)
+  // share the policy on the multi-agent heads (MultiAgentWaveAttenuationPOEnv on rings, MultiAgentAccelPOEnv on loops,
+  // MultiAgentMergePOEnv with its actions applied on the merge's queue kernel: k_merge_queue<POLICY>)
   int launch_policy_act(const fs::PolicyView& pv, int n_ag, const float* obs_in, float* act, float* logp);
   int launch_policy_row16(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act, float* logp,
                           float* rew, uint8_t* done);
@@ -857,10 +860,22 @@ struct Sim : SimBase {
     if (pol->num_hidden < 1 || pol->num_hidden > 3 || pol->hidden_width != 32 || pol->activation != 0)
       why = "fs_policy model (1..3 hidden layers of 32 tanh units)";
     else if (!pol->weights_dev) why = "fs_policy.weights_dev (NULL)";
-    else if (ma) {                                       // one policy shared by the num_rl agents of a replica
-      if (dv.env == FS_ENV_MERGE_MA)
-        why = "env (FS_ENV_MERGE_MA: the merge's agents enter and leave the network; capture single steps instead)";
+    else if (dv.env == FS_ENV_MERGE_MA) {                // agent c: the RL slot of column c, present while it holds a vehicle
+      if (!ov.ma_apply_actions)
+        why = "env (FS_ENV_MERGE_MA with ma_apply_actions = 0: the shipped MultiAgentMergePOEnv never applies an action, "
+              "so actions never reach the simulator; roll out open loop instead)";
       else if (!std::is_same<T, float>::value || mixed)
+        why = "precision (the multi-agent merge is FS_F32 / FS_F16S only: FS_MIXED / FS_F64 handles are not built)";
+      else if (dv.num_rl < 1 || pol->obs_dim * dv.num_rl != obs_dim)
+        why = "fs_policy.obs_dim (one agent's block: fs_obs_dim / num_rl)";
+      else if (!queue_ok(StepArgs{num_steps > 0 ? num_steps : 1, nullptr, nullptr, 0, obs, rew, done, 1}))
+        why = "configuration (what k_merge_queue steps, Sim::queue_ok: IDM / RL / Sim slots without fail-safes, one "
+              "vehicle length, Euler, scheduled inflows only, FLOWSIM_NO_QUEUE unset)";
+      else if (obs != nullptr && reset_done && cfg.warmup_steps != 0)
+        why = "configuration (resets inside a fragment: warmup_steps = 0)";
+    }
+    else if (ma) {                                       // one policy shared by the num_rl agents of a replica
+      if (!std::is_same<T, float>::value || mixed)
         why = "precision (the multi-agent heads are float32 only: FS_MIXED / FS_F64 handles are not built)";
       else if (!loop && dv.env != FS_ENV_WAVE_ATTENUATION_PO_MA)
         why = "env (FS_ENV_ACCEL_PO_MA on a ring: rings take MultiAgentWaveAttenuationPOEnv)";
@@ -917,6 +932,9 @@ struct Sim : SimBase {
     pv.seed_lo = uint32_t(pol->seed & 0xFFFFFFFFull);
     pv.seed_hi = uint32_t(pol->seed >> 32);
     if (obs == nullptr) return launch_policy_act(pv, ma ? dv.num_rl : 1, obs_in, act, logp);      // eager: the policy alone
+    if constexpr (std::is_same<T, float>::value) {
+      if (dv.env == FS_ENV_MERGE_MA) return launch_policy_queue(pv, num_steps, reset_done, obs, act, logp, rew, done);
+    }
     if (loop) return launch_policy_loop16(pv, num_steps, reset_done, obs, act, logp, rew, done);
     return launch_policy_row16(pv, num_steps, reset_done, obs, act, logp, rew, done);
   }

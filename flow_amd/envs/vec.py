@@ -278,7 +278,11 @@ class VecFlowEnv(object):
         multi-agent ring (MultiAgentWaveAttenuationPOEnv) and figure eight (MultiAgentAccelPOEnv), whose ``num_rl``
         agents share ``policy`` (its input: one agent's observation block, ``obs_dim / num_rl``): ``actions`` and
         ``logp`` are then ``[K, R, num_rl]`` (column c: agent c, the RL vehicle of rl_index c) and ``rew`` is the shared
-        reward.  ``capture`` serves every other environment / model."""
+        reward.  The multi-agent merge (MultiAgentMergePOEnv with its actions applied: a subclass with
+        ``APPLY_ENUMERATE_QUIRK = False``) has the same layout with five values per agent; agent c is the RL slot of
+        column c, and while that slot holds no vehicle the agent is absent: its action is NaN (no command), its
+        log-probability 0.  The shipped merge environment never applies an action and is refused (roll it out open
+        loop).  ``capture`` serves every other environment / model."""
         torch, R, K = self.torch, self.num_envs, int(num_steps)
         self.use_current_stream()
         if reset_done and self._resample and not getattr(self, "_warned_pending_length", False):

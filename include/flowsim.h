@@ -421,7 +421,7 @@ int fs_add_vehicle(fs_handle h, int replica, int slot, int route, double x, doub
 /* Family of the step kernel the handle's last fs_step / fs_rollout / fs_policy_rollout launch chose ("k_rollout_pair" with
  * "+speed_mode" and / or "+noise", "k_rollout_idm", "k_ring_pair<Accel | PO | POMA | AccelMA>", "k_rollout_loop",
  * "k_rollout_loop<FULL>", "k_rollout_loop<AccelMA>", "k_rollout_loop<FULL,AccelMA>", "k_ring_policy", "k_loop_policy",
- * "k_ring_policy<POMA>", "k_loop_policy<AccelMA>",
+ * "k_ring_policy<POMA>", "k_loop_policy<AccelMA>", "k_merge_policy",
  * "k_steps<FAST>", "k_steps<CSET>", "k_steps", "k_steps_ml", "k_steps_open" (also "<mixed>"), "k_steps_wide",
  * "k_merge_queue", "k_drop_queue", "k_obs_mixed"; "" before the first launch).  Diagnostics for tests and bench.py: which
  * configuration class a workload landed in (no reference counterpart).  The string is static.
@@ -455,8 +455,17 @@ const char* fs_last_kernel(fs_handle h);
  * obs [R, n_ag * obs_dim] and writes act / logp [R, n_ag]: agent c of replica r draws from Philox column 0x40000000 + c
  * at the replica's counter, which advances by one per call (c = 0 is the single-agent stream).  fs_policy_rollout_dev
  * takes obs [K+1, R, n_ag * obs_dim], act / logp [K, R, n_ag], rew / done [K, R] (the reward all agents share; a
- * collision ends nothing and zeroes no reward, multiagent/base.py:188-190).  FS_MIXED / FS_F64 with a multi-agent head,
- * FS_ENV_ACCEL_PO_MA on a ring and FS_ENV_MERGE_MA are refused by name. */
+ * collision ends nothing and zeroes no reward, multiagent/base.py:188-190).  FS_MIXED / FS_F64 with a multi-agent head and
+ * FS_ENV_ACCEL_PO_MA on a ring are refused by name.
+ * The multi-agent merge (FS_ENV_MERGE_MA, multiagent_merge.py) with ma_apply_actions = 1, FS_F32 or FS_F16S handles that
+ * step on k_merge_queue (the queue-order kernel's conditions: no FLOWSIM_NO_QUEUE, scheduled inflows, no fail-safes, ...;
+ * "k_merge_policy"): n_ag = num_rl agents, obs_dim = 5, the same layouts.  Agent c is the RL slot of column c, and it is
+ * ABSENT while that slot holds no vehicle in the state its observation is taken from (fs_policy_act_dev: the handle's
+ * current state; its observation block is zero).  An absent agent gets act = NaN (fs_step_dev's "no command") and
+ * logp = 0; a present agent draws as above, and the counter advances by one per step whether or not any agent is
+ * present (the reference lists only the RL vehicles present, flow/envs/multiagent/merge.py:98-143).  Resets inside a
+ * fragment: warmup_steps = 0.  ma_apply_actions = 0 (the shipped environment: actions never reach the simulator, roll it
+ * out open loop), FS_MIXED / FS_F64 and handles off the queue kernel are refused by name. */
 typedef struct fs_policy {
   uint32_t struct_size;               /* sizeof(fs_policy) */
   int32_t obs_dim;                    /* must equal fs_obs_dim; shared agents: fs_obs_dim / num_rl */
