@@ -302,7 +302,7 @@ __global__ __launch_bounds__(256) void k_policy_act(PolicyView pv, int R, int n_
 // collision ends nothing (multiagent/base.py:188-190).  Per step the row evaluates the agents in turn (the observation of
 // agent c, the network, the draw of column 0x40000000 + c); each lane keeps the actions of its own slots' columns and of
 // its places in the reward's sum by selects.
-// The simulator part is k_ring_pair's arithmetic statement by statement.
+// The simulator part is RingPairCore (flowsim_ringrl.h): the ONE definition of the ring step, which k_ring_pair runs too.
 template <typename T, int HEAD, bool NOISE, bool FAST>
 __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv, int num_steps, int reset_done,
                                                      int warmup_steps, float* __restrict__ obs, float* __restrict__ act,
@@ -313,209 +313,16 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
   constexpr bool MA = HEAD == 2;
   static_assert(HEAD == 1 || HEAD == 2, "k_ring_policy: the PO heads");
   static_assert(!(MA && MIXED), "the multi-agent head exists in float32 only");
-  constexpr int RPW = 64 / ROW;
   __shared__ PolicyLds PL;
   policy_load(pv, &PL, threadIdx.x, blockDim.x);
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int wib = (threadIdx.x >> 6) & 3;
-  const int row = lane / ROW;
-  const int k = lane % ROW;
-  const int r = wave * RPW + row;
-  const int N = s.N;
-  const int LP = N >> 1;
-  const bool rvalid = r < s.R;
-  const bool valid = rvalid && k < LP;
-  const int rr = rvalid ? r : s.R - 1;
-  const int kk = k < LP ? k : LP - 1;
-  const bool last = (kk == LP - 1);
-  const int iA = 2 * kk, iB = iA + 1;
-  const size_t idx = size_t(rr) * N + iA;
-
-  const bool rlA = s.ctrl[iA] == FS_CTRL_RL, rlB = s.ctrl[iB] == FS_CTRL_RL;
-  f2 p[6];
-#pragma unroll
-  for (int q = 0; q < 6; ++q) p[q] = f2{float(s.p[q * N + iA]), float(s.p[q * N + iB])};
-  {
-    const float dflt[6] = {30.0f, 1.0f, 1.0f, 1.5f, 4.0f, 2.0f};
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-      p[q].x = rlA ? dflt[q] : p[q].x;
-      p[q].y = rlB ? dflt[q] : p[q].y;
-    }
-  }
-  const T lenB = s.length[iB];
-  const T len_nextA = next_a<ROW>(T(s.length[iA]), last, lane);
-  T L = s.ring_len[rr] + T(4) * s.jlen;
-  int tcount = s.time[rr];
-  uint32_t nctr = NOISE ? s.noise_ctr[rr] : 0u;
+  RingPairCore<T, ROW, NOISE, FAST> core(s);
+  const int lane = core.lane, k = core.k, N = core.N, LP = core.LP, rr = core.rr, iA = core.iA, iB = core.iB;
+  const bool rvalid = core.rvalid, valid = core.valid, last = core.last, rlA = core.rlA, rlB = core.rlB;
   uint32_t pctr = pv.ctr[rr];
-  const f2 sigma = NOISE ? f2{float(s.noise[iA]), float(s.noise[iB])} : f2{0.0f, 0.0f};
-  const bool noisyA = NOISE && sigma.x > 0.0f && !rlA, noisyB = NOISE && sigma.y > 0.0f && !rlB;
-  float gA[4] = {0.0f, 0.0f, 0.0f, 0.0f}, gB[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if constexpr (NOISE) {
-    if ((nctr & 3u) != 0u) {
-      gauss4<float>(s.seed_lo, s.seed_hi, s.rep0 + uint32_t(rr), uint32_t(iA), nctr >> 2, gA, s.noise_exact != 0);
-      gauss4<float>(s.seed_lo, s.seed_hi, s.rep0 + uint32_t(rr), uint32_t(iB), nctr >> 2, gB, s.noise_exact != 0);
-      for (uint32_t q = 0; q < (nctr & 3u); ++q) {
-        gA[0] = gA[1]; gA[1] = gA[2]; gA[2] = gA[3];
-        gB[0] = gB[1]; gB[1] = gB[2]; gB[2] = gB[3];
-      }
-    }
-  }
-  const float dt = float(s.dt), ramp = float(s.ramp);
-  const f2 two_sqrt_ab = {2.0f * tsqrt(p[2].x * p[3].x), 2.0f * tsqrt(p[2].y * p[3].y)};
-  const f2 rc_v0 = {1.0f / p[0].x, 1.0f / p[0].y}, rc_ab = {1.0f / two_sqrt_ab.x, 1.0f / two_sqrt_ab.y};
-  const f2 one = splat(1.0f), dt2 = splat(dt), ramp2 = splat(ramp);
-  const f2 gap2 = splat(float(s.crash_gap));
-  const double dt64 = double(s.dt), ramp64 = double(s.ramp);
-  const f2 len_lead = {float(lenB), float(len_nextA)};
-  // the loop length and what depends on it: a reset inside the fragment takes the replica's pending length
-  f2 L2 = splat(float(L));
-  double L64 = double(L);
-  SumoPair sc;
-  double floor0A, floor0B, adtA, adtB, ddtA, ddtB;
-  {
-    const int mA = s.speed_mode[iA], mB = s.speed_mode[iB];
-    const float maA = float(s.max_accel[iA]), maB = float(s.max_accel[iB]);
-    const float mdA = float(s.max_decel[iA]), mdB = float(s.max_decel[iB]);
-    sc.tau = f2{float(s.sumo_tau[iA]), float(s.sumo_tau[iB])};
-    sc.min_gap = f2{float(s.sumo_min_gap[iA]), float(s.sumo_min_gap[iB])};
-    sc.maxa = f2{maA, maB};
-    sc.smax = f2{float(s.sumo_max_speed[iA]), float(s.sumo_max_speed[iB])};
-    sc.rc_smax = f2{1.0f / sc.smax.x, 1.0f / sc.smax.y};
-    sc.ts = f2{2.0f * tsqrt(maA * mdA), 2.0f * tsqrt(maB * mdB)};
-    sc.rc_ts = f2{1.0f / sc.ts.x, 1.0f / sc.ts.y};
-    const float BIG = 3.0e38f;
-    sc.floor0 = f2{(mA & 1) ? 0.0f : BIG, (mB & 1) ? 0.0f : BIG};
-    sc.adt = f2{(mA & 2) ? maA * dt : BIG, (mB & 2) ? maB * dt : BIG};
-    sc.ddt = f2{(mA & 4) ? mdA * dt : BIG, (mB & 4) ? mdB * dt : BIG};
-    floor0A = double(sc.floor0.x); floor0B = double(sc.floor0.y);
-    adtA = (mA & 2) ? double(s.max_accel[iA]) * dt64 : double(BIG);
-    adtB = (mB & 2) ? double(s.max_accel[iB]) * dt64 : double(BIG);
-    ddtA = (mA & 4) ? double(s.max_decel[iA]) * dt64 : double(BIG);
-    ddtB = (mB & 4) ? double(s.max_decel[iB]) * dt64 : double(BIG);
-  }
-
-  f2 x, v;
-  double xdA = 0, xdB = 0, vdA = 0, vdB = 0;
-  auto load_state = [&](const T* px, const T* pvv) {
-    if (MIXED) {
-      xdA = double(px[idx]); xdB = double(px[idx + 1]);
-      vdA = double(pvv[idx]); vdB = double(pvv[idx + 1]);
-      v = f2{float(vdA), float(vdB)};
-      x = f2{0.0f, 0.0f};
-    } else {
-      x = f2{float(px[idx]), float(px[idx + 1])};
-      v = f2{float(pvv[idx]), float(pvv[idx + 1])};
-    }
-  };
-  load_state(s.pos, s.vel);
-  f2 dgap = {0.0f, 0.0f};
-  double dgA = 0, dgB = 0;
-  auto headway = [&]() -> f2 {
-    if (MIXED) {
-      const double xn = next_a<ROW>(xdA, last, lane);
-      double dA = xdB - xdA, dB = xn - xdB;
-      dA = dA < 0.0 ? dA + L64 : dA;
-      dB = dB < 0.0 ? dB + L64 : dB;
-      dgA = dA;
-      dgB = dB;
-      return f2{float(dA - double(lenB)), float(dB - double(len_nextA))};
-    } else {
-      const f2 xl = {x.y, next_a<ROW>(x.x, last, lane)};
-      f2 d = pk_sub(xl, x);
-      const f2 dw = pk_add(d, L2);
-      d.x = nonneg_else(d.x, dw.x);
-      d.y = nonneg_else(d.y, dw.y);
-      dgap = d;
-      return pk_sub(d, len_lead);
-    }
-  };
-  f2 h = headway();
-  f2 vl = {v.y, next_a<ROW>(v.x, last, lane)};
-
-  // (k_ring_pair's forms: an unconditional clamp with +-3e38 bounds without clip_actions; one-instruction min / max
-  // evaluated before the selects that take them)
-  const bool clip_on = s.clip_actions != 0;
-  const float act_lo = clip_on ? float(s.act_lo) : -3.0e38f, act_hi = clip_on ? float(s.act_hi) : 3.0e38f;
-  auto clip = [&](float a) -> float { return hmin(hmax(a, act_lo), act_hi); };
-  auto noise_term = [&](bool live) -> f2 {
-    f2 nz = {-0.0f, -0.0f};
-    if constexpr (NOISE) {
-      const bool fresh = live && (nctr & 3u) == 0u;
-      if (__ballot(fresh) != 0ull) {
-        if (fresh) {
-          gauss4<float>(s.seed_lo, s.seed_hi, s.rep0 + uint32_t(rr), uint32_t(iA), nctr >> 2, gA, s.noise_exact != 0);
-          gauss4<float>(s.seed_lo, s.seed_hi, s.rep0 + uint32_t(rr), uint32_t(iB), nctr >> 2, gB, s.noise_exact != 0);
-        }
-      }
-      const float tA = sigma.x * gA[0], tB = sigma.y * gB[0];
-      nz.x = noisyA ? tA : -0.0f;
-      nz.y = noisyB ? tB : -0.0f;
-      if (live) {
-        gA[0] = gA[1]; gA[1] = gA[2]; gA[2] = gA[3];
-        gB[0] = gB[1]; gB[1] = gB[2]; gB[2] = gB[3];
-        nctr += 1u;
-      }
-    }
-    return nz;
-  };
-  // one step (k_ring_pair's `advance`): `have_act` false = rl_actions None (the warm-up steps of a reset); a_rlA / a_rlB:
-  // the commands of the lane's two slots (one RL vehicle: the same value)
-  auto advance = [&](bool live, bool have_act, float a_rlA, float a_rlB) {
-    f2 acc = idm_pair<FAST, FAST>(v, vl, h, p, two_sqrt_ab, rc_ab, rc_v0, one);
-    if constexpr (NOISE) acc = pk_add(acc, noise_term(live));
-    const float a_clA = clip(a_rlA), a_clB = clip(a_rlB);
-    acc.x = rlA ? a_clA : acc.x;
-    acc.y = rlB ? a_clB : acc.y;
-    const bool cmdA = !rlA || have_act, cmdB = !rlB || have_act;
-    const f2 acc_s = sumo_acc_pair<FAST>(v, vl, h, sc, one);
-    if (MIXED) {
-      const double aA = double(acc.x), aB = double(acc.y);
-      const double nA = tmax(vdA + aA * dt64, 0.0), nB = tmax(vdB + aB * dt64, 0.0);
-      double cA = vdA + (nA - vdA) * ramp64, cB = vdB + (nB - vdB) * ramp64;
-      const double vsA = vdA + double(acc_s.x) * dt64, vsB = vdB + double(acc_s.y) * dt64;
-      cA = tmin(cA, tmax(vsA, floor0A)); cB = tmin(cB, tmax(vsB, floor0B));
-      cA = tmin(cA, vdA + adtA); cB = tmin(cB, vdB + adtB);
-      cA = tmax(cA, vdA - ddtA); cB = tmax(cB, vdB - ddtB);
-      cA = cmdA ? cA : tmax(vsA, 0.0);
-      cB = cmdB ? cB : tmax(vsB, 0.0);
-      const double xA = xdA + cA * dt64, xB = xdB + cB * dt64;
-      const double wA = xA >= L64 ? xA - L64 : xA, wB = xB >= L64 ? xB - L64 : xB;
-      if (live) {
-        vdA = cA; vdB = cB;
-        xdA = wA; xdB = wB;
-      }
-      v = f2{float(vdA), float(vdB)};
-    } else {
-      f2 nv = pk_add(v, pk_mul(acc, dt2));
-      nv.x = hmax(nv.x, 0.0f);
-      nv.y = hmax(nv.y, 0.0f);
-      f2 vc = pk_add(v, pk_mul(pk_sub(nv, v), ramp2));
-      const f2 vs = pk_add(v, pk_mul(acc_s, dt2));
-      const f2 cap1 = pk_add(v, sc.adt), flo = pk_sub(v, sc.ddt);
-      vc.x = hmin(vc.x, hmax(sc.floor0.x, vs.x));
-      vc.y = hmin(vc.y, hmax(sc.floor0.y, vs.y));
-      vc.x = hmax(hmin(vc.x, cap1.x), flo.x);
-      vc.y = hmax(hmin(vc.y, cap1.y), flo.y);
-      const float zA = hmax(0.0f, vs.x), zB = hmax(0.0f, vs.y);
-      vc.x = cmdA ? vc.x : zA;
-      vc.y = cmdB ? vc.y : zB;
-      const f2 xn = pk_add(x, pk_mul(vc, dt2));
-      const f2 xw = pk_sub(xn, L2);
-      f2 xq;
-      xq.x = nonneg_else(xw.x, xn.x);
-      xq.y = nonneg_else(xw.y, xn.y);
-      if (live) {
-        v = vc;
-        x = xq;
-      }
-    }
-    if (live) tcount += 1;
-    h = headway();
-    vl = f2{v.y, next_a<ROW>(v.x, last, lane)};
-  };
+  core.set_length(s.ring_len[rr] + T(4) * s.jlen);
+  core.load_state(s.pos, s.vel);
+  core.snapshot();
+  const f2 &v = core.v, &vl = core.vl, &h = core.h, &dgap = core.dgap;                  // (the core's state, by its names)
 
   // WaveAttenuationPOEnv.get_state of the current snapshot (k_ring_pair's write_obs): computed by the RL vehicle's
   // lane, handed to the row through LDS (the policy's input), stored by that lane
@@ -543,8 +350,8 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
     } else {
       float q0, q1, q2;
       if (MIXED) {
-        const double vdn = next_a<ROW>(vdA, last, lane);
-        const double v_me = poB ? vdB : vdA, v_ld = poB ? vdn : vdB, d_me = poB ? dgB : dgA;
+        const double vdn = next_a<ROW>(core.vdA, last, lane);
+        const double v_me = poB ? core.vdB : core.vdA, v_ld = poB ? vdn : core.vdB, d_me = poB ? core.dgB : core.dgA;
         q0 = float(v_me * rc15);
         q1 = float((v_ld - v_me) * rc15);
         q2 = float(d_me * rc_pml64);
@@ -627,27 +434,21 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
     }
     pctr += 1u;
     // ---- Env.step ------------------------------------------------------------------------------------------------
-    advance(true, true, aA, aB);
-    const f2 hc = pk_sub(h, gap2), vb = pk_sub(v, f2{-100.0f, -100.0f});        // sign masks (k_ring_pair's terms)
-    const unsigned fl = ((__builtin_bit_cast(unsigned, hmin(hc.x, hc.y)) >> 31) |
-                         ((__builtin_bit_cast(unsigned, hmin(vb.x, vb.y)) >> 31) << 1)) & (valid ? 3u : 0u);
-    const unsigned fany = seg_or<ROW>(fl);
+    core.template advance<false>(true, true, aA, aB);
+    const unsigned fany = seg_or<ROW>(core.step_flags());
     const bool crashed = !MA && (fany & 1u) != 0u;          // (multiagent/base.py:188-190: crash = 0)
     const bool bad = (fany & 2u) != 0u || crashed;
     const float sv = seg_sum<ROW>(valid ? v.x + v.y : 0.0f);
-    const float mean_v = div_via_f64(sv, double(N), 1.0 / double(N));
     float mean_a;
     if constexpr (MA) {                                     // k_ring_pair's terms / finish: column i summed where slot i stands
-      const float caA = tabs(clip(arA)), caB = tabs(clip(arB));
+      const float caA = tabs(core.clip(arA)), caB = tabs(core.clip(arB));
       const float sa = seg_sum<ROW>((redA ? caA : 0.0f) + (redB ? caB : 0.0f));
       mean_a = div_via_f64(sa, double(s.num_rl), 1.0 / double(s.num_rl));
     } else {
-      mean_a = tabs(clip(a));                               // (one column: the sum is the value, / 1)
+      mean_a = tabs(core.clip(a));                              // (one column: the sum is the value, / 1)
     }
-    float reward = div_via_f64(4.0f * mean_v, 20.0, 1.0 / 20.0);
-    if (mean_a > 0.0f) reward = reward + 4.0f * (0.0f - mean_a);
-    reward = bad ? 0.0f : reward;
-    const uint8_t dflag = done_flag(tcount >= s.step_limit, crashed);
+    const float reward = wave_reward(sv, N, mean_a, bad);
+    const uint8_t dflag = done_flag(core.tcount >= s.step_limit, crashed);
     if (rvalid && k == 0) {
       rew[size_t(step) * R + rr] = reward;
       done[size_t(step) * R + rr] = dflag;
@@ -657,17 +458,14 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
     const bool fin = reset_done && dflag != 0;
     if (__ballot(fin) != 0ull) {
       if (fin) {
-        load_state(s.init_pos, s.init_vel);
-        L = s.init_ring_len[rr] + T(4) * s.jlen;
-        L2 = splat(float(L));
-        L64 = double(L);
-        tcount = 0;
+        core.load_state(s.init_pos, s.init_vel);
+        core.set_length(s.init_ring_len[rr] + T(4) * s.jlen);
+        core.tcount = 0;
       }
-      h = headway();
-      vl = f2{v.y, next_a<ROW>(v.x, last, lane)};
+      core.snapshot();
 #pragma unroll 1
-      for (int w = 0; w < warmup_steps; ++w) advance(fin, false, 0.0f, 0.0f);
-      if (fin && valid && kk == 0) const_cast<T*>(s.ring_len)[rr] = s.init_ring_len[rr];
+      for (int w = 0; w < warmup_steps; ++w) core.template advance<false>(fin, false, 0.0f, 0.0f);
+      if (fin && valid && core.kk == 0) const_cast<T*>(s.ring_len)[rr] = s.init_ring_len[rr];
     }
     // (MA: the agents' observations are made at the top of the next step, where the policy takes them)
     if constexpr (!MA) observe(obs + (size_t(step + 1) * R + rr) * 3);
@@ -678,18 +476,8 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
   }
 
   if (valid) {
-    if (MIXED) {
-      s.pos[idx] = T(xdA); s.pos[idx + 1] = T(xdB);
-      s.vel[idx] = T(vdA); s.vel[idx + 1] = T(vdB);
-    } else {
-      s.pos[idx] = T(x.x); s.pos[idx + 1] = T(x.y);
-      s.vel[idx] = T(v.x); s.vel[idx + 1] = T(v.y);
-    }
-    if (kk == 0) {
-      s.time[rr] = tcount;
-      pv.ctr[rr] = pctr;
-      if (NOISE) s.noise_ctr[rr] = nctr;
-    }
+    core.store_state();
+    if (core.kk == 0) pv.ctr[rr] = pctr;
   }
 }
 

@@ -7,6 +7,7 @@ rows held by lanes that are inactive at that point would read stale data (found 
 section 4; the open-network kernels read their launch tables from LDS for that reason).  This test pins the premise:
 every float32 instantiation of the step kernels uses zero AGPRs and spills nothing to scratch memory -- it caught
 k_steps_open<float, 32, .> growing past 256 VGPRs once."""
+import json
 import os
 import re
 import subprocess
@@ -108,3 +109,46 @@ def test_hand_written_pair_step_keeps_its_registers(device_asm):
             stale = [r for r in src if (124 <= r <= 127 or 130 <= r <= 133) and r not in written]
             assert not stale, "compiler code reads a clobbered temporary of the asm blocks: " + t
             written.update(dst)
+
+
+# Instantiations that may exceed the recorded register total, and by how much.  The reason is the same for all: the
+# register allocator's choice for the same arithmetic, now that the step comes from RingPairCore.  None crosses an
+# occupancy step (registers are granted in blocks of 8 out of 512 per SIMD lane; before -> after, waves per SIMD).
+_RING = "_ZN2fs11k_ring_pairI%sLi%dELi0ELb%dELb%dELb0EEEvNS_7DevViewIT_EEiPKhPKfmPfS8_Phi"
+RESOURCE_ALLOWANCE = {
+    _RING % ("d", 8, 0, 0): 3,        # 113 -> 116: 4 waves
+    _RING % ("d", 8, 0, 1): 2,        # 112 -> 114: 4 waves
+    _RING % ("d", 8, 1, 0): 1,        # 134 -> 135: 3 waves
+    _RING % ("d", 8, 1, 1): 1,        # 134 -> 135: 3 waves
+    _RING % ("f", 16, 0, 1): 2,       # 126 -> 128: 4 waves
+}
+
+
+def test_ring_and_loop_kernels_keep_their_resources(device_asm):
+    """k_ring_pair and k_ring_policy share RingPairCore (flowsim_ringrl.h): all of it must be inlined into each kernel.  A
+    member that stayed out of line shows as an s_swappc_b64, an expression instead of a number in the kernel's .set
+    num_vgpr line and the struct in scratch memory (seen with a wrapper lambda around `advance`: 1168-1456 bytes per
+    lane).  tests/golden/ring_loop_kernel_resources.json holds the registers, scratch bytes and instruction count of
+    every instantiation of the ring kernels and of the figure-eight pair k_rollout_loop / k_loop_policy (which still
+    repeat each other: the guard is in place for the day they share their step) before the ring step was written once:
+    no instantiation may have gone, none may use scratch where it used none, and VGPRs + AGPRs may not grow."""
+    with open(os.path.join(ROOT, "tests", "golden", "ring_loop_kernel_resources.json")) as f:
+        golden = json.load(f)
+    assert len(golden) >= 90 and set(RESOURCE_ALLOWANCE) <= set(golden)
+    families = {re.match(r"_ZN2fs\d+(k_\w+?)I", n).group(1) for n in golden}
+    assert families == {"k_ring_pair", "k_ring_policy", "k_rollout_loop", "k_loop_policy"}
+    bad = {}
+    for name, ref in golden.items():
+        m = re.search(r"^%s:[^\n]*\n(.*?)^\s*\.set %s\.num_vgpr, ([^\n]*)$" % (re.escape(name), re.escape(name)), device_asm,
+                      re.S | re.M)
+        assert m, "instantiation gone: " + name
+        body, vgpr = m.group(1), m.group(2).strip()
+        get = lambda key: re.search(r"\.set %s\.%s, ([^\n]*)" % (re.escape(name), key), device_asm).group(1).strip()
+        agpr, scratch = get("num_agpr"), get("private_seg_size")
+        if not (vgpr.isdigit() and agpr.isdigit() and scratch.isdigit()) or "s_swappc_b64" in body:
+            bad[name] = "an out-of-line call: num_vgpr = %s" % vgpr
+        elif ref["private_seg_size"] == 0 and int(scratch) != 0:
+            bad[name] = "scratch memory: %s bytes" % scratch
+        elif int(vgpr) + int(agpr) > ref["num_vgpr"] + ref["num_agpr"] + RESOURCE_ALLOWANCE.get(name, 0):
+            bad[name] = "registers: %s + %s, recorded %d + %d" % (vgpr, agpr, ref["num_vgpr"], ref["num_agpr"])
+    assert not bad, bad
