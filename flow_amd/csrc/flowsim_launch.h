@@ -13,8 +13,14 @@ namespace fsim {
 #ifdef FS_PART_QUEUE
   template <typename T>
   int Sim<T>::launch_queue(const StepArgs& a) {
-    const bool noise = (dv.flags & fs::FLAG_HAS_NOISE) != 0, act = a.actions != nullptr && ov.ma_apply_actions != 0;
-    const auto k = pick(noise, [&](auto NZ) { return pick(act, [&](auto ACT) { return &fs::k_merge_queue<NZ, ACT>; }); });
+    // MergePOEnv always applies its action row (one column per place of rl_veh); the multi-agent head when asked to
+    const bool po = dv.env == FS_ENV_MERGE_PO;
+    const bool noise = (dv.flags & fs::FLAG_HAS_NOISE) != 0, act = a.actions != nullptr && (po || ov.ma_apply_actions != 0);
+    const auto k = pick(noise, [&](auto NZ) {
+      return pick(act, [&](auto ACT) {
+        return pick(po, [&](auto PO) { return &fs::k_merge_queue<NZ, ACT, false, PO>; });
+      });
+    });
     last_kernel = "k_merge_queue";
     hipLaunchKernelGGL(k, dim3(dv.R), dim3(64), 0, stream, dv, ov, qc, a.num_steps, a.actions, a.act_stride, a.obs, a.rew,
                        a.done, a.obs_every_step, fs::PolicyView{}, static_cast<float*>(nullptr), static_cast<float*>(nullptr),

@@ -28,9 +28,10 @@
 // bookkeeping on the CPU and proves it equal to the all-pairs rules of oracle/opennet.py at every sub-step; the
 // arithmetic is k_steps_open<float, ., 2, CSET = 1>'s, operation for operation (idm_fd, sumo_speed_fd, the same Philox
 // draws), so the two kernels are bit-identical (tests/test_queue_gpu.py).  Scope (Sim::queue_ok): float32, IDM / RL /
-// Sim-car-following slots without fail-safes, one vehicle length, Euler, the MultiAgentMergePOEnv head (FS_ENV_MERGE_MA:
-// C5 of BASELINE.json), scheduled inflows, no replica mask, one or more steps per launch; everything else steps on
-// k_steps_open.
+// Sim-car-following slots without fail-safes, one vehicle length, Euler, both merge heads -- MultiAgentMergePOEnv
+// (FS_ENV_MERGE_MA: C5 of BASELINE.json) and MergePOEnv (FS_ENV_MERGE_PO, the template parameter PO below:
+// tests/test_queue_po_gpu.py) --, scheduled inflows, no replica mask, one or more steps per launch; everything else steps
+// on k_steps_open.
 #pragma once
 
 namespace fs {
@@ -75,7 +76,18 @@ struct alignas(16) QueueRow {
 // resets it (reset_open_slot, the halves of FS_F16S, update(reset=True)'s follower entries) and set up again from HBM as
 // the next launch would be; obs[k + 1] is then the observation of the new episode.  So a fragment equals
 // K x (fs_policy_act_dev, fs_step_dev, fs_reset_dev(done)) bit for bit (tests/test_policy_merge_gpu.py).
-template <bool NOISE, bool ACT, bool POLICY = false>
+//
+// PO (FS_ENV_MERGE_PO: MergePOEnv, flow/envs/merge.py): the single-agent head.  The controlled vehicles are the list
+// rl_veh of at most num_rl entries; ctl_seq[slot] >= 0 says that the slot is listed and orders the list, so the PLACE of
+// a slot is the rank of its ctl_seq among the listed slots.  All of it is SLOT-view state (lane i speaks for slot i):
+// ctl_seq in a register, the places in LDS (place_row), from where a vehicle's lane reads the place of its label -- the
+// column of the action row that commands it and the block of the observation it fills.  additional_command (the
+// removal pass that skips the entry behind each one it removes, then the queue in departure order) can change the
+// list only while a listed slot has no RL vehicle (a ghost) or an unlisted RL vehicle meets a free place: `po_dirty`,
+// one wave-uniform flag that the events and the pass itself recompute; every other sub-step skips the bookkeeping.
+// A collision ends the env step on this head: the replica's remaining sub-steps do not run (k_steps_open freezes them:
+// no movement, no insertion, no list change, no counter advances), reward 0, the crash bit of `done`.
+template <bool NOISE, bool ACT, bool POLICY = false, bool PO = false>
 __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<float> o, QueueConsts qc, int num_steps,
                                                     const float* __restrict__ actions, size_t act_stride,
                                                     float* __restrict__ obs, float* __restrict__ rew,
@@ -84,6 +96,7 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
                                                     int reset_done) {
   using T = float;
   static_assert(!POLICY || ACT, "k_merge_queue: the policy's actions take the ACT path");
+  static_assert(!(POLICY && PO), "k_merge_queue: the fused policy is built for the multi-agent head only");
   const T BIGV = 3.0e38f;
   const int lane = threadIdx.x;
   const int r = blockIdx.x;                       // one replica per wave (grid = R)
@@ -99,6 +112,7 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
   __shared__ PolicyLds PL;                        // (POLICY) the network
   __shared__ float feat[5][64], lp_row[64];       // (POLICY) the features by column, the log-probabilities of a step
   __shared__ int pcol[64];                        // (POLICY) the present columns, compacted
+  __shared__ int place_row[64];                   // (PO) the place in rl_veh of every slot, -1: not listed
   OpenTabs<T, true> tb;
   tb.load(o, lane, false, &tabs_mem);
   if constexpr (POLICY) policy_load(pv, &PL, lane, 64);
@@ -172,6 +186,8 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
   int nA = 0, n1 = 0, nD = 0;
   unsigned long long alive_lab;                        // bit i: slot i holds a vehicle
   unsigned long long arr_rl;                           // RL slots that arrived in the last sub-step
+  int ctl_seq = -1, ctl_ctr = 0;                       // (PO, slot view) the list entry of my slot; the join counter
+  bool po_dirty = false;                               // (PO, wave-uniform) additional_command has something to do
   // the replica's state from HBM: at launch start, and again after a reset inside the launch (POLICY)
   auto load_state = [&]() {
     tcount = s.time[r];
@@ -199,6 +215,10 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
     alive_lab = __ballot(route >= 0);
     const int a0 = o.arrived_rl[base + li];
     arr_rl = __ballot(slot_ok && a0 != 0);
+    if constexpr (PO) {
+      ctl_seq = slot_ok ? o.ctl_seq[base + li] : -1;
+      ctl_ctr = cnt[CNT_CTL];
+    }
   };
   load_state();
 
@@ -208,6 +228,7 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
   const T merge_x = in_vgpr(float(o.merge_x)), box_in = in_vgpr(float(o.box_in)), end_x = in_vgpr(float(o.end_x));
   const T tgap = in_vgpr(float(s.j_time_gap)), appr_lo = in_vgpr(float(o.box_in) - float(s.j_lookahead));
   const T LEN = in_vgpr(qc.veh_len);
+  const T crash_gap = PO ? in_vgpr(float(s.crash_gap)) : 0.0f;
   const T clip_lo = in_vgpr(s.clip_actions ? float(s.act_lo) : -3.0e38f), clip_hi = in_vgpr(s.clip_actions ? float(s.act_hi) : 3.0e38f);
   const int jm = __builtin_amdgcn_readfirstlane(s.junction_mode), jct = __builtin_amdgcn_readfirstlane(s.junction_on);
   const T c0 = in_vgpr(0.0f), c1000 = in_vgpr(1000.0f), cm1001 = in_vgpr(-1001.0f), cBIG = in_vgpr(3.0e38f);
@@ -421,6 +442,64 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
 #define FS_QT(var_)
 #define FS_QA(slot_, t0_)
 #endif
+  // ---- (PO) rl_veh: places, the pending test, my vehicle's action, additional_command ------------------------------
+  // (slot view) the place of every slot from the ctl_seq of the listed ones, ghosts included, into place_row
+  auto po_places = [&]() {
+    int place = 0;
+    for (unsigned long long u = __ballot(ctl_seq >= 0); u; u &= u - 1ull)
+      place += read_lane_i(ctl_seq, __ffsll((long long)u) - 1) < ctl_seq ? 1 : 0;
+    place_row[lane] = ctl_seq >= 0 ? place : -1;
+    q_fence();
+  };
+  // can additional_command change the list, as the slots stand?  A listed slot without an RL vehicle waits for its
+  // removal; an RL vehicle that is not listed joins when a place is free
+  auto po_pending = [&]() -> bool {
+    const unsigned long long listed = __ballot(ctl_seq >= 0), rl_alive = alive_lab & __ballot(slot_is_rl);
+    return (listed & ~rl_alive) != 0ull || ((rl_alive & ~listed) != 0ull && __popcll(listed) < s.num_rl);
+  };
+  // (lane view) column i of the action row commands the vehicle at place i (envs/base.py:355-357); an RL vehicle that
+  // is not listed gets no command (SUMO's model drives it)
+  auto po_action = [&]() {
+    const int pl = place_row[lab & 63];
+    q_fence();
+    const bool cmd = pl >= 0 && pl < s.num_rl;
+    a_me = act_row[(cmd ? pl : 0) & 63];
+    q_fence();
+    mHaveRl = mKrl & __ballot(cmd);
+  };
+  // MergePOEnv.additional_command (merge.py:189-221) on the vehicles known before this sub-step moves: k_steps_open's
+  // statements on the slot view
+  auto po_command = [&]() {
+    const bool alive_rl = slot_is_rl && ((alive_lab >> lane) & 1ull) != 0ull;
+    const int place = place_row[lane];
+    q_fence();
+    // the removal loop skips the entry behind each one it removes: of a run of consecutive departed entries the 1st,
+    // 3rd, ... go now.  D = the departed entries as a mask over places, run = the departed entries directly in front of mine
+    const bool gone = place >= 0 && !alive_rl;
+    unsigned D = 0u;
+    for (unsigned long long u = __ballot(gone); u; u &= u - 1ull) D |= 1u << (read_lane_i(place, __ffsll((long long)u) - 1) & 31);
+    const unsigned below = place > 0 ? ((1u << (place & 31)) - 1u) : 0u;
+    const unsigned holes = ~D & below;                 // places in front of mine that have NOT left
+    const int run = holes != 0u ? (place - 1) - (31 - __clz(int(holes))) : place;
+    if (gone && (run & 1) == 0) ctl_seq = -1;
+    // the queue, in departure order, fills the free places
+    const int n_ctl = __popcll(__ballot(ctl_seq >= 0));
+    const int free_places = s.num_rl - n_ctl > 0 ? s.num_rl - n_ctl : 0;
+    const bool queued = alive_rl && ctl_seq < 0;
+    const unsigned long long qb = __ballot(queued);
+    if (qb != 0ull && free_places > 0) {
+      const int seq_s = to_slots_i(seq, lane < nA || lane >= 64 - n1, 0);
+      int qrank = 0;
+      for (unsigned long long u = qb; u; u &= u - 1ull) qrank += read_lane_i(seq_s, __ffsll((long long)u) - 1) < seq_s ? 1 : 0;
+      const bool take = queued && qrank < free_places;
+      if (take) ctl_seq = ctl_ctr + qrank;
+      ctl_ctr += __popcll(__ballot(take));
+    }
+    po_places();
+    po_dirty = po_pending();
+    if (ACT) po_action();                              // (the commands of the NEXT sub-step: this one's are taken)
+  };
+
   // ---- the events of a sub-step (cold: a wave-uniform branch of the loop below) -----------------------------------
   auto events = [&](int step, bool structural, bool try_insert) {
     FS_QT(q_ev0);
@@ -507,7 +586,8 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
         const T x_dep = read_lane(f_xdep, f), v_dep = read_lane(f_vdep, f);
         const T two_sqrt = read_lane(f_ts, f), min_gap_f = read_lane(f_gap, f), tau_f = read_lane(f_tau, f);
         // M1: the lowest free slot of the type (a slot freed in this sub-step is not free yet)
-        const unsigned long long fb = __ballot(slot_ok && slot_type == typ) & ~alive_lab & ~just_arrived;
+        // (PO: a listed ghost keeps its slot)
+        const unsigned long long fb = __ballot(slot_ok && slot_type == typ && (!PO || ctl_seq < 0)) & ~alive_lab & ~just_arrived;
         const int slot = fb ? __ffsll((long long)fb) - 1 : 0;
         // M3: the nearest vehicle ahead on the route is the tail of its queue (no queue of its own: the tail of D)
         const int n_d = __popcll(__ballot(isA && x >= merge_x));
@@ -590,7 +670,12 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
     // the end of D moves when the head of U0 passes the merge point: no vehicle changes lane, the lanes' facts do
     if (structural || inserted) classes(reload);
     FS_QA(4, q_cl0);
-    if (ACT) {
+    if constexpr (PO) {
+      if (moved) {
+        po_dirty = po_pending();                       // an RL vehicle came or went: the list has work from the next sub-step on
+        if (ACT) po_action();
+      }
+    } else if (ACT) {
       if (moved) {                                     // my vehicle may be another one now: its action column (the
         a_me = act_row[rl_col & 63];                   // step's row waits in LDS: a global load here was an L2 round trip)
         q_fence();
@@ -602,10 +687,16 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
 
   // ---- get_state / compute_reward / done of the current state: obs_out -> orow (POLICY: and the features to LDS),
   // rew_out -> rrow / drow ----------------------------------------------------------------------------------------
+  bool crashed = false;                                // (PO, wave-uniform) a collision in this env step
   auto head = [&](bool obs_out, bool rew_out) {
     FS_QT(q_hd0);
     const bool isA = lane < nA, isU = lane >= 64 - n1, alive = isA | isU, uh = isU && lane == 63;
     const bool has = ((mHas >> lane) & 1ull) != 0ull, k_rl = ((mKrl >> lane) & 1ull) != 0ull;
+    int my_place = -1;                                 // (PO, lane view) the place of my vehicle in rl_veh
+    if constexpr (PO) {
+      my_place = place_row[lab & 63];
+      q_fence();
+    }
     // the five features of my vehicle (flow/envs/multiagent/merge.py:108-140)
     // Flow's coordinate of x (O5, route_lookup's arithmetic): both routes' tables are launch constants in registers
     // -- five compares and selects each, no table walk through LDS (that walk was half of the head's time)
@@ -634,7 +725,7 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
     // holds it now; the reward's sums run in slot order): four scatters, one wait, the reads, one wait -- a free slot's
     // entry is stale and masked by `alive_lab` (the first version cleared and waited per value: fourteen LDS round trips)
     const T dvt = v - s.target_velocity;
-    const bool use = alive && k_rl && has && (v > 0.0f);
+    const bool use = alive && k_rl && has && (v > 0.0f) && (!PO || my_place >= 0);
     const T t_headway = tmax(h / (use ? v : 1.0f), 0.0f);
     const T term = tmin((t_headway - 1.0f) / 1.0f, 0.0f);
     if (alive) {
@@ -672,7 +763,29 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
     f5[2] = div_via_f64(lead_head, nl64, rc_nl64);
     f5[3] = div_via_f64(this_speed - follow_speed, ms64, rc_ms64);
     f5[4] = div_via_f64(follow_head, nl64, rc_nl64);
-    if (obs_out && alive && k_rl) {
+    if constexpr (PO) {
+      // block i = the vehicle at place i of rl_veh (merge.py:117-158); a listed slot without a vehicle: the accessors'
+      // error values; places beyond the list: zero
+      if (obs_out && alive && k_rl && my_place >= 0 && my_place < s.num_rl) {
+#pragma unroll
+        for (int q = 0; q < 5; ++q) orow[5 * my_place + q] = f5[q];
+      }
+      const int pl_s = place_row[lane];                // (slot view)
+      q_fence();
+      if (obs_out && pl_s >= 0 && pl_s < s.num_rl && !((alive_lab >> lane) & 1ull)) {
+        const T gs = -1001.0f;
+        orow[5 * pl_s + 0] = div_via_f64(gs, ms64, rc_ms64);
+        orow[5 * pl_s + 1] = div_via_f64(s.max_speed - gs, ms64, rc_ms64);
+        orow[5 * pl_s + 2] = div_via_f64(o.net_length, nl64, rc_nl64);
+        orow[5 * pl_s + 3] = div_via_f64(gs - 0.0f, ms64, rc_ms64);
+        orow[5 * pl_s + 4] = div_via_f64(o.net_length, nl64, rc_nl64);
+      }
+      const int n_ctl = __popcll(__ballot(pl_s >= 0));
+      if (obs_out && lane < s.num_rl && lane >= n_ctl) {
+#pragma unroll
+        for (int q = 0; q < 5; ++q) orow[5 * lane + q] = 0.0f;
+      }
+    } else if (obs_out && alive && k_rl) {
       const int col = rows[lab & 63].rl_index;
 #pragma unroll
       for (int q = 0; q < 5; ++q) orow[5 * col + q] = f5[q];
@@ -681,7 +794,7 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
         for (int q = 0; q < 5; ++q) feat[q][col & 63] = f5[q];
       }
     }
-    if (obs_out && slot_is_rl && !((alive_lab >> lane) & 1ull)) {   // (slot view) an RL slot without a vehicle
+    if (!PO && obs_out && slot_is_rl && !((alive_lab >> lane) & 1ull)) {   // (slot view) an RL slot without a vehicle
 #pragma unroll
       for (int q = 0; q < 5; ++q) orow[5 * slot_rl_index + q] = 0.0f;
     }
@@ -702,13 +815,31 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
       const bool bad = (__ballot(alive && (v < -100.0f)) != 0ull) || n_alive == 0;
       cost1 = bad ? 0.0f : cost1;
       T cost2 = 0.0f;
-      for (unsigned long long u = __ballot(use_s != 0); u; u &= u - 1ull) cost2 = cost2 + read_lane(term_s, __ffsll((long long)u) - 1);
+      if constexpr (PO) {                               // the listed vehicles' terms in LIST order: handed from slot to place
+        const int pl_s = place_row[lane];
+        q_fence();
+        scr_j[lane] = 0;
+        q_fence();
+        if (use_s != 0 && pl_s >= 0) {
+          scr_g[pl_s & 63] = term_s;
+          scr_j[pl_s & 63] = 1;
+        }
+        q_fence();
+        const T term_p = scr_g[lane];
+        const int use_p = scr_j[lane];
+        q_fence();
+        for (unsigned long long u = __ballot(use_p != 0); u; u &= u - 1ull) cost2 = cost2 + read_lane(term_p, __ffsll((long long)u) - 1);
+      } else {
+        for (unsigned long long u = __ballot(use_s != 0); u; u &= u - 1ull) cost2 = cost2 + read_lane(term_s, __ffsll((long long)u) - 1);
+      }
       reward = tmax(cost1 + 0.1f * cost2, 0.0f);
+      if (PO && crashed) reward = 0.0f;
     }
     FS_QA(13, q_h3);
     if (lane == 0) {
       *rrow = reward;
-      *drow = done_flag(tcount >= s.step_limit, false);          // multiagent/base.py:188-190: crash = 0
+      // multiagent/base.py:188-190: crash = 0 on the multi-agent head; MergePOEnv ends the episode (envs/base.py:398-400)
+      *drow = done_flag(tcount >= s.step_limit, PO && crashed);
     }
     FS_QA(6, q_hd0);
   };
@@ -738,8 +869,10 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
       o.headway[e] = h;
     }
     if (slot_ok) o.arrived_rl[base + lane] = int((arr_rl >> lane) & 1ull);
+    if (PO && slot_ok) o.ctl_seq[base + lane] = ctl_seq;
     if (lane == 0) {
       if (POLICY) pv.ctr[r] = pctr;
+      if (PO) cnt[CNT_CTL] = ctl_ctr;
       s.time[r] = tcount;
       s.noise_ctr[r] = nctr;
       cnt[CNT_SIM_STEPS] = sim_steps;
@@ -787,6 +920,10 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
 #ifdef FS_QDIAG
   const unsigned long long dg_start = __builtin_readcyclecounter();
 #endif
+  if constexpr (PO) {
+    po_places();
+    po_dirty = po_pending();
+  }
   if constexpr (POLICY) {
     pctr = pv.ctr[r];
     head(true, false);                                 // obs[0]: the state the fragment starts from
@@ -835,12 +972,17 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
     } else if (ACT) {                                  // the step's action row, by RL column, in LDS
       act_row[lane] = lane < s.num_rl ? a_pref : 0.0f;
       q_fence();
-      a_me = act_row[rl_col & 63];
-      q_fence();
+      if constexpr (PO) {
+        po_action();
+      } else {
+        a_me = act_row[rl_col & 63];
+        q_fence();
+      }
       const int nxt = step + 1 < num_steps ? step + 1 : step;
       a_pref = actions[size_t(nxt) * act_stride + size_t(r) * s.num_rl + act_lane];
     }
-    if (ACT) mHaveRl = mKrl & __ballot(!(a_me != a_me));          // NaN: no action for this vehicle this step
+    if (ACT && !PO) mHaveRl = mKrl & __ballot(!(a_me != a_me));   // NaN: no action for this vehicle this step
+    if (PO) crashed = false;
     for (int sub = 0; sub < s.sims_per_step; ++sub) {
       // ---- this sub-step's acceleration noise (S14): one Philox block serves four sub-steps ---------------------
       T g_now = 0.0f;
@@ -888,6 +1030,9 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
         float ar = c0;
         if (ACT) ar = selm(mHaveRl, hmin(hmax(a_me, clip_lo), clip_hi), c0);
         acc = selm(mKidm, a, ar);
+      }
+      if constexpr (PO) {
+        if (po_dirty) po_command();                      // additional_command (envs/base.py:357: after the commands were taken)
       }
       // ---- M7: apply_acceleration + SUMO integration (sumo_speed_fd, k_steps_open's FD form) ---------------------
       // (common to SUMO's speed behind the leader and towards the stop line)
@@ -958,6 +1103,19 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
       vl = vl_n;
       foll = foll_n;
       foll_h = foll_h_n;
+      if constexpr (PO) {
+        // the collision check on the new snapshot: a headway below crash_gap, or both routes inside the junction box
+        // (a vehicle upstream of the merge point is in U0 or U1).  The rest of the env step does not run for the replica
+        unsigned long long c_m = ballot_here(selm(mHas, h, cBIG) < crash_gap);
+        if (jct) {
+          const unsigned long long in_m = ballot_here(x >= box_in && x < merge_x);
+          c_m |= ((in_m & mCU0) != 0ull && (in_m & mU) != 0ull) ? 1ull : 0ull;
+        }
+        if (c_m != 0ull) {
+          crashed = true;
+          break;
+        }
+      }
     }
 
     // ---- get_state / compute_reward / done ------------------------------------------------------------------

@@ -716,11 +716,11 @@ struct Sim : SimBase {
            dv.nseg == 0 && !dv.junction_on && !dv.sort_vehicles && dv.obs_perm == nullptr;
   }
 
-  // the merge network in queue order (flowsim_queue.h): float32, IDM / RL / Sim slots, the multi-agent head, scheduled
-  // inflows, every replica stepping
+  // the merge network in queue order (flowsim_queue.h): float32, IDM / RL / Sim slots, either merge head (MergePOEnv,
+  // MultiAgentMergePOEnv), scheduled inflows, every replica stepping
   bool queue_ok(const StepArgs& a) const {
     if (!std::is_same<T, float>::value || !open_net || cfg.network != FS_NET_MERGE || no_queue || force_generic) return false;
-    if (dv.env != FS_ENV_MERGE_MA || !(dv.flags & fs::FLAG_IDM_SET) || !open_div_ok || ov.n_prob > 0) return false;
+    if ((dv.env != FS_ENV_MERGE_MA && dv.env != FS_ENV_MERGE_PO) || !(dv.flags & fs::FLAG_IDM_SET) || !open_div_ok || ov.n_prob > 0) return false;
     if (!(dv.flags & fs::FLAG_DELTA4) || (dv.flags & fs::FLAG_HAS_FAILSAFE) || dv.integrator != FS_EULER || !qc.ok) return false;
     if (a.mask != nullptr || a.num_steps < 1 || dv.N > 64) return false;
     for (const fs_inflow& f : inflows)
@@ -860,6 +860,9 @@ struct Sim : SimBase {
     if (pol->num_hidden < 1 || pol->num_hidden > 3 || pol->hidden_width != 32 || pol->activation != 0)
       why = "fs_policy model (1..3 hidden layers of 32 tanh units)";
     else if (!pol->weights_dev) why = "fs_policy.weights_dev (NULL)";
+    else if (dv.env == FS_ENV_MERGE_PO)                  // one network, num_rl action columns: fs_policy has no such output
+      why = "env (FS_ENV_MERGE_PO: one policy with num_rl action columns is not built; run the policy in torch around "
+            "the step, e.g. VecFlowEnv.capture)";
     else if (dv.env == FS_ENV_MERGE_MA) {                // agent c: the RL slot of column c, present while it holds a vehicle
       if (!ov.ma_apply_actions)
         why = "env (FS_ENV_MERGE_MA with ma_apply_actions = 0: the shipped MultiAgentMergePOEnv never applies an action, "

@@ -425,6 +425,10 @@ int fs_add_vehicle(fs_handle h, int replica, int slot, int route, double x, doub
  * "k_steps<FAST>", "k_steps<CSET>", "k_steps", "k_steps_ml", "k_steps_open" (also "<mixed>"), "k_steps_wide",
  * "k_merge_queue", "k_drop_queue", "k_obs_mixed"; "" before the first launch).  Diagnostics for tests and bench.py: which
  * configuration class a workload landed in (no reference counterpart).  The string is static.
+ * The queue-order kernel of the merge network (k_merge_queue) steps both merge heads, FS_ENV_MERGE_PO and
+ * FS_ENV_MERGE_MA, on FS_F32 / FS_F16S handles: IDM (delta = 4) / RL / SUMO-driven slots of one length without fail-safes,
+ * Euler, scheduled inflows, at most 64 slots, launches of one or more steps without a replica mask; every other launch
+ * of such a handle (warm-up, masked or zero-step launches) and every other configuration steps on k_steps_open.
  * The queue-order kernel of the lane-drop network (k_drop_queue) reports a replica that outgrew its layout (more than
  * 64 vehicles on one entry path, more than 8 arrivals in one sub-step) through fs_sync /
  * fs_get_state: FS_ERR_UNSUPPORTED with fs_last_error naming it; FLOWSIM_NO_QUEUE=1 in the environment of fs_create
@@ -465,7 +469,11 @@ const char* fs_last_kernel(fs_handle h);
  * logp = 0; a present agent draws as above, and the counter advances by one per step whether or not any agent is
  * present (the reference lists only the RL vehicles present, flow/envs/multiagent/merge.py:98-143).  Resets inside a
  * fragment: warmup_steps = 0.  ma_apply_actions = 0 (the shipped environment: actions never reach the simulator, roll it
- * out open loop), FS_MIXED / FS_F64 and handles off the queue kernel are refused by name. */
+ * out open loop), FS_MIXED / FS_F64 and handles off the queue kernel are refused by name.
+ * The single-agent merge (FS_ENV_MERGE_PO, singleagent_merge.py) is refused by name as well: its ONE policy maps the whole
+ * observation (5 num_rl values) to num_rl action columns, and fs_policy has no such output (the heads above have two
+ * output rows: mean, log std).  Run the policy around fs_step_dev -- VecFlowEnv.capture records K such steps as one
+ * graph; the step inside it is k_merge_queue. */
 typedef struct fs_policy {
   uint32_t struct_size;               /* sizeof(fs_policy) */
   int32_t obs_dim;                    /* must equal fs_obs_dim; shared agents: fs_obs_dim / num_rl */
