@@ -36,6 +36,9 @@ def parse_args(args):
     parser.add_argument('--rollout_size', type=int, default=100, help='env steps per rollout fragment')
     parser.add_argument('--checkpoint_path', type=str, default=None, help='rllib: checkpoint to restore')
     parser.add_argument('--replicas', type=int, default=1024, help='device: environment replicas in the handle')
+    parser.add_argument('--fuse_policy', action='store_true',
+                        help='device: roll an action-vector policy (singleagent_merge) out through the fused policy + '
+                             'step kernel instead of the captured graph')
     return parser.parse_known_args(args)[0]
 
 
@@ -90,7 +93,7 @@ def train_device(submodule, flags, multiagent=False):
     fp = submodule.flow_params
     fp['sim'].render = False
     return train_on_device(fp, replicas=flags.replicas, fragment=flags.rollout_size, iterations=flags.num_steps,
-                           shared_agents=multiagent)
+                           shared_agents=multiagent, fuse_action_vector=flags.fuse_policy and not multiagent)
 
 
 def main(args):

@@ -135,14 +135,18 @@ def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None):
 
 
 def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epochs=4, lr=3e-4, seed=0, log=print,
-                    rank=0, world=1, shared_agents=False):
+                    rank=0, world=1, shared_agents=False, fuse_action_vector=False):
     """PPO on R replicas of ``flow_params`` with everything in HBM: returns the mean step reward per iteration.
     ``world`` > 1: this process is rank ``rank`` of a data-parallel run (torch.distributed is initialised): it steps its
     block of the R replicas on its own GPU.
     ``shared_agents``: a multi-agent experiment whose agents share ONE policy (the reference's multi-agent ring /
     figure-eight / merge experiments map every agent to the policy 'av': examples/exp_configs/rl/multiagent/*.py
     policy_mapping_fn): the observation row holds one block per agent, the action row one column per agent; every agent
-    is a sample of the shared policy and receives the shared reward."""
+    is a sample of the shared policy and receives the shared reward.
+    ``fuse_action_vector``: an experiment whose ONE network emits several action columns (MergePOEnv:
+    singleagent_merge.py) rolls out through the fused policy + step kernel as well (k_merge_policy<PO>).  Off by default:
+    the fused form draws its samples from the library's Philox streams, the captured graph from torch.randn, so the two
+    are different (equally valid) trajectories."""
     from flow_amd.dist import allreduce_sum, shard_range
     from flow_amd.envs import VecFlowEnv
     local = int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else 0
@@ -167,7 +171,10 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     shared = "; one policy shared by %d agents per replica" % n_ag if shared_agents else ""
     try:
         from flow_amd.utils.device_policy import DevicePolicy
-        fused = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=pi.log_std, seed=seed)
+        if fuse_action_vector and not shared_agents:
+            fused = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=pi.log_std, seed=seed, act_dim=vec.act_dim)
+        else:
+            fused = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=pi.log_std, seed=seed)
         vec.reset()
         vec.policy_rollout(fused, 1, reset_done=True)           # (probe: raises NotImplementedError when not built)
         kernel = vec.sim.last_kernel

@@ -27,15 +27,31 @@ namespace fsim {
                        0);
     return launched();
   }
-  // the multi-agent merge with its agents sharing the policy: k_merge_queue's POLICY form (one wave per replica)
+  // the multi-agent merge with its agents sharing the policy: k_merge_queue's POLICY form (one wave per replica);
+  // MergePOEnv with its action-vector policy: k_merge_policy
   template <typename T>
   int Sim<T>::launch_policy_queue(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act,
                                   float* logp, float* rew, uint8_t* done) {
     const bool noise = (dv.flags & fs::FLAG_HAS_NOISE) != 0;
+    if (dv.env == FS_ENV_MERGE_PO) {
+      const auto kp = pick(noise, [&](auto NZ) { return &fs::k_merge_policy<NZ>; });
+      last_kernel = "k_merge_policy<PO>";
+      hipLaunchKernelGGL(kp, dim3(dv.R), dim3(64), 0, stream, dv, ov, qc, num_steps, obs, rew, done, pv, act, logp,
+                         reset_done);
+      return launched();
+    }
     const auto k = pick(noise, [&](auto NZ) { return &fs::k_merge_queue<NZ, true, true>; });
     last_kernel = "k_merge_policy";
     hipLaunchKernelGGL(k, dim3(dv.R), dim3(64), 0, stream, dv, ov, qc, num_steps, static_cast<const float*>(nullptr),
                        size_t(0), obs, rew, done, 1, pv, act, logp, reset_done);
+    return launched();
+  }
+  // the eager form of MergePOEnv's action-vector policy (one wave per replica, as in k_merge_policy)
+  template <typename T>
+  int Sim<T>::launch_policy_act_vec(const fs::PolicyView& pv, const float* obs_in, float* act, float* logp) {
+    last_kernel = "k_policy_act_vec";
+    hipLaunchKernelGGL(fs::k_policy_act_vec<16>, dim3(dv.R), dim3(64), 0, stream, pv, dv.R, dv.num_rl, dv.rep0, obs_in,
+                       act, logp);
     return launched();
   }
   template <typename T>

@@ -1288,7 +1288,7 @@ __global__ __launch_bounds__(64) void k_steps_open(DevView<T> s, OpenView<T> o, 
 
 // Env.reset of an open network for slot i of replica r: the initial vehicle back in its slot or the slot free, and (slot
 // 0) the replica's clocks and id counters restarted (restart_instance: SUMO starts again at time 0, envs/base.py:430-470);
-// S13: one step has run when reset returns.  Shared by k_reset_open and the in-fragment reset of k_merge_queue<POLICY>.
+// S13: one step has run when reset returns.  Shared by k_reset_open and the in-fragment resets of k_merge_queue<POLICY> and k_merge_policy.
 template <typename T>
 __device__ __forceinline__ void reset_open_slot(const DevView<T>& s, const OpenView<T>& o, int r, int i) {
   const int N = s.N;

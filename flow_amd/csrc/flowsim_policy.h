@@ -294,6 +294,156 @@ __global__ __launch_bounds__(256) void k_policy_act(PolicyView pv, int R, int n_
   if (r < R && j == 0) pv.ctr[r] = c0 + 1u;
 }
 
+// ---- the ACTION-VECTOR head (FS_ENV_MERGE_PO: MergePOEnv) ---------------------------------------------------------
+// ONE network maps the whole observation (in_dim = 5 A <= 32 values, A = num_rl) to A actions: the trunk of policy_eval's
+// WIDE form, then an output layer of n_out = 2 A rows (rows 0 .. A-1 the means, rows A .. 2A-1 the log stds: RLlib's
+// DiagGaussian order) or of A rows next to A free log stds.  A WAVE is one replica: its four 16-lane rows run the trunk
+// alike (a row holds the 32 units of a layer), every output is the row's tree sum, lane c of a row then samples column c
+// (Philox column 0x40000000 + c at the replica's counter: agent c's stream of the shared-policy heads) and the wave
+// adds the columns' log-probabilities in ascending order.  policy_vec_act is the ONE definition: k_policy_act_vec (eager)
+// and k_merge_policy (fused, flowsim_queue.h) both call it, so they agree bit for bit by construction.
+constexpr int FS_POLICY_VEC_MAX = 6;                      // 5 A <= 32: the WIDE first layer
+
+struct alignas(16) PolicyVecLds {
+  float w_out[2 * FS_POLICY_VEC_MAX][32];                  // [output][unit]
+  float b_out[2 * FS_POLICY_VEC_MAX];
+  float log_std[FS_POLICY_VEC_MAX];                        // the free log stds (pv.log_std != NULL)
+  float lp[16];                                            // the columns' log-probabilities of a step
+};
+
+// weights -> LDS, once per launch: the trunk through policy_load (which takes the head for one of <= 2 rows: none here),
+// the output layer from where the trunk ends in pv.w.  Ends with policy_load's barrier.
+__device__ __forceinline__ void policy_vec_load(const PolicyView& pv, int A, PolicyLds* L, PolicyVecLds* V, int tid,
+                                                int nthreads) {
+  const float* p = pv.w + 32 * pv.in_dim + 32 + (pv.num_hidden - 1) * (32 * 32 + 32);
+  const int n_out = pv.n_out;                              // A or 2 A
+  for (int e = tid; e < 2 * FS_POLICY_VEC_MAX * 32; e += nthreads) V->w_out[e / 32][e % 32] = (e / 32) < n_out ? p[e] : 0.0f;
+  for (int e = tid; e < 2 * FS_POLICY_VEC_MAX; e += nthreads) V->b_out[e] = e < n_out ? p[n_out * 32 + e] : 0.0f;
+  for (int e = tid; e < FS_POLICY_VEC_MAX; e += nthreads) V->log_std[e] = (pv.log_std != nullptr && e < A) ? pv.log_std[e] : 0.0f;
+  PolicyView trunk = pv;
+  trunk.n_out = 0;
+  policy_load(trunk, L, tid, nthreads);
+}
+
+// the trunk of policy_eval<16, WIDE> -- its statements, in its order: the first layer on two inputs per lane, the hidden
+// layers with four accumulators and the weight quads read one layer ahead -- returning the last layer's units j and j + 16
+// (policy_eval itself ends in the two-output head, and its code generation is held to recorded figures: tests/test_codegen.py)
+__device__ __forceinline__ void policy_trunk_wide(const PolicyView& pv, const PolicyLds* L, int j, float o0, float o1,
+                                                  float& ha, float& hb) {
+  float4 wa0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), wa1 = wa0;
+  auto load_ahead = [&](int l) {
+    wa0 = *reinterpret_cast<const float4*>(L->w_hid[l][0][j]);
+    wa1 = *reinterpret_cast<const float4*>(L->w_hid[l][1][j]);
+  };
+  if (pv.num_hidden > 1) load_ahead(0);
+  // one layer: z[u] = b[u] + sum_i W[u][i] in[i]; input i < 16 is `a` of lane i, input i >= 16 `b` of lane i - 16
+  auto layer = [&](const float4 (&ww)[16], float bj, float bj16, float a, float b) {
+    f2 z0 = {bj, bj16}, z1 = {0.0f, 0.0f}, z2 = {0.0f, 0.0f}, z3 = {0.0f, 0.0f};
+    static_for<4>([&](auto q_c) {
+      constexpr int q = decltype(q_c)::value;
+      const float a0 = dpp<DPP_ROW_NEWBCAST0 + 4 * q>(a), a1 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 1>(a);
+      const float a2 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 2>(a), a3 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 3>(a);
+      const float b0 = dpp<DPP_ROW_NEWBCAST0 + 4 * q>(b), b1 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 1>(b);
+      const float b2 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 2>(b), b3 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 3>(b);
+      z0 = fma2(f2{ww[2 * q].x, ww[2 * q].y}, splat(a0), z0);
+      z1 = fma2(f2{ww[2 * q].z, ww[2 * q].w}, splat(a1), z1);
+      z2 = fma2(f2{ww[2 * q + 1].x, ww[2 * q + 1].y}, splat(a2), z2);
+      z3 = fma2(f2{ww[2 * q + 1].z, ww[2 * q + 1].w}, splat(a3), z3);
+      z0 = fma2(f2{ww[8 + 2 * q].x, ww[8 + 2 * q].y}, splat(b0), z0);
+      z1 = fma2(f2{ww[8 + 2 * q].z, ww[8 + 2 * q].w}, splat(b1), z1);
+      z2 = fma2(f2{ww[8 + 2 * q + 1].x, ww[8 + 2 * q + 1].y}, splat(b2), z2);
+      z3 = fma2(f2{ww[8 + 2 * q + 1].z, ww[8 + 2 * q + 1].w}, splat(b3), z3);
+    });
+    return pk_add(pk_add(z0, z1), pk_add(z2, z3));
+  };
+  {
+    float4 ww[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) ww[q] = *reinterpret_cast<const float4*>(L->w_wide[q][j]);
+    const f2 z = layer(ww, L->b[0][j], L->b[0][j + 16], o0, o1);
+    ha = policy_tanh(z.x);
+    hb = policy_tanh(z.y);
+  }
+#pragma unroll 1
+  for (int l = 0; l + 1 < pv.num_hidden; ++l) {
+    float4 ww[16];
+    ww[0] = wa0;
+    ww[1] = wa1;
+#pragma unroll
+    for (int q = 2; q < 16; ++q) ww[q] = *reinterpret_cast<const float4*>(L->w_hid[l][q][j]);
+    const f2 z = layer(ww, L->b[l + 1][j], L->b[l + 1][j + 16], ha, hb);
+    if (l + 2 < pv.num_hidden) load_ahead(l + 1);        // (wave-uniform)
+    ha = policy_tanh(z.x);
+    hb = policy_tanh(z.y);
+  }
+}
+
+// The A actions and the joint log-probability of ONE replica, computed by its wave (lane = 0 .. 63).  `o`: the replica's
+// observation, 5 A floats (LDS or global); act_row [>= 16 floats of LDS]: columns 0 .. A-1 receive the samples (the rest
+// of its first 16 entries zero).  Returns the joint log-probability: the columns' values added in ascending order.
+// nzb (a fragment): this lane's Philox block kept over four steps (NoiseBlock::draw is gauss() bit for bit).
+__device__ __forceinline__ float policy_vec_act(const PolicyView& pv, int A, const PolicyLds* L, PolicyVecLds* V,
+                                                uint32_t replica, uint32_t ctr, int lane, const float* o, float* act_row,
+                                                NoiseBlock<float>* nzb = nullptr) {
+  const int j = lane & 15, half = policy_half(pv.in_dim);
+  // k_policy_act's WIDE layout: lane j < half holds inputs j and half + j (the latter if < in_dim)
+  const float ia = j < half ? o[j < half ? j : 0] : 0.0f;
+  const float ib = (j < half && half + j < pv.in_dim) ? o[half + j < pv.in_dim ? half + j : 0] : 0.0f;
+  float ha, hb;
+  policy_trunk_wide(pv, L, j, ia, ib, ha, hb);
+  // the outputs: each the row's tree sum of the lanes' two products (policy_eval's head); lane c keeps column c's
+  const bool free_ls = pv.log_std != nullptr;
+  float mu = 0.0f, ls = 0.0f;
+#pragma unroll 1
+  for (int c = 0; c < A; ++c) {
+    float p0 = V->w_out[c][j] * ha;
+    p0 = __builtin_fmaf(V->w_out[c][j + 16], hb, p0);
+    const float m = seg_sum<16>(p0) + V->b_out[c];
+    float l = V->log_std[c];
+    if (!free_ls) {                                        // (wave-uniform)
+      float p1 = V->w_out[A + c][j] * ha;
+      p1 = __builtin_fmaf(V->w_out[A + c][j + 16], hb, p1);
+      l = seg_sum<16>(p1) + V->b_out[A + c];
+    }
+    mu = j == c ? m : mu;
+    ls = j == c ? l : ls;
+  }
+  // every lane samples its column (lanes beyond the A columns: values nobody reads)
+  float a, lp;
+  policy_sample(pv, replica, ctr, mu, ls, a, lp, nzb, uint32_t(j));
+  if (lane < 16) {
+    act_row[lane] = lane < A ? a : 0.0f;
+    V->lp[lane] = lane < A ? lp : 0.0f;
+  }
+  asm volatile("" ::: "memory");                           // (one wave: the hardware keeps its DS instructions in order)
+  float logp = V->lp[0];
+#pragma unroll 1
+  for (int c = 1; c < A; ++c) logp = logp + V->lp[c];
+  asm volatile("" ::: "memory");
+  return logp;
+}
+
+// eager form of the action-vector head: obs [R, 5 A] -> act [R, A], logp [R]; one wave per replica; the replica's counter
+// advances by ONE per call
+template <int ROW>     // (a template so that every object of the library may include this header)
+__global__ __launch_bounds__(64) void k_policy_act_vec(PolicyView pv, int R, int A, uint32_t rep0,
+                                                       const float* __restrict__ obs, float* __restrict__ act,
+                                                       float* __restrict__ logp) {
+  static_assert(ROW == 16, "k_policy_act_vec: a row of 16 lanes holds the 32 units of a layer");
+  __shared__ PolicyLds L;
+  __shared__ PolicyVecLds V;
+  __shared__ float act_row[16];
+  const int lane = threadIdx.x, r = blockIdx.x;            // (grid = R)
+  policy_vec_load(pv, A, &L, &V, lane, 64);
+  const uint32_t c0 = pv.ctr[r];
+  const float lp = policy_vec_act(pv, A, &L, &V, rep0 + uint32_t(r), c0, lane, obs + size_t(r) * pv.in_dim, act_row);
+  if (lane < A) act[size_t(r) * A + lane] = act_row[lane];
+  if (lane == 0) {
+    logp[r] = lp;
+    pv.ctr[r] = c0 + 1u;
+  }
+}
+
 // K x (policy -> action -> Env.step [-> reset of a finished episode]) for rings of IDM vehicles and RL vehicles.
 // HEAD 1: WaveAttenuationPOEnv, ONE RL vehicle: obs [K+1, R, 3] (obs[0]: the observation of the state the fragment starts
 // from), act [K, R], logp [K, R], rew [K, R], done [K, R].

@@ -65,7 +65,8 @@ struct alignas(16) QueueRow {
   int ctrl, speed_mode, rl_index;
 };
 
-// POLICY (k_merge_policy: fs_policy_rollout_dev): one policy shared by the agents, in the loop.  Agent c is the RL slot
+// POLICY (fs_last_kernel "k_merge_policy": fs_policy_rollout_dev on the multi-agent head): one policy shared by the
+// agents, in the loop.  Agent c is the RL slot
 // of column c (rl_index c); it is present when that slot holds a vehicle in the state its observation is taken from.
 // Per env step the head's five features of every present agent wait in LDS by column; the present columns, compacted
 // with a ballot, go four to a pass onto the wave's 16-lane rows, and each row runs policy_eval / policy_sample (what
@@ -87,16 +88,27 @@ struct alignas(16) QueueRow {
 // one wave-uniform flag that the events and the pass itself recompute; every other sub-step skips the bookkeeping.
 // A collision ends the env step on this head: the replica's remaining sub-steps do not run (k_steps_open freezes them:
 // no movement, no insertion, no list change, no counter advances), reward 0, the crash bit of `done`.
-template <bool NOISE, bool ACT, bool POLICY = false, bool PO = false>
-__global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<float> o, QueueConsts qc, int num_steps,
-                                                    const float* __restrict__ actions, size_t act_stride,
-                                                    float* __restrict__ obs, float* __restrict__ rew,
-                                                    uint8_t* __restrict__ done, int obs_every_step, PolicyView pv,
-                                                    float* __restrict__ act_out, float* __restrict__ logp_out,
-                                                    int reset_done) {
+//
+// POLICY && PO (k_merge_policy<PO>, the kernel at the end of this file): MergePOEnv's ONE network maps the whole
+// observation to num_rl accelerations (flowsim_policy.h: the action-vector head).  The head leaves the observation --
+// the blocks by place, ghosts and empty places included -- in LDS as well; per env step the wave evaluates the network
+// ONCE (policy_vec_act: what k_policy_act_vec runs), the num_rl samples go to act_out [K, R, num_rl] and into the action
+// row po_action() reads, their joint log-probability to logp_out [K, R]; every column is sampled every step.
+// reset_done: a collision ends the episode on this head, so a replica is reset in place when its `done` byte is not
+// zero -- the horizon or a collision.  The reset is fs_reset_dev's: the state goes to its slots first, because
+// reset_open_slot keeps the entries of rl_veh (ctl_seq, read with the slots' origins) and the join counter.
+//
+// The body is merge_queue_body, a device function that the two __global__ wrappers at the end of the file inline.
+template <bool NOISE, bool ACT, bool POLICY, bool PO>
+__device__ __forceinline__ void merge_queue_body(const DevView<float>& s, const OpenView<float>& o, const QueueConsts& qc,
+                                                 int num_steps, const float* __restrict__ actions, size_t act_stride,
+                                                 float* __restrict__ obs, float* __restrict__ rew,
+                                                 uint8_t* __restrict__ done, int obs_every_step, const PolicyView& pv,
+                                                 float* __restrict__ act_out, float* __restrict__ logp_out,
+                                                 int reset_done) {
   using T = float;
   static_assert(!POLICY || ACT, "k_merge_queue: the policy's actions take the ACT path");
-  static_assert(!(POLICY && PO), "k_merge_queue: the fused policy is built for the multi-agent head only");
+  constexpr bool VEC = POLICY && PO;                   // the action-vector head: one network, num_rl action columns
   const T BIGV = 3.0e38f;
   const int lane = threadIdx.x;
   const int r = blockIdx.x;                       // one replica per wave (grid = R)
@@ -113,9 +125,12 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
   __shared__ float feat[5][64], lp_row[64];       // (POLICY) the features by column, the log-probabilities of a step
   __shared__ int pcol[64];                        // (POLICY) the present columns, compacted
   __shared__ int place_row[64];                   // (PO) the place in rl_veh of every slot, -1: not listed
+  __shared__ PolicyVecLds PV;                     // (VEC) the output layer of the action-vector head
+  __shared__ float obs_row[32];                   // (VEC) the observation of the current state: the network's input
   OpenTabs<T, true> tb;
   tb.load(o, lane, false, &tabs_mem);
-  if constexpr (POLICY) policy_load(pv, &PL, lane, 64);
+  if constexpr (VEC) policy_vec_load(pv, s.num_rl, &PL, &PV, lane, 64);
+  else if constexpr (POLICY) policy_load(pv, &PL, lane, 64);
 
   // ---- the slot tables as LDS rows --------------------------------------------------------------------------
   {
@@ -766,25 +781,42 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
     if constexpr (PO) {
       // block i = the vehicle at place i of rl_veh (merge.py:117-158); a listed slot without a vehicle: the accessors'
       // error values; places beyond the list: zero
+      // (VEC: every value goes to obs_row as well -- the three cases cover the 5 num_rl entries)
       if (obs_out && alive && k_rl && my_place >= 0 && my_place < s.num_rl) {
 #pragma unroll
         for (int q = 0; q < 5; ++q) orow[5 * my_place + q] = f5[q];
+        if constexpr (VEC) {
+#pragma unroll
+          for (int q = 0; q < 5; ++q) obs_row[5 * my_place + q] = f5[q];
+        }
       }
       const int pl_s = place_row[lane];                // (slot view)
       q_fence();
       if (obs_out && pl_s >= 0 && pl_s < s.num_rl && !((alive_lab >> lane) & 1ull)) {
         const T gs = -1001.0f;
-        orow[5 * pl_s + 0] = div_via_f64(gs, ms64, rc_ms64);
-        orow[5 * pl_s + 1] = div_via_f64(s.max_speed - gs, ms64, rc_ms64);
-        orow[5 * pl_s + 2] = div_via_f64(o.net_length, nl64, rc_nl64);
-        orow[5 * pl_s + 3] = div_via_f64(gs - 0.0f, ms64, rc_ms64);
-        orow[5 * pl_s + 4] = div_via_f64(o.net_length, nl64, rc_nl64);
+        T g5[5];
+        g5[0] = div_via_f64(gs, ms64, rc_ms64);
+        g5[1] = div_via_f64(s.max_speed - gs, ms64, rc_ms64);
+        g5[2] = div_via_f64(o.net_length, nl64, rc_nl64);
+        g5[3] = div_via_f64(gs - 0.0f, ms64, rc_ms64);
+        g5[4] = div_via_f64(o.net_length, nl64, rc_nl64);
+#pragma unroll
+        for (int q = 0; q < 5; ++q) orow[5 * pl_s + q] = g5[q];
+        if constexpr (VEC) {
+#pragma unroll
+          for (int q = 0; q < 5; ++q) obs_row[5 * pl_s + q] = g5[q];
+        }
       }
       const int n_ctl = __popcll(__ballot(pl_s >= 0));
       if (obs_out && lane < s.num_rl && lane >= n_ctl) {
 #pragma unroll
         for (int q = 0; q < 5; ++q) orow[5 * lane + q] = 0.0f;
+        if constexpr (VEC) {
+#pragma unroll
+          for (int q = 0; q < 5; ++q) obs_row[5 * lane + q] = 0.0f;
+        }
       }
+      if constexpr (VEC) q_fence();
     } else if (obs_out && alive && k_rl) {
       const int col = rows[lab & 63].rl_index;
 #pragma unroll
@@ -890,6 +922,10 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
   auto restart = [&](bool reset) {
     __threadfence_block();                           // (the stores of retire() land before the slots are written again)
     if (reset) {
+      if constexpr (PO) {                            // reset_open_slot reads the list, the origins and the join counter
+        store_state();
+        __threadfence_block();
+      }
       if (lane < N) {
         reset_open_slot(s, o, r, lane);
         if (s.st16 != nullptr) state16_store(s, base + lane, s.pos[base + lane], s.vel[base + lane]);
@@ -914,6 +950,10 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
       foll = foll_n;
       foll_h = foll_h_n;
     }
+    if constexpr (PO) {                              // (as at launch start)
+      po_places();
+      po_dirty = po_pending();
+    }
   };
 
   asm volatile("" :: "v"(x), "v"(v), "v"(route), "v"(seq), "v"(origin), "v"(foll), "v"(foll_h), "v"(prev_v), "v"(last_acc), "v"(vmax));
@@ -934,8 +974,18 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
   const int act_lane = lane < s.num_rl ? lane : 0;
   float a_pref = 0.0f;
   if (ACT && !POLICY && num_steps > 0) a_pref = actions[size_t(r) * s.num_rl + act_lane];
+  NoiseBlock<float> act_draws;                       // (VEC) my column's Philox block, kept over four steps
+  act_draws.init();
   for (int step = 0; step < num_steps; ++step) {
-    if constexpr (POLICY) {
+    if constexpr (VEC) {
+      // ---- the policy, ONCE: the observation in obs_row -> num_rl samples in the action row ----------------------
+      const int n_ag = s.num_rl;
+      const float lp = policy_vec_act(pv, n_ag, &PL, &PV, s.rep0 + uint32_t(r), pctr, lane, obs_row, act_row, &act_draws);
+      if (lane < n_ag) act_out[(size_t(step) * s.R + r) * n_ag + lane] = act_row[lane];
+      if (lane == 0) logp_out[size_t(step) * s.R + r] = lp;
+      pctr += 1u;
+      po_action();
+    } else if constexpr (POLICY) {
       // ---- the policy: the present agents' actions, by column, into the action row ------------------------------
       const int n_ag = s.num_rl;
       const unsigned long long pm = __ballot(slot_is_rl && ((alive_lab >> lane) & 1ull));   // (slot view) present RL slots
@@ -1124,7 +1174,8 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
       // (POLICY) the episode ended (the horizon; crash is always 0): reset in place, the observation is the new
       // episode's.  FS_F16S: eager stepping rounds the state through halves between steps, and fs_reset_dev(done)
       // observes every replica again from what was stored -- so does the fragment
-      const bool fin = POLICY && reset_done && tcount >= s.step_limit;
+      // (PO: a collision ends the episode too -- the replica is reset whenever its `done` byte is not zero)
+      const bool fin = POLICY && reset_done && (tcount >= s.step_limit || (PO && crashed));
       const bool again = POLICY && (fin || s.st16 != nullptr);
       head(!again, true);
       if constexpr (POLICY) {
@@ -1151,6 +1202,31 @@ __global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<f
   // ---- the state back to its slots -----------------------------------------------------------------------------
   __threadfence();
   store_state();
+}
+
+// the step forms of both heads (POLICY = 0) and the shared policy of the multi-agent head (POLICY = 1, PO = 0)
+template <bool NOISE, bool ACT, bool POLICY = false, bool PO = false>
+__global__ __launch_bounds__(64) void k_merge_queue(DevView<float> s, OpenView<float> o, QueueConsts qc, int num_steps,
+                                                    const float* __restrict__ actions, size_t act_stride,
+                                                    float* __restrict__ obs, float* __restrict__ rew,
+                                                    uint8_t* __restrict__ done, int obs_every_step, PolicyView pv,
+                                                    float* __restrict__ act_out, float* __restrict__ logp_out,
+                                                    int reset_done) {
+  static_assert(!(POLICY && PO), "k_merge_queue: MergePOEnv's fused policy is k_merge_policy");
+  merge_queue_body<NOISE, ACT, POLICY, PO>(s, o, qc, num_steps, actions, act_stride, obs, rew, done, obs_every_step, pv,
+                                           act_out, logp_out, reset_done);
+}
+
+// MergePOEnv with its action-vector policy in the loop (fs_last_kernel "k_merge_policy<PO>"): obs [K+1, R, 5 num_rl],
+// act [K, R, num_rl], logp / rew / done [K, R]
+template <bool NOISE>
+__global__ __launch_bounds__(64) void k_merge_policy(DevView<float> s, OpenView<float> o, QueueConsts qc, int num_steps,
+                                                     float* __restrict__ obs, float* __restrict__ rew,
+                                                     uint8_t* __restrict__ done, PolicyView pv,
+                                                     float* __restrict__ act_out, float* __restrict__ logp_out,
+                                                     int reset_done) {
+  merge_queue_body<NOISE, true, true, true>(s, o, qc, num_steps, nullptr, 0, obs, rew, done, 1, pv, act_out, logp_out,
+                                            reset_done);
 }
 
 }  // namespace fs

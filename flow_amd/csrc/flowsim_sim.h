@@ -784,7 +784,8 @@ struct Sim : SimBase {
   // ---- the launches, one per kernel family: flowsim_launch.h, compiled into the parts (flowsim_part.hip) ----
   int launch_queue(const StepArgs& a);       // float32 (the queue part)
   int launch_policy_queue(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act, float* logp,
-                          float* rew, uint8_t* done);    // float32 (the queue part): the multi-agent merge's policy
+                          float* rew, uint8_t* done);    // float32 (the queue part): the merge heads' fused policies
+  int launch_policy_act_vec(const fs::PolicyView& pv, const float* obs_in, float* act, float* logp);   // (the queue part)
   int launch_dropq(const StepArgs& a);       // float32 (the queue part)
   template <int W>
   int launch_wide(const StepArgs& a);        // one workgroup of W waves per replica
@@ -844,7 +845,8 @@ struct Sim : SimBase {
   // policy in the loop (flowsim_policy.h; flowsim_launch.h): the eager policy, the fused policy + step kernels of rings
   // (rows of 16 lanes: 18..32 vehicles) and of segment-table loops (the figure eight: up to 16 vehicles); n_ag agents
   // share the policy on the multi-agent heads (MultiAgentWaveAttenuationPOEnv on rings, MultiAgentAccelPOEnv on loops,
-  // MultiAgentMergePOEnv with its actions applied on the merge's queue kernel: k_merge_queue<POLICY>)
+  // MultiAgentMergePOEnv with its actions applied on the merge's queue kernel: k_merge_queue<POLICY>); MergePOEnv's ONE
+  // network with num_rl action columns: k_policy_act_vec (eager) and k_merge_policy (fused)
   int launch_policy_act(const fs::PolicyView& pv, int n_ag, const float* obs_in, float* act, float* logp);
   int launch_policy_row16(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act, float* logp,
                           float* rew, uint8_t* done);
@@ -860,9 +862,22 @@ struct Sim : SimBase {
     if (pol->num_hidden < 1 || pol->num_hidden > 3 || pol->hidden_width != 32 || pol->activation != 0)
       why = "fs_policy model (1..3 hidden layers of 32 tanh units)";
     else if (!pol->weights_dev) why = "fs_policy.weights_dev (NULL)";
-    else if (dv.env == FS_ENV_MERGE_PO)                  // one network, num_rl action columns: fs_policy has no such output
-      why = "env (FS_ENV_MERGE_PO: one policy with num_rl action columns is not built; run the policy in torch around "
-            "the step, e.g. VecFlowEnv.capture)";
+    else if (dv.env == FS_ENV_MERGE_PO) {                // ONE network: the whole observation -> num_rl action columns
+      if (!std::is_same<T, float>::value || mixed)
+        why = "precision (FS_ENV_MERGE_PO is FS_F32 / FS_F16S only: FS_MIXED / FS_F64 handles are not built)";
+      else if (dv.num_rl < 1 || 5 * dv.num_rl > 32)
+        why = "num_rl (FS_ENV_MERGE_PO: the network's first layer takes 5 num_rl <= 32 inputs, num_rl <= 6 -- EXP_NUM 1 "
+              "and 2 of singleagent_merge.py have 13 and 17; run the policy in torch around the step, e.g. "
+              "VecFlowEnv.capture)";
+      else if (pol->obs_dim != obs_dim)
+        why = "fs_policy.obs_dim (FS_ENV_MERGE_PO: the whole observation, fs_obs_dim = 5 num_rl; the output layer has "
+              "num_rl rows next to num_rl free log stds, or 2 num_rl)";
+      else if (!queue_ok(StepArgs{num_steps > 0 ? num_steps : 1, nullptr, nullptr, 0, obs, rew, done, 1}))
+        why = "configuration (FS_ENV_MERGE_PO: what k_merge_queue steps, Sim::queue_ok: IDM / RL / Sim slots without "
+              "fail-safes, one vehicle length, Euler, scheduled inflows only, FLOWSIM_NO_QUEUE unset)";
+      else if (obs != nullptr && reset_done && cfg.warmup_steps != 0)
+        why = "configuration (FS_ENV_MERGE_PO: resets inside a fragment: warmup_steps = 0)";
+    }
     else if (dv.env == FS_ENV_MERGE_MA) {                // agent c: the RL slot of column c, present while it holds a vehicle
       if (!ov.ma_apply_actions)
         why = "env (FS_ENV_MERGE_MA with ma_apply_actions = 0: the shipped MultiAgentMergePOEnv never applies an action, "
@@ -932,12 +947,16 @@ struct Sim : SimBase {
     pv.in_dim = pol->obs_dim;
     pv.num_hidden = pol->num_hidden;
     pv.n_out = pol->log_std_dev ? 1 : 2;
+    if (dv.env == FS_ENV_MERGE_PO) pv.n_out *= dv.num_rl;  // the action-vector head: num_rl means [and num_rl log stds]
     pv.seed_lo = uint32_t(pol->seed & 0xFFFFFFFFull);
     pv.seed_hi = uint32_t(pol->seed >> 32);
-    if (obs == nullptr) return launch_policy_act(pv, ma ? dv.num_rl : 1, obs_in, act, logp);      // eager: the policy alone
     if constexpr (std::is_same<T, float>::value) {
-      if (dv.env == FS_ENV_MERGE_MA) return launch_policy_queue(pv, num_steps, reset_done, obs, act, logp, rew, done);
+      if (dv.env == FS_ENV_MERGE_PO && obs == nullptr) return launch_policy_act_vec(pv, obs_in, act, logp);
+      if (dv.env == FS_ENV_MERGE_MA || dv.env == FS_ENV_MERGE_PO) {
+        if (obs != nullptr) return launch_policy_queue(pv, num_steps, reset_done, obs, act, logp, rew, done);
+      }
     }
+    if (obs == nullptr) return launch_policy_act(pv, ma ? dv.num_rl : 1, obs_in, act, logp);      // eager: the policy alone
     if (loop) return launch_policy_loop16(pv, num_steps, reset_done, obs, act, logp, rew, done);
     return launch_policy_row16(pv, num_steps, reset_done, obs, act, logp, rew, done);
   }

@@ -282,7 +282,11 @@ class VecFlowEnv(object):
         ``APPLY_ENUMERATE_QUIRK = False``) has the same layout with five values per agent; agent c is the RL slot of
         column c, and while that slot holds no vehicle the agent is absent: its action is NaN (no command), its
         log-probability 0.  The shipped merge environment never applies an action and is refused (roll it out open
-        loop).  ``capture`` serves every other environment / model."""
+        loop).  The single-agent merge (MergePOEnv, ``num_rl`` <= 6) takes ONE network with an action vector
+        (``DevicePolicy(..., act_dim=num_rl)``: the whole observation in, ``num_rl`` accelerations out): ``actions`` is
+        ``[K, R, num_rl]`` -- every column sampled every step, the environment ignores those beyond its list of controlled
+        vehicles -- and ``logp [K, R]`` the joint log-probability; with ``reset_done`` a replica is reset when its
+        ``done`` byte is not zero, collisions included.  ``capture`` serves every other environment / model."""
         torch, R, K = self.torch, self.num_envs, int(num_steps)
         self.use_current_stream()
         if reset_done and self._resample and not getattr(self, "_warned_pending_length", False):
@@ -294,9 +298,11 @@ class VecFlowEnv(object):
                           "and keep fragments shorter than an episode if each episode must draw its own.", stacklevel=2)
         n_ag = self.sim.policy_agents
         per_agent = (K, R) if n_ag == 1 else (K, R, n_ag)
+        a_dim = self.sim.policy_action_dim               # (MergePOEnv: one evaluation, num_rl columns, one log-probability)
+        per_act = per_agent if a_dim == 1 else (K, R, a_dim)
         if out is None:
             out = (torch.empty((K + 1, R, self.obs_dim), dtype=torch.float32, device=self.device),
-                   torch.empty(per_agent, dtype=torch.float32, device=self.device),
+                   torch.empty(per_act, dtype=torch.float32, device=self.device),
                    torch.empty(per_agent, dtype=torch.float32, device=self.device),
                    torch.empty((K, R), dtype=torch.float32, device=self.device),
                    torch.empty((K, R), dtype=torch.uint8, device=self.device))

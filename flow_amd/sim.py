@@ -267,12 +267,20 @@ class FlowSim:
         ma = env in (L.FS_ENV_WAVE_ATTENUATION_PO_MA, L.FS_ENV_ACCEL_PO_MA, L.FS_ENV_MERGE_MA)
         return max(self.num_rl, 1) if ma else 1
 
+    @property
+    def policy_action_dim(self):
+        """Action columns of ONE policy evaluation: num_rl on MergePOEnv (FS_ENV_MERGE_PO: one network maps the whole
+        observation to num_rl accelerations, with one joint log-probability), 1 otherwise."""
+        return max(self.num_rl, 1) if int(self.spec.get("env", L.FS_ENV_ACCEL)) == L.FS_ENV_MERGE_PO else 1
+
     def policy_act_dev(self, pol, obs, act, logp):
-        """act / logp [R] (one agent) or [R, policy_agents] for the observations obs [R, obs_dim]."""
+        """act / logp [R] (one agent) or [R, policy_agents] for the observations obs [R, obs_dim]; MergePOEnv:
+        act [R, policy_action_dim], logp [R]."""
         L.check(self.lib.fs_policy_act_dev(self._h, C.byref(pol), _ptr(obs), _ptr(act), _ptr(logp)), self.lib)
 
     def policy_rollout_dev(self, pol, num_steps, obs, act, logp, rew, done, reset_done=False):
-        """obs [K+1, R, obs_dim]; act / logp [K, R] (one agent) or [K, R, policy_agents]; rew / done [K, R]."""
+        """obs [K+1, R, obs_dim]; act / logp [K, R] (one agent) or [K, R, policy_agents]; rew / done [K, R].
+        MergePOEnv: act [K, R, policy_action_dim], logp [K, R]."""
         L.check(self.lib.fs_policy_rollout_dev(self._h, C.byref(pol), int(num_steps), int(bool(reset_done)), _ptr(obs),
                                                _ptr(act), _ptr(logp), _ptr(rew), _ptr(done)), self.lib)
 

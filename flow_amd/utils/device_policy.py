@@ -13,21 +13,28 @@ from flow_amd import _lib as L
 class DevicePolicy(object):
     """``hidden``: the ``nn.Linear`` layers of the trunk (1..3, 32 units each, tanh between them); ``head``: the output
     ``nn.Linear`` (2 outputs = mean and log std; 1 output with ``log_std`` a 1-element parameter / tensor).  ``sync()``
-    copies the current parameter values into the packed device buffer (call it after every optimiser step)."""
+    copies the current parameter values into the packed device buffer (call it after every optimiser step).
 
-    def __init__(self, hidden, head, log_std=None, seed=0):
+    ``act_dim`` > 1: ONE network with an action vector (MergePOEnv, ``FlowSim.policy_action_dim``): ``head`` has
+    ``2 * act_dim`` outputs -- the means, then the log stds: RLlib's DiagGaussian order -- or ``act_dim`` outputs with
+    ``log_std`` of ``act_dim`` elements.  The packed buffer is the same: per layer W [out][in] row-major, then b [out]."""
+
+    def __init__(self, hidden, head, log_std=None, seed=0, act_dim=1):
         import torch
         self.torch = torch
         self.hidden, self.head, self.log_std_param = list(hidden), head, log_std
+        self.act_dim = A = int(act_dim)
         if not 1 <= len(self.hidden) <= 3 or any(l.out_features != 32 for l in self.hidden):
             raise NotImplementedError("DevicePolicy: 1..3 hidden layers of 32 units (the kernel's model class)")
-        n_out = 1 if log_std is not None else 2
-        if head.out_features != n_out or head.in_features != 32:
+        n_out = A if log_std is not None else 2 * A
+        if A < 1 or head.out_features != n_out or head.in_features != 32:
             raise NotImplementedError("DevicePolicy: the head maps 32 units to %d output(s)" % n_out)
+        if log_std is not None and log_std.numel() != A:
+            raise NotImplementedError("DevicePolicy: log_std has %d element(s), one per action column" % A)
         dev = head.weight.device
         n = sum(l.weight.numel() + l.bias.numel() for l in self.hidden) + head.weight.numel() + head.bias.numel()
         self.buf = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.ls = torch.zeros(1, dtype=torch.float32, device=dev) if log_std is not None else None
+        self.ls = torch.zeros(A, dtype=torch.float32, device=dev) if log_std is not None else None
         self.struct = L.fs_policy(struct_size=C.sizeof(L.fs_policy), obs_dim=self.hidden[0].in_features,
                                   num_hidden=len(self.hidden), hidden_width=32, activation=0,
                                   weights_dev=self.buf.data_ptr(),
@@ -42,15 +49,21 @@ class DevicePolicy(object):
                 parts += [l.weight.reshape(-1), l.bias.reshape(-1)]
             self.buf.copy_(torch.cat([p.detach().float() for p in parts]))
             if self.ls is not None:
-                self.ls.copy_(self.log_std_param.detach().float().reshape(1))
+                self.ls.copy_(self.log_std_param.detach().float().reshape(self.act_dim))
 
     def reference(self, obs):
-        """(mean, log std) of the same network evaluated by torch (float32): agrees with the kernels to ~1e-6."""
+        """(mean, log std) of the same network evaluated by torch (float32): agrees with the kernels to ~1e-6.
+        ``act_dim`` > 1: both are ``[..., act_dim]``."""
         torch = self.torch
         h = obs
         for l in self.hidden:
             h = torch.tanh(l(h))
         out = self.head(h)
+        A = self.act_dim
+        if A > 1:
+            if self.ls is not None:
+                return out, self.log_std_param.reshape(A).expand_as(out)
+            return out[..., :A], out[..., A:]
         if self.ls is not None:
             return out[..., 0], self.log_std_param.reshape(1).expand_as(out[..., 0])
         return out[..., 0], out[..., 1]

@@ -421,7 +421,8 @@ int fs_add_vehicle(fs_handle h, int replica, int slot, int route, double x, doub
 /* Family of the step kernel the handle's last fs_step / fs_rollout / fs_policy_rollout launch chose ("k_rollout_pair" with
  * "+speed_mode" and / or "+noise", "k_rollout_idm", "k_ring_pair<Accel | PO | POMA | AccelMA>", "k_rollout_loop",
  * "k_rollout_loop<FULL>", "k_rollout_loop<AccelMA>", "k_rollout_loop<FULL,AccelMA>", "k_ring_policy", "k_loop_policy",
- * "k_ring_policy<POMA>", "k_loop_policy<AccelMA>", "k_merge_policy",
+ * "k_ring_policy<POMA>", "k_loop_policy<AccelMA>", "k_merge_policy", "k_merge_policy<PO>" (fs_policy_act_dev:
+ * "k_policy_act", "k_policy_act_vec"),
  * "k_steps<FAST>", "k_steps<CSET>", "k_steps", "k_steps_ml", "k_steps_open" (also "<mixed>"), "k_steps_wide",
  * "k_merge_queue", "k_drop_queue", "k_obs_mixed"; "" before the first launch).  Diagnostics for tests and bench.py: which
  * configuration class a workload landed in (no reference counterpart).  The string is static.
@@ -470,29 +471,42 @@ const char* fs_last_kernel(fs_handle h);
  * present (the reference lists only the RL vehicles present, flow/envs/multiagent/merge.py:98-143).  Resets inside a
  * fragment: warmup_steps = 0.  ma_apply_actions = 0 (the shipped environment: actions never reach the simulator, roll it
  * out open loop), FS_MIXED / FS_F64 and handles off the queue kernel are refused by name.
- * The single-agent merge (FS_ENV_MERGE_PO, singleagent_merge.py) is refused by name as well: its ONE policy maps the whole
- * observation (5 num_rl values) to num_rl action columns, and fs_policy has no such output (the heads above have two
- * output rows: mean, log std).  Run the policy around fs_step_dev -- VecFlowEnv.capture records K such steps as one
- * graph; the step inside it is k_merge_queue. */
+ * The single-agent merge (FS_ENV_MERGE_PO, singleagent_merge.py; "k_merge_policy<PO>") takes an ACTION-VECTOR head: ONE
+ * network maps the whole observation to A = num_rl (fs_action_dim) accelerations, evaluated once per replica and step.
+ *   obs_dim      fs_obs_dim = 5 A: the whole observation (the first layer takes at most 32 inputs: A <= 6)
+ *   weights_dev  the same trunk; the last layer has 2 A outputs -- rows 0 .. A-1 the means, rows A .. 2A-1 the log stds:
+ *                RLlib's DiagGaussian order -- or, with log_std_dev != NULL, A outputs and log_std_dev points at A floats
+ * Column c draws from Philox column 0x40000000 + c at the replica's counter (the stream agent c of the shared-policy heads
+ * uses), which advances by one per step; logp is the JOINT log-probability: the columns' values added in ascending column
+ * order, in float32.  Every column is sampled every step -- MergePOEnv ignores the columns beyond its list of controlled
+ * vehicles, as it does on an action tape; there is no absent agent on this head.  fs_policy_act_dev takes obs [R, 5 A]
+ * and writes act [R, A] and logp [R]; fs_policy_rollout_dev takes obs [K+1, R, 5 A], act [K, R, A] and logp / rew / done
+ * [K, R].  Clipping stays where fs_step_dev does it (act holds the samples).  reset_done: a collision ends the episode on
+ * this head (bit 1 of done), so a replica is reset in place when done != 0 -- the horizon or a collision -- exactly as
+ * fs_reset_dev(done != 0) resets it: the list of controlled vehicles and its join counter survive, FS_F16S states are
+ * rounded through halves between steps.  A fragment equals K x (fs_policy_act_dev, fs_step_dev, fs_reset_dev(done)) bit
+ * for bit.  Refused by name (every message names FS_ENV_MERGE_PO): num_rl > 6 (EXP_NUM 1 and 2 of singleagent_merge.py:
+ * capture K single steps around the policy instead, VecFlowEnv.capture), FS_MIXED / FS_F64, handles off the queue kernel,
+ * warmup_steps != 0 together with reset_done, and obs_dim != fs_obs_dim. */
 typedef struct fs_policy {
   uint32_t struct_size;               /* sizeof(fs_policy) */
-  int32_t obs_dim;                    /* must equal fs_obs_dim; shared agents: fs_obs_dim / num_rl */
+  int32_t obs_dim;                    /* must equal fs_obs_dim (FS_ENV_MERGE_PO too); shared agents: fs_obs_dim / num_rl */
   int32_t num_hidden;                 /* 1..3 hidden layers ... */
   int32_t hidden_width;               /* ... of 32 units each */
   int32_t activation;                 /* 0 = tanh */
   const float* weights_dev;
-  const float* log_std_dev;           /* NULL: the network's second output is the log std */
+  const float* log_std_dev;           /* NULL: the network's second output is the log std (FS_ENV_MERGE_PO: [num_rl]) */
   uint64_t seed;
 } fs_policy;
 
 /* actions [R] and log-probabilities [R] for the observations obs_dev [R, obs_dim] ([R, n_ag] for [R, n_ag * obs_dim] with
- * shared agents); advances the sampling streams */
+ * shared agents; FS_ENV_MERGE_PO: actions [R, num_rl], log-probabilities [R]); advances the sampling streams */
 int fs_policy_act_dev(fs_handle h, const fs_policy* pol, const float* obs_dev, float* act_dev, float* logp_dev);
 /* K x (policy -> action -> Env.step), with reset_done != 0 followed by Env.reset of the replicas whose episode ended
  * (placement, FS_FIELD_INIT_RING_LENGTH, warm-up steps).  obs_dev [K+1, R, obs_dim]: obs[0] = observation of the state
  * the fragment starts from (written by the call), obs[k+1] = observation after step k (after the reset, if one
- * happened); act_dev [K, R], logp_dev [K, R] ([K, R, n_ag] with shared agents), rew_dev [K, R], done_dev [K, R] (flags as in
- * fs_rollout_dev). */
+ * happened); act_dev [K, R], logp_dev [K, R] ([K, R, n_ag] with shared agents; FS_ENV_MERGE_PO: act_dev [K, R, num_rl],
+ * logp_dev [K, R]), rew_dev [K, R], done_dev [K, R] (flags as in fs_rollout_dev). */
 int fs_policy_rollout_dev(fs_handle h, const fs_policy* pol, int num_steps, int reset_done, float* obs_dev,
                           float* act_dev, float* logp_dev, float* rew_dev, uint8_t* done_dev);
 
