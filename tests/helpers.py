@@ -234,6 +234,19 @@ def bottleneck_spec(R=4, cap_human=40, cap_rl=8, horizon=300, seed=0, q=2300.0, 
     return spec
 
 
+def bottleneck_layout(R, N, layout, end_x=None):
+    """A constructed initial state of the lane-drop network: ``layout`` = {slot: (metres before end_x, speed, path)},
+    the same in every replica.  Returns the init_alive / init_pos / init_vel / init_route entries of a spec
+    (bottleneck_spec takes them through **kw)."""
+    end_x = bottleneck_tables()["end_x"] if end_x is None else end_x
+    alive = np.zeros((R, N), dtype=bool)
+    X, V = np.zeros((R, N)), np.zeros((R, N))
+    route = np.zeros((R, N), dtype=np.int32)
+    for slot, (before_end, speed, path) in layout.items():
+        alive[:, slot], X[:, slot], V[:, slot], route[:, slot] = True, end_x - before_end, speed, path
+    return dict(init_alive=alive, init_pos=X, init_vel=V, init_route=route)
+
+
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 

@@ -19,17 +19,22 @@ def actions(spec, seed, lo=-1.0, hi=1.0):
     return lambda k: rng.uniform(lo, hi, (R, A)).astype(np.float32)
 
 
-def run(spec, steps, action_fn=None, check_every=10, expect="k_drop_queue"):
+def run(spec, steps, action_fn=None, check_every=10, expect="k_drop_queue", watch=None):
+    """``watch(k, oracle, done)``, if given, sees the oracle after its reset (k = -1) and after each of its steps, before the
+    kernel takes that step: the tests of test_dropq_edges_gpu.py count the oracle's events with it."""
     ora = O.MergeOracle(dict(spec, cell_sum="fixed"), np.float32)
     sim = make(spec, "f32")
     np.testing.assert_array_equal(sim.reset(), ora.reset().astype(np.float32))
     compare_state(sim, ora)
+    if watch is not None:
+        watch(-1, ora, np.zeros(ora.R, dtype=bool))
     for k in range(steps):
         a = None if action_fn is None else action_fn(k)
         o_ref, r_ref, d_ref = ora.step(a)
+        if watch is not None:
+            watch(k, ora, d_ref)
         o_gpu, r_gpu, d_gpu = sim.step(a)
-        if k == 0:
-            assert sim.last_kernel == expect
+        assert sim.last_kernel == expect, "step %d" % k
         np.testing.assert_array_equal(o_gpu, o_ref.astype(np.float32), err_msg="obs, step %d" % k)
         np.testing.assert_array_equal(r_gpu, r_ref.astype(np.float32), err_msg="reward, step %d" % k)
         np.testing.assert_array_equal(d_gpu, d_ref, err_msg="done, step %d" % k)

@@ -520,6 +520,70 @@ def test_wide_oracle_runs_beyond_64_slots_and_the_queue_outgrows_one_wave():
     assert (o64.total_dropped > ora.total_dropped).all()             # the 64-slot pool drops what does not fit
 
 
+def test_fixed_point_and_slot_order_cell_sums_stay_within_their_derived_bounds_of_the_float64_sum():
+    """The mean-speed observations of BottleneckDesiredVelocityEnv (flow/envs/bottleneck.py:900-935: the speeds of a
+    lane-segment added in float64 in id order, divided by the count and by 50) as the float32 oracle states them, against
+    that float64 sum of the oracle's OWN float32 speeds, with bounds derived here (u = 2^-24, the relative error of one
+    float32 rounding; gamma(k) = k u / (1 - k u) bounds k roundings in a row):
+      cell_sum = 'fixed' (k_drop_queue, k_steps_wide): every speed is rounded to a multiple of 2^-16 m/s, at most 2^-17 off,
+        the integer sum is exact, so the sum of n speeds is at most n 2^-17 off and the mean 2^-17; three roundings follow
+        (integer -> float32; / n: fl(fl(n / 20) 20) == n is checked below; / 50):
+            (2^-17 (1 + gamma(3)) + gamma(3) speed_limit) / 50  =  2.35e-7 per entry;
+      cell_sum = 'slot' (k_steps_open): a float32 sum of n speeds in slot order, n - 1 roundings, then / n and / 50:
+            gamma(n + 1) speed_limit / 50  =  (n + 1) 2.74e-8 per entry -- 1e-6 up to 35 vehicles in a lane-segment, the
+        figure of tests/test_dropq_gpu.py's comparison of the two kernels.
+    The vehicle counts are equal, and the largest deviation seen is positive: the sums compared are different sums."""
+    from helpers import bottleneck_spec
+    spec = bottleneck_spec(R=2, cap_human=100, cap_rl=20, horizon=300, seed=6, q=3600.0)
+    ora = O.MergeOracle(dict(spec, cell_sum="fixed"), np.float32)
+    ora.reset()
+    N, C, vlim = ora.N, len(spec["obs_cells"]), float(spec["speed_limit"])
+    u = 2.0 ** -24
+    gamma = lambda k: k * u / (1.0 - k * u)                          # noqa: E731
+    cnts = np.arange(1, N + 1, dtype=np.float32)
+    np.testing.assert_array_equal((cnts / np.float32(20)) * np.float32(20), cnts)      # un-normalising the count is exact
+    bound_fixed = (2.0 ** -17 * (1.0 + gamma(3)) + gamma(3) * vlim) / 50.0
+    assert 2.3e-7 < bound_fixed < 2.4e-7
+    rng = np.random.default_rng(1)
+    worst_fixed = worst_slot = 0.0
+    most_in_a_cell = 0
+    for k in range(200):
+        ora.spec["cell_sum"] = "fixed"
+        obs_fixed = ora.step(rng.uniform(-1.0, 1.0, (2, spec["num_rl"])).astype(np.float32))[0]
+        ora.spec["cell_sum"] = "slot"
+        obs_slot = ora.get_state() if k % 4 == 3 else None            # (the oracle's slot-order sum is its slow one)
+        assert obs_fixed.dtype == np.float32
+        assert float(ora.v[ora.alive].max()) <= vlim
+        cell = ora._cell_of(ora.cells, last_of_edge=True)
+        for r in range(2):
+            num = np.zeros((2, C))                                     # [human | RL], float64 as in the reference
+            speeds = np.zeros((2, C))
+            for i in sorted(np.flatnonzero(cell[r] >= 0), key=lambda i: ora.seq[r, i]):       # id order
+                speeds[int(ora.is_rl[i]), cell[r, i]] += float(ora.v[r, i])
+                num[int(ora.is_rl[i]), cell[r, i]] += 1
+            norm = num / 20
+            unnorm = norm * 20
+            mean = np.array([[speeds[t, c] / unnorm[t, c] if int(unnorm[t, c]) else 0 for c in range(C)]
+                             for t in range(2)]) / 50
+            want = np.concatenate([norm[0], norm[1], mean[0], mean[1]])
+            n_c = np.concatenate([num[0], num[1]])
+            most_in_a_cell = max(most_in_a_cell, int(n_c.max()))
+            np.testing.assert_array_equal(obs_fixed[r, :2 * C], want[:2 * C].astype(np.float32))
+            dev_fixed = np.abs(obs_fixed[r, 2 * C:4 * C].astype(np.float64) - want[2 * C:])
+            assert (dev_fixed <= bound_fixed).all(), (k, dev_fixed.max())
+            worst_fixed = max(worst_fixed, dev_fixed.max())
+            if obs_slot is not None:
+                assert obs_slot.dtype == np.float32
+                np.testing.assert_array_equal(obs_slot[r, :2 * C], want[:2 * C].astype(np.float32))
+                dev_slot = np.abs(obs_slot[r, 2 * C:4 * C].astype(np.float64) - want[2 * C:])
+                assert (dev_slot <= gamma(n_c + 1) * vlim / 50.0).all(), (k, dev_slot.max())
+                worst_slot = max(worst_slot, dev_slot.max())
+    print("largest deviation: fixed %.3g (bound %.3g), slot %.3g; most vehicles in a lane-segment %d"
+          % (worst_fixed, bound_fixed, worst_slot, most_in_a_cell))
+    assert worst_fixed > 0 and worst_slot > 0
+    assert most_in_a_cell >= 8 and ora.alive.sum(axis=1).min() > 40     # (sums of several speeds were compared)
+
+
 def test_simplified_lane_changing_facts():
     """M11: vehicles change to an adjacent lane with a clearly larger leader gap, never inside a zipper zone or on an
     internal edge, at most one per replica and step, not again before the cool-down, never into an unsafe gap."""
