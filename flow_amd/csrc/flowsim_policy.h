@@ -13,10 +13,16 @@
 // (folded into the FMAs), its weights are read from an LDS copy (16 b128 reads per lane and layer), the two outputs are
 // reduced over the row with the xor-tree of seg_sum.  The sampled action uses the replica's own Philox stream (keyed by
 // the policy's seed, the global replica index and a per-replica counter that a fragment continues where the last one
-// stopped).  policy_eval is ONE device function shared with k_policy_act (the eager form: fs_policy_act_dev followed by
-// fs_step_dev), so the fragment is bit-identical to eager stepping by construction (tests/test_policy_gpu.py).
-// Every operation is an explicit fma / hardware exp2 / rcp: the arithmetic is defined by this file (a torch module with
-// the same weights agrees to ~1e-6, not bit for bit).
+// stopped).
+//
+// The network is written ONCE: policy_layer is the 32-input layer, policy_trunk the layer sequence (narrow or WIDE first
+// layer, then the hidden layers), policy_load_trunk its weights' way into LDS.  All six kernels that evaluate a policy
+// call that trunk -- the eager k_policy_act and k_policy_act_vec (fs_policy_act_dev), the fused k_ring_policy,
+// k_loop_policy, k_merge_queue<POLICY> and k_merge_policy (flowsim_queue.h) -- through policy_eval (the trunk and the
+// two-output Gaussian head) or policy_vec_act (the trunk and the action-vector head), so a fragment is bit-identical to
+// eager stepping by construction (tests/test_policy_gpu.py and its siblings).  Every operation is an explicit fma /
+// hardware exp2 / rcp: the arithmetic is defined by this file (a torch module with the same weights agrees to ~1e-6, not
+// bit for bit) and its float32 bits are pinned by tests/test_policy_bits_gpu.py.
 #pragma once
 #include "flowsim_ringrl.h"
 
@@ -46,11 +52,21 @@ struct alignas(16) PolicyLds {
   float obs[4][4][4];      // [wave of the block][row][value]: the observation of a replica, handed from its RL lane to the row
 };
 
-// the inputs of a WIDE observation per lane: lane j < half holds inputs j and half + j (the latter if < in_dim)
-__host__ __device__ __forceinline__ int policy_half(int in_dim) { return (in_dim + 1) >> 1; }
+// THE layout of a WIDE observation (in_dim > 4): lane j < half of a row holds inputs j and half + j (the latter if
+// < in_dim, else zero), every other lane zeros.  policy_wide_inputs reads it from a row of in_dim values in memory; the
+// fused kernels that hold the values in registers gather them into the same places.
+__host__ __device__ constexpr int policy_half(int in_dim) { return (in_dim + 1) >> 1; }
 
-__device__ __forceinline__ void policy_load(const PolicyView& pv, PolicyLds* L, int tid, int nthreads) {
-  // weights -> LDS (once per launch); layout of pv.w: [W1 32x3][b1 32][W2 32x32][b2][W3 32x32][b3][Wout n_out x 32][bout]
+__device__ __forceinline__ void policy_wide_inputs(const float* o, int in_dim, int j, float& ia, float& ib) {
+  const int half = policy_half(in_dim);
+  ia = j < half ? o[j < half ? j : 0] : 0.0f;               // (the loads unconditional, at a valid index)
+  ib = (j < half && half + j < in_dim) ? o[half + j < in_dim ? half + j : 0] : 0.0f;
+}
+
+// weights -> LDS (once per launch); layout of pv.w: [W1 32 x in_dim][b1 32][W2 32x32][b2][W3 32x32][b3][Wout n_out x 32][bout].
+// policy_load_trunk: layers 1 .. num_hidden and their biases; returns where the output layer starts.  No barrier: the
+// caller loads its output layer and ends with ONE __syncthreads.
+__device__ __forceinline__ const float* policy_load_trunk(const PolicyView& pv, PolicyLds* L, int tid, int nthreads) {
   const float* p = pv.w;
   const bool wide = pv.in_dim > 4;
   for (int e = tid; e < 32 * 4; e += nthreads) L->w_in[e / 4][e % 4] = (!wide && (e % 4) < pv.in_dim) ? p[(e / 4) * pv.in_dim + (e % 4)] : 0.0f;
@@ -76,33 +92,31 @@ __device__ __forceinline__ void policy_load(const PolicyView& pv, PolicyLds* L, 
     for (int e = tid; e < 32; e += nthreads) L->b[l + 1][e] = have ? p[e] : 0.0f;
     if (have) p += 32;
   }
+  return p;
+}
+
+// the trunk and the Gaussian head of n_out <= 2 rows (mean [, log std])
+__device__ __forceinline__ void policy_load(const PolicyView& pv, PolicyLds* L, int tid, int nthreads) {
+  const float* p = policy_load_trunk(pv, L, tid, nthreads);
   for (int e = tid; e < 2 * 32; e += nthreads) L->w_out[e / 32][e % 32] = (e / 32) < pv.n_out ? p[e] : 0.0f;
   p += pv.n_out * 32;
   if (tid < 2) L->b_out[tid] = tid < pv.n_out ? p[tid] : 0.0f;
   __syncthreads();
 }
 
-// (a, b, c) of lanes (k, k + 1, k + 2) mod 16 of every 16-lane row -> all lanes of the row (k wave-uniform): three DPP row
-// broadcasts behind one jump on k, where three ds_bpermute would be an LDS round trip the wave waits out (nothing else
-// to issue: the policy's first layer needs the three values)
-__device__ __forceinline__ void row_bcast3(int k, float a, float b, float c, float& oa, float& ob, float& oc) {
-#define FS_RB3(K_) case K_: oa = dpp<DPP_ROW_NEWBCAST0 + K_>(a); ob = dpp<DPP_ROW_NEWBCAST0 + ((K_ + 1) & 15)>(b); \
-                           oc = dpp<DPP_ROW_NEWBCAST0 + ((K_ + 2) & 15)>(c); break;
+// (a, b, c) of lanes (k, k + D1, k + D2) mod 16 of every 16-lane row -> all lanes of the row (k wave-uniform): three DPP
+// row broadcasts behind ONE jump on k, where three ds_bpermute would be an LDS round trip the wave waits out (nothing
+// else to issue: the policy's first layer needs the three values).  <1, 2>: a lane and its two neighbours; <0, 0>: the
+// same lane three times.
+template <int D1, int D2>
+__device__ __forceinline__ void row_bcast(int k, float a, float b, float c, float& oa, float& ob, float& oc) {
+#define FS_RB(K_) case K_: oa = dpp<DPP_ROW_NEWBCAST0 + K_>(a); ob = dpp<DPP_ROW_NEWBCAST0 + ((K_ + D1) & 15)>(b); \
+                          oc = dpp<DPP_ROW_NEWBCAST0 + ((K_ + D2) & 15)>(c); break;
   switch (k & 15) {
-    FS_RB3(0) FS_RB3(1) FS_RB3(2) FS_RB3(3) FS_RB3(4) FS_RB3(5) FS_RB3(6) FS_RB3(7)
-    FS_RB3(8) FS_RB3(9) FS_RB3(10) FS_RB3(11) FS_RB3(12) FS_RB3(13) FS_RB3(14) FS_RB3(15)
+    FS_RB(0) FS_RB(1) FS_RB(2) FS_RB(3) FS_RB(4) FS_RB(5) FS_RB(6) FS_RB(7)
+    FS_RB(8) FS_RB(9) FS_RB(10) FS_RB(11) FS_RB(12) FS_RB(13) FS_RB(14) FS_RB(15)
   }
-#undef FS_RB3
-}
-// the same lane k three times
-__device__ __forceinline__ void row_bcast1x3(int k, float a, float b, float c, float& oa, float& ob, float& oc) {
-#define FS_RB1(K_) case K_: oa = dpp<DPP_ROW_NEWBCAST0 + K_>(a); ob = dpp<DPP_ROW_NEWBCAST0 + K_>(b); \
-                           oc = dpp<DPP_ROW_NEWBCAST0 + K_>(c); break;
-  switch (k & 15) {
-    FS_RB1(0) FS_RB1(1) FS_RB1(2) FS_RB1(3) FS_RB1(4) FS_RB1(5) FS_RB1(6) FS_RB1(7)
-    FS_RB1(8) FS_RB1(9) FS_RB1(10) FS_RB1(11) FS_RB1(12) FS_RB1(13) FS_RB1(14) FS_RB1(15)
-  }
-#undef FS_RB1
+#undef FS_RB
 }
 
 __device__ __forceinline__ float policy_tanh(float z) {
@@ -111,13 +125,38 @@ __device__ __forceinline__ float policy_tanh(float z) {
   return __builtin_fmaf(-2.0f, r, 1.0f);                                // 1 - 2 / (exp(2 z) + 1)
 }
 
-// mean and log std of the action distribution for the observation (o0, o1, o2) of THIS row's replica (every lane of the
-// row passes the same three values); j = lane within the row
-// WIDE: the observation is two values per lane (o0: input j, o1: input half + j of THIS lane; o2 unused)
-template <int ROW, bool WIDE = false>
-__device__ __forceinline__ void policy_eval(const PolicyView& pv, const PolicyLds* L, int j, float o0, float o1, float o2,
-                                            float& mu, float& log_std) {
-  static_assert(ROW == 16, "policy_eval: a row of 16 lanes holds the 32 units of a layer");
+// ONE layer on 32 inputs, the only place it is written: z[u] = b[u] + sum_i W[u][i] in[i] for this lane's units u = j and
+// j + 16 (bias b_j, b_j16).  Input i < 16 is `a` of lane i, input i >= 16 `b` of lane i - 16: row broadcasts, folded into
+// the packed FMAs.  ww[i / 2] = the weights of inputs i, i + 1 -- all sixteen quads read by the caller first (the LDS
+// reads in flight together) --, then four independent accumulators (inputs i with the same i mod 4 share one; the chain
+// of dependent packed FMAs is 8 long instead of 32), combined as ((b + z0) + z1) + (z2 + z3).
+__device__ __forceinline__ f2 policy_layer(const float4 (&ww)[16], float b_j, float b_j16, float a, float b) {
+  f2 z0 = {b_j, b_j16}, z1 = {0.0f, 0.0f}, z2 = {0.0f, 0.0f}, z3 = {0.0f, 0.0f};
+  static_for<4>([&](auto q_c) {                    // inputs 4q .. 4q + 3 (`a` of lanes 4q ..) and 16 + 4q .. (`b`)
+    constexpr int q = decltype(q_c)::value;
+    const float a0 = dpp<DPP_ROW_NEWBCAST0 + 4 * q>(a), a1 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 1>(a);
+    const float a2 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 2>(a), a3 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 3>(a);
+    const float b0 = dpp<DPP_ROW_NEWBCAST0 + 4 * q>(b), b1 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 1>(b);
+    const float b2 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 2>(b), b3 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 3>(b);
+    z0 = fma2(f2{ww[2 * q].x, ww[2 * q].y}, splat(a0), z0);
+    z1 = fma2(f2{ww[2 * q].z, ww[2 * q].w}, splat(a1), z1);
+    z2 = fma2(f2{ww[2 * q + 1].x, ww[2 * q + 1].y}, splat(a2), z2);
+    z3 = fma2(f2{ww[2 * q + 1].z, ww[2 * q + 1].w}, splat(a3), z3);
+    z0 = fma2(f2{ww[8 + 2 * q].x, ww[8 + 2 * q].y}, splat(b0), z0);
+    z1 = fma2(f2{ww[8 + 2 * q].z, ww[8 + 2 * q].w}, splat(b1), z1);
+    z2 = fma2(f2{ww[8 + 2 * q + 1].x, ww[8 + 2 * q + 1].y}, splat(b2), z2);
+    z3 = fma2(f2{ww[8 + 2 * q + 1].z, ww[8 + 2 * q + 1].w}, splat(b3), z3);
+  });
+  return pk_add(pk_add(z0, z1), pk_add(z2, z3));
+}
+
+// THE trunk, the only place the layer sequence is written: the last hidden layer's units j and j + 16 (ha, hb) for the
+// observation of THIS row's replica; j = lane within the row.  Narrow first layer: (o0, o1, o2), the same three values
+// in every lane of the row.  WIDE: two values per lane in policy_wide_inputs' layout (o0: input j, o1: input half + j of
+// THIS lane; o2 unused) -- a hidden layer's form and summation order.
+template <bool WIDE>
+__device__ __forceinline__ void policy_trunk(const PolicyView& pv, const PolicyLds* L, int j, float o0, float o1, float o2,
+                                             float& ha, float& hb) {
   // The first two weight quads of a hidden layer are read one layer AHEAD (before the previous layer's tanh): the layer's
   // FMAs start on them while its other fourteen reads are in flight, instead of waiting out an LDS round trip at the top
   // of every layer.  (All sixteen ahead was measured slower: the 64 registers stay live through tanh and the kernel spills.)
@@ -128,29 +167,11 @@ __device__ __forceinline__ void policy_eval(const PolicyView& pv, const PolicyLd
   };
   if (pv.num_hidden > 1) load_ahead(0);
   // layer 1
-  float ha, hb;      // units j and j + 16
   if constexpr (WIDE) {
-    // the hidden layers' form (below): four independent accumulators, inputs by row broadcasts folded into packed FMAs
     float4 ww[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) ww[q] = *reinterpret_cast<const float4*>(L->w_wide[q][j]);
-    f2 z0 = {L->b[0][j], L->b[0][j + 16]}, z1 = {0.0f, 0.0f}, z2 = {0.0f, 0.0f}, z3 = {0.0f, 0.0f};
-    static_for<4>([&](auto q_c) {
-      constexpr int q = decltype(q_c)::value;
-      const float a0 = dpp<DPP_ROW_NEWBCAST0 + 4 * q>(o0), a1 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 1>(o0);
-      const float a2 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 2>(o0), a3 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 3>(o0);
-      const float b0 = dpp<DPP_ROW_NEWBCAST0 + 4 * q>(o1), b1 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 1>(o1);
-      const float b2 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 2>(o1), b3 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 3>(o1);
-      z0 = fma2(f2{ww[2 * q].x, ww[2 * q].y}, splat(a0), z0);
-      z1 = fma2(f2{ww[2 * q].z, ww[2 * q].w}, splat(a1), z1);
-      z2 = fma2(f2{ww[2 * q + 1].x, ww[2 * q + 1].y}, splat(a2), z2);
-      z3 = fma2(f2{ww[2 * q + 1].z, ww[2 * q + 1].w}, splat(a3), z3);
-      z0 = fma2(f2{ww[8 + 2 * q].x, ww[8 + 2 * q].y}, splat(b0), z0);
-      z1 = fma2(f2{ww[8 + 2 * q].z, ww[8 + 2 * q].w}, splat(b1), z1);
-      z2 = fma2(f2{ww[8 + 2 * q + 1].x, ww[8 + 2 * q + 1].y}, splat(b2), z2);
-      z3 = fma2(f2{ww[8 + 2 * q + 1].z, ww[8 + 2 * q + 1].w}, splat(b3), z3);
-    });
-    const f2 z = pk_add(pk_add(z0, z1), pk_add(z2, z3));
+    const f2 z = policy_layer(ww, L->b[0][j], L->b[0][j + 16], o0, o1);
     ha = policy_tanh(z.x);
     hb = policy_tanh(z.y);
   } else {
@@ -162,40 +183,29 @@ __device__ __forceinline__ void policy_eval(const PolicyView& pv, const PolicyLd
     ha = policy_tanh(za);
     hb = policy_tanh(zb);
   }
-  // hidden layers 2 .. num_hidden: z[u] = b[u] + sum_i W[u][i] h[i], i ascending; input i < 16 sits in `ha` of lane i,
-  // input i >= 16 in `hb` of lane i - 16 (row broadcasts, folded into the FMAs)
+  // hidden layers 2 .. num_hidden: input i < 16 sits in `ha` of lane i, input i >= 16 in `hb` of lane i - 16
 #pragma unroll 1
   for (int l = 0; l + 1 < pv.num_hidden; ++l) {
-    // all sixteen weight quads of the layer first (the LDS reads in flight together), then four independent accumulators
-    // (inputs i with the same i mod 4 share one; the chain of dependent packed FMAs is 8 long instead of 32), combined
-    // as ((b + z0) + z1) + (z2 + z3)
-    float4 ww[16];                                 // ww[i / 2] = weights of inputs i, i + 1
+    float4 ww[16];
     ww[0] = wa0;
     ww[1] = wa1;
 #pragma unroll
     for (int q = 2; q < 16; ++q) ww[q] = *reinterpret_cast<const float4*>(L->w_hid[l][q][j]);
-    f2 z0 = {L->b[l + 1][j], L->b[l + 1][j + 16]}, z1 = {0.0f, 0.0f}, z2 = {0.0f, 0.0f}, z3 = {0.0f, 0.0f};
-    static_for<4>([&](auto q_c) {                  // inputs 4q .. 4q + 3 (`ha` of lanes 4q ..) and 16 + 4q .. (`hb`)
-      constexpr int q = decltype(q_c)::value;
-      const float a0 = dpp<DPP_ROW_NEWBCAST0 + 4 * q>(ha), a1 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 1>(ha);
-      const float a2 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 2>(ha), a3 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 3>(ha);
-      const float b0 = dpp<DPP_ROW_NEWBCAST0 + 4 * q>(hb), b1 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 1>(hb);
-      const float b2 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 2>(hb), b3 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 3>(hb);
-      z0 = fma2(f2{ww[2 * q].x, ww[2 * q].y}, splat(a0), z0);
-      z1 = fma2(f2{ww[2 * q].z, ww[2 * q].w}, splat(a1), z1);
-      z2 = fma2(f2{ww[2 * q + 1].x, ww[2 * q + 1].y}, splat(a2), z2);
-      z3 = fma2(f2{ww[2 * q + 1].z, ww[2 * q + 1].w}, splat(a3), z3);
-      z0 = fma2(f2{ww[8 + 2 * q].x, ww[8 + 2 * q].y}, splat(b0), z0);
-      z1 = fma2(f2{ww[8 + 2 * q].z, ww[8 + 2 * q].w}, splat(b1), z1);
-      z2 = fma2(f2{ww[8 + 2 * q + 1].x, ww[8 + 2 * q + 1].y}, splat(b2), z2);
-      z3 = fma2(f2{ww[8 + 2 * q + 1].z, ww[8 + 2 * q + 1].w}, splat(b3), z3);
-    });
+    const f2 z = policy_layer(ww, L->b[l + 1][j], L->b[l + 1][j + 16], ha, hb);
     if (l + 2 < pv.num_hidden) load_ahead(l + 1);  // (wave-uniform)
-    const f2 z = pk_add(pk_add(z0, z1), pk_add(z2, z3));
-    const float za = z.x, zb = z.y;
-    ha = policy_tanh(za);
-    hb = policy_tanh(zb);
+    ha = policy_tanh(z.x);
+    hb = policy_tanh(z.y);
   }
+}
+
+// mean and log std of the action distribution for the observation of THIS row's replica: policy_trunk and the Gaussian
+// head of two outputs
+template <int ROW, bool WIDE = false>
+__device__ __forceinline__ void policy_eval(const PolicyView& pv, const PolicyLds* L, int j, float o0, float o1, float o2,
+                                            float& mu, float& log_std) {
+  static_assert(ROW == 16, "policy_eval: a row of 16 lanes holds the 32 units of a layer");
+  float ha, hb;      // units j and j + 16
+  policy_trunk<WIDE>(pv, L, j, o0, o1, o2, ha, hb);
   // head: two outputs, each the row's tree sum of the lanes' two products
   float p0 = L->w_out[0][j] * ha, p1 = L->w_out[1][j] * ha;
   p0 = __builtin_fmaf(L->w_out[0][j + 16], hb, p0);
@@ -276,9 +286,9 @@ __global__ __launch_bounds__(256) void k_policy_act(PolicyView pv, int R, int n_
   for (int c = 0; c < n_ag; ++c) {
     const float* o = obs + (size_t(rr) * n_ag + c) * pv.in_dim;
     float mu, ls;
-    if (pv.in_dim > 4) {                                   // (wave-uniform) two values per lane: inputs j and half + j
-      const int half = policy_half(pv.in_dim);
-      const float ia = j < half ? o[j] : 0.0f, ib = (j < half && half + j < pv.in_dim) ? o[half + j] : 0.0f;
+    if (pv.in_dim > 4) {                                   // (wave-uniform)
+      float ia, ib;
+      policy_wide_inputs(o, pv.in_dim, j, ia, ib);
       policy_eval<ROW, true>(pv, &L, j, ia, ib, 0.0f, mu, ls);
     } else {
       policy_eval<ROW>(pv, &L, j, o[0], pv.in_dim > 1 ? o[1] : 0.0f, pv.in_dim > 2 ? o[2] : 0.0f, mu, ls);
@@ -295,13 +305,14 @@ __global__ __launch_bounds__(256) void k_policy_act(PolicyView pv, int R, int n_
 }
 
 // ---- the ACTION-VECTOR head (FS_ENV_MERGE_PO: MergePOEnv) ---------------------------------------------------------
-// ONE network maps the whole observation (in_dim = 5 A <= 32 values, A = num_rl) to A actions: the trunk of policy_eval's
-// WIDE form, then an output layer of n_out = 2 A rows (rows 0 .. A-1 the means, rows A .. 2A-1 the log stds: RLlib's
-// DiagGaussian order) or of A rows next to A free log stds.  A WAVE is one replica: its four 16-lane rows run the trunk
+// ONE network maps the whole observation (in_dim = 5 A <= 32 values, A = num_rl) to A actions: policy_trunk<WIDE> (the
+// trunk every policy kernel runs), then an output layer of n_out = 2 A rows (rows 0 .. A-1 the means, rows A .. 2A-1 the
+// log stds: RLlib's DiagGaussian order) or of A rows next to A free log stds.  A WAVE is one replica: its four 16-lane rows run the trunk
 // alike (a row holds the 32 units of a layer), every output is the row's tree sum, lane c of a row then samples column c
 // (Philox column 0x40000000 + c at the replica's counter: agent c's stream of the shared-policy heads) and the wave
-// adds the columns' log-probabilities in ascending order.  policy_vec_act is the ONE definition: k_policy_act_vec (eager)
-// and k_merge_policy (fused, flowsim_queue.h) both call it, so they agree bit for bit by construction.
+// adds the columns' log-probabilities in ascending order.  policy_vec_act is the head's one definition: k_policy_act_vec
+// (eager) and k_merge_policy (fused, flowsim_queue.h) both call it, and it calls the shared trunk, so they agree bit for
+// bit by construction.
 constexpr int FS_POLICY_VEC_MAX = 6;                      // 5 A <= 32: the WIDE first layer
 
 struct alignas(16) PolicyVecLds {
@@ -311,71 +322,16 @@ struct alignas(16) PolicyVecLds {
   float lp[16];                                            // the columns' log-probabilities of a step
 };
 
-// weights -> LDS, once per launch: the trunk through policy_load (which takes the head for one of <= 2 rows: none here),
-// the output layer from where the trunk ends in pv.w.  Ends with policy_load's barrier.
+// weights -> LDS, once per launch: policy_load_trunk, then the output layer of n_out = A or 2 A rows and the free log stds;
+// one barrier
 __device__ __forceinline__ void policy_vec_load(const PolicyView& pv, int A, PolicyLds* L, PolicyVecLds* V, int tid,
                                                 int nthreads) {
-  const float* p = pv.w + 32 * pv.in_dim + 32 + (pv.num_hidden - 1) * (32 * 32 + 32);
-  const int n_out = pv.n_out;                              // A or 2 A
+  const float* p = policy_load_trunk(pv, L, tid, nthreads);
+  const int n_out = pv.n_out;
   for (int e = tid; e < 2 * FS_POLICY_VEC_MAX * 32; e += nthreads) V->w_out[e / 32][e % 32] = (e / 32) < n_out ? p[e] : 0.0f;
   for (int e = tid; e < 2 * FS_POLICY_VEC_MAX; e += nthreads) V->b_out[e] = e < n_out ? p[n_out * 32 + e] : 0.0f;
   for (int e = tid; e < FS_POLICY_VEC_MAX; e += nthreads) V->log_std[e] = (pv.log_std != nullptr && e < A) ? pv.log_std[e] : 0.0f;
-  PolicyView trunk = pv;
-  trunk.n_out = 0;
-  policy_load(trunk, L, tid, nthreads);
-}
-
-// the trunk of policy_eval<16, WIDE> -- its statements, in its order: the first layer on two inputs per lane, the hidden
-// layers with four accumulators and the weight quads read one layer ahead -- returning the last layer's units j and j + 16
-// (policy_eval itself ends in the two-output head, and its code generation is held to recorded figures: tests/test_codegen.py)
-__device__ __forceinline__ void policy_trunk_wide(const PolicyView& pv, const PolicyLds* L, int j, float o0, float o1,
-                                                  float& ha, float& hb) {
-  float4 wa0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), wa1 = wa0;
-  auto load_ahead = [&](int l) {
-    wa0 = *reinterpret_cast<const float4*>(L->w_hid[l][0][j]);
-    wa1 = *reinterpret_cast<const float4*>(L->w_hid[l][1][j]);
-  };
-  if (pv.num_hidden > 1) load_ahead(0);
-  // one layer: z[u] = b[u] + sum_i W[u][i] in[i]; input i < 16 is `a` of lane i, input i >= 16 `b` of lane i - 16
-  auto layer = [&](const float4 (&ww)[16], float bj, float bj16, float a, float b) {
-    f2 z0 = {bj, bj16}, z1 = {0.0f, 0.0f}, z2 = {0.0f, 0.0f}, z3 = {0.0f, 0.0f};
-    static_for<4>([&](auto q_c) {
-      constexpr int q = decltype(q_c)::value;
-      const float a0 = dpp<DPP_ROW_NEWBCAST0 + 4 * q>(a), a1 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 1>(a);
-      const float a2 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 2>(a), a3 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 3>(a);
-      const float b0 = dpp<DPP_ROW_NEWBCAST0 + 4 * q>(b), b1 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 1>(b);
-      const float b2 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 2>(b), b3 = dpp<DPP_ROW_NEWBCAST0 + 4 * q + 3>(b);
-      z0 = fma2(f2{ww[2 * q].x, ww[2 * q].y}, splat(a0), z0);
-      z1 = fma2(f2{ww[2 * q].z, ww[2 * q].w}, splat(a1), z1);
-      z2 = fma2(f2{ww[2 * q + 1].x, ww[2 * q + 1].y}, splat(a2), z2);
-      z3 = fma2(f2{ww[2 * q + 1].z, ww[2 * q + 1].w}, splat(a3), z3);
-      z0 = fma2(f2{ww[8 + 2 * q].x, ww[8 + 2 * q].y}, splat(b0), z0);
-      z1 = fma2(f2{ww[8 + 2 * q].z, ww[8 + 2 * q].w}, splat(b1), z1);
-      z2 = fma2(f2{ww[8 + 2 * q + 1].x, ww[8 + 2 * q + 1].y}, splat(b2), z2);
-      z3 = fma2(f2{ww[8 + 2 * q + 1].z, ww[8 + 2 * q + 1].w}, splat(b3), z3);
-    });
-    return pk_add(pk_add(z0, z1), pk_add(z2, z3));
-  };
-  {
-    float4 ww[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) ww[q] = *reinterpret_cast<const float4*>(L->w_wide[q][j]);
-    const f2 z = layer(ww, L->b[0][j], L->b[0][j + 16], o0, o1);
-    ha = policy_tanh(z.x);
-    hb = policy_tanh(z.y);
-  }
-#pragma unroll 1
-  for (int l = 0; l + 1 < pv.num_hidden; ++l) {
-    float4 ww[16];
-    ww[0] = wa0;
-    ww[1] = wa1;
-#pragma unroll
-    for (int q = 2; q < 16; ++q) ww[q] = *reinterpret_cast<const float4*>(L->w_hid[l][q][j]);
-    const f2 z = layer(ww, L->b[l + 1][j], L->b[l + 1][j + 16], ha, hb);
-    if (l + 2 < pv.num_hidden) load_ahead(l + 1);        // (wave-uniform)
-    ha = policy_tanh(z.x);
-    hb = policy_tanh(z.y);
-  }
+  __syncthreads();
 }
 
 // The A actions and the joint log-probability of ONE replica, computed by its wave (lane = 0 .. 63).  `o`: the replica's
@@ -385,12 +341,10 @@ __device__ __forceinline__ void policy_trunk_wide(const PolicyView& pv, const Po
 __device__ __forceinline__ float policy_vec_act(const PolicyView& pv, int A, const PolicyLds* L, PolicyVecLds* V,
                                                 uint32_t replica, uint32_t ctr, int lane, const float* o, float* act_row,
                                                 NoiseBlock<float>* nzb = nullptr) {
-  const int j = lane & 15, half = policy_half(pv.in_dim);
-  // k_policy_act's WIDE layout: lane j < half holds inputs j and half + j (the latter if < in_dim)
-  const float ia = j < half ? o[j < half ? j : 0] : 0.0f;
-  const float ib = (j < half && half + j < pv.in_dim) ? o[half + j < pv.in_dim ? half + j : 0] : 0.0f;
-  float ha, hb;
-  policy_trunk_wide(pv, L, j, ia, ib, ha, hb);
+  const int j = lane & 15;
+  float ia, ib, ha, hb;
+  policy_wide_inputs(o, pv.in_dim, j, ia, ib);
+  policy_trunk<true>(pv, L, j, ia, ib, 0.0f, ha, hb);
   // the outputs: each the row's tree sum of the lanes' two products (policy_eval's head); lane c keeps column c's
   const bool free_ls = pv.log_std != nullptr;
   float mu = 0.0f, ls = 0.0f;
@@ -479,25 +433,30 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
   const bool poA = valid && rlA, poB = valid && rlB;
   const double rc15 = 1.0 / 15.0, pml64 = double(s.po_max_length), rc_pml64 = 1.0 / pml64;
   float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f;
-  // float32: the three quotients are exact divisions through float64 (five instructions each, issued for one lane):
-  // the RL vehicle's lane hands its second and third numerator to its two neighbours (row rotations) and the three lanes
-  // divide one value each -- one division sequence per step instead of three
+  // THE PO observation of a row of 16, float32 -- [v / 15, (v_lead - v) / 15, third / max_length] of the RL vehicle in
+  // lane k_rl of the row (selB: its vehicle B, else A), stored at orow[0 .. 2] and handed to the row as the policy's
+  // input.  The three quotients are exact divisions through float64 (five instructions each, issued for one lane): the
+  // RL vehicle's lane hands its second and third numerator to its two neighbours (row rotations) and the three lanes
+  // divide one value each -- one division sequence per step instead of three -- and three row broadcasts return them.
+  auto observe_po = [&](int k_rl, bool selB, float third, float* orow) {
+    const float v_me = selB ? v.y : v.x, v_ld = selB ? vl.y : vl.x;
+    const float n1 = dpp<0x120 + 1>(v_ld - v_me), n2 = dpp<0x120 + 2>(third);     // row_ror: lane i <- lane i - 1 / i - 2
+    const int pc = (k - k_rl) & (ROW - 1);                                        // 0: the RL vehicle's lane, 1 / 2: its helpers
+    const float n = pc == 0 ? v_me : (pc == 1 ? n1 : n2);
+    const float q = div_via_f64(n, pc == 2 ? pml64 : 15.0, pc == 2 ? rc_pml64 : rc15);
+    if (rvalid && pc < 3) orow[pc] = q;
+    row_bcast<1, 2>(k_rl, q, q, q, o0, o1, o2);
+  };
+  // the single-agent head: the third value is the RL vehicle's distance to its leader
   const unsigned long long po_m = __ballot(poA || poB);
   const int k_po = po_m ? (__builtin_ctzll(po_m) & (ROW - 1)) : 0;
-  const int po_c = (k - k_po) & (ROW - 1);                               // 0: the RL vehicle's lane, 1 / 2: its helpers
-  const double po_div = po_c == 2 ? pml64 : 15.0, po_rc = po_c == 2 ? rc_pml64 : rc15;
-  // (hand-off to the row through the LDS crossbar, ds_bpermute: one round trip and no memory, where the first version
-  // wrote the three values to LDS and read them back between two wave barriers)
-  const int src0 = (lane - k) + k_po, src1 = (lane - k) + ((k_po + 1) & (ROW - 1)), src2 = (lane - k) + ((k_po + 2) & (ROW - 1));
+  const int src0 = (lane - k) + k_po;
   auto observe = [&](float* orow) {
     if constexpr (!MIXED && ROW == 16) {
-      const float v_me = poB ? v.y : v.x, v_ld = poB ? vl.y : vl.x, d_me = poB ? dgap.y : dgap.x;
-      const float n1 = dpp<0x120 + 1>(v_ld - v_me), n2 = dpp<0x120 + 2>(d_me);      // row_ror: lane i <- lane i - 1 / i - 2
-      const float n = po_c == 0 ? v_me : (po_c == 1 ? n1 : n2);
-      const float q = div_via_f64(n, po_div, po_rc);
-      if (rvalid && po_c < 3) orow[po_c] = q;
-      row_bcast3(k_po, q, q, q, o0, o1, o2);
+      observe_po(k_po, poB, poB ? dgap.y : dgap.x, orow);
     } else {
+      // (hand-off to the row through the LDS crossbar, ds_bpermute: one round trip and no memory, where the first version
+      // wrote the three values to LDS and read them back between two wave barriers)
       float q0, q1, q2;
       if (MIXED) {
         const double vdn = next_a<ROW>(core.vdA, last, lane);
@@ -522,10 +481,9 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
     }
   };
 
-  // MultiAgentWaveAttenuationPOEnv.get_state of agent c (k_ring_pair<POMA>'s write_obs: [v / 15, (v_lead - v) / 15,
-  // bumper-to-bumper headway / max_length]).  The lane of column c's RL slot -- and whether it is A or B -- is a slot
-  // role, the same in every row of the wave: that lane and its two row neighbours divide one value each (the PO head's
-  // helpers above), store it in block c and hand the three to the row as the policy's input.
+  // MultiAgentWaveAttenuationPOEnv.get_state of agent c (k_ring_pair<POMA>'s write_obs: the third value is the
+  // bumper-to-bumper headway), block c of the row.  The lane of column c's RL slot -- and whether it is A or B -- is a slot
+  // role, the same in every row of the wave.
   const int n_ag = MA ? s.num_rl : 1;
   const int colA = rlA ? s.rl_index[iA] : -1, colB = rlB ? s.rl_index[iB] : -1;
   const bool redA = MA && valid && iA < s.num_rl, redB = MA && valid && iB < s.num_rl;    // (finish()'s places)
@@ -533,14 +491,7 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
   auto observe_agent = [&](int c, float* orow) {
     const unsigned long long m = __ballot(k < LP && (colA == c || colB == c));
     const int k_c = m ? (__builtin_ctzll(m) & (ROW - 1)) : 0;
-    const bool selB = colB == c;
-    const float v_me = selB ? v.y : v.x, v_ld = selB ? vl.y : vl.x, h_me = selB ? h.y : h.x;
-    const float n1 = dpp<0x120 + 1>(v_ld - v_me), n2 = dpp<0x120 + 2>(h_me);      // row_ror: lane i <- lane i - 1 / i - 2
-    const int pc = (k - k_c) & (ROW - 1);
-    const float n = pc == 0 ? v_me : (pc == 1 ? n1 : n2);
-    const float q = div_via_f64(n, pc == 2 ? pml64 : 15.0, pc == 2 ? rc_pml64 : rc15);
-    if (rvalid && pc < 3) orow[3 * c + pc] = q;
-    row_bcast3(k_c, q, q, q, o0, o1, o2);
+    observe_po(k_c, colB == c, colB == c ? h.y : h.x, orow + 3 * c);
   };
 
   const size_t R = size_t(s.R);
@@ -643,8 +594,7 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
 // HEAD 2: MultiAgentAccelPOEnv (examples/exp_configs/rl/multiagent/multiagent_figure_eight.py), n_ag = num_rl agents sharing
 // the policy: obs [K+1, R, 6 n_ag], act / logp [K, R, n_ag], the shared desired-velocity reward, no crash
 // (tests/test_policy_ma_gpu.py).  Agent c's six values sit on two lanes -- its RL vehicle's (four) and its follower's (two,
-// k_rollout_loop's flush_obs) -- and are gathered into policy_eval<16, WIDE>'s layout with half = 3 (lane i < 3: inputs i
-// and 3 + i), the layout k_policy_act gives a 6-value block.
+// k_rollout_loop's flush_obs) -- and are gathered from registers into policy_wide_inputs' layout for in_dim = 6.
 template <int HEAD, bool DELTA4, bool FASTC>
 __global__ __launch_bounds__(256) void k_loop_policy(DevView<float> s, PolicyView pv, int num_steps, int reset_done,
                                                      float* __restrict__ obs, float* __restrict__ act,
@@ -799,7 +749,7 @@ __global__ __launch_bounds__(256) void k_loop_policy(DevView<float> s, PolicyVie
     } else if (HEAD == 1) {
       const float po0 = divc(v, d_15), po1 = divc(vl - v, d_15), po2 = divc(d, d_po);      // wave_attenuation.py:248-269
       if (obs_lane) { orow[0] = po0; orow[1] = po1; orow[2] = po2; }
-      row_bcast1x3(k_rl, po0, po1, po2, o0, o1, o2);
+      row_bcast<0, 0>(k_rl, po0, po1, po2, o0, o1, o2);
     } else {
       const X xo = c_fs + c_sl * (x - c_st);
       const float po0 = divc(v, d_ms), po1 = divc(xo, d_L);                                   // accel.py:116-123
@@ -828,8 +778,8 @@ __global__ __launch_bounds__(256) void k_loop_policy(DevView<float> s, PolicyVie
         const int i_c = m ? (__builtin_ctzll(m) & (SEG - 1)) : 0;
         const int f_c = i_c == 0 ? N - 1 : i_c - 1;
         float a0, a1, a2, b0, b1, b2;
-        row_bcast1x3(i_c, m0, m1, m2, a0, a1, a2);
-        row_bcast1x3(f_c, m3l, m2, m5, b0, b1, b2);
+        row_bcast<0, 0>(i_c, m0, m1, m2, a0, a1, a2);
+        row_bcast<0, 0>(f_c, m3l, m2, m5, b0, b1, b2);
         const float ia = i == 0 ? a0 : (i == 1 ? a1 : (i == 2 ? a2 : 0.0f));
         const float ib = i == 0 ? b0 : (i == 1 ? b1 : (i == 2 ? b2 : 0.0f));
         float ac;

@@ -994,7 +994,7 @@ __device__ __forceinline__ void merge_queue_body(const DevView<float>& s, const 
       act_row[lane] = lane < n_ag ? policy_no_action() : 0.0f;
       lp_row[lane] = 0.0f;
       q_fence();
-      constexpr int HALF = 3;                          // policy_half(5): lane j < 3 holds inputs j and 3 + j (< 5)
+      constexpr int HALF = policy_half(5);             // policy_wide_inputs' layout, from the features in LDS by column
       const int prow = lane >> 4, j = lane & 15;
       for (int p0 = 0; p0 < np; p0 += 4) {             // (wave-uniform) four agents per pass, one per 16-lane row
         const int idx = p0 + prow;
