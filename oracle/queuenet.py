@@ -16,9 +16,11 @@ The structure (two routes, zipper_distance = 0: flow/networks/merge.py, one lane
   leader(A[k]) = A[k-1];  leader(U1[k]) = U1[k-1], leader(U1[0]) = the last vehicle of D (M5: a vehicle on the other
   branch upstream of the merge point is not a leader);  follower candidates of X (O1: vehicles whose leader is X) = its
   successor in its queue and, for the last vehicle of D, the head of U1.
-Events after a move, in this order: a vehicle no longer strictly behind its queue predecessor -> both queues are
-re-sorted by (x descending, equal x: lower slot first); arrivals leave from the head of A; the head of U1 joins A at
-the place its position gives when it has passed the merge point; an inserted vehicle becomes the tail of its queue.
+Events after a move, in the kernel's order: a vehicle no longer strictly behind its queue predecessor -> both queues
+are re-sorted by (x descending, equal x: lower slot first); the head of U1 joins A at the place its position gives when
+it has passed the merge point; arrivals leave from the head of A (so a ramp vehicle that passes the merge point AND the
+end of the network in one sub-step joins first and leaves as the head of A); an inserted vehicle becomes the tail of
+its queue.  `joins_now` [R] = the joins of the last sub-step, `resorts` / `joins` = totals.
 """
 import numpy as np
 
@@ -36,6 +38,7 @@ class QueueMergeOracle(MergeOracle):
         self.resorts = 0
         self.joins = 0
         self.checks = 0
+        self.joins_now = np.zeros(self.R, dtype=np.int64)
         self._pending = np.zeros(self.R, dtype=bool)
 
     # ------------------------------------------------------------------ structure
@@ -64,6 +67,7 @@ class QueueMergeOracle(MergeOracle):
         for r in range(self.R):
             if not active[r]:
                 continue
+            self.joins_now[r] = 0
             alive_now = [int(i) for i in np.flatnonzero(self.route[r] >= 0)]
             known = self.A[r] + self.U1[r]
             if self._pending[r]:                      # the launch after a reset builds the queues from the slots
@@ -75,6 +79,16 @@ class QueueMergeOracle(MergeOracle):
                 if not (self._ordered(r, self.A[r]) and self._ordered(r, self.U1[r])):
                     self._rebuild(r, known, route_of)
                     self.resorts += 1
+                # the head of U1 passed the merge point: it joins A where its position puts it (before the arrivals: a
+                # ramp vehicle that runs through to the end of the network in one sub-step leaves as the head of A)
+                n_join = 0
+                while self.U1[r] and self.x[r, self.U1[r][0]] >= self.merge_x:
+                    e = self.U1[r].pop(0)
+                    k = sum(1 for a in self.A[r] if (self.x[r, a] > self.x[r, e]) or (self.x[r, a] == self.x[r, e] and a < e))
+                    self.A[r].insert(k, e)
+                    self.joins += 1
+                    n_join += 1
+                self.joins_now[r] = n_join
                 # M4: arrivals are the head of A
                 arrived = set(int(i) for i in np.flatnonzero(self._just_arrived[r]))
                 n_arr = 0
@@ -82,12 +96,6 @@ class QueueMergeOracle(MergeOracle):
                     n_arr += 1
                 assert set(self.A[r][:n_arr]) == arrived, (r, self.A[r][:n_arr], arrived)
                 self.A[r] = self.A[r][n_arr:]
-                # the head of U1 passed the merge point: it joins A where its position puts it
-                while self.U1[r] and self.x[r, self.U1[r][0]] >= self.merge_x:
-                    e = self.U1[r].pop(0)
-                    k = sum(1 for a in self.A[r] if (self.x[r, a] > self.x[r, e]) or (self.x[r, a] == self.x[r, e] and a < e))
-                    self.A[r].insert(k, e)
-                    self.joins += 1
                 # M3: a vehicle inserted in this sub-step is the tail of its queue
                 for i in alive_now:
                     if i not in known:

@@ -9,6 +9,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from oracle import network as Net   # noqa: E402
 from oracle import refsim as S      # noqa: E402
+from oracle.opennet import ENV_MERGE_MA   # noqa: E402
 
 IDM_DEFAULT = [30, 1, 1, 1.5, 4, 2, 0, 0]       # car_following_models.py:437-447
 
@@ -161,6 +162,307 @@ def merge_spec(R=4, cap_human=12, cap_rl=4, num_rl=2, pre=200.0, merge=100.0, po
                 network="merge", **tb)
     spec.update(kw)
     return spec
+
+
+def merge_layout(spec, layout):
+    """A constructed initial state of the merge network: ``layout`` = {slot: (x, speed, route)} on the routes' common
+    coordinate (spec['merge_x'], spec['end_x']), the same in every replica.  Returns the init_alive / init_pos /
+    init_vel / init_route entries of a spec (merge_spec takes them through **kw; dict.update on a built spec too)."""
+    R, N = int(spec["num_replicas"]), int(spec["num_vehicles"])
+    alive = np.zeros((R, N), dtype=bool)
+    X, V = np.zeros((R, N)), np.zeros((R, N))
+    route = np.zeros((R, N), dtype=np.int32)
+    for slot, (x, speed, rt) in layout.items():
+        assert 0 <= slot < N and not alive[0, slot]
+        alive[:, slot], X[:, slot], V[:, slot], route[:, slot] = True, x, speed, rt
+    return dict(init_alive=alive, init_pos=X, init_vel=V, init_route=route)
+
+
+def quiet_spec(spec):
+    """The same spec with the acceleration noise switched off (bit-exact comparisons)."""
+    spec = dict(spec)
+    spec["vehicles"] = [dict(v, noise=0.0) for v in spec["vehicles"]]
+    return spec
+
+
+def nan_actions(R, A, seed, p_nan=0.2):
+    """k -> [R, A] actions (call in step order), NaN with probability p_nan: "the vehicle just entered", no action."""
+    rng = np.random.default_rng(seed)
+
+    def acts(k):
+        a = rng.uniform(-1.0, 1.5, (R, A)).astype(np.float32)
+        a[rng.random((R, A)) < p_nan] = np.nan
+        return a
+    return acts
+
+
+def action_tape(action_fn, K):
+    """[K, R, A]: the actions of steps 0 .. K - 1."""
+    return np.stack([action_fn(k) for k in range(K)])
+
+
+# ------------------------------------------------------------------ constructed edge states of the merge network
+# (tests/test_queue_model.py proves the queue formulation on them on the CPU, tests/test_queue_edges_gpu.py runs them on
+# k_merge_queue), the event counters of an oracle run and the floors the tests assert on them
+class SubSteps:
+    """Per sub-step event counts of an oracle run, [sub-step, R]: vehicles alive when the sub-step starts, arrivals,
+    insertions and (QueueMergeOracle) joins and re-sorts.  SubSteps(ora) hooks the oracle's _substep."""
+
+    def __init__(self, ora):
+        self.ora, self.alive0, self.arrived, self.departed, self.joins, self.resorts = ora, [], [], [], [], []
+        inner = ora._substep
+
+        def substep(actions, active):
+            n0, rs0 = ora.alive.sum(axis=1), getattr(ora, "resorts", 0)
+            crash = inner(actions, active)
+            self.alive0.append(np.where(active, n0, 0))
+            self.arrived.append(np.where(active, ora.num_arrived, 0))
+            self.departed.append(np.where(active, ora.num_departed, 0))
+            self.joins.append(np.where(active, getattr(ora, "joins_now", np.zeros(ora.R, dtype=np.int64)), 0))
+            self.resorts.append(getattr(ora, "resorts", 0) - rs0)
+            return crash
+        ora._substep = substep
+
+    def table(self):
+        """[sub-step, R] arrays: (alive at the start, arrivals, insertions, joins)."""
+        return tuple(np.array(a).reshape(-1, self.ora.R) for a in (self.alive0, self.arrived, self.departed, self.joins))
+
+    def full_wave_figures(self, full):
+        """(sub-steps that start with `full` vehicles, joins from there, arrivals from there) -- the least of any replica."""
+        alive0, arrived, _, joins = self.table()
+        at = alive0 == full
+        return int(at.sum(axis=0).min()), int((joins * at).sum(axis=0).min()), int((arrived * at).sum(axis=0).min())
+
+
+def full_wave_spec(R=2, env=ENV_MERGE_MA, spacing=7.0, ramp_head=8.0, hole=0.0, **kw):
+    """All 64 slots of a 64-lane wave alive from the start: 40 vehicles on the highway, the first 8 m before the end of
+    the network, and 24 on the ramp, the first `ramp_head` m before the merge point, `spacing` m apart at 5 m/s, slots shuffled
+    (36 humans + 4 RL vehicles on the highway, 22 + 2 on the ramp); busy inflows keep the pool full."""
+    kw.setdefault("horizon", 1000)
+    spec = quiet_spec(merge_spec(R=R, cap_human=58, cap_rl=6, num_rl=6, q_highway=2400.0, q_merge=900.0, sim_step=0.2, env=env, **kw))
+    rng = np.random.default_rng(64)
+    humans, rls = rng.permutation(58), 58 + rng.permutation(6)
+    on0 = rng.permutation(np.concatenate([humans[:36], rls[:4]]))
+    on1 = rng.permutation(np.concatenate([humans[36:], rls[4:]]))
+    at0 = spec["end_x"] - 8.0 - spacing * np.arange(40)
+    at0 = np.where(at0 < spec["merge_x"], at0 - hole, at0)     # `hole` m of free highway before the merge point
+    lay = {int(s): (float(at0[i]), 5.0, 0) for i, s in enumerate(on0)}
+    lay.update({int(s): (spec["merge_x"] - ramp_head - spacing * i, 5.0, 1) for i, s in enumerate(on1)})
+    assert len(lay) == 64
+    spec.update(merge_layout(spec, lay))
+    return spec
+
+
+def two_spec(R=2, rl_arrives=False, **kw):
+    """sim_step 2 s: the two highway vehicles pass the end of the network and the two ramp vehicles the merge point in
+    the FIRST sub-step, and (begin = 1 s <= now = 2 s) the inflows insert.  rl_arrives: the first vehicle is an RL one."""
+    kw.setdefault("horizon", 1000)
+    spec = quiet_spec(merge_spec(R=R, cap_human=20, cap_rl=2, sim_step=2.0, **kw))
+    e, m = spec["end_x"], spec["merge_x"]
+    spec.update(merge_layout(spec, {(20 if rl_arrives else 0): (e - 5.0, 20.0, 0), 1: (e - 32.0, 20.0, 0),
+                                    2: (m - 3.0, 15.0, 1), 3: (m - 28.0, 15.0, 1)}))
+    return spec
+
+
+def join_tie_spec(ramp_slot, highway_slot, R=2, **kw):
+    """A highway and a ramp vehicle 12 m before the merge point at 10 m/s, no right of way: they pass it side by side, at
+    bit-equal x, and the join orders them by slot."""
+    kw.setdefault("horizon", 1000)
+    spec = quiet_spec(merge_spec(R=R, cap_human=10, cap_rl=2, sim_step=0.5, **kw))
+    spec["junction"] = dict(spec["junction"], enabled=0)
+    m = spec["merge_x"]
+    spec.update(merge_layout(spec, {highway_slot: (m - 12.0, 10.0, 0), ramp_slot: (m - 12.0, 10.0, 1)}))
+    return spec
+
+
+def through_spec(R=2, **kw):
+    """sim_step 2 s, 50 m from the merge point to the end: the ramp vehicle (slot 0, 28 m/s, 4 m before the merge point)
+    passes the merge point AND the end of the network in the first sub-step -- it joins and arrives at once."""
+    kw.setdefault("horizon", 1000)
+    spec = quiet_spec(merge_spec(R=R, cap_rl=4, num_rl=4, sim_step=2.0, post=50.0, **kw))
+    spec["junction"] = dict(spec["junction"], enabled=0)
+    m = spec["merge_x"]
+    spec.update(merge_layout(spec, {0: (m - 4.0, 28.0, 1), 1: (m - 40.0, 20.0, 0)}))
+    return spec
+
+
+def tail_tie_spec(moving_slot, resting_slot, R=2, route=0, speeds=(4.0, 0.0), **kw):
+    """An insertion checked against a tail of TWO vehicles at one position (M3; oracle/opennet.py takes the lowest slot):
+    RL vehicles with action 0 and no speed-mode clamp keep their speed exactly, so the one at rest at X and the one 2 m
+    behind it at 4 m/s (sim_step 0.5) are both at X after the first sub-step.  The inflow on that route (begin 0: due in
+    that sub-step) finds a gap of 24 m: the SUMO-IDM desired gap is 27.1 m behind the vehicle at rest and 21.3 m behind
+    the moving one, so WHICH of the two is the tail decides whether the vehicle enters.  speeds = (0, 0): the plain case of two vehicles
+    at rest at equal init_pos (nothing enters)."""
+    kw.setdefault("horizon", 1000)
+    spec = quiet_spec(merge_spec(R=R, cap_human=6, cap_rl=4, num_rl=4, sim_step=0.5, env=ENV_MERGE_MA, ma_apply_actions=True, **kw))
+    spec["vehicles"] = [dict(v, speed_mode=0) if v["rl_index"] >= 0 else v for v in spec["vehicles"]]
+    x_dep = spec["routes"][route]["start"] + 5.0
+    X = x_dep + 5.0 + 24.0
+    spec.update(merge_layout(spec, {moving_slot: (X - speeds[0] * 0.5, speeds[0], route), resting_slot: (X, speeds[1], route)}))
+    spec["inflows"] = [dict(spec["inflows"][0], route=route, begin=0.0, period=50.0)]
+    return spec
+
+
+def resort_tie_spec(R=2, **kw):
+    """Three vehicles at ONE position after the first sub-step, reached from behind: RL vehicles with action 0 and no
+    speed-mode clamp (they keep their speed exactly) 0, 2 and 4 m behind X at 0, 4 and 8 m/s, in a slot order that is
+    not the queue order -- the re-sort ranks three equal positions by slot."""
+    kw.setdefault("horizon", 1000)
+    spec = quiet_spec(merge_spec(R=R, cap_human=6, cap_rl=4, num_rl=4, sim_step=0.5, env=ENV_MERGE_MA, ma_apply_actions=True, **kw))
+    spec["vehicles"] = [dict(v, speed_mode=0) if v["rl_index"] >= 0 else v for v in spec["vehicles"]]
+    X = spec["routes"][0]["start"] + 150.0
+    spec.update(merge_layout(spec, {8: (X, 0.0, 0), 6: (X - 2.0, 4.0, 0), 7: (X - 4.0, 8.0, 0), 0: (X - 40.0, 0.0, 0)}))
+    return spec
+
+
+def schedule_spec(which, R=2, **kw):
+    """Inflow schedules at their edges (M2), sim_step 0.2 s, a pool of 10 + 3 slots that runs full, empty at reset.
+    'always_due': RL vehicles on the highway, begin 0, period 3 sim_step, number = 3 (first in InFlows order: they take the
+    first three gaps); humans on the highway, begin 0, period = sim_step (a vehicle is due every sub-step: one always
+    waits); humans on the ramp, begin 0, period = 3 sim_step.
+    'window': humans on the ramp, begin 1, period 0.2, end = 20 s (~95 vehicles are due by then and wait for a gap or a slot
+    long after); two humans on the highway from begin = 3 * (3 * 0.2) = 1.8000000000000003 > 9 * 0.2 in float64: the first
+    is due at sub-step index 10, not 9, and the entrance is free then; the default highway inflow from 4 s; RL vehicles on
+    the highway due at 2, 6 and 10 s, end = 11 s: the fourth (14 s) is beyond the end -- the inflow closes after three."""
+    kw.setdefault("horizon", 1000)
+    spec = quiet_spec(merge_spec(R=R, cap_human=10, cap_rl=3, num_rl=3, sim_step=0.2, env=ENV_MERGE_MA, n_init=0, **kw))
+    hw, rl, ramp = spec["inflows"]
+    if which == "always_due":
+        spec["inflows"] = [dict(rl, begin=0.0, period=3 * 0.2, number=3), dict(hw, begin=0.0, period=0.2),
+                           dict(ramp, begin=0.0, period=3 * 0.2)]
+    else:
+        spec["inflows"] = [dict(ramp, begin=1.0, period=0.2, end=20.0), dict(hw, begin=3 * (3 * 0.2), period=3 * 0.2, number=2),
+                           dict(hw, begin=4.0), dict(rl, begin=2.0, period=4.0, end=11.0)]
+    return spec
+
+
+def places32_spec(R=2, **kw):
+    """MergePOEnv with a list of 32 places on 64 slots: 26 RL vehicles on the highway, the first 6 m before the end of
+    the network, 6 on the ramp, 15 m apart, one human behind the highway's.  The list's order is the slots' order at
+    reset: in replica 0 that is the driving order (the vehicle that leaves is at place 0), replica 1 holds the same
+    vehicles in the RL slots REVERSED (it leaves from place 31, 30, ...), replica 2: see below."""
+    kw.setdefault("horizon", 10 ** 6)
+    spec = quiet_spec(merge_spec(R=R, cap_human=32, cap_rl=32, num_rl=32, pre=500.0, q_rl=1800.0, q_highway=600.0, sim_step=0.5,
+                                 **kw))
+    e, m = spec["end_x"], spec["merge_x"]
+    lay = {32 + i: (e - 6.0 - 15.0 * i, 8.0, 0) for i in range(26)}
+    lay.update({58 + i: (m - 40.0 - 15.0 * i, 5.0, 1) for i in range(6)})
+    lay[0] = (e - 6.0 - 15.0 * 26, 8.0, 0)
+    spec.update(merge_layout(spec, lay))
+    if R > 1:
+        perm = np.arange(64)
+        perm[32:] = perm[32:][::-1]
+        for key in ("init_alive", "init_pos", "init_vel", "init_route"):
+            spec[key][1, perm] = spec[key][1].copy()
+    if R > 2:
+        # replica 2: 18 + 6 RL vehicles in the HIGH RL slots 40 .. 63, 100 m further back (nobody leaves for 30 s): the RL
+        # inflow fills slots 32 .. 39 and places 24 .. 31.  reset() keeps rl_veh (merge.py:223-231): a reset then leaves
+        # those eight as a run of departed entries at places 24 .. 31, which the removal loop takes in four passes
+        for key in ("init_alive", "init_pos", "init_vel", "init_route"):
+            spec[key][2] = 0
+        late = {40 + i: (e - 106.0 - 15.0 * i, 8.0, 0) for i in range(18)}
+        late.update({58 + i: (m - 40.0 - 15.0 * i, 5.0, 1) for i in range(6)})
+        for slot, (x, v, rt) in late.items():
+            for key, val in (("init_alive", True), ("init_pos", x), ("init_vel", v), ("init_route", rt)):
+                spec[key][2, slot] = val
+    return spec
+
+
+class ReferenceLists:
+    """MergePOEnv.additional_command (merge.py:189-221) with its own Python list operations, driven by the vehicles the
+    oracle has in the network at every call (tests/test_open_cpu.py holds the oracle to them at four places): the oracle's
+    rl_veh must be that list at every sub-step.  Counts what the run reached: `most_listed`, and `skipped_at` = the
+    places of the entries the removal loop skipped (it removes from the list it iterates)."""
+
+    def __init__(self, ora):
+        import collections
+        self.ora, self.most_listed, self.skipped_at = ora, 0, []
+        self.queues = [collections.deque() for _ in range(ora.R)]
+        self.lists = [[] for _ in range(ora.R)]
+        inner = ora._additional_command
+
+        def hooked(active):
+            for r in range(ora.R):
+                if active[r]:
+                    self.reference(r)
+            inner(active)
+            for r in range(ora.R):
+                if active[r]:
+                    ids = self.vehicle_ids(r)
+                    got = [self.name(r, i) if ora.alive[r, i] and ora.is_rl[i] else None
+                           for i in sorted(np.flatnonzero(ora.ctl_seq[r] >= 0), key=lambda i: ora.ctl_seq[r, i])]
+                    assert got == [v if v in ids else None for v in self.lists[r]], (r, got, self.lists[r])
+                    self.most_listed = max(self.most_listed, sum(1 for v in self.lists[r] if v in ids))
+        ora._additional_command = hooked
+
+    def name(self, r, i):
+        return (int(self.ora.episode[r]) if self.ora.origin[r, i] >= 0 else -1, int(self.ora.origin[r, i]))
+
+    def vehicle_ids(self, r):
+        ora = self.ora
+        slots = sorted(np.flatnonzero(ora.alive[r] & ora.is_rl), key=lambda i: ora.seq[r, i])
+        return [self.name(r, i) for i in slots]
+
+    def reference(self, r):
+        rl_ids, rl_queue, rl_veh = self.vehicle_ids(r), self.queues[r], self.lists[r]
+        for veh_id in rl_ids:                                         # merge.py:201-203
+            if veh_id not in list(rl_queue) + rl_veh:
+                rl_queue.append(veh_id)
+        for veh_id in list(rl_queue):                                 # :205-207
+            if veh_id not in rl_ids:
+                rl_queue.remove(veh_id)
+        gone = [(p, v) for p, v in enumerate(rl_veh) if v not in rl_ids]
+        for veh_id in rl_veh:                                         # :208-210 (iterates the list it shrinks)
+            if veh_id not in rl_ids:
+                rl_veh.remove(veh_id)
+        self.skipped_at += [p for p, v in gone if v in rl_veh]
+        while len(rl_queue) > 0 and len(rl_veh) < self.ora.num_rl:    # :213-215
+            rl_veh.append(rl_queue.popleft())
+
+
+# the floors of the full wave (measured on this layout, 400 steps, R = 2, the least of the replicas: MultiAgentMergePOEnv
+# as shipped 232 sub-steps that start with 64 vehicles, 3 joins and 20 arrivals from there, 19 insertions; actions applied
+# 263 / 3 / 20 / 19; MergePOEnv on the spaced layout 176 / 4 / 11 / 16, no collision; actions: nan_actions seeds 13 and 7)
+FULL_WAVE_FLOORS = dict(full=100, joins=1, arrivals=10, departed=8)
+FULL_WAVE_PO = dict(hole=40.0)          # MergePOEnv: 40 m of free highway before the merge point
+
+
+def assert_full_wave(q, sub, floors=FULL_WAVE_FLOORS):
+    full, joins, arrivals = sub.full_wave_figures(64)
+    assert full >= floors["full"] and arrivals >= floors["arrivals"], (full, joins, arrivals)
+    if hasattr(q, "joins"):
+        assert joins >= floors["joins"], (full, joins, arrivals)
+    assert q.total_departed.min() >= floors["departed"]
+    return full, joins, arrivals
+
+
+def assert_two_of_each(sub):
+    alive0, arrived, departed, joins = sub.table()
+    assert (alive0[0] == 4).all() and (arrived[0] == 2).all() and (departed[0] == 2).all()
+    if hasattr(sub.ora, "joins"):
+        assert (joins[0] == 2).all()
+
+
+def tie_at_the_join(q, ramp_slot, highway_slot):
+    """the sub-step of the (first) join: both vehicles are past the merge point at bit-equal x"""
+    x = q.x[:, [ramp_slot, highway_slot]]
+    return (x[:, 0] == x[:, 1]).all() and (x[:, 0] >= q.merge_x).all()
+
+
+def assert_schedule(which, emitted):
+    """emitted [step, R, flow] of 300 steps of schedule_spec(which), by the oracle."""
+    if which == "always_due":
+        assert (emitted[0, :, 0] == 1).all() and (emitted[0, :, 2] == 1).all()        # begin = 0: in at sub-step 0
+        assert (emitted[-1, :, 0] == 3).all()                                          # emitted == number (at step 13)
+        assert (emitted[-1, :, 1] >= 8).all() and (emitted[-1, :, 2] >= 3).all()        # (measured 16, 6)
+    else:
+        # the highway vehicle due at 1.8000000000000003 s enters at n = 10 (step 9), not at n = 9: 9 * 0.2 = 1.8 < due
+        assert (emitted[8, :, 1] == 0).all() and (emitted[9, :, 1] == 1).all() and (emitted[-1, :, 1] == 2).all()
+        # now = (k + 1) * 0.2 > end = 20 s from step 100 on: the vehicles that were due by then still enter
+        assert (emitted[-1, :, 0] - emitted[100, :, 0] >= 5).all()                      # (measured 13: 5 by 20 s, 18 by 60 s)
+        assert (emitted[-1, :, 0] < 96).all()
+        # the inflow with end = 11 s closed itself: due at 2, 6, 10 s, the vehicle of 14 s never comes
+        assert (emitted[-1, :, 3] == 3).all() and (emitted[150, :, 3] == 3).all()
 
 
 def bottleneck_tables(junction_length=0.1, zipper_length=20.0, scaling=1):

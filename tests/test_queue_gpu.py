@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import merge_spec
+from helpers import merge_spec, nan_actions           # noqa: F401 (nan_actions: other test modules take it from here)
 from oracle import opennet as O
 from test_open_gpu import compare_state, make, quiet, run_pair
 
@@ -17,16 +17,6 @@ pytestmark = pytest.mark.gpu
 def ma_spec(**kw):
     kw.setdefault("env", O.ENV_MERGE_MA)
     return merge_spec(**kw)
-
-
-def nan_actions(R, A, seed, p_nan=0.2):
-    rng = np.random.default_rng(seed)
-
-    def acts(k):
-        a = rng.uniform(-1.0, 1.5, (R, A)).astype(np.float32)
-        a[rng.random((R, A)) < p_nan] = np.nan              # "the vehicle just entered": no action
-        return a
-    return acts
 
 
 def test_queue_kernel_is_chosen_and_bit_exact_against_the_oracle():
