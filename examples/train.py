@@ -38,7 +38,8 @@ def parse_args(args):
     parser.add_argument('--replicas', type=int, default=1024, help='device: environment replicas in the handle')
     parser.add_argument('--fuse_policy', action='store_true',
                         help='device: roll an action-vector policy (singleagent_merge) out through the fused policy + '
-                             'step kernel instead of the captured graph')
+                             'step kernel instead of the captured graph; where there is none (singleagent_bottleneck), '
+                             'capture the graph around the policy kernel instead of the torch module')
     return parser.parse_known_args(args)[0]
 
 

@@ -144,9 +144,11 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     policy_mapping_fn): the observation row holds one block per agent, the action row one column per agent; every agent
     is a sample of the shared policy and receives the shared reward.
     ``fuse_action_vector``: an experiment whose ONE network emits several action columns (MergePOEnv:
-    singleagent_merge.py) rolls out through the fused policy + step kernel as well (k_merge_policy<PO>).  Off by default:
-    the fused form draws its samples from the library's Philox streams, the captured graph from torch.randn, so the two
-    are different (equally valid) trajectories."""
+    singleagent_merge.py) rolls out through the fused policy + step kernel as well (k_merge_policy<PO>); where no fused
+    kernel exists but the eager policy kernel does (BottleneckDesiredVelocityEnv: singleagent_bottleneck.py,
+    k_policy_act_wide), the captured graph holds that kernel instead of the torch module.  Off by default: the library's
+    kernels draw their samples from its Philox streams, the torch policy from torch.randn, so the two are different
+    (equally valid) trajectories."""
     from flow_amd.dist import allreduce_sum, shard_range
     from flow_amd.envs import VecFlowEnv
     local = int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else 0
@@ -167,7 +169,7 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     # otherwise K single steps around the torch policy captured as one HIP graph.  (Shared agents: the network's input is
     # one agent's block, k_ag values; on the merge an agent whose RL slot is empty has a NaN action, which ppo_update
     # leaves out.)
-    fused, graph = None, None
+    fused, graph, graph_policy = None, None, None
     shared = "; one policy shared by %d agents per replica" % n_ag if shared_agents else ""
     try:
         from flow_amd.utils.device_policy import DevicePolicy
@@ -181,8 +183,22 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
         vec.reset()
         log("rollout: fused policy + step kernel (%s)%s" % (kernel, shared))
     except NotImplementedError as e:
-        fused = None
-        log("rollout: HIP graph of %d single steps around the torch policy (%s)%s" % (fragment, e, shared))
+        why = e
+        graph_policy, fused = (fused if fuse_action_vector and not shared_agents else None), None
+        if graph_policy is not None:
+            # no fused kernel for this head (BottleneckDesiredVelocityEnv): the library's eager policy kernel, where it is
+            # built, goes into the captured fragment in the torch module's place -- one launch per step instead of ten-odd
+            try:
+                vec.reset()
+                vec.policy_act(graph_policy)                   # (probe)
+                kernel = vec.sim.last_kernel
+                graph = vec.capture(fragment, policy=graph_policy, reset_done=True)
+                graph.begin(vec.reset())
+                log("rollout: HIP graph of %d single steps around the policy kernel (%s)" % (fragment, kernel))
+            except NotImplementedError:
+                graph_policy = None
+    if fused is None and graph is None:
+        log("rollout: HIP graph of %d single steps around the torch policy (%s)%s" % (fragment, why, shared))
         if world > 1:
             torch.manual_seed(seed + 1000 * (rank + 1))       # the graph's torch.randn: another stream per rank
         R_ = hi - lo
@@ -201,6 +217,8 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
             obs, act, _, rew, done = vec.policy_rollout(fused, K, reset_done=True)
             torch.cuda.synchronize(dev)
         else:
+            if graph_policy is not None:
+                graph_policy.sync()                            # the graph reads the weights at the packed buffer's address
             obs, act, rew, done = graph.replay()               # K closed-loop steps of R replicas: one graph launch
             graph.synchronize()
         t_roll = time.perf_counter() - t0

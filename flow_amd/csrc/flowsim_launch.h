@@ -54,6 +54,15 @@ namespace fsim {
                        act, logp);
     return launched();
   }
+  // the eager form of BottleneckDesiredVelocityEnv's action-vector policy (more than 32 inputs: one wave per replica, four
+  // replicas per workgroup)
+  template <typename T>
+  int Sim<T>::launch_policy_act_wide(const fs::PolicyView& pv, const float* obs_in, float* act, float* logp) {
+    last_kernel = "k_policy_act_wide";
+    hipLaunchKernelGGL(fs::k_policy_act_wide<16>, dim3((dv.R + 3) / 4), dim3(256), 0, stream, pv, dv.R, dv.num_rl, dv.rep0,
+                       obs_in, act, logp);
+    return launched();
+  }
   template <typename T>
   int Sim<T>::launch_dropq(const StepArgs& a) {
     const auto k = dv.env == FS_ENV_BOTTLENECK_DV ? &fs::k_drop_queue<true> : &fs::k_drop_queue<false>;

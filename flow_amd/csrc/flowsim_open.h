@@ -64,6 +64,7 @@ struct OpenView {
   int lc_enabled, lc_cooldown;
   T lc_min_gain;
   T out_norm;                  // 2000 * scaling
+  int mask_skip;               // 1: a masked launch runs its zero-step form where it selects nothing (0: FLOWSIM_NO_MASK_SKIP=1)
 };
 
 enum {
@@ -302,7 +303,7 @@ __device__ __forceinline__ int cell_of(const TABS& tb, int span, T x, int seg_k,
 // PO: the MergePOEnv head (rl_veh / rl_queue bookkeeping, places -> action columns); the other merge head
 // (MultiAgentMergePOEnv, C5) is its own instantiation without any of it
 template <typename T, int SEG, int P, int CSET = 0, bool PROB = false, bool PO = false>
-__global__ __launch_bounds__(64) void k_steps_open(DevView<T> s, OpenView<T> o, int num_steps,
+__global__ __launch_bounds__(64) void k_steps_open(DevView<T> s, OpenView<T> o, int num_steps_arg,
                                                    const uint8_t* __restrict__ mask,
                                                    const float* __restrict__ actions, size_t act_stride,
                                                    float* __restrict__ obs, float* __restrict__ rew,
@@ -379,6 +380,12 @@ __global__ __launch_bounds__(64) void k_steps_open(DevView<T> s, OpenView<T> o, 
   RouteCursor<T, OpenTabs<T, TABS_IN_LDS>> cur;
 
   const bool live_replica = rvalid && (mask == nullptr || mask[rr] != 0);
+  // a masked launch (the warm-up steps of a reset: one observation at the end) advances nothing in a wave none of whose
+  // replicas is selected: it only has to report the observation of the unchanged state, the zero-step form -- as in
+  // k_steps (flowsim_kernels.h); what makes a reset of the few finished episodes cheap inside a captured closed-loop
+  // fragment (VecFlowEnv.capture with warm-up steps).  o.mask_skip = 0 (FLOWSIM_NO_MASK_SKIP=1): every wave steps.
+  const int num_steps = (mask != nullptr && !obs_every_step && o.mask_skip != 0 && __ballot(live_replica) == 0ull)
+                            ? 0 : num_steps_arg;
   int tcount = s.time[rr];
   uint32_t nctr = s.noise_ctr[rr];
   int32_t* cnt = o.counters + size_t(rr) * 8;

@@ -11,6 +11,7 @@ template int Sim<FS_PART_T>::launch_queue(const StepArgs&);
 template int Sim<FS_PART_T>::launch_dropq(const StepArgs&);
 template int Sim<FS_PART_T>::launch_policy_queue(const fs::PolicyView&, int, int, float*, float*, float*, float*, uint8_t*);
 template int Sim<FS_PART_T>::launch_policy_act_vec(const fs::PolicyView&, const float*, float*, float*);
+template int Sim<FS_PART_T>::launch_policy_act_wide(const fs::PolicyView&, const float*, float*, float*);
 #elif defined(FS_PART_WIDE)
 template int Sim<FS_PART_T>::launch_wide<FS_PART_WIDE>(const StepArgs&);
 #elif defined(FS_PART_SEG)

@@ -16,8 +16,9 @@
 // stopped).
 //
 // The network is written ONCE: policy_layer is the 32-input layer, policy_trunk the layer sequence (narrow or WIDE first
-// layer, then the hidden layers), policy_load_trunk its weights' way into LDS.  All six kernels that evaluate a policy
-// call that trunk -- the eager k_policy_act and k_policy_act_vec (fs_policy_act_dev), the fused k_ring_policy,
+// layer, then the hidden layers), policy_load_trunk its weights' way into LDS.  All seven kernels that evaluate a policy
+// call that trunk -- the eager k_policy_act, k_policy_act_vec and k_policy_act_wide (fs_policy_act_dev; the last with a
+// first layer of more than 32 inputs, policy_wide_layer1, which is policy_layer over chunks), the fused k_ring_policy,
 // k_loop_policy, k_merge_queue<POLICY> and k_merge_policy (flowsim_queue.h) -- through policy_eval (the trunk and the
 // two-output Gaussian head) or policy_vec_act (the trunk and the action-vector head), so a fragment is bit-identical to
 // eager stepping by construction (tests/test_policy_gpu.py and its siblings).  Every operation is an explicit fma /
@@ -154,7 +155,9 @@ __device__ __forceinline__ f2 policy_layer(const float4 (&ww)[16], float b_j, fl
 // observation of THIS row's replica; j = lane within the row.  Narrow first layer: (o0, o1, o2), the same three values
 // in every lane of the row.  WIDE: two values per lane in policy_wide_inputs' layout (o0: input j, o1: input half + j of
 // THIS lane; o2 unused) -- a hidden layer's form and summation order.
-template <bool WIDE>
+// PRE (the first layer of MORE than 32 inputs, policy_wide_layer1 below): o0 / o1 are this lane's two first-layer sums,
+// bias included; the trunk starts at their tanh.
+template <bool WIDE, bool PRE = false>
 __device__ __forceinline__ void policy_trunk(const PolicyView& pv, const PolicyLds* L, int j, float o0, float o1, float o2,
                                              float& ha, float& hb) {
   // The first two weight quads of a hidden layer are read one layer AHEAD (before the previous layer's tanh): the layer's
@@ -167,7 +170,10 @@ __device__ __forceinline__ void policy_trunk(const PolicyView& pv, const PolicyL
   };
   if (pv.num_hidden > 1) load_ahead(0);
   // layer 1
-  if constexpr (WIDE) {
+  if constexpr (PRE) {
+    ha = policy_tanh(o0);
+    hb = policy_tanh(o1);
+  } else if constexpr (WIDE) {
     float4 ww[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) ww[q] = *reinterpret_cast<const float4*>(L->w_wide[q][j]);
@@ -392,6 +398,153 @@ __global__ __launch_bounds__(64) void k_policy_act_vec(PolicyView pv, int R, int
   const uint32_t c0 = pv.ctr[r];
   const float lp = policy_vec_act(pv, A, &L, &V, rep0 + uint32_t(r), c0, lane, obs + size_t(r) * pv.in_dim, act_row);
   if (lane < A) act[size_t(r) * A + lane] = act_row[lane];
+  if (lane == 0) {
+    logp[r] = lp;
+    pv.ctr[r] = c0 + 1u;
+  }
+}
+
+// ---- the WIDE action-vector head (FS_ENV_BOTTLENECK_DV: BottleneckDesiredVelocityEnv, 141 -> 20) ----------------------
+// ONE network maps the whole observation (in_dim = 4 cells + 1 values, 33 .. 513) to A = num_rl <= 64 action columns.  A
+// WAVE is one replica, as in policy_vec_act; nothing below depends on R, the grid, or the place of the wave in its
+// workgroup, so a fused kernel that gives a replica's wave to policy_wide_act computes the same bits.
+//
+// THE FIRST LAYER (policy_wide_layer1), its summation order:
+//   * the observation is cut into CHUNKS of 32 inputs, chunk n = inputs 32 n .. 32 n + 31 (inputs from in_dim on: zero,
+//     and so are their weights);
+//   * row w (lanes 16 w .. 16 w + 15) of the wave takes chunks w, w + 4, w + 8, ... in ascending order and runs each
+//     through policy_layer -- THE 32-input layer, with its four accumulators and its ((b + z0) + z1) + (z2 + z3) --
+//     with the row's running sum in the bias' place: P_w = layer(chunk w + 4 m, layer(..., layer(chunk w, b_w))),
+//     b_0 = the unit's bias, b_1 = b_2 = b_3 = 0; every row makes ceil(chunks / 4) passes, a pass beyond the last
+//     chunk adds zeros;
+//   * the unit's sum is (P_0 + P_1) + (P_2 + P_3): v_permlane16_swap, then v_permlane32_swap (a + b is commutative,
+//     so the four rows hold the same bits).
+// Lane j of every row ends with the sums of units j and j + 16: what policy_trunk<., PRE> takes.
+// Weights: a first-layer weight is used ONCE per replica, so it is not staged in LDS (32 x 513 floats would not fit the
+// 64 KB of static LDS either, and a workgroup would write as many bytes to LDS as it then reads).  Lane j reads the 32
+// floats of rows j and j + 16 of W1 at its chunk as eight 16-byte loads each, straight from the packed buffer (W1 is
+// row-major and in_dim is odd: the loads are 4-byte aligned, which global memory takes); the four rows of the wave read
+// four consecutive 128-byte pieces of the same 32 weight rows, and every replica reads the same 18 .. 66 KB, which stay
+// in L2.  A 16-byte load of the last chunk may run past the end of a weight row into the next one, and past W1 into b1
+// and the layers behind it (at most 31 floats: inside the buffer); those values are replaced by zero before use.
+__device__ __forceinline__ f2 policy_wide_layer1(const PolicyView& pv, const PolicyLds* L, int lane, const float* o) {
+  const int j = lane & 15, row = lane >> 4;
+  const int in_dim = pv.in_dim, nch = (in_dim + 31) >> 5;
+  const float* wa = pv.w + size_t(j) * in_dim;
+  const float* wb = pv.w + size_t(j + 16) * in_dim;
+  f2 z = {row == 0 ? L->b[0][j] : 0.0f, row == 0 ? L->b[0][j + 16] : 0.0f};
+#pragma unroll 1
+  for (int n0 = 0; n0 < nch; n0 += 4) {
+    const int n = n0 + row;
+    const int base = 32 * (n < nch ? n : nch - 1);         // (a pass beyond the last chunk: a valid address, nothing used)
+    const int left = in_dim - 32 * n;                      // inputs of this chunk that exist (<= 0: none)
+    const int ia = base + j, ib = base + 16 + j;
+    const float a = j < left ? o[ia < in_dim ? ia : 0] : 0.0f;
+    const float b = 16 + j < left ? o[ib < in_dim ? ib : 0] : 0.0f;
+    float4 ww[16];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {                          // inputs 4 t .. 4 t + 3 of the chunk: rows j and j + 16 of W1
+      float4 ra, rb;
+      __builtin_memcpy(&ra, wa + base + 4 * t, 16);
+      __builtin_memcpy(&rb, wb + base + 4 * t, 16);
+      const bool k0 = 4 * t < left, k1 = 4 * t + 1 < left, k2 = 4 * t + 2 < left, k3 = 4 * t + 3 < left;
+      ww[2 * t] = make_float4(k0 ? ra.x : 0.0f, k0 ? rb.x : 0.0f, k1 ? ra.y : 0.0f, k1 ? rb.y : 0.0f);
+      ww[2 * t + 1] = make_float4(k2 ? ra.z : 0.0f, k2 ? rb.z : 0.0f, k3 ? ra.w : 0.0f, k3 ? rb.w : 0.0f);
+    }
+    z = policy_layer(ww, z.x, z.y, a, b);
+  }
+  z.x = add_swap32(add_swap16(z.x));
+  z.y = add_swap32(add_swap16(z.y));
+  return z;
+}
+
+struct alignas(16) PolicyWideLds {
+  float lp[4][64];                                         // [wave of the block][column]: the log-probabilities of a step
+};
+
+// The A actions and the joint log-probability of ONE replica, computed by its wave (lane = 0 .. 63): policy_wide_layer1,
+// policy_trunk's hidden layers, then the output rows -- each the row's tree sum of the lanes' two products, as in
+// policy_vec_act; row w of the wave works out columns 16 w .. 16 w + 15 and lane c keeps column c's.  w_out: where the
+// output layer starts in pv.w (policy_load_trunk's return value; each of its weights is used once per replica: read from
+// global memory, 64 consecutive bytes per row and half).  Lane c < A samples column c (Philox column 0x40000000 + c at
+// the replica's counter) and returns the action in `action` (other lanes: 0); lp_row: 64 floats of LDS of THIS wave.
+// Returns the joint log-probability: the columns' values added in ascending order, float32, the same in every lane.
+__device__ __forceinline__ float policy_wide_act(const PolicyView& pv, int A, const PolicyLds* L, const float* w_out,
+                                                 float* lp_row, uint32_t replica, uint32_t ctr, int lane, const float* o,
+                                                 float& action, NoiseBlock<float>* nzb = nullptr) {
+  const int j = lane & 15, row = lane >> 4;
+  // the output rows of this row's columns 16 row .. 16 row + 15 (a column >= A: row A - 1 again, its value is not kept):
+  // their loads are issued first and land while the first layer runs
+  const bool free_ls = pv.log_std != nullptr;
+  const float* b_out = w_out + size_t(pv.n_out) * 32;
+  const int cols = A < 16 ? A : 16;                         // (wave-uniform)
+  float wm_a[16], wm_b[16], wl_a[16], wl_b[16], bm[16], bl[16];
+#pragma unroll
+  for (int t = 0; t < 16; ++t) {
+    const int c = 16 * row + t, cc = c < A ? c : A - 1;
+    wm_a[t] = wm_b[t] = wl_a[t] = wl_b[t] = bm[t] = bl[t] = 0.0f;
+    if (t < cols) {                                        // (wave-uniform)
+      wm_a[t] = w_out[size_t(cc) * 32 + j];
+      wm_b[t] = w_out[size_t(cc) * 32 + j + 16];
+      bm[t] = b_out[cc];
+      if (!free_ls) {
+        wl_a[t] = w_out[size_t(A + cc) * 32 + j];
+        wl_b[t] = w_out[size_t(A + cc) * 32 + j + 16];
+        bl[t] = b_out[A + cc];
+      }
+    }
+  }
+  const f2 z = policy_wide_layer1(pv, L, lane, o);
+  float ha, hb;
+  policy_trunk<true, true>(pv, L, j, z.x, z.y, 0.0f, ha, hb);
+  float mu = 0.0f, ls = 0.0f;
+#pragma unroll
+  for (int t = 0; t < 16; ++t) {
+    if (t < cols) {                                        // (wave-uniform)
+      float p0 = wm_a[t] * ha;
+      p0 = __builtin_fmaf(wm_b[t], hb, p0);
+      const float m = seg_sum<16>(p0) + bm[t];
+      float l = 0.0f;
+      if (!free_ls) {                                      // (wave-uniform)
+        float p1 = wl_a[t] * ha;
+        p1 = __builtin_fmaf(wl_b[t], hb, p1);
+        l = seg_sum<16>(p1) + bl[t];
+      }
+      mu = j == t ? m : mu;
+      ls = j == t ? l : ls;
+    }
+  }
+  if (free_ls) ls = pv.log_std[lane < A ? lane : A - 1];
+  float a, lp;
+  policy_sample(pv, replica, ctr, mu, ls, a, lp, nzb, uint32_t(lane));
+  action = lane < A ? a : 0.0f;
+  lp_row[lane] = lane < A ? lp : 0.0f;
+  asm volatile("" ::: "memory");                           // (one wave: the hardware keeps its DS instructions in order)
+  float logp = lp_row[0];
+#pragma unroll 1
+  for (int c = 1; c < A; ++c) logp = logp + lp_row[c];
+  asm volatile("" ::: "memory");
+  return logp;
+}
+
+// eager form of the wide action-vector head: obs [R, in_dim] -> act [R, A], logp [R]; one wave per replica, four replicas
+// per workgroup (they share the LDS copy of the hidden layers); the replica's counter advances by ONE per call
+template <int ROW>     // (a template so that every object of the library may include this header)
+__global__ __launch_bounds__(256) void k_policy_act_wide(PolicyView pv, int R, int A, uint32_t rep0,
+                                                         const float* __restrict__ obs, float* __restrict__ act,
+                                                         float* __restrict__ logp) {
+  static_assert(ROW == 16, "k_policy_act_wide: a row of 16 lanes holds the 32 units of a layer");
+  __shared__ PolicyLds L;
+  __shared__ PolicyWideLds W;
+  const float* w_out = policy_load_trunk(pv, &L, threadIdx.x, blockDim.x);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = blockIdx.x * 4 + wave;                     // (grid = ceil(R / 4))
+  if (r >= R) return;                                      // (wave-uniform, after the only barrier)
+  const uint32_t c0 = pv.ctr[r];
+  float a;
+  const float lp = policy_wide_act(pv, A, &L, w_out, W.lp[wave], rep0 + uint32_t(r), c0, lane, obs + size_t(r) * pv.in_dim, a);
+  if (lane < A) act[size_t(r) * A + lane] = a;
   if (lane == 0) {
     logp[r] = lp;
     pv.ctr[r] = c0 + 1u;

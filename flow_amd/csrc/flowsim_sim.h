@@ -98,6 +98,7 @@ struct SimBase {
   bool no_loop_kernel = false;  // FLOWSIM_NO_LOOP_KERNEL=1: keep the generic k_steps for segment-table loops (tests)
   bool no_loop_full = false;    // FLOWSIM_NO_LOOP_FULL=1: keep the run-time-flag instantiation of k_rollout_loop (tests)
   bool no_ring_rl = false;      // FLOWSIM_NO_RING_RL=1: keep the generic k_steps for IDM + RL rings (tests)
+  bool no_mask_skip = false;    // FLOWSIM_NO_MASK_SKIP=1: a masked k_steps_open / k_steps_wide launch steps every wave (A/B, tests)
   bool no_queue = false;        // FLOWSIM_NO_QUEUE=1: keep k_steps_open / k_steps_wide for the open networks (tests)
   int* d_qflag = nullptr;       // k_drop_queue: bit 0 = a path held more than its 64 lanes (the launch's results are invalid)
   bool qflag_armed = false;     // a queue-order launch ran since the flag was last read
@@ -523,6 +524,7 @@ struct Sim : SimBase {
       ov.obs_span = ranges(ov.n_obs_groups, fs::CELL_OBS_START, 0);
       ov.act_span = ranges(ov.n_act_groups, fs::CELL_ACT_START, 16);
       ov.track_followers = cfg.track_followers;
+      ov.mask_skip = no_mask_skip ? 0 : 1;
       std::vector<int32_t> lca(N, 0);
       int any_lc = 0;
       for (int i = 0; i < N; ++i) {
@@ -786,6 +788,7 @@ struct Sim : SimBase {
   int launch_policy_queue(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act, float* logp,
                           float* rew, uint8_t* done);    // float32 (the queue part): the merge heads' fused policies
   int launch_policy_act_vec(const fs::PolicyView& pv, const float* obs_in, float* act, float* logp);   // (the queue part)
+  int launch_policy_act_wide(const fs::PolicyView& pv, const float* obs_in, float* act, float* logp);  // (the queue part)
   int launch_dropq(const StepArgs& a);       // float32 (the queue part)
   template <int W>
   int launch_wide(const StepArgs& a);        // one workgroup of W waves per replica
@@ -846,7 +849,8 @@ struct Sim : SimBase {
   // (rows of 16 lanes: 18..32 vehicles) and of segment-table loops (the figure eight: up to 16 vehicles); n_ag agents
   // share the policy on the multi-agent heads (MultiAgentWaveAttenuationPOEnv on rings, MultiAgentAccelPOEnv on loops,
   // MultiAgentMergePOEnv with its actions applied on the merge's queue kernel: k_merge_queue<POLICY>); MergePOEnv's ONE
-  // network with num_rl action columns: k_policy_act_vec (eager) and k_merge_policy (fused)
+  // network with num_rl action columns: k_policy_act_vec (eager) and k_merge_policy (fused); BottleneckDesiredVelocityEnv's
+  // (more than 32 inputs, up to 64 columns): k_policy_act_wide, eager only
   int launch_policy_act(const fs::PolicyView& pv, int n_ag, const float* obs_in, float* act, float* logp);
   int launch_policy_row16(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act, float* logp,
                           float* rew, uint8_t* done);
@@ -877,6 +881,19 @@ struct Sim : SimBase {
               "fail-safes, one vehicle length, Euler, scheduled inflows only, FLOWSIM_NO_QUEUE unset)";
       else if (obs != nullptr && reset_done && cfg.warmup_steps != 0)
         why = "configuration (FS_ENV_MERGE_PO: resets inside a fragment: warmup_steps = 0)";
+    }
+    else if (dv.env == FS_ENV_BOTTLENECK_DV) {           // ONE network: the whole observation (33 .. 513) -> num_rl columns
+      if (!std::is_same<T, float>::value || mixed)
+        why = "precision (FS_ENV_BOTTLENECK_DV is FS_F32 only: k_policy_act_wide is a float32 kernel)";
+      else if (obs != nullptr)
+        why = "fs_policy_rollout_dev (FS_ENV_BOTTLENECK_DV: the policy is not fused into k_drop_queue; the eager "
+              "fs_policy_act_dev is built (k_policy_act_wide) -- capture it around the step: VecFlowEnv.capture with a "
+              "DevicePolicy)";
+      else if (dv.num_rl < 1 || dv.num_rl > 64)
+        why = "num_rl (FS_ENV_BOTTLENECK_DV: 1..64 action cells, one column per lane of a wave)";
+      else if (pol->obs_dim != obs_dim)
+        why = "fs_policy.obs_dim (FS_ENV_BOTTLENECK_DV: the whole observation, fs_obs_dim = 4 cells + 1; the output "
+              "layer has num_rl rows next to num_rl free log stds, or 2 num_rl)";
     }
     else if (dv.env == FS_ENV_MERGE_MA) {                // agent c: the RL slot of column c, present while it holds a vehicle
       if (!ov.ma_apply_actions)
@@ -934,7 +951,12 @@ struct Sim : SimBase {
              (dv.flags & fs::FLAG_HAS_FAILSAFE) || dv.sims_per_step != 1 || dv.integrator != FS_EULER || dv.junction_mode ||
              dv.track_aux || dv.sort_vehicles || dv.obs_perm != nullptr || dv.evaluate || (dv.N % 2) != 0)
       why = "configuration (what k_ring_pair steps: single-lane ring of IDM / RL vehicles, Euler, track_aux = 0)";
-    if (why) return fail(FS_ERR_UNSUPPORTED, std::string("fs_policy: not built for this handle: ") + why);
+    if (why) {
+      std::string msg = std::string("fs_policy: not built for this handle: ") + why;
+      if (dv.env == FS_ENV_BOTTLENECK_DV && msg.find("FS_ENV_BOTTLENECK_DV") == std::string::npos)
+        msg += " (FS_ENV_BOTTLENECK_DV)";                // (the checks shared by every head: model class, weights)
+      return fail(FS_ERR_UNSUPPORTED, msg);
+    }
     if (!d_pol_ctr) {
       int rc = dev_alloc(&d_pol_ctr, size_t(dv.R));
       if (rc) return rc;
@@ -947,11 +969,12 @@ struct Sim : SimBase {
     pv.in_dim = pol->obs_dim;
     pv.num_hidden = pol->num_hidden;
     pv.n_out = pol->log_std_dev ? 1 : 2;
-    if (dv.env == FS_ENV_MERGE_PO) pv.n_out *= dv.num_rl;  // the action-vector head: num_rl means [and num_rl log stds]
+    if (dv.env == FS_ENV_MERGE_PO || dv.env == FS_ENV_BOTTLENECK_DV) pv.n_out *= dv.num_rl;  // the action-vector heads: num_rl means [and num_rl log stds]
     pv.seed_lo = uint32_t(pol->seed & 0xFFFFFFFFull);
     pv.seed_hi = uint32_t(pol->seed >> 32);
     if constexpr (std::is_same<T, float>::value) {
       if (dv.env == FS_ENV_MERGE_PO && obs == nullptr) return launch_policy_act_vec(pv, obs_in, act, logp);
+      if (dv.env == FS_ENV_BOTTLENECK_DV) return launch_policy_act_wide(pv, obs_in, act, logp);
       if (dv.env == FS_ENV_MERGE_MA || dv.env == FS_ENV_MERGE_PO) {
         if (obs != nullptr) return launch_policy_queue(pv, num_steps, reset_done, obs, act, logp, rew, done);
       }

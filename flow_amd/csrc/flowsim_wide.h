@@ -63,7 +63,7 @@ __device__ __forceinline__ int last_bit(unsigned long long m) { return 63 - __cl
 
 // P = entry lanes of the lane-drop network: 4 (4 -> 2 -> 1 lanes) or 8 (scaling 2: 8 -> 4 -> 2)
 template <typename T, int W, int CSET = 0, int P = 4>
-__global__ __launch_bounds__(64 * W) void k_steps_wide(DevView<T> s, OpenView<T> o, int num_steps,
+__global__ __launch_bounds__(64 * W) void k_steps_wide(DevView<T> s, OpenView<T> o, int num_steps_arg,
                                                        const uint8_t* __restrict__ mask,
                                                        const float* __restrict__ actions, size_t act_stride,
                                                        float* __restrict__ obs, float* __restrict__ rew,
@@ -130,6 +130,9 @@ __global__ __launch_bounds__(64 * W) void k_steps_wide(DevView<T> s, OpenView<T>
   if (tid < 20) L.hist[tid] = o.arr_hist[size_t(rr) * 20 + tid];
 
   const bool live_replica = mask == nullptr || mask[rr] != 0;
+  // a masked launch (the warm-up steps of a reset) that does not select this workgroup's replica: the zero-step form, the
+  // observation of the unchanged state (k_steps_open; o.mask_skip = 0, FLOWSIM_NO_MASK_SKIP=1: the full launch)
+  const int num_steps = (!live_replica && !obs_every_step && o.mask_skip != 0) ? 0 : num_steps_arg;
   const uint32_t episode = uint32_t(o.episode[rr]);
   int tcount = s.time[rr];
   uint32_t nctr = s.noise_ctr[rr];

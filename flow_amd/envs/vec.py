@@ -259,6 +259,13 @@ class VecFlowEnv(object):
         do with one Python call + socket round trips per step (examples/train.py:110-212) costs one graph launch per
         fragment here; observations and actions never leave HBM.
 
+        ``policy`` may be a ``flow_amd.utils.device_policy.DevicePolicy``: the graph then holds ONE policy kernel per
+        step (``fs_policy_act_dev``: k_policy_act, k_policy_act_vec or k_policy_act_wide, whichever the handle takes)
+        instead of a torch module's ten-odd, samples the actions from the policy's own Philox streams and keeps their
+        log-probabilities in ``graph.logp``.  The graph reads the weights at ``policy.buf``'s fixed address: call
+        ``policy.sync()`` between replays to hand it new ones.  A handle without an eager policy kernel raises
+        NotImplementedError here.
+
         ``done`` is the simulator's flag byte (bit 0: horizon reached, bit 1: collision), not a 0/1 value."""
         if reset_done and self._resample:
             import warnings
@@ -268,6 +275,30 @@ class VecFlowEnv(object):
                           "vec.reset_done() instead.  Call vec.redraw_ring_lengths() between replays to give every "
                           "replica a fresh pending length for its next in-graph reset.", stacklevel=2)
         return StepGraph(self, num_steps, policy, reset_done)
+
+    def policy_act(self, policy, obs=None, out=None):
+        """ONE evaluation of ``policy`` (a ``DevicePolicy``) for every replica in one kernel launch
+        (``fs_policy_act_dev``): actions sampled from the policy's Philox streams and their log-probabilities, for the
+        observations ``obs [R, obs_dim]`` (default: those of the last reset / step).  Returns ``(act [R, A], logp [R])``
+        on the action-vector heads (MergePOEnv, BottleneckDesiredVelocityEnv: ``A = sim.policy_action_dim`` columns,
+        one joint log-probability), ``(act [R, n], logp [R, n])`` for ``n = sim.policy_agents`` agents sharing the
+        policy.  Every call advances the replicas' draw counters by one."""
+        torch, R = self.torch, self.num_envs
+        self.use_current_stream()
+        A, n_ag = self.sim.policy_action_dim, self.sim.policy_agents
+        if policy.act_dim != A:
+            raise ValueError("VecFlowEnv.policy_act: the policy has act_dim = %d, this environment takes %d action "
+                             "column(s) per evaluation (sim.policy_action_dim)" % (policy.act_dim, A))
+        obs = self._obs if obs is None else self._check(obs, (R, self.obs_dim), torch.float32)
+        lp_shape = (R,) if n_ag == 1 else (R, n_ag)
+        if out is None:
+            out = (torch.empty((R, max(A, n_ag)), dtype=torch.float32, device=self.device),
+                   torch.empty(lp_shape, dtype=torch.float32, device=self.device))
+        else:
+            self._check(out[0], (R, max(A, n_ag)), torch.float32)
+            self._check(out[1], lp_shape, torch.float32)
+        self.sim.policy_act_dev(policy.struct, obs, out[0], out[1])
+        return out
 
     def policy_rollout(self, policy, num_steps, reset_done=False, out=None):
         """``num_steps`` x (policy -> action -> Env.step [-> Env.reset of finished episodes]) in ONE kernel launch
@@ -341,7 +372,12 @@ class StepGraph(object):
     ``done [K, R]`` uint8.  With ``reset_done`` every replica whose episode ended is reset inside the graph
     (masked fs_reset_dev) and ``obs[k+1]`` holds the first observation of its next episode, as a vectorised
     Gym / RLlib VectorEnv does.  The policy must be capturable (no host synchronisation, static shapes).
-    Building the graph runs up to two eager warm-up steps: call ``vec.reset()`` and ``begin(obs)`` afterwards."""
+    Building the graph runs up to two eager warm-up steps: call ``vec.reset()`` and ``begin(obs)`` afterwards.
+
+    ``policy`` a ``DevicePolicy``: per step ONE ``fs_policy_act_dev`` launch writes ``actions[k]`` and ``logp[k]``
+    (``logp [K, R]``; ``[K, R, num_rl]`` where ``num_rl`` agents share the policy).  The warm-up steps then advance the
+    policy's draw counters too (two draws per replica), as they advance the simulator; the weights are read at
+    ``policy.buf``'s address on every replay (``policy.sync()`` hands the graph new ones)."""
 
     def __init__(self, vec, num_steps, policy=None, reset_done=False):
         torch = vec.torch
@@ -353,6 +389,16 @@ class StepGraph(object):
         self.done = torch.zeros((K, R), dtype=torch.uint8, device=dev)
         self.actions = torch.zeros((K, R, max(vec.act_dim, 1)), dtype=torch.float32, device=dev)
         self._carry = torch.zeros((R, vec.obs_dim), dtype=torch.float32, device=dev)
+        from flow_amd.utils.device_policy import DevicePolicy
+        self._device_policy = isinstance(policy, DevicePolicy)
+        self.logp = None
+        if self._device_policy:
+            n_ag = vec.sim.policy_agents
+            if not vec.act_dim or policy.act_dim != vec.sim.policy_action_dim:
+                raise ValueError("VecFlowEnv.capture: the policy has act_dim = %d, this environment takes %d action "
+                                 "column(s) per evaluation (sim.policy_action_dim)"
+                                 % (policy.act_dim, vec.sim.policy_action_dim if vec.act_dim else 0))
+            self.logp = torch.zeros((K, R) if n_ag == 1 else (K, R, n_ag), dtype=torch.float32, device=dev)
         self.stream = torch.cuda.Stream(dev)
         with torch.cuda.stream(self.stream):
             vec.use_current_stream()                 # bind BEFORE the capture: fs_set_stream synchronises
@@ -373,7 +419,9 @@ class StepGraph(object):
         for k in range(steps):
             a = None
             if vec.act_dim:
-                if self.policy is not None:
+                if self._device_policy:
+                    sim.policy_act_dev(self.policy.struct, self.obs[k], self.actions[k], self.logp[k])
+                elif self.policy is not None:
                     self.actions[k].copy_(self.policy(self.obs[k]))
                 a = self.actions[k]
             sim.step_dev(self.obs[k + 1], self.rew[k], self.done[k], a)

@@ -270,12 +270,14 @@ class FlowSim:
     @property
     def policy_action_dim(self):
         """Action columns of ONE policy evaluation: num_rl on MergePOEnv (FS_ENV_MERGE_PO: one network maps the whole
-        observation to num_rl accelerations, with one joint log-probability), 1 otherwise."""
-        return max(self.num_rl, 1) if int(self.spec.get("env", L.FS_ENV_ACCEL)) == L.FS_ENV_MERGE_PO else 1
+        observation to num_rl accelerations, with one joint log-probability) and on BottleneckDesiredVelocityEnv
+        (FS_ENV_BOTTLENECK_DV: one column per action cell), 1 otherwise."""
+        vec_heads = (L.FS_ENV_MERGE_PO, L.FS_ENV_BOTTLENECK_DV)
+        return max(self.num_rl, 1) if int(self.spec.get("env", L.FS_ENV_ACCEL)) in vec_heads else 1
 
     def policy_act_dev(self, pol, obs, act, logp):
-        """act / logp [R] (one agent) or [R, policy_agents] for the observations obs [R, obs_dim]; MergePOEnv:
-        act [R, policy_action_dim], logp [R]."""
+        """act / logp [R] (one agent) or [R, policy_agents] for the observations obs [R, obs_dim]; MergePOEnv and
+        BottleneckDesiredVelocityEnv: act [R, policy_action_dim], logp [R]."""
         L.check(self.lib.fs_policy_act_dev(self._h, C.byref(pol), _ptr(obs), _ptr(act), _ptr(logp)), self.lib)
 
     def policy_rollout_dev(self, pol, num_steps, obs, act, logp, rew, done, reset_done=False):

@@ -422,7 +422,7 @@ int fs_add_vehicle(fs_handle h, int replica, int slot, int route, double x, doub
  * "+speed_mode" and / or "+noise", "k_rollout_idm", "k_ring_pair<Accel | PO | POMA | AccelMA>", "k_rollout_loop",
  * "k_rollout_loop<FULL>", "k_rollout_loop<AccelMA>", "k_rollout_loop<FULL,AccelMA>", "k_ring_policy", "k_loop_policy",
  * "k_ring_policy<POMA>", "k_loop_policy<AccelMA>", "k_merge_policy", "k_merge_policy<PO>" (fs_policy_act_dev:
- * "k_policy_act", "k_policy_act_vec"),
+ * "k_policy_act", "k_policy_act_vec", "k_policy_act_wide"),
  * "k_steps<FAST>", "k_steps<CSET>", "k_steps", "k_steps_ml", "k_steps_open" (also "<mixed>"), "k_steps_wide",
  * "k_merge_queue", "k_drop_queue", "k_obs_mixed"; "" before the first launch).  Diagnostics for tests and bench.py: which
  * configuration class a workload landed in (no reference counterpart).  The string is static.
@@ -487,20 +487,33 @@ const char* fs_last_kernel(fs_handle h);
  * rounded through halves between steps.  A fragment equals K x (fs_policy_act_dev, fs_step_dev, fs_reset_dev(done)) bit
  * for bit.  Refused by name (every message names FS_ENV_MERGE_PO): num_rl > 6 (EXP_NUM 1 and 2 of singleagent_merge.py:
  * capture K single steps around the policy instead, VecFlowEnv.capture), FS_MIXED / FS_F64, handles off the queue kernel,
- * warmup_steps != 0 together with reset_done, and obs_dim != fs_obs_dim. */
+ * warmup_steps != 0 together with reset_done, and obs_dim != fs_obs_dim.
+ * The lane drop (FS_ENV_BOTTLENECK_DV, singleagent_bottleneck.py: 141 observations, 20 speed offsets) takes the same
+ * action-vector head through fs_policy_act_dev ONLY ("k_policy_act_wide", FS_F32 handles): A = num_rl action cells
+ * (1..64), obs_dim = fs_obs_dim = 4 cells + 1 (up to 513), the last layer 2 A rows (means, then log stds) or A rows next
+ * to A free log stds; obs [R, obs_dim] -> act [R, A], logp [R].  Column c is sampled by lane c of the replica's wave from
+ * Philox column 0x40000000 + c at the replica's counter (keyed by the global replica id), which advances by one per call;
+ * logp is the float32 sum of the columns in ascending order.  The first layer's sum runs over chunks of 32 inputs in an
+ * order that depends on obs_dim alone (flowsim_policy.h policy_wide_layer1), never on R or the launch.
+ * fs_policy_rollout_dev is refused by name on these handles (no fused kernel yet): capture K x (fs_policy_act_dev,
+ * fs_step_dev, fs_reset_dev(done)) as one graph instead (VecFlowEnv.capture with a DevicePolicy).  Every refusal on
+ * this head -- another precision, obs_dim != fs_obs_dim, num_rl outside 1..64, the model class -- names
+ * FS_ENV_BOTTLENECK_DV. */
 typedef struct fs_policy {
   uint32_t struct_size;               /* sizeof(fs_policy) */
-  int32_t obs_dim;                    /* must equal fs_obs_dim (FS_ENV_MERGE_PO too); shared agents: fs_obs_dim / num_rl */
+  int32_t obs_dim;                    /* must equal fs_obs_dim (FS_ENV_MERGE_PO / BOTTLENECK_DV too); shared agents: fs_obs_dim / num_rl */
   int32_t num_hidden;                 /* 1..3 hidden layers ... */
   int32_t hidden_width;               /* ... of 32 units each */
   int32_t activation;                 /* 0 = tanh */
   const float* weights_dev;
-  const float* log_std_dev;           /* NULL: the network's second output is the log std (FS_ENV_MERGE_PO: [num_rl]) */
+  const float* log_std_dev;           /* NULL: the network's second output is the log std (action-vector heads: [num_rl]) */
   uint64_t seed;
 } fs_policy;
 
 /* actions [R] and log-probabilities [R] for the observations obs_dev [R, obs_dim] ([R, n_ag] for [R, n_ag * obs_dim] with
- * shared agents; FS_ENV_MERGE_PO: actions [R, num_rl], log-probabilities [R]); advances the sampling streams */
+ * shared agents; FS_ENV_MERGE_PO and FS_ENV_BOTTLENECK_DV: actions [R, num_rl], log-probabilities [R]); advances the
+ * sampling streams by one draw per replica.  One kernel launch on the handle's stream, no host synchronisation: it can be
+ * captured into a graph between fs_step_dev launches (after one eager call, which allocates the draw counters). */
 int fs_policy_act_dev(fs_handle h, const fs_policy* pol, const float* obs_dev, float* act_dev, float* logp_dev);
 /* K x (policy -> action -> Env.step), with reset_done != 0 followed by Env.reset of the replicas whose episode ended
  * (placement, FS_FIELD_INIT_RING_LENGTH, warm-up steps).  obs_dev [K+1, R, obs_dim]: obs[0] = observation of the state
