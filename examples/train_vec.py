@@ -144,7 +144,8 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     policy_mapping_fn): the observation row holds one block per agent, the action row one column per agent; every agent
     is a sample of the shared policy and receives the shared reward.
     ``fuse_action_vector``: an experiment whose ONE network emits several action columns (MergePOEnv:
-    singleagent_merge.py) rolls out through the fused policy + step kernel as well (k_merge_policy<PO>); where no fused
+    singleagent_merge.py) rolls out through the fused policy + step kernel as well (k_merge_policy<PO>; with more than six
+    places, EXP_NUM 1 and 2, k_merge_policy<PO,WIDE>); where no fused
     kernel exists but the eager policy kernel does (BottleneckDesiredVelocityEnv: singleagent_bottleneck.py,
     k_policy_act_wide), the captured graph holds that kernel instead of the torch module.  Off by default: the library's
     kernels draw their samples from its Philox streams, the torch policy from torch.randn, so the two are different

@@ -34,8 +34,10 @@ namespace fsim {
                                   float* logp, float* rew, uint8_t* done) {
     const bool noise = (dv.flags & fs::FLAG_HAS_NOISE) != 0;
     if (dv.env == FS_ENV_MERGE_PO) {
-      const auto kp = pick(noise, [&](auto NZ) { return &fs::k_merge_policy<NZ>; });
-      last_kernel = "k_merge_policy<PO>";
+      const bool wide = dv.num_rl > fs::FS_POLICY_VEC_MAX;       // more than 32 inputs: policy_wide_act in the loop
+      const auto kp = wide ? pick(noise, [&](auto NZ) { return &fs::k_merge_wide_policy<NZ>; })
+                           : pick(noise, [&](auto NZ) { return &fs::k_merge_policy<NZ>; });
+      last_kernel = wide ? "k_merge_policy<PO,WIDE>" : "k_merge_policy<PO>";
       hipLaunchKernelGGL(kp, dim3(dv.R), dim3(64), 0, stream, dv, ov, qc, num_steps, obs, rew, done, pv, act, logp,
                          reset_done);
       return launched();
@@ -54,8 +56,8 @@ namespace fsim {
                        act, logp);
     return launched();
   }
-  // the eager form of BottleneckDesiredVelocityEnv's action-vector policy (more than 32 inputs: one wave per replica, four
-  // replicas per workgroup)
+  // the eager form of an action-vector policy with more than 32 inputs (BottleneckDesiredVelocityEnv; MergePOEnv with 7 .. 32
+  // places): one wave per replica, four replicas per workgroup
   template <typename T>
   int Sim<T>::launch_policy_act_wide(const fs::PolicyView& pv, const float* obs_in, float* act, float* logp) {
     last_kernel = "k_policy_act_wide";

@@ -16,11 +16,12 @@
 // stopped).
 //
 // The network is written ONCE: policy_layer is the 32-input layer, policy_trunk the layer sequence (narrow or WIDE first
-// layer, then the hidden layers), policy_load_trunk its weights' way into LDS.  All seven kernels that evaluate a policy
+// layer, then the hidden layers), policy_load_trunk its weights' way into LDS.  All eight kernels that evaluate a policy
 // call that trunk -- the eager k_policy_act, k_policy_act_vec and k_policy_act_wide (fs_policy_act_dev; the last with a
 // first layer of more than 32 inputs, policy_wide_layer1, which is policy_layer over chunks), the fused k_ring_policy,
-// k_loop_policy, k_merge_queue<POLICY> and k_merge_policy (flowsim_queue.h) -- through policy_eval (the trunk and the
-// two-output Gaussian head) or policy_vec_act (the trunk and the action-vector head), so a fragment is bit-identical to
+// k_loop_policy, k_merge_queue<POLICY>, k_merge_policy and k_merge_wide_policy (flowsim_queue.h) -- through policy_eval
+// (the trunk and the two-output Gaussian head), policy_vec_act (the trunk and the action-vector head) or policy_wide_act
+// (the same head behind a first layer of more than 32 inputs), so a fragment is bit-identical to
 // eager stepping by construction (tests/test_policy_gpu.py and its siblings).  Every operation is an explicit fma /
 // hardware exp2 / rcp: the arithmetic is defined by this file (a torch module with the same weights agrees to ~1e-6, not
 // bit for bit) and its float32 bits are pinned by tests/test_policy_bits_gpu.py.
@@ -404,10 +405,12 @@ __global__ __launch_bounds__(64) void k_policy_act_vec(PolicyView pv, int R, int
   }
 }
 
-// ---- the WIDE action-vector head (FS_ENV_BOTTLENECK_DV: BottleneckDesiredVelocityEnv, 141 -> 20) ----------------------
+// ---- the WIDE action-vector head (FS_ENV_BOTTLENECK_DV: BottleneckDesiredVelocityEnv, 141 -> 20; FS_ENV_MERGE_PO with 7 ..
+// 32 places: 35 .. 160 -> num_rl, eagerly here and fused in k_merge_wide_policy, flowsim_queue.h) --------------------------
 // ONE network maps the whole observation (in_dim = 4 cells + 1 values, 33 .. 513) to A = num_rl <= 64 action columns.  A
 // WAVE is one replica, as in policy_vec_act; nothing below depends on R, the grid, or the place of the wave in its
-// workgroup, so a fused kernel that gives a replica's wave to policy_wide_act computes the same bits.
+// workgroup, so a fused kernel that gives a replica's wave to policy_wide_act computes the same bits (k_merge_wide_policy
+// does).
 //
 // THE FIRST LAYER (policy_wide_layer1), its summation order:
 //   * the observation is cut into CHUNKS of 32 inputs, chunk n = inputs 32 n .. 32 n + 31 (inputs from in_dim on: zero,
@@ -469,37 +472,48 @@ struct alignas(16) PolicyWideLds {
 // global memory, 64 consecutive bytes per row and half).  Lane c < A samples column c (Philox column 0x40000000 + c at
 // the replica's counter) and returns the action in `action` (other lanes: 0); lp_row: 64 floats of LDS of THIS wave.
 // Returns the joint log-probability: the columns' values added in ascending order, float32, the same in every lane.
+// AHEAD: WHEN the output rows are loaded, which changes no value.  true (the eager kernel): first, so that they land
+// while the first layer runs.  false (a fused kernel, whose wave holds a replica's simulator state in registers as well):
+// behind the trunk, FS_WIDE_OUT_GROUP columns at a time, each group in front of the columns that use it -- 96 more
+// registers live through the first layer, or 96 at once behind it, is what the fused kernel does not have (with all
+// sixteen columns loaded together k_merge_wide_policy spilled to scratch memory).
+constexpr int FS_WIDE_OUT_GROUP = 4;
+template <bool AHEAD = true>
 __device__ __forceinline__ float policy_wide_act(const PolicyView& pv, int A, const PolicyLds* L, const float* w_out,
                                                  float* lp_row, uint32_t replica, uint32_t ctr, int lane, const float* o,
                                                  float& action, NoiseBlock<float>* nzb = nullptr) {
   const int j = lane & 15, row = lane >> 4;
-  // the output rows of this row's columns 16 row .. 16 row + 15 (a column >= A: row A - 1 again, its value is not kept):
-  // their loads are issued first and land while the first layer runs
+  // the output rows of this row's columns 16 row .. 16 row + 15 (a column >= A: row A - 1 again, its value is not kept)
   const bool free_ls = pv.log_std != nullptr;
   const float* b_out = w_out + size_t(pv.n_out) * 32;
   const int cols = A < 16 ? A : 16;                         // (wave-uniform)
   float wm_a[16], wm_b[16], wl_a[16], wl_b[16], bm[16], bl[16];
+  auto load_out = [&](auto t0_c) {                          // columns t0 .. of this row: all sixteen, or one group
+    constexpr int t0 = decltype(t0_c)::value;
 #pragma unroll
-  for (int t = 0; t < 16; ++t) {
-    const int c = 16 * row + t, cc = c < A ? c : A - 1;
-    wm_a[t] = wm_b[t] = wl_a[t] = wl_b[t] = bm[t] = bl[t] = 0.0f;
-    if (t < cols) {                                        // (wave-uniform)
-      wm_a[t] = w_out[size_t(cc) * 32 + j];
-      wm_b[t] = w_out[size_t(cc) * 32 + j + 16];
-      bm[t] = b_out[cc];
-      if (!free_ls) {
-        wl_a[t] = w_out[size_t(A + cc) * 32 + j];
-        wl_b[t] = w_out[size_t(A + cc) * 32 + j + 16];
-        bl[t] = b_out[A + cc];
+    for (int t = t0; t < t0 + (AHEAD ? 16 : FS_WIDE_OUT_GROUP); ++t) {
+      const int c = 16 * row + t, cc = c < A ? c : A - 1;
+      wm_a[t] = wm_b[t] = wl_a[t] = wl_b[t] = bm[t] = bl[t] = 0.0f;
+      if (t < cols) {                                      // (wave-uniform)
+        wm_a[t] = w_out[size_t(cc) * 32 + j];
+        wm_b[t] = w_out[size_t(cc) * 32 + j + 16];
+        bm[t] = b_out[cc];
+        if (!free_ls) {
+          wl_a[t] = w_out[size_t(A + cc) * 32 + j];
+          wl_b[t] = w_out[size_t(A + cc) * 32 + j + 16];
+          bl[t] = b_out[A + cc];
+        }
       }
     }
-  }
+  };
+  if constexpr (AHEAD) load_out(std::integral_constant<int, 0>{});
   const f2 z = policy_wide_layer1(pv, L, lane, o);
   float ha, hb;
   policy_trunk<true, true>(pv, L, j, z.x, z.y, 0.0f, ha, hb);
   float mu = 0.0f, ls = 0.0f;
-#pragma unroll
-  for (int t = 0; t < 16; ++t) {
+  static_for<16>([&](auto t_c) {
+    constexpr int t = decltype(t_c)::value;
+    if constexpr (!AHEAD && t % FS_WIDE_OUT_GROUP == 0) load_out(t_c);
     if (t < cols) {                                        // (wave-uniform)
       float p0 = wm_a[t] * ha;
       p0 = __builtin_fmaf(wm_b[t], hb, p0);
@@ -513,7 +527,7 @@ __device__ __forceinline__ float policy_wide_act(const PolicyView& pv, int A, co
       mu = j == t ? m : mu;
       ls = j == t ? l : ls;
     }
-  }
+  });
   if (free_ls) ls = pv.log_std[lane < A ? lane : A - 1];
   float a, lp;
   policy_sample(pv, replica, ctr, mu, ls, a, lp, nzb, uint32_t(lane));

@@ -97,9 +97,12 @@ struct alignas(16) QueueRow {
 // reset_done: a collision ends the episode on this head, so a replica is reset in place when its `done` byte is not
 // zero -- the horizon or a collision.  The reset is fs_reset_dev's: the state goes to its slots first, because
 // reset_open_slot keeps the entries of rl_veh (ctl_seq, read with the slots' origins) and the join counter.
+// WIDE (k_merge_wide_policy, "k_merge_policy<PO,WIDE>"): the same head with 7 .. 32 places.  The observation row in LDS
+// is 5 * 32 floats, and the wave gives it to policy_wide_act (flowsim_policy.h: the first layer in chunks of 32 inputs,
+// lane c samples column c) instead of policy_vec_act; the samples go into the action row and po_action() runs as above.
 //
 // The body is merge_queue_body, a device function that the two __global__ wrappers at the end of the file inline.
-template <bool NOISE, bool ACT, bool POLICY, bool PO>
+template <bool NOISE, bool ACT, bool POLICY, bool PO, bool WIDE = false>
 __device__ __forceinline__ void merge_queue_body(const DevView<float>& s, const OpenView<float>& o, const QueueConsts& qc,
                                                  int num_steps, const float* __restrict__ actions, size_t act_stride,
                                                  float* __restrict__ obs, float* __restrict__ rew,
@@ -108,6 +111,7 @@ __device__ __forceinline__ void merge_queue_body(const DevView<float>& s, const 
                                                  int reset_done) {
   using T = float;
   static_assert(!POLICY || ACT, "k_merge_queue: the policy's actions take the ACT path");
+  static_assert(!WIDE || (POLICY && PO), "k_merge_queue: the wide first layer belongs to the action-vector head");
   constexpr bool VEC = POLICY && PO;                   // the action-vector head: one network, num_rl action columns
   const T BIGV = 3.0e38f;
   const int lane = threadIdx.x;
@@ -126,10 +130,12 @@ __device__ __forceinline__ void merge_queue_body(const DevView<float>& s, const 
   __shared__ int pcol[64];                        // (POLICY) the present columns, compacted
   __shared__ int place_row[64];                   // (PO) the place in rl_veh of every slot, -1: not listed
   __shared__ PolicyVecLds PV;                     // (VEC) the output layer of the action-vector head
-  __shared__ float obs_row[32];                   // (VEC) the observation of the current state: the network's input
+  __shared__ float obs_row[WIDE ? 5 * 32 : 32];   // (VEC) the observation of the current state: the network's input
   OpenTabs<T, true> tb;
   tb.load(o, lane, false, &tabs_mem);
-  if constexpr (VEC) policy_vec_load(pv, s.num_rl, &PL, &PV, lane, 64);
+  const float* w_out = nullptr;                   // (WIDE) where the output layer starts in pv.w: read from global memory
+  if constexpr (WIDE) w_out = policy_load_trunk(pv, &PL, lane, 64);     // (the barrier: the one behind the slot tables)
+  else if constexpr (VEC) policy_vec_load(pv, s.num_rl, &PL, &PV, lane, 64);
   else if constexpr (POLICY) policy_load(pv, &PL, lane, 64);
 
   // ---- the slot tables as LDS rows --------------------------------------------------------------------------
@@ -246,8 +252,11 @@ __device__ __forceinline__ void merge_queue_body(const DevView<float>& s, const 
   const T crash_gap = PO ? in_vgpr(float(s.crash_gap)) : 0.0f;
   const T clip_lo = in_vgpr(s.clip_actions ? float(s.act_lo) : -3.0e38f), clip_hi = in_vgpr(s.clip_actions ? float(s.act_hi) : 3.0e38f);
   const int jm = __builtin_amdgcn_readfirstlane(s.junction_mode), jct = __builtin_amdgcn_readfirstlane(s.junction_on);
-  const T c0 = in_vgpr(0.0f), c1000 = in_vgpr(1000.0f), cm1001 = in_vgpr(-1001.0f), cBIG = in_vgpr(3.0e38f);
-  const int im1 = __builtin_bit_cast(int, in_vgpr(__builtin_bit_cast(float, -1)));
+  // (WIDE: the five literals stay literals -- the policy's first layer needs the registers, and a literal can be made
+  // again where it is used, which a launch constant in a register cannot)
+  auto lit = [](float c) { return WIDE ? c : in_vgpr(c); };
+  const T c0 = lit(0.0f), c1000 = lit(1000.0f), cm1001 = lit(-1001.0f), cBIG = lit(3.0e38f);
+  const int im1 = __builtin_bit_cast(int, lit(__builtin_bit_cast(float, -1)));
 
   // ---- my vehicle's parameters (by label) and the facts of my lane: recomputed by the events only --------------
   T p_v0 = 1.0f, p_T = 0.0f, p_a = 0.0f, p_s0 = 0.0f, p_ts = 1.0f, p_sig = 0.0f;          // IDM
@@ -977,7 +986,18 @@ __device__ __forceinline__ void merge_queue_body(const DevView<float>& s, const 
   NoiseBlock<float> act_draws;                       // (VEC) my column's Philox block, kept over four steps
   act_draws.init();
   for (int step = 0; step < num_steps; ++step) {
-    if constexpr (VEC) {
+    if constexpr (WIDE) {
+      // ---- the policy, ONCE, with a first layer of 33 .. 160 inputs: policy_wide_act, what k_policy_act_wide runs ------
+      const int n_ag = s.num_rl;
+      float a;
+      const float lp = policy_wide_act<false>(pv, n_ag, &PL, w_out, lp_row, s.rep0 + uint32_t(r), pctr, lane, obs_row, a, &act_draws);
+      act_row[lane] = a;                               // (lanes from num_rl on: zero)
+      if (lane < n_ag) act_out[(size_t(step) * s.R + r) * n_ag + lane] = a;
+      if (lane == 0) logp_out[size_t(step) * s.R + r] = lp;
+      pctr += 1u;
+      q_fence();
+      po_action();
+    } else if constexpr (VEC) {
       // ---- the policy, ONCE: the observation in obs_row -> num_rl samples in the action row ----------------------
       const int n_ag = s.num_rl;
       const float lp = policy_vec_act(pv, n_ag, &PL, &PV, s.rep0 + uint32_t(r), pctr, lane, obs_row, act_row, &act_draws);
@@ -1227,6 +1247,19 @@ __global__ __launch_bounds__(64) void k_merge_policy(DevView<float> s, OpenView<
                                                      int reset_done) {
   merge_queue_body<NOISE, true, true, true>(s, o, qc, num_steps, nullptr, 0, obs, rew, done, 1, pv, act_out, logp_out,
                                             reset_done);
+}
+
+// the same with num_rl = 7 .. 32 places (fs_last_kernel "k_merge_policy<PO,WIDE>"; EXP_NUM 1 and 2 of singleagent_merge.py:
+// 13 and 17): the first layer takes 35 .. 160 inputs, so the wave runs policy_wide_act on the observation row -- what
+// k_policy_act_wide runs --, W1 and the output rows read from global memory every step
+template <bool NOISE>
+__global__ __launch_bounds__(64) void k_merge_wide_policy(DevView<float> s, OpenView<float> o, QueueConsts qc, int num_steps,
+                                                          float* __restrict__ obs, float* __restrict__ rew,
+                                                          uint8_t* __restrict__ done, PolicyView pv,
+                                                          float* __restrict__ act_out, float* __restrict__ logp_out,
+                                                          int reset_done) {
+  merge_queue_body<NOISE, true, true, true, true>(s, o, qc, num_steps, nullptr, 0, obs, rew, done, 1, pv, act_out,
+                                                  logp_out, reset_done);
 }
 
 }  // namespace fs

@@ -849,8 +849,9 @@ struct Sim : SimBase {
   // (rows of 16 lanes: 18..32 vehicles) and of segment-table loops (the figure eight: up to 16 vehicles); n_ag agents
   // share the policy on the multi-agent heads (MultiAgentWaveAttenuationPOEnv on rings, MultiAgentAccelPOEnv on loops,
   // MultiAgentMergePOEnv with its actions applied on the merge's queue kernel: k_merge_queue<POLICY>); MergePOEnv's ONE
-  // network with num_rl action columns: k_policy_act_vec (eager) and k_merge_policy (fused); BottleneckDesiredVelocityEnv's
-  // (more than 32 inputs, up to 64 columns): k_policy_act_wide, eager only
+  // network with num_rl action columns: k_policy_act_vec (eager) and k_merge_policy (fused) up to 6 places, k_policy_act_wide
+  // and k_merge_wide_policy with 7 .. 32; BottleneckDesiredVelocityEnv's (more than 32 inputs, up to 64 columns):
+  // k_policy_act_wide, eager only
   int launch_policy_act(const fs::PolicyView& pv, int n_ag, const float* obs_in, float* act, float* logp);
   int launch_policy_row16(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act, float* logp,
                           float* rew, uint8_t* done);
@@ -869,10 +870,14 @@ struct Sim : SimBase {
     else if (dv.env == FS_ENV_MERGE_PO) {                // ONE network: the whole observation -> num_rl action columns
       if (!std::is_same<T, float>::value || mixed)
         why = "precision (FS_ENV_MERGE_PO is FS_F32 / FS_F16S only: FS_MIXED / FS_F64 handles are not built)";
-      else if (dv.num_rl < 1 || 5 * dv.num_rl > 32)
-        why = "num_rl (FS_ENV_MERGE_PO: the network's first layer takes 5 num_rl <= 32 inputs, num_rl <= 6 -- EXP_NUM 1 "
-              "and 2 of singleagent_merge.py have 13 and 17; run the policy in torch around the step, e.g. "
-              "VecFlowEnv.capture)";
+      else if (dv.num_rl < 1 || dv.num_rl > 32)
+        why = "num_rl (FS_ENV_MERGE_PO: 1..32 places; num_rl <= 6 runs k_policy_act_vec / k_merge_policy<PO>, 7..32 "
+              "k_policy_act_wide / k_merge_policy<PO,WIDE>)";
+      else if (pol->obs_dim != obs_dim && dv.num_rl > fs::FS_POLICY_VEC_MAX)
+        why = "fs_policy.obs_dim (FS_ENV_MERGE_PO: a first layer of at most 32 inputs is the num_rl <= 6 head's; this "
+              "handle has more places and needs the whole observation, obs_dim = fs_obs_dim = 5 num_rl, with num_rl "
+              "output rows next to num_rl free log stds, or 2 num_rl; any other policy can run in torch around the "
+              "step, e.g. VecFlowEnv.capture)";
       else if (pol->obs_dim != obs_dim)
         why = "fs_policy.obs_dim (FS_ENV_MERGE_PO: the whole observation, fs_obs_dim = 5 num_rl; the output layer has "
               "num_rl rows next to num_rl free log stds, or 2 num_rl)";
@@ -973,8 +978,9 @@ struct Sim : SimBase {
     pv.seed_lo = uint32_t(pol->seed & 0xFFFFFFFFull);
     pv.seed_hi = uint32_t(pol->seed >> 32);
     if constexpr (std::is_same<T, float>::value) {
-      if (dv.env == FS_ENV_MERGE_PO && obs == nullptr) return launch_policy_act_vec(pv, obs_in, act, logp);
-      if (dv.env == FS_ENV_BOTTLENECK_DV) return launch_policy_act_wide(pv, obs_in, act, logp);
+      const bool po_wide = dv.env == FS_ENV_MERGE_PO && dv.num_rl > fs::FS_POLICY_VEC_MAX;   // 35 .. 160 inputs
+      if (dv.env == FS_ENV_MERGE_PO && obs == nullptr && !po_wide) return launch_policy_act_vec(pv, obs_in, act, logp);
+      if (dv.env == FS_ENV_BOTTLENECK_DV || (po_wide && obs == nullptr)) return launch_policy_act_wide(pv, obs_in, act, logp);
       if (dv.env == FS_ENV_MERGE_MA || dv.env == FS_ENV_MERGE_PO) {
         if (obs != nullptr) return launch_policy_queue(pv, num_steps, reset_done, obs, act, logp, rew, done);
       }

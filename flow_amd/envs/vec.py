@@ -313,7 +313,8 @@ class VecFlowEnv(object):
         ``APPLY_ENUMERATE_QUIRK = False``) has the same layout with five values per agent; agent c is the RL slot of
         column c, and while that slot holds no vehicle the agent is absent: its action is NaN (no command), its
         log-probability 0.  The shipped merge environment never applies an action and is refused (roll it out open
-        loop).  The single-agent merge (MergePOEnv, ``num_rl`` <= 6) takes ONE network with an action vector
+        loop).  The single-agent merge (MergePOEnv, ``num_rl`` 1 to 32: k_merge_policy<PO> up to six places,
+        k_merge_policy<PO,WIDE> beyond) takes ONE network with an action vector
         (``DevicePolicy(..., act_dim=num_rl)``: the whole observation in, ``num_rl`` accelerations out): ``actions`` is
         ``[K, R, num_rl]`` -- every column sampled every step, the environment ignores those beyond its list of controlled
         vehicles -- and ``logp [K, R]`` the joint log-probability; with ``reset_done`` a replica is reset when its

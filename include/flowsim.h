@@ -421,8 +421,8 @@ int fs_add_vehicle(fs_handle h, int replica, int slot, int route, double x, doub
 /* Family of the step kernel the handle's last fs_step / fs_rollout / fs_policy_rollout launch chose ("k_rollout_pair" with
  * "+speed_mode" and / or "+noise", "k_rollout_idm", "k_ring_pair<Accel | PO | POMA | AccelMA>", "k_rollout_loop",
  * "k_rollout_loop<FULL>", "k_rollout_loop<AccelMA>", "k_rollout_loop<FULL,AccelMA>", "k_ring_policy", "k_loop_policy",
- * "k_ring_policy<POMA>", "k_loop_policy<AccelMA>", "k_merge_policy", "k_merge_policy<PO>" (fs_policy_act_dev:
- * "k_policy_act", "k_policy_act_vec", "k_policy_act_wide"),
+ * "k_ring_policy<POMA>", "k_loop_policy<AccelMA>", "k_merge_policy", "k_merge_policy<PO>", "k_merge_policy<PO,WIDE>"
+ * (fs_policy_act_dev: "k_policy_act", "k_policy_act_vec", "k_policy_act_wide"),
  * "k_steps<FAST>", "k_steps<CSET>", "k_steps", "k_steps_ml", "k_steps_open" (also "<mixed>"), "k_steps_wide",
  * "k_merge_queue", "k_drop_queue", "k_obs_mixed"; "" before the first launch).  Diagnostics for tests and bench.py: which
  * configuration class a workload landed in (no reference counterpart).  The string is static.
@@ -471,9 +471,13 @@ const char* fs_last_kernel(fs_handle h);
  * present (the reference lists only the RL vehicles present, flow/envs/multiagent/merge.py:98-143).  Resets inside a
  * fragment: warmup_steps = 0.  ma_apply_actions = 0 (the shipped environment: actions never reach the simulator, roll it
  * out open loop), FS_MIXED / FS_F64 and handles off the queue kernel are refused by name.
- * The single-agent merge (FS_ENV_MERGE_PO, singleagent_merge.py; "k_merge_policy<PO>") takes an ACTION-VECTOR head: ONE
- * network maps the whole observation to A = num_rl (fs_action_dim) accelerations, evaluated once per replica and step.
- *   obs_dim      fs_obs_dim = 5 A: the whole observation (the first layer takes at most 32 inputs: A <= 6)
+ * The single-agent merge (FS_ENV_MERGE_PO, singleagent_merge.py; "k_merge_policy<PO>", with more than six places
+ * "k_merge_policy<PO,WIDE>") takes an ACTION-VECTOR head: ONE network maps the whole observation to A = num_rl
+ * (fs_action_dim, 1..32) accelerations, evaluated once per replica and step.
+ *   obs_dim      fs_obs_dim = 5 A: the whole observation.  A <= 6 (at most 32 inputs): "k_policy_act_vec" /
+ *                "k_merge_policy<PO>".  A = 7..32 (35..160 inputs; EXP_NUM 1 and 2 of singleagent_merge.py: 13 and 17): the
+ *                wide head's first layer, "k_policy_act_wide" / "k_merge_policy<PO,WIDE>" -- its sum runs over chunks of
+ *                32 inputs in an order that depends on obs_dim alone, and lane c of the replica's wave samples column c
  *   weights_dev  the same trunk; the last layer has 2 A outputs -- rows 0 .. A-1 the means, rows A .. 2A-1 the log stds:
  *                RLlib's DiagGaussian order -- or, with log_std_dev != NULL, A outputs and log_std_dev points at A floats
  * Column c draws from Philox column 0x40000000 + c at the replica's counter (the stream agent c of the shared-policy heads
@@ -485,9 +489,9 @@ const char* fs_last_kernel(fs_handle h);
  * this head (bit 1 of done), so a replica is reset in place when done != 0 -- the horizon or a collision -- exactly as
  * fs_reset_dev(done != 0) resets it: the list of controlled vehicles and its join counter survive, FS_F16S states are
  * rounded through halves between steps.  A fragment equals K x (fs_policy_act_dev, fs_step_dev, fs_reset_dev(done)) bit
- * for bit.  Refused by name (every message names FS_ENV_MERGE_PO): num_rl > 6 (EXP_NUM 1 and 2 of singleagent_merge.py:
- * capture K single steps around the policy instead, VecFlowEnv.capture), FS_MIXED / FS_F64, handles off the queue kernel,
- * warmup_steps != 0 together with reset_done, and obs_dim != fs_obs_dim.
+ * for bit, on either kernel.  Refused by name (every message names FS_ENV_MERGE_PO): num_rl outside 1..32 (fs_create
+ * refuses more than 32 itself), FS_MIXED / FS_F64, handles off the queue kernel, warmup_steps != 0 together with
+ * reset_done, and obs_dim != fs_obs_dim (any other policy can run around the step: VecFlowEnv.capture).
  * The lane drop (FS_ENV_BOTTLENECK_DV, singleagent_bottleneck.py: 141 observations, 20 speed offsets) takes the same
  * action-vector head through fs_policy_act_dev ONLY ("k_policy_act_wide", FS_F32 handles): A = num_rl action cells
  * (1..64), obs_dim = fs_obs_dim = 4 cells + 1 (up to 513), the last layer 2 A rows (means, then log stds) or A rows next
