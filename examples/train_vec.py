@@ -212,6 +212,7 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     history = []
     for it in range(iterations):
         vec.redraw_ring_lengths()                              # pending ring length per replica for its next in-graph reset
+        vec.redraw_inflow_rates()                              # ... pending total inflow (reset_inflow; a no-op without it)
         t0 = time.perf_counter()
         if fused is not None:
             fused.sync()                                       # the optimiser moved the weights: repack them for the kernel

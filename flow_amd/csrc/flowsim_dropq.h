@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void k_drop_queue(DevView<float> s, OpenView<f
   int hist_l = (l < 20) ? o.arr_hist[size_t(rr) * 20 + l] : 0;           // arrivals of sub-step % 20 == lane
   const bool my_flow = l < o.n_inflows;                                    // lane f of every wave keeps inflow f (M2)
   const int fl = my_flow ? l : 0;
-  const double my_per = o.flow_tab_d[fl], my_begin = o.flow_tab_d[64 + fl], my_end = o.flow_tab_d[128 + fl];
+  const double my_per = o.flow_per(s.R)[size_t(rr) * FS_MAX_INFLOWS + fl], my_begin = o.flow_tab_d[64 + fl], my_end = o.flow_tab_d[128 + fl];
   const int my_number = o.flow_tab_i[128 + fl];
   const float f_xdep = o.lane_tab[TAB_FL_XDEP * 64 + fl], f_vdep = o.lane_tab[TAB_FL_VDEP * 64 + fl];
   const float f_ts = o.lane_tab[TAB_FL_TWOSQRT * 64 + fl], f_gap = o.lane_tab[TAB_FL_MINGAP * 64 + fl],

@@ -34,13 +34,24 @@ struct OpenView {
   int32_t* counters;     // [R,8]
   int32_t* emitted;      // [R,FS_MAX_INFLOWS]
   int32_t* generated;    // [R,FS_MAX_INFLOWS] vehicles a probabilistic inflow has generated so far (M2b)
+  // The inflow periods of every replica follow `generated` in the same allocation (Sim::init_open) and are reached from it:
+  // k_merge_wide_policy keeps its kernel arguments in SGPRs it spills by the hundred, and two more pointers in this struct
+  // pushed its VGPR spills into scratch memory (tests/test_merge_wide_policy_codegen.py).
+  //   flow_per      [R,FS_MAX_INFLOWS] period of inflow f in this replica (FS_FIELD_INFLOW_PERIOD): fs_create fills it from
+  //                 the handle's schedule, -(threshold + 1) of a probabilistic inflow included
+  //   init_flow_per [R,FS_MAX_INFLOWS] the period the replica takes at its next reset (FS_FIELD_INIT_INFLOW_PERIOD)
+  __host__ __device__ __forceinline__ double* flow_per(int R) const {
+    return reinterpret_cast<double*>(generated + size_t(R) * FS_MAX_INFLOWS);
+  }
+  __host__ __device__ __forceinline__ double* init_flow_per(int R) const { return flow_per(R) + size_t(R) * FS_MAX_INFLOWS; }
   int32_t* episode;      // [R] resets of the replica since fs_create (-1 before the first): keys the entry-lane draws (M9)
   const uint8_t* init_alive;   // [R,N]
   const int32_t* slot_type;    // [N]
   // Launch constants the step loop reads are kept one-per-lane in a few VGPRs and fetched with v_readlane, so the
   // loop body makes no memory access for them: lane_tab[row][lane], rows = enum below (host: Sim::init_open)
   const T* lane_tab;
-  const double* flow_tab_d;    // [3][64] lane f: period, begin, end of inflow f (the schedule is evaluated in double)
+  const double* flow_tab_d;    // [3][64] lane f: period, begin, end of inflow f (the schedule is evaluated in double);
+                               // the period the kernels step with is the replica's own (flow_per), row 0 its value at fs_create
   const int32_t* flow_tab_i;   // [3][64] lane f: vehicle type, route, number (-1 = unlimited)
   int n_inflows, ma_apply_actions, n_rl_slots;
   int n_prob;                  // inflows with a probability instead of a period (flow_tab_d row 0 holds -(threshold + 1))
@@ -149,12 +160,17 @@ struct OpenTabs<T, false> {
 template <typename T>
 struct OpenTabs<T, true> {
   const OpenTabsLds<T>* L;
-  __device__ __forceinline__ void load(const OpenView<T>& o, int lane, bool cells, OpenTabsLds<T>* lds) {
+  // `per`: the periods of the ONE replica the tables serve (its row of OpenView::flow_per), for the kernels that read the
+  // period through fd<0> (k_steps_wide, the WIDE policy form of k_merge_queue); nullptr everywhere else -- those kernels
+  // keep the replica's period in a register and row 0 holds the handle's value at fs_create, which nobody may read
+  __device__ __forceinline__ void load(const OpenView<T>& o, int lane, bool cells, OpenTabsLds<T>* lds,
+                                       const double* per = nullptr) {
 #pragma unroll
     for (int r = 0; r < TAB_ROWS; ++r) lds->tab[r][lane] = o.lane_tab[r * 64 + lane];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-      lds->ftd[r][lane] = o.flow_tab_d[r * 64 + lane];
+      const bool mine = r == 0 && per != nullptr && lane < FS_MAX_INFLOWS;
+      lds->ftd[r][lane] = mine ? per[lane] : o.flow_tab_d[r * 64 + lane];
       lds->fti[r][lane] = o.flow_tab_i[r * 64 + lane];
     }
 #pragma unroll
@@ -400,7 +416,7 @@ __global__ __launch_bounds__(64) void k_steps_open(DevView<T> s, OpenView<T> o, 
   // vehicles generated; vehicle k of the flow is due once k < generated
   constexpr bool prob_any = PROB;
   const bool my_flow = i < o.n_inflows;            // lane f of a segment keeps inflow f's schedule (and evaluates it, M2)
-  const double my_per = my_flow ? o.flow_tab_d[i] : 0.0;
+  const double my_per = my_flow ? o.flow_per(s.R)[size_t(rr) * FS_MAX_INFLOWS + i] : 0.0;
   const bool my_prob = prob_any && my_per < 0.0;
   const uint32_t my_thr = my_prob ? uint32_t(-my_per - 1.0) : 0u;
   const double my_begin = my_flow ? o.flow_tab_d[64 + i] : 0.0, my_end = my_flow ? o.flow_tab_d[128 + i] : 0.0;
@@ -1293,6 +1309,16 @@ __global__ __launch_bounds__(64) void k_steps_open(DevView<T> s, OpenView<T> o, 
   if (bn_env && rvalid && live_replica && i < 20) o.arr_hist[size_t(rr) * 20 + i] = hist_l;
 }
 
+// Env.reset for inflow f of replica r: no vehicle emitted or generated yet, and the schedule the replica was given for its
+// next episode (FS_FIELD_INIT_INFLOW_PERIOD)
+template <typename T>
+__device__ __forceinline__ void reset_inflow(const OpenView<T>& o, int R, int r, int f) {
+  const size_t e = size_t(r) * FS_MAX_INFLOWS + f;
+  o.emitted[e] = 0;
+  o.generated[e] = 0;
+  o.flow_per(R)[e] = o.init_flow_per(R)[e];
+}
+
 // Env.reset of an open network for slot i of replica r: the initial vehicle back in its slot or the slot free, and (slot
 // 0) the replica's clocks and id counters restarted (restart_instance: SUMO starts again at time 0, envs/base.py:430-470);
 // S13: one step has run when reset returns.  Shared by k_reset_open and the in-fragment resets of k_merge_queue<POLICY> and k_merge_policy.
@@ -1330,10 +1356,7 @@ __device__ __forceinline__ void reset_open_slot(const DevView<T>& s, const OpenV
   s.last_lc[e] = -(1 << 30);
   o.lead[e] = -1;
   o.headway[e] = T(1000);
-  if (i < FS_MAX_INFLOWS) {
-    o.emitted[size_t(r) * FS_MAX_INFLOWS + i] = 0;
-    o.generated[size_t(r) * FS_MAX_INFLOWS + i] = 0;
-  }
+  if (i < FS_MAX_INFLOWS) reset_inflow(o, s.R, r, i);
   if (i == 0) {
     int total = 0;
     for (int j = 0; j < N; ++j) total += al[j] ? 1 : 0;
@@ -1363,10 +1386,7 @@ __global__ void k_reset_open(DevView<T> s, OpenView<T> o, const uint8_t* __restr
     for (size_t e = size_t(blockIdx.x) * blockDim.x + threadIdx.x; e < size_t(s.R) * FS_MAX_INFLOWS;
          e += size_t(gridDim.x) * blockDim.x) {
       const int r = int(e / FS_MAX_INFLOWS);
-      if (mask == nullptr || mask[r] != 0) {
-        o.emitted[e] = 0;
-        o.generated[e] = 0;
-      }
+      if (mask == nullptr || mask[r] != 0) reset_inflow(o, s.R, r, int(e % FS_MAX_INFLOWS));
     }
 }
 

@@ -132,7 +132,8 @@ __device__ __forceinline__ void merge_queue_body(const DevView<float>& s, const 
   __shared__ PolicyVecLds PV;                     // (VEC) the output layer of the action-vector head
   __shared__ float obs_row[WIDE ? 5 * 32 : 32];   // (VEC) the observation of the current state: the network's input
   OpenTabs<T, true> tb;
-  tb.load(o, lane, false, &tabs_mem);
+  // (the WIDE policy form reads the replica's periods from the table: SCHED_IN_LDS below)
+  tb.load(o, lane, false, &tabs_mem, WIDE ? o.flow_per(s.R) + size_t(r) * FS_MAX_INFLOWS : nullptr);
   const float* w_out = nullptr;                   // (WIDE) where the output layer starts in pv.w: read from global memory
   if constexpr (WIDE) w_out = policy_load_trunk(pv, &PL, lane, 64);     // (the barrier: the one behind the slot tables)
   else if constexpr (VEC) policy_vec_load(pv, s.num_rl, &PL, &PV, lane, 64);
@@ -164,9 +165,14 @@ __device__ __forceinline__ void merge_queue_body(const DevView<float>& s, const 
   uint32_t nctr;
   int32_t* cnt = o.counters + size_t(r) * 8;
   const bool my_flow = lane < o.n_inflows;             // lane f keeps inflow f's schedule (M2)
-  const double my_per = my_flow ? o.flow_tab_d[lane] : 0.0;
-  const double my_begin = my_flow ? o.flow_tab_d[64 + lane] : 0.0, my_end = my_flow ? o.flow_tab_d[128 + lane] : 0.0;
-  const int my_number = my_flow ? o.flow_tab_i[128 + lane] : 0;
+  // ... in registers; the period is the replica's own, and a reset inside the launch hands the replica another
+  // (restart()).  The WIDE policy form has no registers left for them -- with them its NOISE form spills into scratch
+  // memory (tests/test_merge_wide_policy_codegen.py) -- and reads the lane's entries of the LDS table where it needs them
+  constexpr bool SCHED_IN_LDS = WIDE;
+  double my_per = (!SCHED_IN_LDS && my_flow) ? o.flow_per(s.R)[size_t(r) * FS_MAX_INFLOWS + lane] : 0.0;
+  const double my_begin = (!SCHED_IN_LDS && my_flow) ? o.flow_tab_d[64 + lane] : 0.0;
+  const double my_end = (!SCHED_IN_LDS && my_flow) ? o.flow_tab_d[128 + lane] : 0.0;
+  const int my_number = (!SCHED_IN_LDS && my_flow) ? o.flow_tab_i[128 + lane] : 0;
   // ... and its insertion constants (M3): coordinate, speed, and minGap / tau / 2 sqrt(accel decel) of its vehicle type
   const int fl = my_flow ? lane : 0;
   const float f_xdep = o.lane_tab[TAB_FL_XDEP * 64 + fl], f_vdep = o.lane_tab[TAB_FL_VDEP * 64 + fl];
@@ -192,8 +198,14 @@ __device__ __forceinline__ void merge_queue_body(const DevView<float>& s, const 
   };
 
   auto my_due_of = [&](int k_me) -> int {
-    const double due_t = my_begin + double(k_me) * my_per;
-    const bool open_me = my_flow && (due_t <= my_end) && (my_number < 0 || k_me < my_number);
+    double per = my_per, begin = my_begin, end = my_end;
+    int number = my_number;
+    if constexpr (SCHED_IN_LDS) {
+      per = tabs_mem.ftd[0][lane]; begin = tabs_mem.ftd[1][lane]; end = tabs_mem.ftd[2][lane];
+      number = tabs_mem.fti[2][lane];
+    }
+    const double due_t = begin + double(k_me) * per;
+    const bool open_me = my_flow && (due_t <= end) && (number < 0 || k_me < number);
     return open_me ? due_index(due_t) : 0x7fffffff;
   };
   int my_due;
@@ -939,8 +951,13 @@ __device__ __forceinline__ void merge_queue_body(const DevView<float>& s, const 
         reset_open_slot(s, o, r, lane);
         if (s.st16 != nullptr) state16_store(s, base + lane, s.pos[base + lane], s.vel[base + lane]);
       } else if (lane < FS_MAX_INFLOWS) {
-        o.emitted[size_t(r) * FS_MAX_INFLOWS + lane] = 0;
-        o.generated[size_t(r) * FS_MAX_INFLOWS + lane] = 0;
+        reset_inflow(o, s.R, r, lane);
+      }
+      // the reset handed the replica its pending periods (lane f wrote inflow f's above and reads it back here)
+      if (my_flow) {
+        const double per = o.flow_per(s.R)[size_t(r) * FS_MAX_INFLOWS + lane];
+        if constexpr (SCHED_IN_LDS) tabs_mem.ftd[0][lane] = per;      // (one replica per workgroup: my entry is mine alone)
+        else my_per = per;
       }
       if (lane == 0) s.noise_ctr[r] = nctr;          // (the reset keeps the noise stream going)
     } else {

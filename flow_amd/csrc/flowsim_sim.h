@@ -397,8 +397,10 @@ struct Sim : SimBase {
     if ((rc = dev_alloc(&ov.vmax, RN))) return rc;
     if ((rc = dev_alloc(&ov.arr_hist, size_t(R) * 20))) return rc;
     if ((rc = dev_alloc(&ov.counters, size_t(R) * 8))) return rc;
-    if ((rc = dev_alloc(&ov.emitted, size_t(R) * FS_MAX_INFLOWS))) return rc;
-    if ((rc = dev_alloc(&ov.generated, size_t(R) * FS_MAX_INFLOWS))) return rc;
+    // one allocation: emitted, generated (int32 each), then the current and the pending periods (float64 each; 8-byte
+    // aligned behind 64 R bytes of counters) -- OpenView::flow_per() says why the periods have no pointers of their own
+    if ((rc = dev_alloc(&ov.emitted, size_t(R) * FS_MAX_INFLOWS * 6))) return rc;
+    ov.generated = ov.emitted + size_t(R) * FS_MAX_INFLOWS;
     if ((rc = dev_alloc(&ov.episode, size_t(R)))) return rc;
     if ((rc = dev_alloc(&d_qflag, size_t(1)))) return rc;
     HIP_TRY(hipMemset(d_qflag, 0, sizeof(int)));
@@ -468,6 +470,13 @@ struct Sim : SimBase {
     }
     if ((rc = upload(&ov.lane_tab, tab))) return rc;
     if ((rc = upload(&ov.flow_tab_d, ftd))) return rc;
+    {   // every replica starts on the handle's schedule, and returns to it at a reset until told otherwise
+      std::vector<double> per(size_t(R) * FS_MAX_INFLOWS, 0.0);
+      for (int r = 0; r < R; ++r)
+        for (int f = 0; f < cfg.num_inflows; ++f) per[size_t(r) * FS_MAX_INFLOWS + f] = ftd[f];
+      HIP_TRY(hipMemcpy(ov.flow_per(R), per.data(), per.size() * sizeof(double), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(ov.init_flow_per(R), per.data(), per.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
     if ((rc = upload(&ov.flow_tab_i, fti))) return rc;
     {   // lane drops + bottleneck heads
       const bool bn = cfg.network == FS_NET_BOTTLENECK;
@@ -1028,7 +1037,29 @@ struct Sim : SimBase {
     }
   }
 
+  // FS_FIELD_INFLOW_PERIOD / FS_FIELD_INIT_INFLOW_PERIOD: float64 [R, FS_MAX_INFLOWS] whatever the handle's precision
+  int inflow_period_check(int field, size_t bytes, const char** name) {
+    *name = field == FS_FIELD_INFLOW_PERIOD ? "FS_FIELD_INFLOW_PERIOD" : "FS_FIELD_INIT_INFLOW_PERIOD";
+    const std::string n(*name);
+    if (!open_net || cfg.num_inflows == 0)
+      return fail(FS_ERR_INVALID, (n + ": exists for open networks with inflows only").c_str());
+    if (ov.n_prob > 0)
+      return fail(FS_ERR_UNSUPPORTED, (n + ": per-replica rates are built for scheduled inflows; this handle has a "
+                                           "probabilistic one").c_str());
+    if (bytes != size_t(dv.R) * FS_MAX_INFLOWS * sizeof(double))
+      return fail(FS_ERR_INVALID, (n + ": wrong byte count (float64 [R, FS_MAX_INFLOWS])").c_str());
+    return FS_OK;
+  }
+
   int get_state(int field, void* dst, size_t bytes) override {
+    if (field == FS_FIELD_INFLOW_PERIOD || field == FS_FIELD_INIT_INFLOW_PERIOD) {
+      const char* name;
+      if (int rc = inflow_period_check(field, bytes, &name)) return rc;
+      HIP_TRY(hipStreamSynchronize(stream));
+      if (int qrc = check_qflag()) return qrc;
+      HIP_TRY(hipMemcpy(dst, field == FS_FIELD_INFLOW_PERIOD ? ov.flow_per(dv.R) : ov.init_flow_per(dv.R), bytes, hipMemcpyDeviceToHost));
+      return FS_OK;                                   // (columns >= num_inflows were created 0 and are never written)
+    }
     if (dv.st16 && (field == FS_FIELD_POS || field == FS_FIELD_VEL)) {     // the halves -> the float32 staging arrays
       hipLaunchKernelGGL((fs::k_state16_unpack<T>), dim3(256), dim3(256), 0, stream, dv);
       HIP_TRY(hipGetLastError());
@@ -1156,6 +1187,24 @@ struct Sim : SimBase {
 
   int set_state(int field, const void* src, size_t bytes) override {
     HIP_TRY(hipStreamSynchronize(stream));
+    if (field == FS_FIELD_INFLOW_PERIOD || field == FS_FIELD_INIT_INFLOW_PERIOD) {
+      const char* name;
+      if (int rc = inflow_period_check(field, bytes, &name)) return rc;
+      std::vector<double> per(size_t(dv.R) * FS_MAX_INFLOWS, 0.0);
+      const double* vals = static_cast<const double*>(src);
+      for (int r = 0; r < dv.R; ++r)
+        for (int f = 0; f < cfg.num_inflows; ++f) {
+          const double p = vals[size_t(r) * FS_MAX_INFLOWS + f];
+          if (!std::isfinite(p) || !(p > 0.0))
+            return fail(FS_ERR_INVALID, (std::string(name) + ": a period must be finite and > 0 (replica " +
+                                         std::to_string(r) + ", inflow " + std::to_string(f) + ")").c_str());
+          per[size_t(r) * FS_MAX_INFLOWS + f] = p;
+        }
+      HIP_TRY(hipMemcpy(ov.init_flow_per(dv.R), per.data(), bytes, hipMemcpyHostToDevice));
+      if (field == FS_FIELD_INFLOW_PERIOD)            // the running episode too (as FS_FIELD_RING_LENGTH sets both)
+        HIP_TRY(hipMemcpy(ov.flow_per(dv.R), per.data(), bytes, hipMemcpyHostToDevice));
+      return FS_OK;
+    }
     if (field == FS_FIELD_TIME) {
       if (bytes != size_t(dv.R) * sizeof(int32_t)) return fail(FS_ERR_INVALID, "FS_FIELD_TIME: wrong byte count");
       HIP_TRY(hipMemcpy(dv.time, src, bytes, hipMemcpyHostToDevice));

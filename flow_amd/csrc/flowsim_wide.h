@@ -112,7 +112,7 @@ __global__ __launch_bounds__(64 * W) void k_steps_wide(DevView<T> s, OpenView<T>
   const bool is_rl = sl.ctrl == FS_CTRL_RL;
   constexpr bool TABS_IN_LDS = true;
   OpenTabs<T, TABS_IN_LDS> tb;
-  tb.load(o, l, dv_env, &L.tabs);
+  tb.load(o, l, dv_env, &L.tabs, o.flow_per(s.R) + size_t(rr) * FS_MAX_INFLOWS);
   static_assert(TABS_IN_LDS, "RouteCursor reads the tables with per-lane indices under divergent control flow");
   RouteCursor<T, OpenTabs<T, TABS_IN_LDS>> cur;
   if (tid < FS_MAX_INFLOWS) {
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(64 * W) void k_steps_wide(DevView<T> s, OpenView<T>
   // M2b (flowsim_open.h): thread f makes the per-sub-step trial of probabilistic inflow f
   const bool prob_any = o.n_prob > 0;
   const bool my_flow = prob_any && tid < o.n_inflows;
-  const double my_per = my_flow ? o.flow_tab_d[tid] : 0.0;
+  const double my_per = my_flow ? o.flow_per(s.R)[size_t(rr) * FS_MAX_INFLOWS + tid] : 0.0;
   const bool my_prob = my_per < 0.0;
   const uint32_t my_thr = my_prob ? uint32_t(-my_per - 1.0) : 0u;
   const double my_begin = my_flow ? o.flow_tab_d[64 + tid] : 0.0, my_end = my_flow ? o.flow_tab_d[128 + tid] : 0.0;

@@ -21,6 +21,36 @@ def handle_seed(sim_params):
     return int(sim_params.seed)
 
 
+def inflow_base_rates(flows):
+    """veh/h of every ``InFlows.add`` entry (``InFlows.get()``), as given or from its period; a probabilistic entry has
+    no schedule to scale and is refused."""
+    rates = []
+    for f in flows:
+        if "probability" in f:
+            raise NotImplementedError("per-replica inflow rates are built for scheduled inflows (vehs_per_hour / period), "
+                                      "not for InFlows.add(probability=...)")
+        rates.append(float(f["vehsPerHour"]) if "vehsPerHour" in f else 3600.0 / float(f["period"]))
+    return rates
+
+
+def inflow_periods(total, base_rates):
+    """Periods [s], float64 ``[R, num_inflows]``, of a handle's inflows for a total demand ``total [R]`` (veh/h) per
+    replica: every inflow keeps its share of the handle's own total, ``rate_f = total * base_f / sum(base)``, and its
+    period is ``3600.0 / rate_f`` -- the float64 expression of build_open_spec.  A replica given exactly the handle's
+    own total gets ``base_f`` itself, hence the handle's own periods bit for bit (the product may be an
+    ulp off ``base_f``)."""
+    total = np.atleast_1d(np.asarray(total, dtype=np.float64))
+    base = np.asarray(base_rates, dtype=np.float64)
+    if total.ndim != 1 or base.ndim != 1 or base.size == 0:
+        raise ValueError("inflow_periods: total [R] and base_rates [num_inflows] expected")
+    if not (np.all(np.isfinite(total)) and np.all(total > 0) and np.all(np.isfinite(base)) and np.all(base > 0)):
+        raise ValueError("inflow_periods: rates must be finite and > 0")
+    s = base.sum()
+    rate = total[:, None] * (base / s)[None, :]            # (one inflow: its share is exactly 1, its rate the total)
+    rate = np.where(total[:, None] == s, base[None, :], rate)
+    return 3600.0 / rate
+
+
 def vehicle_slots(vehicle_kernel, rl_order, ids=None):
     """One fs_vehicle_spec dict per vehicle, in id (insertion) order (vehicle/traci.py:109-117); ``ids`` restricts
     the table to some of the vehicles."""

@@ -66,6 +66,9 @@ class VecFlowEnv(object):
         import numpy as np
         self._resample = env.env_params.additional_params.get('ring_length', None) is not None \
             and env.FS_ENV in (L.FS_ENV_WAVE_ATTENUATION, L.FS_ENV_WAVE_ATTENUATION_PO, L.FS_ENV_WAVE_ATTENUATION_PO_MA)
+        # BottleneckDesiredVelocityEnv(reset_inflow=True): a new total inflow per episode (_draw_inflow_totals)
+        self._reset_inflow = env.FS_ENV == L.FS_ENV_BOTTLENECK_DV \
+            and bool(env.env_params.additional_params.get("reset_inflow"))
         self._rng = np.random.default_rng(sim_params.seed)
         self._placement_cache = {}
         self.use_current_stream()
@@ -147,23 +150,104 @@ class VecFlowEnv(object):
         self.sim.set_state(L.FS_FIELD_INIT_RING_LENGTH, lengths)
         self.sim.set_state(L.FS_FIELD_INIT_POS, init)
 
+    # ---- per-replica inflow rates (open networks with scheduled inflows) ----------------------------------------
+    def _base_inflow_rates(self):
+        from flow_amd.envs.spec import inflow_base_rates
+        return inflow_base_rates(self.env.net_params.inflows.get())
+
+    def set_inflow_rates(self, vehs_per_hour, pending=False):
+        """Give every replica its own demand.  ``vehs_per_hour``: ``[R]`` totals -- every inflow of the network keeps
+        its share of the network's own total (``flow_amd.envs.spec.inflow_periods``) -- or ``[R, num_inflows]``, one
+        rate per ``InFlows.add`` entry.  Written as periods to FS_FIELD_INFLOW_PERIOD: the running episodes step on with
+        them (vehicle k of a flow is due at ``begin + k * period``, k the vehicles the replica has emitted so far, so a
+        rate written mid-episode moves the next vehicle's due time) and later resets keep them.  ``pending=True``
+        writes FS_FIELD_INIT_INFLOW_PERIOD instead: the running episodes are left alone and a replica takes its new rate
+        at its next reset, inside a fragment with ``reset_done=True`` included.  Begin, end, number, vehicle types, lanes
+        and speeds of the inflows stay the network's.  Uploads synchronise the handle's stream."""
+        import numpy as np
+        from flow_amd.envs.spec import inflow_periods
+        base = self._base_inflow_rates()
+        rates = np.asarray(vehs_per_hour, dtype=np.float64)
+        R, nf = self.num_envs, len(base)
+        if rates.shape == (R,):
+            per = inflow_periods(rates, base)
+        elif rates.shape == (R, nf):
+            if not (np.all(np.isfinite(rates)) and np.all(rates > 0)):
+                raise ValueError("VecFlowEnv.set_inflow_rates: rates must be finite and > 0")
+            per = 3600.0 / rates
+        else:
+            raise ValueError("VecFlowEnv.set_inflow_rates: expected [R] = (%d,) totals or [R, num_inflows] = (%d, %d) "
+                             "rates, got %s" % (R, R, nf, rates.shape))
+        full = np.zeros((R, L.FS_MAX_INFLOWS))
+        full[:, :nf] = per
+        self.sim.set_state(L.FS_FIELD_INIT_INFLOW_PERIOD if pending else L.FS_FIELD_INFLOW_PERIOD, full)
+
+    def inflow_rates(self, pending=False):
+        """veh/h ``[R, num_inflows]`` the replicas run on now (``pending``: will take at their next reset)."""
+        nf = len(self.env._spec["inflows"])
+        per = self.sim.get_state(L.FS_FIELD_INIT_INFLOW_PERIOD if pending else L.FS_FIELD_INFLOW_PERIOD)
+        return 3600.0 / per[:, :nf]
+
+    def _draw_inflow_totals(self, n):
+        """bottleneck.py:1003-1007: ``uniform(min(inflow_range), max(inflow_range)) * scaling`` per replica."""
+        rng_ = self.env.env_params.additional_params["inflow_range"]
+        return self._rng.uniform(min(rng_), max(rng_), n) * self.env.scaling
+
+    def _resample_inflow_rates(self, mask_host):
+        """BottleneckDesiredVelocityEnv.reset with ``reset_inflow`` (flow/envs/bottleneck.py:988-1085) for the replicas
+        being reset: each draws its own total inflow, written as its pending rate -- the reset that follows makes it the
+        current one.  Deviation from the reference: the network's inflows keep their order, types, lanes and speeds
+        and their shares of the total; the reference rebuilds them as "followerstopper" 10 % / "human" 90 %
+        (:1012-1024), the same split whenever the experiment has those shares (exp_configs/rl/singleagent/
+        singleagent_bottleneck.py has)."""
+        import numpy as np
+        from flow_amd.envs.spec import inflow_periods
+        idx = np.flatnonzero(mask_host)
+        if idx.size == 0:
+            return
+        base = self._base_inflow_rates()
+        pending = self.sim.get_state(L.FS_FIELD_INIT_INFLOW_PERIOD)
+        pending[idx, :len(base)] = inflow_periods(self._draw_inflow_totals(idx.size), base)
+        self.sim.set_state(L.FS_FIELD_INIT_INFLOW_PERIOD, pending)
+
+    def redraw_inflow_rates(self):
+        """Give EVERY replica a fresh pending total inflow for its NEXT reset without touching the episode it is in
+        (FS_FIELD_INIT_INFLOW_PERIOD): call between fragments that reset inside the launch or graph
+        (``reset_done=True``), so that those resets redraw the demand per episode as BottleneckDesiredVelocityEnv.reset
+        does with ``reset_inflow`` (flow/envs/bottleneck.py:988-1085).  The twin of ``redraw_ring_lengths``; a no-op
+        unless the environment has ``reset_inflow`` set."""
+        import numpy as np
+        if not self._reset_inflow:
+            return
+        self._resample_inflow_rates(np.ones(self.num_envs, bool))
+
     def reset(self, mask=None):
-        """Reset all replicas (or those where ``mask`` [R] uint8/bool tensor is set); returns obs [R, obs_dim]."""
+        """Reset all replicas (or those where ``mask`` [R] uint8/bool tensor is set); returns obs [R, obs_dim].
+        BottleneckDesiredVelocityEnv with ``reset_inflow``: exactly the replicas being reset draw a new total inflow
+        first (_resample_inflow_rates; its docstring states how this differs from the reference's rebuilt network)."""
         self.use_current_stream()
         if mask is not None:
             mask = self._check(mask.to(self.torch.uint8), (self.num_envs,), self.torch.uint8)
-        if self._resample:
+        if self._resample or self._reset_inflow:
             import numpy as np
-            self._resample_ring_lengths(np.ones(self.num_envs, bool) if mask is None else mask.cpu().numpy() != 0)
+            mask_host = np.ones(self.num_envs, bool) if mask is None else mask.cpu().numpy() != 0
+            if self._resample:
+                self._resample_ring_lengths(mask_host)
+            if self._reset_inflow:
+                self._resample_inflow_rates(mask_host)
         self.sim.reset_dev(self._obs, mask)
         return self._obs
 
     def reset_done(self):
         """Reset exactly the replicas whose last ``done`` flag is set.  No host synchronisation, unless the
-        environment redraws its network per episode (WaveAttenuationEnv with ``ring_length``)."""
+        environment redraws its network or demand per episode (WaveAttenuationEnv with ``ring_length``,
+        BottleneckDesiredVelocityEnv with ``reset_inflow``): those two paths copy the done flags to the host, draw there
+        and upload the pending values, so they synchronise the handle's stream with the host on EVERY call."""
         self.use_current_stream()
         if self._resample:
             self._resample_ring_lengths(self._done.cpu().numpy() != 0)
+        if self._reset_inflow:
+            self._resample_inflow_rates(self._done.cpu().numpy() != 0)
         self.sim.reset_dev(self._obs, self._done)
         return self._obs
 
@@ -274,7 +358,19 @@ class VecFlowEnv(object):
                           "the captured graph re-places a replica on the length it drew at the last vec.reset() / "
                           "vec.reset_done() instead.  Call vec.redraw_ring_lengths() between replays to give every "
                           "replica a fresh pending length for its next in-graph reset.", stacklevel=2)
+        if reset_done:
+            self._warn_pending_inflow("capture")
         return StepGraph(self, num_steps, policy, reset_done)
+
+    def _warn_pending_inflow(self, what):
+        if not self._reset_inflow or getattr(self, "_warned_pending_inflow", False):
+            return
+        import warnings
+        self._warned_pending_inflow = True
+        warnings.warn("VecFlowEnv.%s(reset_done=True): this environment redraws its inflow on reset (reset_inflow, "
+                      "flow/envs/bottleneck.py:988-1085); every reset inside ONE fragment takes the replica's pending "
+                      "rate (FS_FIELD_INIT_INFLOW_PERIOD) -- call vec.redraw_inflow_rates() between fragments, and keep "
+                      "fragments shorter than an episode if each episode must draw its own." % what, stacklevel=3)
 
     def policy_act(self, policy, obs=None, out=None):
         """ONE evaluation of ``policy`` (a ``DevicePolicy``) for every replica in one kernel launch
@@ -328,6 +424,8 @@ class VecFlowEnv(object):
                           "(flow/envs/ring/wave_attenuation.py:157-210); every reset inside ONE fragment takes the replica's "
                           "pending length (FS_FIELD_INIT_RING_LENGTH) -- call vec.redraw_ring_lengths() between fragments, "
                           "and keep fragments shorter than an episode if each episode must draw its own.", stacklevel=2)
+        if reset_done:
+            self._warn_pending_inflow("policy_rollout")
         n_ag = self.sim.policy_agents
         per_agent = (K, R) if n_ag == 1 else (K, R, n_ag)
         a_dim = self.sim.policy_action_dim               # (MergePOEnv: one evaluation, num_rl columns, one log-probability)

@@ -299,6 +299,8 @@ class FlowSim:
             return (self.R, self.N), self.real
         if field in (L.FS_FIELD_RING_LENGTH, L.FS_FIELD_INIT_RING_LENGTH):
             return (self.R,), self.real
+        if field in (L.FS_FIELD_INFLOW_PERIOD, L.FS_FIELD_INIT_INFLOW_PERIOD):
+            return (self.R, L.FS_MAX_INFLOWS), np.float64
         return (self.R, self.N), self.real
 
     def get_state(self, field):

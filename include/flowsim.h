@@ -168,11 +168,24 @@ enum fs_field {
   FS_FIELD_MAX_SPEED = 21, /* real[R,N]  get_max_speed / set_max_speed: maxSpeed of the SUMO car-following model */
   FS_FIELD_SORT_KEY = 23,  /* real[R,N] AccelEnv.absolute_position as of the last additional_command (sort_vehicles only,
                               flow/envs/ring/accel.py:150-169): the key the kernel ranks observations and actions by */
-  FS_FIELD_INIT_RING_LENGTH = 22 /* real[R] the ring length a replica takes at its NEXT reset (WaveAttenuationEnv.reset
+  FS_FIELD_INIT_RING_LENGTH = 22,/* real[R] the ring length a replica takes at its NEXT reset (WaveAttenuationEnv.reset
                               draws a new length per episode, flow/envs/ring/wave_attenuation.py:157-210): fs_reset[_dev]
                               copies it into FS_FIELD_RING_LENGTH for the replicas it resets, so a reset inside a
                               captured graph can change the length without touching replicas that are mid-episode.
                               Writing FS_FIELD_RING_LENGTH sets both. */
+  FS_FIELD_INFLOW_PERIOD = 24, /* float64[R,FS_MAX_INFLOWS] (whatever the handle's precision) the period [s] of inflow f
+                              in replica r: vehicle k of the flow is due at begin + k * period, k the vehicles the replica
+                              has emitted (begin, end and number stay the handle's).  fs_create fills it from
+                              fs_inflow.period.  Columns >= num_inflows read as 0 and are ignored on write.  A period
+                              written mid-episode moves the due time of the replica's next vehicle.  Refused, with the
+                              field's name: closed networks and open ones without inflows (FS_ERR_INVALID), a handle
+                              with a probabilistic inflow (FS_ERR_UNSUPPORTED), a period that is not finite or not > 0
+                              (FS_ERR_INVALID; nothing is written).  Writing it sets FS_FIELD_INIT_INFLOW_PERIOD too. */
+  FS_FIELD_INIT_INFLOW_PERIOD = 25 /* float64[R,FS_MAX_INFLOWS] the period a replica takes at its NEXT reset (the twin of
+                              FS_FIELD_INIT_RING_LENGTH; BottleneckDesiredVelocityEnv.reset draws a new inflow per
+                              episode, flow/envs/bottleneck.py:988-1085): fs_reset[_dev] and the resets inside a
+                              policy rollout copy it into FS_FIELD_INFLOW_PERIOD for the replicas they reset; writing
+                              it leaves the running episodes alone. */
 };
 
 #define FS_MAX_CTRL_PARAMS 8
