@@ -40,6 +40,9 @@ def parse_args(args):
                         help='device: roll an action-vector policy (singleagent_merge) out through the fused policy + '
                              'step kernel instead of the captured graph; where there is none (singleagent_bottleneck), '
                              'capture the graph around the policy kernel instead of the torch module')
+    parser.add_argument('--device_update', action='store_true',
+                        help='device: run the PPO update on the library\'s kernels (fs_ppo_eval_dev, fs_gae_dev, '
+                             'fs_ppo_grad_dev) instead of torch')
     return parser.parse_known_args(args)[0]
 
 
@@ -94,7 +97,8 @@ def train_device(submodule, flags, multiagent=False):
     fp = submodule.flow_params
     fp['sim'].render = False
     return train_on_device(fp, replicas=flags.replicas, fragment=flags.rollout_size, iterations=flags.num_steps,
-                           shared_agents=multiagent, fuse_action_vector=flags.fuse_policy and not multiagent)
+                           shared_agents=multiagent, fuse_action_vector=flags.fuse_policy and not multiagent,
+                           device_update=flags.device_update)
 
 
 def main(args):

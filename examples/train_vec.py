@@ -82,27 +82,38 @@ def gae(rew, val, done, last_val, gamma=0.999, lam=0.97):
     return adv, adv + val
 
 
-def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None):
+def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None, learner=None):
     """One PPO update over `shards` = [(obs [K+1, R, D], act [K, R, A], rew [K, R], done [K, R])]: the shards this
     process holds (one per rank in data-parallel runs, all of them in a single process).  Every quantity that couples the
     shards is a SUM: the advantage statistics and the gradient -- summed over the local shards here, over the ranks by
     allreduce_sum / allreduce_gradients -- so N ranks with one shard each and one process with N shards agree.
     A sample whose action is NaN is an agent that was absent (the multi-agent merge's fused rollout: its RL slot held no
-    vehicle): it is left out of the advantage statistics and the loss, and its action is never read."""
+    vehicle): it is left out of the advantage statistics and the loss, and its action is never read.
+    ``learner`` (flow_amd.utils.device_ppo.DeviceLearner over pi's parameters): the three torch stages -- the no_grad pass,
+    gae() and every epoch's forward and backward pass -- run on the library's kernels instead (fs_ppo_eval_dev, fs_gae_dev,
+    fs_ppo_grad_dev); the float64 advantage statistics, the all-reduces and opt.step() are the same code.  Without one, the
+    update is torch alone."""
     from flow_amd.dist import allreduce_gradients, allreduce_sum
     prepared, stats = [], None
+    if learner is not None:
+        learner.sync()
     for obs, act, rew, done in shards:
         K, R = rew.shape
         o, a = obs[:K].reshape(K * R, -1), act.reshape(K * R, -1)
         present = ~torch.isnan(a).any(-1)
         if bool(present.all()):
             present = None                                   # (every sample present: the plain sums)
-        else:
+        elif learner is None:
             a = torch.where(present[:, None], a, torch.zeros_like(a))
         with torch.no_grad():
-            logp_old, val = pi.logp_value(o, a)
-            last_val = pi.value(obs[K]).squeeze(-1)
-            adv, ret = gae(rew, val.view(K, R), done, last_val)
+            if learner is not None:                          # (the kernels take the NaN rows as they are: absent)
+                logp_old, val = learner.evaluate(o, a)
+                last_val = learner.evaluate(obs[K], None)[1]
+                adv, ret = learner.gae(rew, val.view(K, R), last_val, done)
+            else:
+                logp_old, val = pi.logp_value(o, a)
+                last_val = pi.value(obs[K]).squeeze(-1)
+                adv, ret = gae(rew, val.view(K, R), done, last_val)
             adv = adv.reshape(-1).double()
             if present is None:
                 st = torch.stack([adv.sum(), (adv * adv).sum(), torch.tensor(float(adv.numel()), dtype=torch.float64, device=adv.device)])
@@ -117,25 +128,35 @@ def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None):
     std = ((stats[1] - n * mean * mean) / (n - 1)).clamp_min(0).sqrt()
     params = list(pi.parameters())
     for _ in range(epochs):
-        opt.zero_grad()
-        for o, a, logp_old, adv, ret, present in prepared:
-            adv_n = ((adv - mean) / (std + 1e-8)).float()
-            logp, v = pi.logp_value(o, a)
-            ratio = (logp - logp_old).exp()
-            pg = torch.min(ratio * adv_n, ratio.clamp(1 - clip, 1 + clip) * adv_n)
-            vf = (v - ret).pow(2)
-            if present is not None:
-                pg = torch.where(present, pg, torch.zeros_like(pg))
-                vf = torch.where(present, vf, torch.zeros_like(vf))
-            # the GLOBAL mean as a sum of per-shard sums
-            loss = (-pg.sum() + 0.5 * vf.sum()) / float(n)
-            loss.backward()                                  # (accumulates over the local shards)
+        if learner is not None:
+            # one launch per shard writes (the first shard) or adds to (the others, in this order) the packed gradient
+            # that every parameter's .grad is a view of
+            for j, (o, a, logp_old, adv, ret, present) in enumerate(prepared):
+                learner.gradients(o, a, logp_old, adv, ret, mean, std, clip=clip, vf_coef=0.5, n_total=float(n),
+                                  accumulate=j > 0)
+            learner.attach_grads()
+        else:
+            opt.zero_grad()
+            for o, a, logp_old, adv, ret, present in prepared:
+                adv_n = ((adv - mean) / (std + 1e-8)).float()
+                logp, v = pi.logp_value(o, a)
+                ratio = (logp - logp_old).exp()
+                pg = torch.min(ratio * adv_n, ratio.clamp(1 - clip, 1 + clip) * adv_n)
+                vf = (v - ret).pow(2)
+                if present is not None:
+                    pg = torch.where(present, pg, torch.zeros_like(pg))
+                    vf = torch.where(present, vf, torch.zeros_like(vf))
+                # the GLOBAL mean as a sum of per-shard sums
+                loss = (-pg.sum() + 0.5 * vf.sum()) / float(n)
+                loss.backward()                              # (accumulates over the local shards)
         allreduce_gradients(params, group)
         opt.step()
+        if learner is not None:
+            learner.sync()                                   # the optimiser moved the weights: repack them for the kernels
 
 
 def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epochs=4, lr=3e-4, seed=0, log=print,
-                    rank=0, world=1, shared_agents=False, fuse_action_vector=False):
+                    rank=0, world=1, shared_agents=False, fuse_action_vector=False, device_update=False):
     """PPO on R replicas of ``flow_params`` with everything in HBM: returns the mean step reward per iteration.
     ``world`` > 1: this process is rank ``rank`` of a data-parallel run (torch.distributed is initialised): it steps its
     block of the R replicas on its own GPU.
@@ -149,7 +170,9 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     kernel exists but the eager policy kernel does (BottleneckDesiredVelocityEnv: singleagent_bottleneck.py,
     k_policy_act_wide), the captured graph holds that kernel instead of the torch module.  Off by default: the library's
     kernels draw their samples from its Philox streams, the torch policy from torch.randn, so the two are different
-    (equally valid) trajectories."""
+    (equally valid) trajectories.
+    ``device_update``: the PPO update runs on the library's kernels (DeviceLearner: fs_ppo_eval_dev, fs_gae_dev,
+    fs_ppo_grad_dev) instead of torch forward passes, the Python loop of gae() and autograd.  Off by default."""
     from flow_amd.dist import allreduce_sum, shard_range
     from flow_amd.envs import VecFlowEnv
     local = int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else 0
@@ -209,6 +232,11 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
         graph = vec.capture(fragment, policy=act_shared if shared_agents else pi.act, reset_done=True)
         graph.begin(vec.reset())
     K, R = fragment, hi - lo
+    learner = None
+    if device_update:
+        from flow_amd.utils.device_ppo import DeviceLearner
+        learner = DeviceLearner(vec, [pi.mu[0], pi.mu[2]], pi.mu[4], pi.log_std, [pi.value[0], pi.value[2]], pi.value[4])
+        log("update: on the device (k_ppo_eval, k_gae, k_ppo_grad)")
     history = []
     for it in range(iterations):
         vec.redraw_ring_lengths()                              # pending ring length per replica for its next in-graph reset
@@ -229,7 +257,7 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
                      rew.repeat_interleave(n_ag, dim=1), done.repeat_interleave(n_ag, dim=1))
         else:
             shard = (obs, act, rew, done)
-        ppo_update(pi, opt, [shard], epochs=epochs)
+        ppo_update(pi, opt, [shard], epochs=epochs, learner=learner)
         tot = allreduce_sum(torch.stack([rew.double().sum(), torch.tensor(float(rew.numel()), dtype=torch.float64, device=dev),
                                          (done != 0).sum().double()]))
         mean_rew = float(tot[0] / tot[1])
@@ -272,6 +300,8 @@ def main(argv=None):
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--lr", type=float, default=3e-4)
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel over this many GPUs of the node (one process each)")
+    ap.add_argument("--device_update", action="store_true",
+                    help="run the PPO update on the library's kernels (DeviceLearner) instead of torch")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     force = os.environ.get("TRAIN_FORCE_DIST") == "1"            # the N > 1 code path (RCCL init, all-reduces) with one rank
@@ -288,7 +318,8 @@ def main(argv=None):
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local))
     try:
         return train_on_device(ring_flow_params(args.horizon), replicas=args.replicas, fragment=args.fragment,
-                               iterations=args.iterations, epochs=args.epochs, lr=args.lr, rank=rank, world=world)
+                               iterations=args.iterations, epochs=args.epochs, lr=args.lr, rank=rank, world=world,
+                               device_update=args.device_update)
     finally:
         if world > 1 or force:
             import torch.distributed as dist

@@ -45,7 +45,7 @@ FS_EULER, FS_BALLISTIC = 0, 1
 EXPORTS = ["fs_create", "fs_destroy", "fs_last_error", "fs_abi_version", "fs_obs_dim", "fs_action_dim", "fs_set_stream",
            "fs_use_own_stream", "fs_sync", "fs_reset", "fs_reset_dev", "fs_step", "fs_step_dev", "fs_rollout_dev",
            "fs_get_state", "fs_set_state", "fs_add_vehicle", "fs_dump_trajectory", "fs_last_kernel", "fs_policy_act_dev",
-           "fs_policy_rollout_dev"]
+           "fs_policy_rollout_dev", "fs_ppo_eval_dev", "fs_gae_dev", "fs_ppo_workspace", "fs_ppo_grad_dev"]
 
 
 class fs_vehicle_spec(C.Structure):
@@ -115,6 +115,12 @@ class fs_policy(C.Structure):
                 ("log_std_dev", C.c_void_p), ("seed", C.c_uint64)]
 
 
+class fs_ppo_model(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("num_hidden", C.c_int32),
+                ("hidden_width", C.c_int32), ("activation", C.c_int32), ("policy_weights_dev", C.c_void_p),
+                ("log_std_dev", C.c_void_p), ("value_weights_dev", C.c_void_p)]
+
+
 _libs = {}
 
 
@@ -177,6 +183,16 @@ def load(path=None):
     lib.fs_policy_act_dev.restype = C.c_int
     lib.fs_policy_rollout_dev.argtypes = [h, C.POINTER(fs_policy), C.c_int, C.c_int, f32p, f32p, f32p, f32p, u8p]
     lib.fs_policy_rollout_dev.restype = C.c_int
+    f64p = C.c_void_p
+    lib.fs_ppo_eval_dev.argtypes = [h, C.POINTER(fs_ppo_model), C.c_int64, f32p, f32p, f32p, f32p]
+    lib.fs_ppo_eval_dev.restype = C.c_int
+    lib.fs_gae_dev.argtypes = [h, C.c_int, C.c_int64, f32p, f32p, f32p, u8p, C.c_double, C.c_double, f32p, f32p]
+    lib.fs_gae_dev.restype = C.c_int
+    lib.fs_ppo_workspace.argtypes = [C.POINTER(fs_ppo_model), C.c_int64]
+    lib.fs_ppo_workspace.restype = C.c_size_t
+    lib.fs_ppo_grad_dev.argtypes = [h, C.POINTER(fs_ppo_model), C.c_int64, f32p, f32p, f32p, f64p, f32p, f64p, C.c_float,
+                                    C.c_float, C.c_float, C.c_int, f32p, f32p, f32p, C.c_size_t]
+    lib.fs_ppo_grad_dev.restype = C.c_int
     if lib.fs_abi_version() != FS_ABI_VERSION:
         raise FatalFlowError("libflowsim.so ABI %d != binding ABI %d" % (lib.fs_abi_version(), FS_ABI_VERSION))
     _libs[path] = lib

@@ -1,7 +1,8 @@
 """Build libflowsim.so (HIP, gfx950) in-tree.  hipcc cross-compiles without a GPU.
 
 The library is several objects: `flowsim.hip` (C ABI, validation, handle) and `flowsim_part.hip` compiled once per
-(precision, lanes per replica) pair -- each pair instantiates its own step kernels, so the objects compile in parallel.
+(precision, lanes per replica) pair -- each pair instantiates its own step kernels, so the objects compile in parallel --
+and once more for the PPO update's kernels (`learn_f32`, flowsim_learn.h).
 Objects are cached under flow_amd/csrc/_obj/ with a stamp = hash of the CONTENTS of every source and header plus the
 flags: an edit to any of them recompiles every object (they share the headers' struct layouts), a change of flags only
 the objects it concerns.  The library is current only if every object's stamp is (needs_build)."""
@@ -25,6 +26,7 @@ VALIDATED_ROCM = "7.2"
 
 HEADERS = ["flowsim_sim.h", "flowsim_launch.h", "flowsim_kernels.h", "flowsim_open.h", "flowsim_wide.h",
            "flowsim_pair.h", "flowsim_pair_step_a.inc", "flowsim_pair_step_a_sm.inc", "flowsim_fig8.h", "flowsim_ringrl.h", "flowsim_policy.h", "flowsim_queue.h", "flowsim_queue_consts.h", "flowsim_dropq.h",
+           "flowsim_learn.h",
            "flowsim_part.hip"]
 DEPS = [SRC] + [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(ROOT, "include", "flowsim.h")]
 assert all(os.path.exists(d) for d in DEPS)
@@ -46,6 +48,7 @@ def parts():
             out.append(("wide%d_%s" % (w, tn), PART, ["-DFS_PART_T=" + t, "-DFS_PART_WIDE=%d" % w]))
     out.append(("queue_f32", PART, ["-DFS_PART_T=float", "-DFS_PART_QUEUE=1"] +
                 (["-DFS_QDIAG=1"] if os.environ.get("FLOWSIM_QDIAG") else [])))     # cycle counters of k_merge_queue's sections
+    out.append(("learn_f32", PART, ["-DFS_PART_T=float", "-DFS_PART_LEARN=1"]))     # the PPO update (flowsim_learn.h)
     return out
 
 
@@ -175,7 +178,7 @@ def user_header(body):
 
 def build_user(body, verbose=False):
     """A copy of the library whose FS_CTRL_USER slots run the user's controller: flow_amd/_user/<hash>/libflowsim.so.
-    Every part but the queue kernels' is recompiled with -DFS_USER_CONTROLLER_HEADER (in parallel; the C ABI object too:
+    Every part but the queue kernels' and the learner's is recompiled with -DFS_USER_CONTROLLER_HEADER (in parallel; the C ABI object too:
     its Sim::launch_steps refuses FS_CTRL_USER slots without the header); cached by the hash of the body and of the
     sources."""
     text = user_header(body)
@@ -199,7 +202,7 @@ def build_user(body, verbose=False):
         f.write(text)
     objs, todo = [], []
     for name, src, extra in parts():
-        if name.startswith("queue"):
+        if name.startswith(("queue", "learn")):           # (no controller in them: the plain build's objects)
             objs.append(os.path.join(OBJ, name + ".o"))
             continue
         out = os.path.join(out_dir, name + ".o")

@@ -4,6 +4,7 @@
 // returns is computed on the GPU.  There is no CPU fallback: without a HIP
 // device fs_create fails with FS_ERR_HIP.
 #include "flowsim_sim.h"
+#include "flowsim_learn.h"
 
 namespace fsim {
 
@@ -499,6 +500,72 @@ int fs_policy_rollout_dev(fs_handle h, const fs_policy* pol, int num_steps, int 
   if (num_steps < 1) return fail(FS_ERR_INVALID, "fs_policy_rollout_dev: num_steps < 1");
   DeviceGuard guard(S(h)->cfg.device);
   return S(h)->launch_policy(pol, num_steps, reset_done ? 1 : 0, nullptr, obs_dev, act_dev, logp_dev, rew_dev, done_dev);
+}
+
+// ---- the PPO update on the device (flowsim_learn.h): the handle lends its device, its stream and fs_last_error
+static int ppo_view(const char* who, const fs_ppo_model* m, bool need_policy, fs::PpoView* out) {
+  const std::string w = std::string(who) + ": fs_ppo_model: ";
+  if (!m) return fail(FS_ERR_INVALID, w + "NULL");
+  if (m->struct_size != sizeof(fs_ppo_model)) return fail(FS_ERR_INVALID, w + "struct_size mismatch");
+  if (m->obs_dim < 1 || m->obs_dim > fs::PPO_MAX_OBS)
+    return fail(FS_ERR_UNSUPPORTED, w + "obs_dim must be 1..160");
+  if (m->act_dim < 1 || m->act_dim > fs::PPO_MAX_ACT)
+    return fail(FS_ERR_UNSUPPORTED, w + "act_dim must be 1..32");
+  if (m->num_hidden < 1 || m->num_hidden > 3 || m->hidden_width != 32)
+    return fail(FS_ERR_UNSUPPORTED, w + "1..3 hidden layers of 32 units");
+  if (m->activation != 0) return fail(FS_ERR_UNSUPPORTED, w + "activation must be 0 (tanh)");
+  if (need_policy && !m->log_std_dev)
+    return fail(FS_ERR_UNSUPPORTED, w + "the head of 2 A outputs (no free log_std) is not built: log_std_dev is NULL");
+  if (!m->value_weights_dev || (need_policy && !m->policy_weights_dev)) return fail(FS_ERR_INVALID, w + "NULL weights");
+  *out = fs::PpoView{m->policy_weights_dev, m->log_std_dev, m->value_weights_dev, m->obs_dim, m->act_dim, m->num_hidden};
+  return FS_OK;
+}
+
+int fs_ppo_eval_dev(fs_handle h, const fs_ppo_model* model, int64_t n, const float* obs_dev, const float* act_dev,
+                    float* logp_dev, float* val_dev) {
+  if (!h || !obs_dev || !val_dev || (act_dev && !logp_dev)) return fail(FS_ERR_INVALID, "fs_ppo_eval_dev: NULL argument");
+  if (n < 1 || n > INT32_MAX) return fail(FS_ERR_INVALID, "fs_ppo_eval_dev: n must be 1 .. 2^31 - 1");
+  fs::PpoView pv;
+  if (int rc = ppo_view("fs_ppo_eval_dev", model, act_dev != nullptr, &pv)) return rc;
+  DeviceGuard guard(S(h)->cfg.device);
+  S(h)->last_kernel = "k_ppo_eval";
+  return launch_ppo_eval(S(h)->stream, pv, n, obs_dev, act_dev, logp_dev, val_dev);
+}
+
+int fs_gae_dev(fs_handle h, int num_steps, int64_t num_cols, const float* rew_dev, const float* val_dev,
+               const float* last_val_dev, const uint8_t* done_dev, double gamma, double lam, float* adv_dev, float* ret_dev) {
+  if (!h || !rew_dev || !val_dev || !last_val_dev || !done_dev || !adv_dev || !ret_dev)
+    return fail(FS_ERR_INVALID, "fs_gae_dev: NULL argument");
+  if (num_steps < 1 || num_cols < 1 || num_cols > INT32_MAX) return fail(FS_ERR_INVALID, "fs_gae_dev: num_steps / num_cols out of range");
+  DeviceGuard guard(S(h)->cfg.device);
+  S(h)->last_kernel = "k_gae";
+  return launch_gae(S(h)->stream, num_steps, num_cols, rew_dev, val_dev, last_val_dev, done_dev, float(gamma),
+                    float(gamma * lam), adv_dev, ret_dev);
+}
+
+size_t fs_ppo_workspace(const fs_ppo_model* model, int64_t n) {
+  fs::PpoView pv;
+  if (n < 1 || n > INT32_MAX || ppo_view("fs_ppo_workspace", model, false, &pv)) return 0;
+  return fs::ppo_work_floats(n, pv.D, pv.A, pv.L);
+}
+
+int fs_ppo_grad_dev(fs_handle h, const fs_ppo_model* model, int64_t n, const float* obs_dev, const float* act_dev,
+                    const float* logp_old_dev, const double* adv_dev, const float* ret_dev, const double* mean_std_dev,
+                    float clip, float vf_coef, float inv_n_total, int accumulate, float* grad_dev, float* loss_dev,
+                    float* work_dev, size_t work_floats) {
+  if (!h || !obs_dev || !act_dev || !logp_old_dev || !adv_dev || !ret_dev || !mean_std_dev || !grad_dev || !loss_dev || !work_dev)
+    return fail(FS_ERR_INVALID, "fs_ppo_grad_dev: NULL argument");
+  if (n < 1 || n > INT32_MAX) return fail(FS_ERR_INVALID, "fs_ppo_grad_dev: n must be 1 .. 2^31 - 1");
+  fs::PpoView pv;
+  if (int rc = ppo_view("fs_ppo_grad_dev", model, true, &pv)) return rc;
+  if (work_floats < fs::ppo_work_floats(n, pv.D, pv.A, pv.L))
+    return fail(FS_ERR_INVALID, "fs_ppo_grad_dev: work_dev is smaller than fs_ppo_workspace(model, n) floats");
+  DeviceGuard guard(S(h)->cfg.device);
+  S(h)->last_kernel = "k_ppo_grad";
+  // the clamp's bounds as torch takes them: the doubles 1 -+ clip rounded to float32
+  return launch_ppo_grad(S(h)->stream, pv, n, obs_dev, act_dev, logp_old_dev, adv_dev, ret_dev, mean_std_dev,
+                         float(1.0 - double(clip)), float(1.0 + double(clip)), vf_coef, inv_n_total, accumulate ? 1 : 0,
+                         grad_dev, loss_dev, work_dev);
 }
 
 const char* fs_last_kernel(fs_handle h) { return h ? reinterpret_cast<SimBase*>(h)->last_kernel : ""; }

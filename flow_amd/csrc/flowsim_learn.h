@@ -1,0 +1,487 @@
+// flowsim_learn.h -- the PPO update on the device: what examples/train_vec.py ppo_update does in torch between two
+// rollouts, as three kernels (fs_ppo_eval_dev, fs_gae_dev, fs_ppo_grad_dev: include/flowsim.h).
+//
+//   k_ppo_eval   forward only: logp [n] and val [n] of n samples (the no_grad pass; act == NULL: values alone)
+//   k_gae        the reverse recurrence of train_vec.gae, one lane per replica, float32 bits of CPU torch
+//   k_ppo_grad   forward, PPO loss and backward of both networks in ONE launch: one partial gradient per workgroup,
+//   k_ppo_reduce ... summed over the workgroups in ascending order (no float atomics: the same inputs give the same bits)
+//
+// Model class (DevicePolicy's): 1..3 hidden layers of 32 tanh units on 1..160 inputs, a head of A <= 32 means with a free
+// log_std [A]; the value network is the same trunk with one output.  Packed weights per network: per layer W [out][in]
+// row-major, then b [out] (fs_policy's layout).
+//
+// Mapping: a workgroup is ONE wave and a lane is ONE sample of a 64-sample tile; tile t belongs to workgroup t mod G and a
+// workgroup takes its tiles in ascending order.  G depends on (n, D, A, layers) alone (ppo_groups), and so does the order
+// of every sum.  A layer's 32 outputs are 32 registers of the lane; its inputs come from an LDS staging buffer [input][lane]
+// (the lane's own column), its weights from the LDS copy of the network, transposed to [input][unit] so that one
+// ds_read_b128 broadcasts four units' weights of an input to the wave.  The network is written ONCE (net_forward): both
+// kernels call it for both networks.  A weight gradient dW[u][i] = sum_s dz[s][u] h[s][i] is NOT a cross-lane reduction
+// here: the lanes re-map to (input i, half of the units), and each walks the tile's 64 samples in ascending order over the
+// staged dz [sample][unit] and h [input][sample] -- 16 FMAs per five LDS reads, exact float32, fixed order.  (The
+// FP32-input MFMA runs at the vector FMA rate on this chip, so it buys nothing here; at D = 3 the update is a GFLOP.)
+// The workgroup's gradient lives in LDS in the packed layout and is written out once, at the end.
+// Every fused multiply-add is an explicit fmaf (the library is compiled with -ffp-contract=off).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace fs {
+
+constexpr int PPO_MAX_OBS = 160, PPO_MAX_ACT = 32, PPO_TILE = 64;
+constexpr int PPO_TS = 65;     // stride of the staging buffer S [input][sample]: conflict-free by rows and by columns
+constexpr int PPO_TT = 36;     // stride of the staging buffer T [sample][unit]: rows stay 16-byte aligned
+constexpr int PPO_LDS_BYTES = 160 * 1024;
+
+struct PpoView {
+  const float* pw;         // policy weights (packed)
+  const float* log_std;    // [A]
+  const float* vw;         // value weights (packed)
+  int D, A, L;
+};
+
+// packed parameter counts: a network with n_out outputs; the whole gradient [policy][log_std A][value]
+__host__ __device__ constexpr int ppo_net_params(int D, int L, int n_out) { return 32 * D + 32 + (L - 1) * 1056 + 33 * n_out; }
+__host__ __device__ constexpr int ppo_params(int D, int A, int L) { return ppo_net_params(D, L, A) + A + ppo_net_params(D, L, 1); }
+// the LDS copy of a network: [input][unit] per layer, the head padded to 32 units
+__host__ __device__ constexpr int ppo_net_lds(int D, int L) { return 32 * D + 32 + L * 1056; }
+__host__ __device__ constexpr int ppo_stage_floats() { return 32 * PPO_TS + PPO_TILE * PPO_TT; }
+__host__ __device__ constexpr int round4(int x) { return (x + 3) & ~3; }
+__host__ __device__ constexpr size_t ppo_eval_lds(int D, int L) { return sizeof(float) * size_t(2 * ppo_net_lds(D, L) + ppo_stage_floats()); }
+__host__ __device__ constexpr size_t ppo_grad_lds(int D, int A, int L) {
+  return sizeof(float) * size_t(2 * ppo_net_lds(D, L) + ppo_stage_floats() + round4(ppo_params(D, A, L) + 2));
+}
+// workgroups of k_ppo_grad: one per tile up to what the chip holds at once (256 CUs, as many workgroups per CU as their LDS
+// allows, four at the most) -- a function of (n, D, A, L) alone
+__host__ __device__ constexpr int ppo_groups(long long n, int D, int A, int L) {
+  const long long tiles = (n + PPO_TILE - 1) / PPO_TILE;
+  const int per_cu = int(size_t(PPO_LDS_BYTES) / ppo_grad_lds(D, A, L));
+  const long long cap = 256LL * (per_cu > 4 ? 4 : per_cu < 1 ? 1 : per_cu);
+  return int(tiles < cap ? (tiles < 1 ? 1 : tiles) : cap);
+}
+// floats of the partial-gradient workspace of one fs_ppo_grad_dev call
+__host__ __device__ constexpr size_t ppo_work_floats(long long n, int D, int A, int L) {
+  return size_t(ppo_groups(n, D, A, L)) * size_t(ppo_params(D, A, L) + 2);
+}
+
+}  // namespace fs
+
+namespace fsim {
+// (defined in the learn_f32 part: flowsim_part.hip with -DFS_PART_LEARN=1)
+int launch_ppo_eval(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act, float* logp,
+                    float* val);
+int launch_gae(hipStream_t stream, int K, long long R, const float* rew, const float* val, const float* last_val,
+               const uint8_t* done, float g, float gl, float* adv, float* ret);
+int launch_ppo_grad(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act,
+                    const float* logp_old, const double* adv, const float* ret, const double* mean_std, float lo, float hi,
+                    float vf_coef, float inv_n, int accumulate, float* grad, float* loss, float* work);
+}  // namespace fsim
+
+#ifdef FS_PART_LEARN
+namespace fs {
+
+__device__ __forceinline__ float ppo_tanh(float z) {                     // (flowsim_policy.h policy_tanh)
+  const float e = __builtin_amdgcn_exp2f(z * 2.885390081777927f);       // exp(2 z)
+  const float r = __builtin_amdgcn_rcpf(e + 1.0f);
+  return __builtin_fmaf(-2.0f, r, 1.0f);                                // 1 - 2 / (exp(2 z) + 1)
+}
+
+// a packed network -> LDS (all 64 lanes; the caller ends with a barrier): layer l at lds + ppo_layer_off(l), Wt [in][32]
+// then b [32]; the head's units >= n_out are zero
+__device__ __forceinline__ int ppo_layer_off(int D, int l) { return l == 0 ? 0 : 32 * D + 32 + (l - 1) * 1056; }
+
+__device__ __forceinline__ void net_load(const float* w, int D, int L, int n_out, float* lds, int lane) {
+  for (int e = lane; e < 32 * D; e += 64) lds[(e % D) * 32 + e / D] = w[e];
+  if (lane < 32) lds[32 * D + lane] = w[32 * D + lane];
+  w += 32 * D + 32;
+  for (int l = 1; l <= L; ++l) {
+    float* q = lds + ppo_layer_off(D, l);
+    const int rows = l < L ? 32 : n_out;
+    for (int e = lane; e < 1024; e += 64) q[(e & 31) * 32 + (e >> 5)] = (e >> 5) < rows ? w[e] : 0.0f;
+    if (lane < 32) q[1024 + lane] = lane < rows ? w[rows * 32 + lane] : 0.0f;
+    w += rows * 33;
+  }
+}
+
+// z[u] += sum_i Wt[i][u] S[i][lane], i ascending: the one place a layer's product is written
+__device__ __forceinline__ void layer_acc(const float* wt, const float* S, int n_in, int lane, float (&z)[32]) {
+  for (int i = 0; i < n_in; ++i) {
+    const float x = S[i * PPO_TS + lane];
+    const float4* w4 = reinterpret_cast<const float4*>(wt + i * 32);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const float4 w = w4[q];
+      z[4 * q + 0] = __builtin_fmaf(w.x, x, z[4 * q + 0]);
+      z[4 * q + 1] = __builtin_fmaf(w.y, x, z[4 * q + 1]);
+      z[4 * q + 2] = __builtin_fmaf(w.z, x, z[4 * q + 2]);
+      z[4 * q + 3] = __builtin_fmaf(w.w, x, z[4 * q + 3]);
+    }
+  }
+}
+
+// inputs [c0, c0 + 32) of the tile's observations -> S [input][sample]: coalesced rows of 32 floats; a sample beyond n,
+// or one that `keep` (a lane mask of the tile) leaves out, is staged as zeros
+__device__ __forceinline__ void stage_obs(const float* obs, long long s0, long long n, int D, int c0, unsigned long long keep,
+                                          float* S, int lane) {
+  const int i = lane & 31, col = c0 + i;
+#pragma unroll 4
+  for (int r = 0; r < 32; ++r) {
+    const int s = 2 * r + (lane >> 5);
+    const bool ok = s0 + s < n && col < D && ((keep >> s) & 1ull);
+    S[i * PPO_TS + s] = ok ? obs[size_t(s0 + s) * size_t(D) + size_t(col)] : 0.0f;
+  }
+}
+
+__device__ __forceinline__ void stage_units(const float (&h)[32], float* S, int lane) {
+#pragma unroll
+  for (int u = 0; u < 32; ++u) S[u * PPO_TS + lane] = h[u];
+}
+
+// THE forward pass of one network on one tile: h[l] = the lane's activations of hidden layer l (l < L), out = the head's 32
+// padded outputs.  Ends without a barrier: S holds the lane's own column.
+__device__ __forceinline__ void net_forward(const float* net, int D, int L, const float* obs, long long s0, long long n,
+                                            unsigned long long keep, float* S, int lane, float (&h)[3][32], float (&out)[32]) {
+  float z[32];
+#pragma unroll
+  for (int u = 0; u < 32; ++u) z[u] = net[32 * D + u];
+  for (int c0 = 0; c0 < D; c0 += 32) {
+    __syncthreads();                                       // (the last readers of S are done)
+    stage_obs(obs, s0, n, D, c0, keep, S, lane);
+    __syncthreads();
+    layer_acc(net + c0 * 32, S, D - c0 < 32 ? D - c0 : 32, lane, z);
+  }
+#pragma unroll
+  for (int u = 0; u < 32; ++u) h[0][u] = ppo_tanh(z[u]);
+#pragma unroll
+  for (int l = 1; l < 3; ++l) {
+    if (l < L) {
+      const float* q = net + ppo_layer_off(D, l);
+      stage_units(h[l - 1], S, lane);
+#pragma unroll
+      for (int u = 0; u < 32; ++u) z[u] = q[1024 + u];
+      layer_acc(q, S, 32, lane, z);
+#pragma unroll
+      for (int u = 0; u < 32; ++u) h[l][u] = ppo_tanh(z[u]);
+    }
+  }
+  const float* q = net + ppo_layer_off(D, L);
+  if (L == 1) stage_units(h[0], S, lane);
+  else if (L == 2) stage_units(h[1], S, lane);
+  else stage_units(h[2], S, lane);
+#pragma unroll
+  for (int u = 0; u < 32; ++u) out[u] = q[1024 + u];
+  layer_acc(q, S, 32, lane, out);
+}
+
+// log-probability of the lane's action row under the Gaussian head (train_vec.GaussianPolicy.logp_value): zc = the
+// standardised actions, inv_std = exp(-log_std) is not used: the division is the reference's
+__device__ __forceinline__ float ppo_logp(const float (&mu)[32], const float (&a)[32], const float* log_std, int A,
+                                          float (&zc)[32], float (&sd)[32]) {
+  float logp = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 32; ++c) {
+    zc[c] = 0.0f;
+    sd[c] = 1.0f;
+    if (c < A) {
+      const float ls = log_std[c];
+      sd[c] = expf(ls);
+      zc[c] = (a[c] - mu[c]) / sd[c];
+      logp += (-0.5f * (zc[c] * zc[c]) - ls) - 0.9189385f;
+    }
+  }
+  return logp;
+}
+
+// the lane's action row; returns false when it holds a NaN (an absent agent: the row is replaced by zeros)
+__device__ __forceinline__ bool ppo_load_act(const float* act, long long s, bool valid, int A, float (&a)[32]) {
+  bool present = true;
+#pragma unroll
+  for (int c = 0; c < 32; ++c) {
+    a[c] = 0.0f;
+    if (c < A && valid) a[c] = act[size_t(s) * size_t(A) + size_t(c)];
+    present = present && a[c] == a[c];
+  }
+  if (!present) {
+#pragma unroll
+    for (int c = 0; c < 32; ++c) a[c] = 0.0f;
+  }
+  return present;
+}
+
+__global__ __launch_bounds__(64) void k_ppo_eval(PpoView m, long long n, const float* __restrict__ obs,
+                                                 const float* __restrict__ act, float* __restrict__ logp_out,
+                                                 float* __restrict__ val_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* pnet = reinterpret_cast<float*>(smem);
+  float* vnet = pnet + ppo_net_lds(m.D, m.L);
+  float* S = vnet + ppo_net_lds(m.D, m.L);
+  const int lane = threadIdx.x;
+  if (act != nullptr) net_load(m.pw, m.D, m.L, m.A, pnet, lane);
+  net_load(m.vw, m.D, m.L, 1, vnet, lane);
+  __syncthreads();
+  const long long tiles = (n + PPO_TILE - 1) / PPO_TILE;
+  for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const long long s0 = t * PPO_TILE, s = s0 + lane;
+    const bool valid = s < n;
+    float h[3][32], out[32];
+    if (act != nullptr) {
+      float a[32], zc[32], sd[32];
+      ppo_load_act(act, s, valid, m.A, a);
+      net_forward(pnet, m.D, m.L, obs, s0, n, ~0ull, S, lane, h, out);
+      const float lp = ppo_logp(out, a, m.log_std, m.A, zc, sd);
+      if (valid) logp_out[s] = lp;
+    }
+    net_forward(vnet, m.D, m.L, obs, s0, n, ~0ull, S, lane, h, out);
+    if (valid) val_out[s] = out[0];
+  }
+}
+
+// one lane per replica: adv, ret [K, R] of rew, val, done [K, R] and last_val [R].  The float32 operation sequence is the
+// one CPU torch runs for train_vec.gae (no contraction: -ffp-contract=off), g = float32(gamma), gl = float32(gamma * lam)
+__global__ __launch_bounds__(256) void k_gae(int K, long long R, const float* __restrict__ rew, const float* __restrict__ val,
+                                             const float* __restrict__ last_val, const uint8_t* __restrict__ done, float g,
+                                             float gl, float* __restrict__ adv, float* __restrict__ ret) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= R) return;
+  float run = 0.0f, nxt = last_val[r];
+  for (int t = K - 1; t >= 0; --t) {
+    const size_t e = size_t(t) * size_t(R) + size_t(r);
+    const float live = done[e] == 0 ? 1.0f : 0.0f, v = val[e];
+    const float delta = (rew[e] + (g * nxt) * live) - v;
+    run = delta + ((gl * live) * run);
+    adv[e] = run;
+    ret[e] = run + v;
+    nxt = v;
+  }
+}
+
+// G[u][col0 + i] += sum_s T[s][u] S[i][s] for u < 32, i < n_in (rows u >= n_out and columns i >= n_in are not written): lane
+// = (input i = lane mod 32, units 16 (lane / 32) ..+16), s ascending
+__device__ __forceinline__ void grad_block(const float* T, const float* S, int n_in, int n_out, float* G, int ld, int col0,
+                                           int lane) {
+  const int i = lane & 31, u0 = (lane >> 5) * 16;
+  float acc[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) acc[k] = 0.0f;
+  for (int s = 0; s < PPO_TILE; ++s) {
+    const float x = S[i * PPO_TS + s];
+    const float4* d4 = reinterpret_cast<const float4*>(T + s * PPO_TT + u0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float4 d = d4[q];
+      acc[4 * q + 0] = __builtin_fmaf(d.x, x, acc[4 * q + 0]);
+      acc[4 * q + 1] = __builtin_fmaf(d.y, x, acc[4 * q + 1]);
+      acc[4 * q + 2] = __builtin_fmaf(d.z, x, acc[4 * q + 2]);
+      acc[4 * q + 3] = __builtin_fmaf(d.w, x, acc[4 * q + 3]);
+    }
+  }
+  if (i < n_in) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (u0 + k < n_out) G[(u0 + k) * ld + col0 + i] += acc[k];
+  }
+}
+
+// G[u] += sum_s T[s][u], s ascending, u < n_out <= 32
+__device__ __forceinline__ void col_sum(const float* T, int n_out, float* G, int lane) {
+  if (lane < n_out) {
+    float acc = 0.0f;
+    for (int s = 0; s < PPO_TILE; ++s) acc += T[s * PPO_TT + lane];
+    G[lane] += acc;
+  }
+}
+
+__device__ __forceinline__ void stage_dz(const float (&dz)[32], float* T, int lane) {
+  float4* t4 = reinterpret_cast<float4*>(T + lane * PPO_TT);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) t4[q] = make_float4(dz[4 * q], dz[4 * q + 1], dz[4 * q + 2], dz[4 * q + 3]);
+}
+
+// one layer of the backward pass (LYR = 1 .. L; the head when LYR == L): its weight and bias gradients from dz and its input
+// h[LYR-1], then dz of the layer below: (Wt dz) (1 - h^2), through the lane's own column of S
+template <int LYR>
+__device__ __forceinline__ void back_layer(const float* net, int D, int L, int n_out, float* S, float* T, int lane,
+                                           const float (&h)[3][32], float (&dz)[32], float* G) {
+  const float* q = net + ppo_layer_off(D, LYR);
+  const int rows = LYR < L ? 32 : n_out;
+  float* g = G + 32 * D + 32 + (LYR - 1) * 1056;
+  stage_units(h[LYR - 1], S, lane);
+  stage_dz(dz, T, lane);
+  __syncthreads();
+  grad_block(T, S, 32, rows, g, 32, 0, lane);
+  col_sum(T, rows, g + rows * 32, lane);
+  __syncthreads();
+  for (int i = 0; i < 32; ++i) {
+    const float4* w4 = reinterpret_cast<const float4*>(q + i * 32);
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float4 w = w4[k];
+      a0 = __builtin_fmaf(w.x, dz[4 * k + 0], a0);
+      a1 = __builtin_fmaf(w.y, dz[4 * k + 1], a1);
+      a2 = __builtin_fmaf(w.z, dz[4 * k + 2], a2);
+      a3 = __builtin_fmaf(w.w, dz[4 * k + 3], a3);
+    }
+    S[i * PPO_TS + lane] = (a0 + a1) + (a2 + a3);
+  }
+#pragma unroll
+  for (int u = 0; u < 32; ++u) dz[u] = S[u * PPO_TS + lane] * __builtin_fmaf(-h[LYR - 1][u], h[LYR - 1][u], 1.0f);
+}
+
+// the backward pass of one network on one tile: dz = the loss's gradient at the head's 32 padded outputs (zero for the
+// samples that do not count); G = the network's gradient in LDS (packed layout)
+__device__ __forceinline__ void net_backward(const float* net, int D, int L, int n_out, const float* obs, long long s0,
+                                             long long n, unsigned long long keep, float* S, float* T, int lane,
+                                             const float (&h)[3][32], float (&dz)[32], float* G) {
+  if (L >= 3) back_layer<3>(net, D, L, n_out, S, T, lane, h, dz, G);
+  if (L >= 2) back_layer<2>(net, D, L, n_out, S, T, lane, h, dz, G);
+  back_layer<1>(net, D, L, n_out, S, T, lane, h, dz, G);
+  // layer 0: the bias, then the weights by chunks of 32 inputs
+  stage_dz(dz, T, lane);
+  __syncthreads();
+  col_sum(T, 32, G + 32 * D, lane);
+  for (int c0 = 0; c0 < D; c0 += 32) {
+    __syncthreads();
+    stage_obs(obs, s0, n, D, c0, keep, S, lane);
+    __syncthreads();
+    grad_block(T, S, D - c0 < 32 ? D - c0 : 32, 32, G, D, c0, lane);
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const float* __restrict__ obs,
+                                                 const float* __restrict__ act, const float* __restrict__ logp_old,
+                                                 const double* __restrict__ adv, const float* __restrict__ ret,
+                                                 const double* __restrict__ mean_std, float lo, float hi, float vf_coef,
+                                                 float inv_n, float* __restrict__ work) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int D = m.D, A = m.A, L = m.L, P = ppo_params(D, A, L);
+  float* pnet = reinterpret_cast<float*>(smem);
+  float* vnet = pnet + ppo_net_lds(D, L);
+  float* S = vnet + ppo_net_lds(D, L);
+  float* T = S + 32 * PPO_TS;
+  float* G = T + PPO_TILE * PPO_TT;                          // [P + 2]: the gradient, then the two loss sums
+  const int lane = threadIdx.x;
+  net_load(m.pw, D, L, A, pnet, lane);
+  net_load(m.vw, D, L, 1, vnet, lane);
+  for (int e = lane; e < P + 2; e += 64) G[e] = 0.0f;
+  __syncthreads();
+  const int Pp = ppo_net_params(D, L, A);
+  const double mean = mean_std[0], scale = mean_std[1] + 1e-8;
+  const long long tiles = (n + PPO_TILE - 1) / PPO_TILE;
+  for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const long long s0 = t * PPO_TILE, s = s0 + lane;
+    const bool valid = s < n;
+    float a[32], h[3][32], out[32], dz[32];
+    const bool present = ppo_load_act(act, s, valid, A, a) && valid;
+    const unsigned long long keep = __ballot(present);
+    // ---- the policy: logp, the clipped surrogate, its gradient at the means and at log_std
+    net_forward(pnet, D, L, obs, s0, n, keep, S, lane, h, out);
+    float pg = 0.0f, vf = 0.0f;
+    {
+      float zc[32], sd[32];
+      const float logp = ppo_logp(out, a, m.log_std, A, zc, sd);
+      const float adv_n = present ? float((adv[s] - mean) / scale) : 0.0f;
+      const float ratio = present ? expf(logp - logp_old[s]) : 1.0f;
+      const float clamped = ratio < lo ? lo : ratio > hi ? hi : ratio;
+      const float s1 = ratio * adv_n, s2 = clamped * adv_n;
+      pg = s1 < s2 ? s1 : s2;
+      // d(-pg / n_total) / d logp: the unclipped branch is live inside [lo, hi] (both branches are it) or where it is the smaller
+      const bool live = present && ((ratio >= lo && ratio <= hi) || s1 < s2);
+      const float g_logp = live ? (-inv_n * adv_n) * ratio : 0.0f;
+      float gls[32];
+#pragma unroll
+      for (int c = 0; c < 32; ++c) {
+        dz[c] = c < A ? g_logp * (zc[c] / sd[c]) : 0.0f;
+        gls[c] = c < A ? g_logp * __builtin_fmaf(zc[c], zc[c], -1.0f) : 0.0f;
+      }
+      __syncthreads();
+      stage_dz(gls, T, lane);
+      __syncthreads();
+      col_sum(T, A, G + Pp, lane);
+      __syncthreads();
+    }
+    net_backward(pnet, D, L, A, obs, s0, n, keep, S, T, lane, h, dz, G);
+    // ---- the value network: (v - ret)^2
+    net_forward(vnet, D, L, obs, s0, n, keep, S, lane, h, out);
+    {
+      const float err = present ? out[0] - ret[s] : 0.0f;
+      vf = err * err;
+#pragma unroll
+      for (int c = 0; c < 32; ++c) dz[c] = 0.0f;
+      dz[0] = (vf_coef * inv_n) * (2.0f * err);
+    }
+    net_backward(vnet, D, L, 1, obs, s0, n, keep, S, T, lane, h, dz, G + Pp + A);
+    // ---- the two loss sums
+    T[lane * PPO_TT + 0] = pg;
+    T[lane * PPO_TT + 1] = vf;
+    __syncthreads();
+    col_sum(T, 2, G + P, lane);
+    __syncthreads();
+  }
+  float* w = work + size_t(blockIdx.x) * size_t(P + 2);
+  for (int e = lane; e < P + 2; e += 64) w[e] = G[e];
+}
+
+// the partial gradients of the G workgroups, summed in ascending order: grad [P], loss [2] (accumulate: added to what is there)
+__global__ __launch_bounds__(256) void k_ppo_reduce(const float* __restrict__ work, int G, int P, int accumulate,
+                                                    float* __restrict__ grad, float* __restrict__ loss) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= P + 2) return;
+  float acc = work[p];
+  for (int g = 1; g < G; ++g) acc += work[size_t(g) * size_t(P + 2) + size_t(p)];
+  float* dst = p < P ? grad + p : loss + (p - P);
+  *dst = accumulate ? *dst + acc : acc;
+}
+
+}  // namespace fs
+
+namespace fsim {
+
+// the kernels' dynamic LDS may exceed the default limit of a launch: raise it once per process and device
+inline int ppo_lds_limit() {
+  static thread_local int done_dev = -1;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (done_dev == dev) return FS_OK;
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_eval), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              fs::PPO_LDS_BYTES));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_grad), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              fs::PPO_LDS_BYTES));
+  done_dev = dev;
+  return FS_OK;
+}
+
+int launch_ppo_eval(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act, float* logp,
+                    float* val) {
+  if (int rc = ppo_lds_limit()) return rc;
+  const long long tiles = (n + fs::PPO_TILE - 1) / fs::PPO_TILE;
+  const int grid = int(tiles < 1024 ? tiles : 1024);
+  hipLaunchKernelGGL(fs::k_ppo_eval, dim3(grid), dim3(64), fs::ppo_eval_lds(m.D, m.L), stream, m, n, obs, act, logp, val);
+  HIP_TRY(hipGetLastError());
+  return FS_OK;
+}
+
+int launch_gae(hipStream_t stream, int K, long long R, const float* rew, const float* val, const float* last_val,
+               const uint8_t* done, float g, float gl, float* adv, float* ret) {
+  hipLaunchKernelGGL(fs::k_gae, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stream, K, R, rew, val, last_val, done, g, gl,
+                     adv, ret);
+  HIP_TRY(hipGetLastError());
+  return FS_OK;
+}
+
+int launch_ppo_grad(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act,
+                    const float* logp_old, const double* adv, const float* ret, const double* mean_std, float lo, float hi,
+                    float vf_coef, float inv_n, int accumulate, float* grad, float* loss, float* work) {
+  if (int rc = ppo_lds_limit()) return rc;
+  const int G = fs::ppo_groups(n, m.D, m.A, m.L), P = fs::ppo_params(m.D, m.A, m.L);
+  hipLaunchKernelGGL(fs::k_ppo_grad, dim3(G), dim3(64), fs::ppo_grad_lds(m.D, m.A, m.L), stream, m, n, obs, act, logp_old, adv,
+                     ret, mean_std, lo, hi, vf_coef, inv_n, work);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(fs::k_ppo_reduce, dim3((P + 2 + 255) / 256), dim3(256), 0, stream, work, G, P, accumulate, grad, loss);
+  HIP_TRY(hipGetLastError());
+  return FS_OK;
+}
+
+}  // namespace fsim
+#endif  // FS_PART_LEARN

@@ -2,11 +2,14 @@
 //   -DFS_PART_T=float|double  and  -DFS_PART_SEG=8|16|32|64  (one wave carries 64 / SEG replicas)
 //                              or  -DFS_PART_WIDE=2|4         (one workgroup of 2 / 4 waves per replica)
 //                              or  -DFS_PART_QUEUE=1          (the queue-order kernels of the open networks, float32)
+//                              or  -DFS_PART_LEARN=1          (the PPO update's kernels and their launchers, float32)
 // so that the step kernels of the pairs compile in parallel and an edit to one kernel family rebuilds few objects.
 #include "flowsim_launch.h"
+#include "flowsim_learn.h"       // (FS_PART_LEARN: defines k_ppo_eval, k_gae, k_ppo_grad and fsim::launch_ppo_* / launch_gae)
 
 namespace fsim {
-#if defined(FS_PART_QUEUE)
+#if defined(FS_PART_LEARN)
+#elif defined(FS_PART_QUEUE)
 template int Sim<FS_PART_T>::launch_queue(const StepArgs&);
 template int Sim<FS_PART_T>::launch_dropq(const StepArgs&);
 template int Sim<FS_PART_T>::launch_policy_queue(const fs::PolicyView&, int, int, float*, float*, float*, float*, uint8_t*);
@@ -33,6 +36,6 @@ template int Sim<FS_PART_T>::launch_policy_row16(const fs::PolicyView&, int, int
 template int Sim<FS_PART_T>::launch_obs_mixed(const StepArgs&);     // (one object: the kernel does not depend on the width)
 #endif
 #else
-#error "flowsim_part.hip: define FS_PART_T and FS_PART_SEG or FS_PART_WIDE"
+#error "flowsim_part.hip: define FS_PART_T and FS_PART_SEG, FS_PART_WIDE, FS_PART_QUEUE or FS_PART_LEARN"
 #endif
 }  // namespace fsim

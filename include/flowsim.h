@@ -435,7 +435,8 @@ int fs_add_vehicle(fs_handle h, int replica, int slot, int route, double x, doub
  * "+speed_mode" and / or "+noise", "k_rollout_idm", "k_ring_pair<Accel | PO | POMA | AccelMA>", "k_rollout_loop",
  * "k_rollout_loop<FULL>", "k_rollout_loop<AccelMA>", "k_rollout_loop<FULL,AccelMA>", "k_ring_policy", "k_loop_policy",
  * "k_ring_policy<POMA>", "k_loop_policy<AccelMA>", "k_merge_policy", "k_merge_policy<PO>", "k_merge_policy<PO,WIDE>"
- * (fs_policy_act_dev: "k_policy_act", "k_policy_act_vec", "k_policy_act_wide"),
+ * (fs_policy_act_dev: "k_policy_act", "k_policy_act_vec", "k_policy_act_wide"; the PPO update's entry points: "k_ppo_eval",
+ * "k_gae", "k_ppo_grad"),
  * "k_steps<FAST>", "k_steps<CSET>", "k_steps", "k_steps_ml", "k_steps_open" (also "<mixed>"), "k_steps_wide",
  * "k_merge_queue", "k_drop_queue", "k_obs_mixed"; "" before the first launch).  Diagnostics for tests and bench.py: which
  * configuration class a workload landed in (no reference counterpart).  The string is static.
@@ -539,6 +540,57 @@ int fs_policy_act_dev(fs_handle h, const fs_policy* pol, const float* obs_dev, f
  * logp_dev [K, R]), rew_dev [K, R], done_dev [K, R] (flags as in fs_rollout_dev). */
 int fs_policy_rollout_dev(fs_handle h, const fs_policy* pol, int num_steps, int reset_done, float* obs_dev,
                           float* act_dev, float* logp_dev, float* rew_dev, uint8_t* done_dev);
+
+/* ---- the PPO update on the device ---------------------------------------------
+ * What examples/train_vec.py ppo_update runs in torch between two rollouts -- the no_grad pass, generalised advantage
+ * estimation, and per epoch the forward pass, the clipped-surrogate loss and autograd's backward pass over a policy and a
+ * value network -- as three launches on the handle's stream (kernels: flow_amd/csrc/flowsim_learn.h).  The handle lends its
+ * device, its stream and fs_last_error; none of the calls touches the simulation state, none synchronises the host, so a
+ * sequence of them can be captured into a graph.  fs_last_kernel reports "k_ppo_eval", "k_gae", "k_ppo_grad".
+ * Model class (fs_policy's): 1..3 hidden layers of 32 tanh units on obs_dim = 1..160 inputs; the policy's head has act_dim
+ * = 1..32 outputs, the MEANS, next to a free log std [act_dim]; the value network is the same trunk with one output.
+ * Both weight buffers: float32, device, per layer W [out][in] row-major then b [out].  Everything else -- the head of
+ * 2 act_dim outputs (log_std_dev == NULL), another width or activation, obs_dim / act_dim out of range -- is refused with
+ * FS_ERR_UNSUPPORTED and a message that names fs_ppo_model. */
+typedef struct fs_ppo_model {
+  uint32_t struct_size;               /* sizeof(fs_ppo_model) */
+  int32_t obs_dim;                    /* D: 1..160 */
+  int32_t act_dim;                    /* A: 1..32 */
+  int32_t num_hidden;                 /* 1..3 hidden layers ... */
+  int32_t hidden_width;               /* ... of 32 units each */
+  int32_t activation;                 /* 0 = tanh */
+  const float* policy_weights_dev;    /* [32 D + 32][(num_hidden - 1) x 1056][33 A] */
+  const float* log_std_dev;           /* [A] */
+  const float* value_weights_dev;     /* [32 D + 32][(num_hidden - 1) x 1056][33] */
+} fs_ppo_model;
+
+/* Forward only: logp_dev [n] = log-probability of act_dev [n, A] under the policy at obs_dev [n, D] (the sum over the
+ * columns of -0.5 ((a - mean) / std)^2 - log_std - 0.9189385), val_dev [n] = the value network's output.  act_dev == NULL:
+ * values only (logp_dev is not written, the policy's pointers are not read).  A sample whose action row holds a NaN is an
+ * absent agent: its action is taken as 0 and its outputs mean nothing (ppo_update never uses them). */
+int fs_ppo_eval_dev(fs_handle h, const fs_ppo_model* model, int64_t n, const float* obs_dev, const float* act_dev,
+                    float* logp_dev, float* val_dev);
+/* Generalised advantage estimation over a fragment: rew, val, done, adv, ret [num_steps, num_cols], last_val [num_cols]; done
+ * is the flag byte of fs_rollout_dev, and the episode went on where it is 0.  Backwards over t, in float32, exactly
+ *   delta = (rew + (g * nxt) * live) - val;  run = delta + ((gl * live) * run);  adv = run;  ret = adv + val;  nxt = val
+ * with g = (float)gamma, gl = (float)(gamma * lam): bit for bit what train_vec.gae computes with torch on the CPU. */
+int fs_gae_dev(fs_handle h, int num_steps, int64_t num_cols, const float* rew_dev, const float* val_dev,
+               const float* last_val_dev, const uint8_t* done_dev, double gamma, double lam, float* adv_dev, float* ret_dev);
+/* Floats of work_dev that fs_ppo_grad_dev needs for n samples of this model (0: the model or n is not valid). */
+size_t fs_ppo_workspace(const fs_ppo_model* model, int64_t n);
+/* The gradient of ppo_update's loss over n samples, forward and backward in one launch plus a small reduction:
+ *   adv_n = (float)((adv - mean) / (std + 1e-8))           adv_dev [n] and mean_std_dev = {mean, std} are float64, device
+ *   ratio = exp(logp - logp_old);  pg = min(ratio adv_n, clamp(ratio, 1 - clip, 1 + clip) adv_n);  vf = (v - ret)^2
+ *   loss  = (-sum pg + vf_coef sum vf) inv_n_total
+ * grad_dev [P]: d loss / d parameter, packed as [policy weights][log_std A][value weights] (the layouts of fs_ppo_model);
+ * loss_dev [2] = {sum pg, sum vf}.  accumulate != 0 adds both to what the buffers hold (several shards of one update).
+ * Samples with a NaN in their action row are absent: they add nothing, and nothing of their rows reaches an output.
+ * The sum over samples has a fixed order that depends on (n, obs_dim, act_dim, num_hidden) alone -- one partial gradient per
+ * workgroup in work_dev, added in ascending order, no float atomics -- so the same inputs give the same bits on every call. */
+int fs_ppo_grad_dev(fs_handle h, const fs_ppo_model* model, int64_t n, const float* obs_dev, const float* act_dev,
+                    const float* logp_old_dev, const double* adv_dev, const float* ret_dev, const double* mean_std_dev,
+                    float clip, float vf_coef, float inv_n_total, int accumulate, float* grad_dev, float* loss_dev,
+                    float* work_dev, size_t work_floats);
 
 /* Append the CURRENT state of one replica to a CSV file (header `time,id,x,speed,lane_number` when the file is new;
  * one row per vehicle, id = slot index, free slots of open networks skipped): the trajectory ("emission") dump of
