@@ -43,6 +43,9 @@ def parse_args(args):
     parser.add_argument('--device_update', action='store_true',
                         help='device: run the PPO update on the library\'s kernels (fs_ppo_eval_dev, fs_gae_dev, '
                              'fs_ppo_grad_dev) instead of torch')
+    parser.add_argument('--device_adam', action='store_true',
+                        help='device: run the whole PPO update, Adam included, on the device with no host round trip '
+                             '(DeviceLearner.update); implies --device_update')
     return parser.parse_known_args(args)[0]
 
 
@@ -98,7 +101,7 @@ def train_device(submodule, flags, multiagent=False):
     fp['sim'].render = False
     return train_on_device(fp, replicas=flags.replicas, fragment=flags.rollout_size, iterations=flags.num_steps,
                            shared_agents=multiagent, fuse_action_vector=flags.fuse_policy and not multiagent,
-                           device_update=flags.device_update)
+                           device_update=flags.device_update or flags.device_adam, device_adam=flags.device_adam)
 
 
 def main(args):

@@ -156,7 +156,7 @@ def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None, learner=None):
 
 
 def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epochs=4, lr=3e-4, seed=0, log=print,
-                    rank=0, world=1, shared_agents=False, fuse_action_vector=False, device_update=False):
+                    rank=0, world=1, shared_agents=False, fuse_action_vector=False, device_update=False, device_adam=False):
     """PPO on R replicas of ``flow_params`` with everything in HBM: returns the mean step reward per iteration.
     ``world`` > 1: this process is rank ``rank`` of a data-parallel run (torch.distributed is initialised): it steps its
     block of the R replicas on its own GPU.
@@ -172,7 +172,12 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     kernels draw their samples from its Philox streams, the torch policy from torch.randn, so the two are different
     (equally valid) trajectories.
     ``device_update``: the PPO update runs on the library's kernels (DeviceLearner: fs_ppo_eval_dev, fs_gae_dev,
-    fs_ppo_grad_dev) instead of torch forward passes, the Python loop of gae() and autograd.  Off by default."""
+    fs_ppo_grad_dev) instead of torch forward passes, the Python loop of gae() and autograd.  Off by default.
+    ``device_adam``: the WHOLE update runs on the device (DeviceLearner.update: the statistics, the gradient and Adam
+    as well -- fs_adv_stats_dev, fs_adv_finish_dev, fs_ppo_grad_n_dev, fs_adam_dev), with no host round trip between two
+    rollouts; it implies the device update.  The learner is built first and the policy's parameters become views into
+    its packed weights before anything is captured; a fused or graph DevicePolicy runs on that same buffer, and no
+    torch.optim.Adam is built.  Off by default."""
     from flow_amd.dist import allreduce_sum, shard_range
     from flow_amd.envs import VecFlowEnv
     local = int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else 0
@@ -186,7 +191,13 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
         raise ValueError("shared_agents: the observation (%d) is not one block per action column (%d)" % (vec.obs_dim, vec.act_dim))
     k_ag = vec.obs_dim // n_ag
     pi = GaussianPolicy(k_ag if shared_agents else vec.obs_dim, 1 if shared_agents else vec.act_dim).to(dev)
-    opt = torch.optim.Adam(pi.parameters(), lr=lr)
+    learner, opt = None, None
+    if device_adam:
+        from flow_amd.utils.device_ppo import DeviceLearner
+        learner = DeviceLearner(vec, [pi.mu[0], pi.mu[2]], pi.mu[4], pi.log_std, [pi.value[0], pi.value[2]], pi.value[4])
+        learner.adopt_parameters()                             # (before the rollout graph captures the parameters' addresses)
+    else:
+        opt = torch.optim.Adam(pi.parameters(), lr=lr)
     # the rollout: ONE kernel per fragment where the library has the fused policy + step form for this experiment and
     # model (fs_policy_rollout_dev: rings / the figure eight with one RL vehicle, the multi-agent ring, figure eight and
     # merge -- its actions applied -- with their agents sharing the policy, 1..3 hidden layers of 32 tanh units);
@@ -201,6 +212,8 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
             fused = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=pi.log_std, seed=seed, act_dim=vec.act_dim)
         else:
             fused = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=pi.log_std, seed=seed)
+        if device_adam:
+            fused.share(learner)                               # the rollout kernels read the buffer the learner's Adam writes
         vec.reset()
         vec.policy_rollout(fused, 1, reset_done=True)           # (probe: raises NotImplementedError when not built)
         kernel = vec.sim.last_kernel
@@ -232,8 +245,9 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
         graph = vec.capture(fragment, policy=act_shared if shared_agents else pi.act, reset_done=True)
         graph.begin(vec.reset())
     K, R = fragment, hi - lo
-    learner = None
-    if device_update:
+    if device_adam:
+        log("update: on the device, Adam included (k_ppo_eval, k_gae, k_adv_stats, k_adv_finish, k_ppo_grad, k_adam)")
+    elif device_update:
         from flow_amd.utils.device_ppo import DeviceLearner
         learner = DeviceLearner(vec, [pi.mu[0], pi.mu[2]], pi.mu[4], pi.log_std, [pi.value[0], pi.value[2]], pi.value[4])
         log("update: on the device (k_ppo_eval, k_gae, k_ppo_grad)")
@@ -257,7 +271,10 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
                      rew.repeat_interleave(n_ag, dim=1), done.repeat_interleave(n_ag, dim=1))
         else:
             shard = (obs, act, rew, done)
-        ppo_update(pi, opt, [shard], epochs=epochs, learner=learner)
+        if device_adam:
+            learner.update([shard], epochs=epochs, lr=lr)
+        else:
+            ppo_update(pi, opt, [shard], epochs=epochs, learner=learner)
         tot = allreduce_sum(torch.stack([rew.double().sum(), torch.tensor(float(rew.numel()), dtype=torch.float64, device=dev),
                                          (done != 0).sum().double()]))
         mean_rew = float(tot[0] / tot[1])
@@ -302,6 +319,8 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel over this many GPUs of the node (one process each)")
     ap.add_argument("--device_update", action="store_true",
                     help="run the PPO update on the library's kernels (DeviceLearner) instead of torch")
+    ap.add_argument("--device_adam", action="store_true",
+                    help="run the whole PPO update, Adam included, on the device (DeviceLearner.update); implies --device_update")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     force = os.environ.get("TRAIN_FORCE_DIST") == "1"            # the N > 1 code path (RCCL init, all-reduces) with one rank
@@ -319,7 +338,7 @@ def main(argv=None):
     try:
         return train_on_device(ring_flow_params(args.horizon), replicas=args.replicas, fragment=args.fragment,
                                iterations=args.iterations, epochs=args.epochs, lr=args.lr, rank=rank, world=world,
-                               device_update=args.device_update)
+                               device_update=args.device_update or args.device_adam, device_adam=args.device_adam)
     finally:
         if world > 1 or force:
             import torch.distributed as dist

@@ -45,7 +45,8 @@ FS_EULER, FS_BALLISTIC = 0, 1
 EXPORTS = ["fs_create", "fs_destroy", "fs_last_error", "fs_abi_version", "fs_obs_dim", "fs_action_dim", "fs_set_stream",
            "fs_use_own_stream", "fs_sync", "fs_reset", "fs_reset_dev", "fs_step", "fs_step_dev", "fs_rollout_dev",
            "fs_get_state", "fs_set_state", "fs_add_vehicle", "fs_dump_trajectory", "fs_last_kernel", "fs_policy_act_dev",
-           "fs_policy_rollout_dev", "fs_ppo_eval_dev", "fs_gae_dev", "fs_ppo_workspace", "fs_ppo_grad_dev"]
+           "fs_policy_rollout_dev", "fs_ppo_eval_dev", "fs_gae_dev", "fs_ppo_workspace", "fs_ppo_grad_dev",
+           "fs_ppo_grad_n_dev", "fs_adv_stats_dev", "fs_adv_finish_dev", "fs_adam_dev"]
 
 
 class fs_vehicle_spec(C.Structure):
@@ -193,6 +194,15 @@ def load(path=None):
     lib.fs_ppo_grad_dev.argtypes = [h, C.POINTER(fs_ppo_model), C.c_int64, f32p, f32p, f32p, f64p, f32p, f64p, C.c_float,
                                     C.c_float, C.c_float, C.c_int, f32p, f32p, f32p, C.c_size_t]
     lib.fs_ppo_grad_dev.restype = C.c_int
+    lib.fs_ppo_grad_n_dev.argtypes = [h, C.POINTER(fs_ppo_model), C.c_int64, f32p, f32p, f32p, f64p, f32p, f64p, C.c_float,
+                                      C.c_float, C.c_int, f32p, f32p, f32p, C.c_size_t]
+    lib.fs_ppo_grad_n_dev.restype = C.c_int
+    lib.fs_adv_stats_dev.argtypes = [h, C.c_int64, f32p, f32p, C.c_int, C.c_int, f64p, f64p]
+    lib.fs_adv_stats_dev.restype = C.c_int
+    lib.fs_adv_finish_dev.argtypes = [h, f64p, f64p]
+    lib.fs_adv_finish_dev.restype = C.c_int
+    lib.fs_adam_dev.argtypes = [h, C.c_int64, f32p, f32p, f32p, f32p, f64p, C.c_double, C.c_double, C.c_double, C.c_double]
+    lib.fs_adam_dev.restype = C.c_int
     if lib.fs_abi_version() != FS_ABI_VERSION:
         raise FatalFlowError("libflowsim.so ABI %d != binding ABI %d" % (lib.fs_abi_version(), FS_ABI_VERSION))
     _libs[path] = lib

@@ -568,6 +568,60 @@ int fs_ppo_grad_dev(fs_handle h, const fs_ppo_model* model, int64_t n, const flo
                          grad_dev, loss_dev, work_dev);
 }
 
+int fs_ppo_grad_n_dev(fs_handle h, const fs_ppo_model* model, int64_t n, const float* obs_dev, const float* act_dev,
+                      const float* logp_old_dev, const double* adv_dev, const float* ret_dev, const double* mean_std_n_dev,
+                      float clip, float vf_coef, int accumulate, float* grad_dev, float* loss_dev, float* work_dev,
+                      size_t work_floats) {
+  if (!h || !obs_dev || !act_dev || !logp_old_dev || !adv_dev || !ret_dev || !mean_std_n_dev || !grad_dev || !loss_dev || !work_dev)
+    return fail(FS_ERR_INVALID, "fs_ppo_grad_n_dev: NULL argument");
+  if (n < 1 || n > INT32_MAX) return fail(FS_ERR_INVALID, "fs_ppo_grad_n_dev: n must be 1 .. 2^31 - 1");
+  fs::PpoView pv;
+  if (int rc = ppo_view("fs_ppo_grad_n_dev", model, true, &pv)) return rc;
+  if (work_floats < fs::ppo_work_floats(n, pv.D, pv.A, pv.L))
+    return fail(FS_ERR_INVALID, "fs_ppo_grad_n_dev: work_dev is smaller than fs_ppo_workspace(model, n) floats");
+  DeviceGuard guard(S(h)->cfg.device);
+  S(h)->last_kernel = "k_ppo_grad";
+  return launch_ppo_grad_n(S(h)->stream, pv, n, obs_dev, act_dev, logp_old_dev, adv_dev, ret_dev, mean_std_n_dev,
+                           float(1.0 - double(clip)), float(1.0 + double(clip)), vf_coef, accumulate ? 1 : 0, grad_dev,
+                           loss_dev, work_dev);
+}
+
+int fs_adv_stats_dev(fs_handle h, int64_t n, const float* adv_dev, const float* act_dev, int act_dim, int accumulate,
+                     double* adv64_dev, double* stats_dev) {
+  if (!h || !adv_dev || !adv64_dev || !stats_dev) return fail(FS_ERR_INVALID, "fs_adv_stats_dev: NULL argument");
+  if (n < 1 || n > INT32_MAX) return fail(FS_ERR_INVALID, "fs_adv_stats_dev: n must be 1 .. 2^31 - 1");
+  if (act_dev && (act_dim < 1 || act_dim > fs::PPO_MAX_ACT)) return fail(FS_ERR_INVALID, "fs_adv_stats_dev: act_dim must be 1..32");
+  SimBase* s = S(h);
+  DeviceGuard guard(s->cfg.device);
+  if (!s->d_adv_scratch) {
+    // the first call on a handle allocates (and synchronises the device once): make it outside a stream capture
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, fs::ADV_SCRATCH_BYTES));
+    s->allocs.push_back(p);
+    HIP_TRY(hipMemset(p, 0, fs::ADV_SCRATCH_BYTES));
+    HIP_TRY(hipDeviceSynchronize());
+    s->d_adv_scratch = static_cast<double*>(p);
+  }
+  s->last_kernel = "k_adv_stats";
+  return launch_adv_stats(s->stream, n, adv_dev, act_dev, act_dim, accumulate ? 1 : 0, adv64_dev, stats_dev, s->d_adv_scratch);
+}
+
+int fs_adv_finish_dev(fs_handle h, const double* stats_dev, double* mean_std_n_dev) {
+  if (!h || !stats_dev || !mean_std_n_dev) return fail(FS_ERR_INVALID, "fs_adv_finish_dev: NULL argument");
+  DeviceGuard guard(S(h)->cfg.device);
+  S(h)->last_kernel = "k_adv_finish";
+  return launch_adv_finish(S(h)->stream, stats_dev, mean_std_n_dev);
+}
+
+int fs_adam_dev(fs_handle h, int64_t num_params, float* weights_dev, const float* grad_dev, float* m_dev, float* v_dev,
+                double* state_dev, double lr, double beta1, double beta2, double eps) {
+  if (!h || !weights_dev || !grad_dev || !m_dev || !v_dev || !state_dev) return fail(FS_ERR_INVALID, "fs_adam_dev: NULL argument");
+  if (num_params < 1 || num_params > INT32_MAX) return fail(FS_ERR_INVALID, "fs_adam_dev: num_params must be 1 .. 2^31 - 1");
+  DeviceGuard guard(S(h)->cfg.device);
+  S(h)->last_kernel = "k_adam";
+  return launch_adam(S(h)->stream, int(num_params), weights_dev, grad_dev, m_dev, v_dev, state_dev, lr, beta1, beta2, eps);
+}
+
 const char* fs_last_kernel(fs_handle h) { return h ? reinterpret_cast<SimBase*>(h)->last_kernel : ""; }
 
 int fs_dump_trajectory(fs_handle h, int replica, const char* csv_path) {

@@ -1,10 +1,14 @@
 // flowsim_learn.h -- the PPO update on the device: what examples/train_vec.py ppo_update does in torch between two
-// rollouts, as three kernels (fs_ppo_eval_dev, fs_gae_dev, fs_ppo_grad_dev: include/flowsim.h).
+// rollouts, as kernels (fs_ppo_eval_dev, fs_gae_dev, fs_adv_stats_dev, fs_adv_finish_dev, fs_ppo_grad_dev / fs_ppo_grad_n_dev,
+// fs_adam_dev: include/flowsim.h).
 //
 //   k_ppo_eval   forward only: logp [n] and val [n] of n samples (the no_grad pass; act == NULL: values alone)
 //   k_gae        the reverse recurrence of train_vec.gae, one lane per replica, float32 bits of CPU torch
 //   k_ppo_grad   forward, PPO loss and backward of both networks in ONE launch: one partial gradient per workgroup,
 //   k_ppo_reduce ... summed over the workgroups in ascending order (no float atomics: the same inputs give the same bits)
+//   k_adv_stats  the float64 advantage statistics {sum adv, sum adv^2, count} of the present rows and the float64 copy of adv
+//   k_adv_finish {mean, std, n} of the three sums (one thread; the data-parallel all-reduce of the sums comes before it)
+//   k_adam       torch's Adam on the packed buffers, its step count and the powers of the betas in device memory
 //
 // Model class (DevicePolicy's): 1..3 hidden layers of 32 tanh units on 1..160 inputs, a head of A <= 32 means with a free
 // log_std [A]; the value network is the same trunk with one output.  Packed weights per network: per layer W [out][in]
@@ -64,6 +68,15 @@ __host__ __device__ constexpr size_t ppo_work_floats(long long n, int D, int A, 
   return size_t(ppo_groups(n, D, A, L)) * size_t(ppo_params(D, A, L) + 2);
 }
 
+// k_adv_stats: workgroups (a function of n alone) and the handle's scratch [ticket][G x 3 partial sums]
+constexpr int ADV_THREADS = 256, ADV_MAX_GROUPS = 512;
+constexpr size_t ADV_SCRATCH_BYTES = sizeof(double) * (1 + 3 * ADV_MAX_GROUPS);      // [ticket][G x 3 partial sums]
+
+__host__ __device__ constexpr int adv_groups(long long n) {
+  const long long g = (n + 4 * ADV_THREADS - 1) / (4 * ADV_THREADS);                 // four rows per lane before G saturates
+  return int(g < 1 ? 1 : g > ADV_MAX_GROUPS ? ADV_MAX_GROUPS : g);
+}
+
 }  // namespace fs
 
 namespace fsim {
@@ -75,6 +88,16 @@ int launch_gae(hipStream_t stream, int K, long long R, const float* rew, const f
 int launch_ppo_grad(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act,
                     const float* logp_old, const double* adv, const float* ret, const double* mean_std, float lo, float hi,
                     float vf_coef, float inv_n, int accumulate, float* grad, float* loss, float* work);
+// (mean_std_n [3] = {mean, std, n}: the kernel takes inv_n = float(1.0 / n) from the device)
+int launch_ppo_grad_n(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act,
+                      const float* logp_old, const double* adv, const float* ret, const double* mean_std_n, float lo, float hi,
+                      float vf_coef, int accumulate, float* grad, float* loss, float* work);
+// (scratch: fs::ADV_SCRATCH_BYTES of device memory, zero before its first use: the handle owns it)
+int launch_adv_stats(hipStream_t stream, long long n, const float* adv, const float* act, int A, int accumulate, double* adv64,
+                     double* stats, double* scratch);
+int launch_adv_finish(hipStream_t stream, const double* stats, double* mean_std_n);
+int launch_adam(hipStream_t stream, int P, float* w, const float* g, float* m, float* v, double* state, double lr, double beta1,
+                double beta2, double eps);
 }  // namespace fsim
 
 #ifdef FS_PART_LEARN
@@ -349,11 +372,15 @@ __device__ __forceinline__ void net_backward(const float* net, int D, int L, int
   __syncthreads();
 }
 
+// N_DEV: mean_std is {mean, std, n} and the sample count of the whole update comes from it, inv_n = float(1.0 / n) -- the
+// bits a host passes as inv_n for the same n -- so that nothing between the statistics and the gradient needs the host
+template <bool N_DEV>
 __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const float* __restrict__ obs,
                                                  const float* __restrict__ act, const float* __restrict__ logp_old,
                                                  const double* __restrict__ adv, const float* __restrict__ ret,
                                                  const double* __restrict__ mean_std, float lo, float hi, float vf_coef,
                                                  float inv_n, float* __restrict__ work) {
+  if (N_DEV) inv_n = float(1.0 / mean_std[2]);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int D = m.D, A = m.A, L = m.L, P = ppo_params(D, A, L);
   float* pnet = reinterpret_cast<float*>(smem);
@@ -434,6 +461,125 @@ __global__ __launch_bounds__(256) void k_ppo_reduce(const float* __restrict__ wo
   *dst = accumulate ? *dst + acc : acc;
 }
 
+// ---- the advantage statistics.  G = adv_groups(n) workgroups of ADV_THREADS lanes; lane t of workgroup b adds its rows
+// b ADV_THREADS + t + k G ADV_THREADS, k ascending, in double; a workgroup's lanes meet in a binary tree over LDS (lane t +=
+// lane t + half, half = 128 .. 1) and lane 0 writes the workgroup's three partial sums to the handle's scratch.  The
+// workgroup that arrives last (an integer ticket; agent-scope release before it, acquire after) adds the G partials -- lane
+// t those of workgroups t and t + ADV_THREADS, then the same tree -- so the order of every sum depends on n alone, whichever
+// workgroup that is, and resets the ticket for the next launch.  A row whose action row holds a NaN is absent: it is selected out of the three sums and its
+// adv64 is 0, so nothing it holds reaches an output.
+__global__ __launch_bounds__(ADV_THREADS) void k_adv_stats(long long n, const float* __restrict__ adv,
+                                                           const float* __restrict__ act, int A, int accumulate,
+                                                           double* __restrict__ adv64, double* __restrict__ stats,
+                                                           double* scratch) {
+  __shared__ double red[3][ADV_THREADS];
+  const int t = threadIdx.x, G = gridDim.x;
+  double s0 = 0.0, s1 = 0.0, cnt = 0.0;
+  for (long long i = (long long)blockIdx.x * ADV_THREADS + t; i < n; i += (long long)G * ADV_THREADS) {
+    bool present = true;
+    if (act != nullptr) {
+      const float* row = act + size_t(i) * size_t(A);
+      for (int c = 0; c < A; ++c) present = present && row[c] == row[c];
+    }
+    const double a = present ? double(adv[i]) : 0.0;
+    adv64[i] = a;
+    s0 += a;
+    s1 += a * a;
+    cnt += present ? 1.0 : 0.0;
+  }
+  red[0][t] = s0;
+  red[1][t] = s1;
+  red[2][t] = cnt;
+  __syncthreads();
+  for (int half = ADV_THREADS / 2; half >= 1; half >>= 1) {
+    if (t < half) {
+      red[0][t] += red[0][t + half];
+      red[1][t] += red[1][t + half];
+      red[2][t] += red[2][t + half];
+    }
+    __syncthreads();
+  }
+  // lane 0 publishes the partial sums and draws a ticket; the workgroup that draws the last one adds all of them up
+  unsigned* ticket = reinterpret_cast<unsigned*>(scratch);
+  double* part = scratch + 1;
+  if (t == 0) {
+    for (int k = 0; k < 3; ++k) part[3 * blockIdx.x + k] = red[k][0];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool last = drawn == unsigned(G - 1);
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    red[0][1] = last ? 1.0 : 0.0;                            // ("I am last", through the array that is there)
+  }
+  __syncthreads();
+  if (red[0][1] == 0.0) return;
+  __syncthreads();                                           // (every lane has read the flag: red is free again)
+  // lane t adds the partial sums of workgroups t, t + ADV_THREADS (G <= 2 ADV_THREADS), then the same tree
+  s0 = s1 = cnt = 0.0;
+  for (int g = t; g < G; g += ADV_THREADS) {
+    s0 += part[3 * g + 0];
+    s1 += part[3 * g + 1];
+    cnt += part[3 * g + 2];
+  }
+  red[0][t] = s0;
+  red[1][t] = s1;
+  red[2][t] = cnt;
+  __syncthreads();
+  for (int half = ADV_THREADS / 2; half >= 1; half >>= 1) {
+    if (t < half) {
+      red[0][t] += red[0][t + half];
+      red[1][t] += red[1][t + half];
+      red[2][t] += red[2][t + half];
+    }
+    __syncthreads();
+  }
+  if (t < 3) stats[t] = accumulate ? stats[t] + red[t][0] : red[t][0];
+  if (t == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ppo_update's formula, in double (division and square root are correctly rounded; nothing contracts): a NaN variance
+// (n = 1) stays a NaN, as torch's clamp_min leaves it
+__global__ __launch_bounds__(64) void k_adv_finish(const double* __restrict__ stats, double* __restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const double s0 = stats[0], s1 = stats[1], n = stats[2];
+  const double mean = s0 / n;
+  const double var = (s1 - (n * mean) * mean) / (n - 1.0);
+  out[0] = mean;
+  out[1] = sqrt(var < 0.0 ? 0.0 : var);
+  out[2] = n;
+}
+
+// ---- Adam (torch.optim.Adam without weight decay, amsgrad or maximize) on the packed buffers.  state = {t, beta1^t,
+// beta2^t} in double, on the device, so that a graph replay advances it.  ONE workgroup: every lane reads the state, the
+// barrier follows, then lane 0 alone writes it -- no lane of another workgroup exists that could read the new state for the
+// old step.  P is at most ppo_params(160, 32, 3) = 15 649: sixteen elements per lane.
+constexpr int ADAM_THREADS = 1024;
+
+__global__ __launch_bounds__(ADAM_THREADS) void k_adam(int P, float* __restrict__ w, const float* __restrict__ g,
+                                                        float* __restrict__ m, float* __restrict__ v, double* state, double lr,
+                                                        double beta1, double beta2, double eps) {
+  const double t = state[0] + 1.0, p1 = state[1] * beta1, p2 = state[2] * beta2;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    state[0] = t;
+    state[1] = p1;
+    state[2] = p2;
+  }
+  const float step = float(lr / (1.0 - p1)), rs = float(sqrt(1.0 - p2));
+  const float c1 = float(1.0 - beta1), b2 = float(beta2), c2 = float(1.0 - beta2), e = float(eps);
+  for (int i = threadIdx.x; i < P; i += ADAM_THREADS) {
+    const float gi = g[i];
+    const float mi = m[i] + (gi - m[i]) * c1;
+    const float vi = v[i] * b2 + (gi * gi) * c2;
+    m[i] = mi;
+    v[i] = vi;
+    w[i] = w[i] - step * (mi / (sqrtf(vi) / rs + e));
+  }
+}
+
 }  // namespace fs
 
 namespace fsim {
@@ -446,7 +592,9 @@ inline int ppo_lds_limit() {
   if (done_dev == dev) return FS_OK;
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_eval), hipFuncAttributeMaxDynamicSharedMemorySize,
                               fs::PPO_LDS_BYTES));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_grad), hipFuncAttributeMaxDynamicSharedMemorySize,
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_grad<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              fs::PPO_LDS_BYTES));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_grad<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               fs::PPO_LDS_BYTES));
   done_dev = dev;
   return FS_OK;
@@ -470,15 +618,52 @@ int launch_gae(hipStream_t stream, int K, long long R, const float* rew, const f
   return FS_OK;
 }
 
+// the two forms of the gradient launch: inv_n from the host, or n from the device (mean_std [3])
+template <bool N_DEV>
+static int launch_ppo_grad_any(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act,
+                               const float* logp_old, const double* adv, const float* ret, const double* mean_std, float lo,
+                               float hi, float vf_coef, float inv_n, int accumulate, float* grad, float* loss, float* work) {
+  if (int rc = ppo_lds_limit()) return rc;
+  const int G = fs::ppo_groups(n, m.D, m.A, m.L), P = fs::ppo_params(m.D, m.A, m.L);
+  hipLaunchKernelGGL(fs::k_ppo_grad<N_DEV>, dim3(G), dim3(64), fs::ppo_grad_lds(m.D, m.A, m.L), stream, m, n, obs, act,
+                     logp_old, adv, ret, mean_std, lo, hi, vf_coef, inv_n, work);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(fs::k_ppo_reduce, dim3((P + 2 + 255) / 256), dim3(256), 0, stream, work, G, P, accumulate, grad, loss);
+  HIP_TRY(hipGetLastError());
+  return FS_OK;
+}
+
 int launch_ppo_grad(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act,
                     const float* logp_old, const double* adv, const float* ret, const double* mean_std, float lo, float hi,
                     float vf_coef, float inv_n, int accumulate, float* grad, float* loss, float* work) {
-  if (int rc = ppo_lds_limit()) return rc;
-  const int G = fs::ppo_groups(n, m.D, m.A, m.L), P = fs::ppo_params(m.D, m.A, m.L);
-  hipLaunchKernelGGL(fs::k_ppo_grad, dim3(G), dim3(64), fs::ppo_grad_lds(m.D, m.A, m.L), stream, m, n, obs, act, logp_old, adv,
-                     ret, mean_std, lo, hi, vf_coef, inv_n, work);
+  return launch_ppo_grad_any<false>(stream, m, n, obs, act, logp_old, adv, ret, mean_std, lo, hi, vf_coef, inv_n, accumulate,
+                                    grad, loss, work);
+}
+
+int launch_ppo_grad_n(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act,
+                      const float* logp_old, const double* adv, const float* ret, const double* mean_std_n, float lo, float hi,
+                      float vf_coef, int accumulate, float* grad, float* loss, float* work) {
+  return launch_ppo_grad_any<true>(stream, m, n, obs, act, logp_old, adv, ret, mean_std_n, lo, hi, vf_coef, 0.0f, accumulate,
+                                   grad, loss, work);
+}
+
+int launch_adv_stats(hipStream_t stream, long long n, const float* adv, const float* act, int A, int accumulate, double* adv64,
+                     double* stats, double* scratch) {
+  hipLaunchKernelGGL(fs::k_adv_stats, dim3(fs::adv_groups(n)), dim3(fs::ADV_THREADS), 0, stream, n, adv, act, A, accumulate,
+                     adv64, stats, scratch);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(fs::k_ppo_reduce, dim3((P + 2 + 255) / 256), dim3(256), 0, stream, work, G, P, accumulate, grad, loss);
+  return FS_OK;
+}
+
+int launch_adv_finish(hipStream_t stream, const double* stats, double* mean_std_n) {
+  hipLaunchKernelGGL(fs::k_adv_finish, dim3(1), dim3(64), 0, stream, stats, mean_std_n);
+  HIP_TRY(hipGetLastError());
+  return FS_OK;
+}
+
+int launch_adam(hipStream_t stream, int P, float* w, const float* g, float* m, float* v, double* state, double lr, double beta1,
+                double beta2, double eps) {
+  hipLaunchKernelGGL(fs::k_adam, dim3(1), dim3(fs::ADAM_THREADS), 0, stream, P, w, g, m, v, state, lr, beta1, beta2, eps);
   HIP_TRY(hipGetLastError());
   return FS_OK;
 }

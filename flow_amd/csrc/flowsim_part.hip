@@ -5,7 +5,7 @@
 //                              or  -DFS_PART_LEARN=1          (the PPO update's kernels and their launchers, float32)
 // so that the step kernels of the pairs compile in parallel and an edit to one kernel family rebuilds few objects.
 #include "flowsim_launch.h"
-#include "flowsim_learn.h"       // (FS_PART_LEARN: defines k_ppo_eval, k_gae, k_ppo_grad and fsim::launch_ppo_* / launch_gae)
+#include "flowsim_learn.h"       // (FS_PART_LEARN: defines k_ppo_eval, k_gae, k_ppo_grad, k_adv_stats, k_adv_finish, k_adam and their fsim::launch_*)
 
 namespace fsim {
 #if defined(FS_PART_LEARN)

@@ -13,7 +13,8 @@ from flow_amd import _lib as L
 class DevicePolicy(object):
     """``hidden``: the ``nn.Linear`` layers of the trunk (1..3, 32 units each, tanh between them); ``head``: the output
     ``nn.Linear`` (2 outputs = mean and log std; 1 output with ``log_std`` a 1-element parameter / tensor).  ``sync()``
-    copies the current parameter values into the packed device buffer (call it after every optimiser step).
+    copies the current parameter values into the packed device buffer (call it after every optimiser step);
+    ``share(learner)`` runs the policy on a DeviceLearner's packed weights instead, with nothing to copy.
 
     ``act_dim`` > 1: ONE network with an action vector (MergePOEnv, ``FlowSim.policy_action_dim``): ``head`` has
     ``2 * act_dim`` outputs -- the means, then the log stds: RLlib's DiagGaussian order -- or ``act_dim`` outputs with
@@ -41,7 +42,33 @@ class DevicePolicy(object):
                                   log_std_dev=self.ls.data_ptr() if self.ls is not None else None, seed=int(seed))
         self.sync()
 
+    def share(self, learner):
+        """Run on the storage of ``learner`` (a ``flow_amd.utils.device_ppo.DeviceLearner`` over the same network): the
+        struct's ``weights_dev`` and ``log_std_dev`` point into ``learner.weights`` -- [policy weights][log_std A][value
+        weights], the policy's part in this class's own layout -- so the rollout kernels read the very buffer the
+        learner's Adam writes, and ``sync()`` has nothing to do.  Only the free-``log_std`` form can share, and the layer
+        shapes must be the learner's.  Share before a graph captures the policy (``vec.capture``)."""
+        if self.ls is None:
+            raise NotImplementedError("DevicePolicy.share: the head of 2 x act_dim outputs (no free log_std) cannot share a "
+                                      "DeviceLearner's storage: its packed weights hold the act_dim means next to log_std")
+        mine = (self.hidden[0].in_features, len(self.hidden), self.act_dim)
+        theirs = (learner.D, learner.num_hidden, learner.A)
+        if mine != theirs:
+            raise NotImplementedError("DevicePolicy.share: the policy has (obs_dim, hidden layers, act_dim) = %s, the "
+                                      "learner %s: the packed layouts differ" % (mine, theirs))
+        if learner.weights.device != self.buf.device or learner.n_policy != self.buf.numel():
+            raise ValueError("DevicePolicy.share: the learner's weights live on %s with %d policy values; the policy has %d on %s"
+                             % (learner.weights.device, learner.n_policy, self.buf.numel(), self.buf.device))
+        self.shared = learner
+        self.buf = learner.weights[:learner.n_policy]
+        self.ls = learner.weights[learner.n_policy:learner.n_policy + self.act_dim]
+        self.struct.weights_dev = self.buf.data_ptr()
+        self.struct.log_std_dev = self.ls.data_ptr()
+        return self
+
     def sync(self):
+        if getattr(self, "shared", None) is not None:        # (the learner's buffer is the policy's: nothing to repack)
+            return
         torch = self.torch
         with torch.no_grad():
             parts = []

@@ -5,6 +5,12 @@ steps), then per epoch a forward pass, the clipped-surrogate loss and autograd's
 points of the library (include/flowsim.h ``fs_ppo_eval_dev``, ``fs_gae_dev``, ``fs_ppo_grad_dev``; kernels:
 flow_amd/csrc/flowsim_learn.h).  The optimiser stays torch's: every parameter's ``.grad`` is a VIEW into the packed
 gradient buffer the kernel writes, so ``allreduce_gradients`` and ``opt.step()`` work on it unchanged.
+
+``update()`` is the whole of ``ppo_update`` on the learner's stream: the float64 advantage statistics
+(``fs_adv_stats_dev``, ``fs_adv_finish_dev``), the gradient with its sample count read on the device
+(``fs_ppo_grad_n_dev``) and Adam on the packed buffers (``fs_adam_dev``) join the three kernels above, so nothing between
+two rollouts needs the host: a fixed sequence of launches that can be captured into a graph.  After
+``adopt_parameters()`` the module's parameters ARE views into the packed weights, the counterpart of ``attach_grads()``.
 """
 import ctypes as C
 
@@ -78,6 +84,9 @@ class DeviceLearner(object):
         self.loss = torch.zeros(2, dtype=torch.float32, device=dev)              # {sum pg, sum vf} of the last gradients()
         self._mean_std = torch.zeros(2, dtype=torch.float64, device=dev)
         self._work, self._bound_stream = None, None
+        self._adopted, self._cache = False, {}
+        self.m = self.v = self.state = None                                      # Adam's buffers (adam_step)
+        self._stats = self._mean_std_n = None
         off = self.n_policy
         self.struct = L.fs_ppo_model(struct_size=C.sizeof(L.fs_ppo_model), obs_dim=D, act_dim=A, num_hidden=self.num_hidden,
                                      hidden_width=WIDTH, activation=0, policy_weights_dev=self.weights.data_ptr(),
@@ -86,6 +95,8 @@ class DeviceLearner(object):
         self.sync()
 
     def sync(self):
+        if self._adopted:                                    # (the parameters are views into self.weights: nothing to move)
+            return
         torch = self.torch
         with torch.no_grad():
             self.weights.copy_(torch.cat([p.detach().reshape(-1) for p in self.params]))
@@ -97,6 +108,19 @@ class DeviceLearner(object):
             n = p.numel()
             p.grad = self.grad[off:off + n].view_as(p)
             off += n
+
+    def adopt_parameters(self):
+        """Every parameter's ``.data`` becomes its view into ``self.weights`` (no copies afterwards: ``sync()`` has nothing
+        to move, and a torch module over the same parameters reads what the kernels write).  Call it before anything
+        captures the module's addresses (``vec.capture`` around the torch policy): a graph captured earlier goes on
+        reading the old storage."""
+        self.sync()
+        off = 0
+        for p in self.params:
+            n = p.numel()
+            p.data = self.weights[off:off + n].view_as(p)
+            off += n
+        self._adopted = True
 
     def _bind(self):
         """The launches go on torch's current stream, where the tensors they read and write are produced and used."""
@@ -169,4 +193,141 @@ class DeviceLearner(object):
                                              float(clip), float(vf_coef), 1.0 / float(n if n_total is None else n_total),
                                              int(bool(accumulate)), self.grad.data_ptr(), self.loss.data_ptr(),
                                              self._work.data_ptr(), self._work.numel()), self.sim.lib)
+        return self.loss
+
+    # ---- the rest of ppo_update on the device: statistics, the gradient with n on the device, Adam, the whole update
+    def _f64(self, n):
+        return self.torch.zeros(n, dtype=self.torch.float64, device=self.device)
+
+    def adv_stats(self, adv, act=None, accumulate=False, adv64=None, stats=None):
+        """``(adv64 [n], stats [3])``: the float64 copy of the float32 advantages ``adv`` (any shape of n elements) and
+        ``{sum adv, sum adv^2, count}`` over the present rows -- a row of ``act [n, A]`` with a NaN is absent; its adv64
+        is 0.  ``accumulate=True`` adds the sums to what ``stats`` holds."""
+        torch = self.torch
+        n = int(adv.numel())
+        adv = self._f32(adv.reshape(-1), (n,), "adv")
+        act = None if act is None else self._f32(act, (n, int(act.shape[-1])), "act")
+        adv64 = torch.empty(n, dtype=torch.float64, device=self.device) if adv64 is None else adv64
+        stats = self._f64(3) if stats is None else stats
+        self._bind()
+        self._adv_stats(n, adv, act, accumulate, adv64, stats)
+        return adv64, stats
+
+    def _adv_stats(self, n, adv, act, accumulate, adv64, stats):
+        L.check(self.sim.lib.fs_adv_stats_dev(self.sim._h, n, adv.data_ptr(), act.data_ptr() if act is not None else None,
+                                              int(act.shape[-1]) if act is not None else 0, int(bool(accumulate)),
+                                              adv64.data_ptr(), stats.data_ptr()), self.sim.lib)
+
+    def adv_finish(self, stats, out=None):
+        """``{mean, std, n}`` (float64 [3]) of ``stats = {sum, sum of squares, count}``: ppo_update's formula."""
+        out = self._f64(3) if out is None else out
+        self._bind()
+        L.check(self.sim.lib.fs_adv_finish_dev(self.sim._h, stats.data_ptr(), out.data_ptr()), self.sim.lib)
+        return out
+
+    def _workspace(self, n):
+        need = int(self.sim.lib.fs_ppo_workspace(C.byref(self.struct), n))
+        if self._work is None or self._work.numel() < need:
+            self._work = self.torch.empty(need, dtype=self.torch.float32, device=self.device)
+        return self._work
+
+    def gradients_n(self, obs, act, logp_old, adv, ret, mean_std_n, clip=0.2, vf_coef=0.5, accumulate=False):
+        """``gradients()`` with the statistics and the sample count of the whole update on the device: ``mean_std_n`` is
+        the float64 ``{mean, std, n}`` of ``adv_finish``; no host value of ``n`` is needed."""
+        torch = self.torch
+        n = int(obs.shape[0])
+        obs, act = self._f32(obs, (n, self.D), "obs"), self._f32(act, (n, self.A), "act")
+        logp_old, ret = self._f32(logp_old, (n,), "logp_old"), self._f32(ret, (n,), "ret")
+        if adv.dtype != torch.float64 or tuple(adv.shape) != (n,) or adv.device != self.device:
+            raise ValueError("DeviceLearner: adv must be a float64 tensor of shape (%d,) on %s" % (n, self.device))
+        if mean_std_n.dtype != torch.float64 or mean_std_n.numel() != 3 or mean_std_n.device != self.device:
+            raise ValueError("DeviceLearner: mean_std_n must be a float64 tensor of 3 elements on %s" % self.device)
+        work = self._workspace(n)
+        self._bind()
+        self._grad_n(n, obs, act, logp_old, adv.contiguous(), ret, mean_std_n, clip, vf_coef, accumulate, work)
+        return self.loss
+
+    def _grad_n(self, n, obs, act, logp_old, adv64, ret, mean_std_n, clip, vf_coef, accumulate, work):
+        L.check(self.sim.lib.fs_ppo_grad_n_dev(self.sim._h, C.byref(self.struct), n, obs.data_ptr(), act.data_ptr(),
+                                               logp_old.data_ptr(), adv64.data_ptr(), ret.data_ptr(), mean_std_n.data_ptr(),
+                                               float(clip), float(vf_coef), int(bool(accumulate)), self.grad.data_ptr(),
+                                               self.loss.data_ptr(), work.data_ptr(), work.numel()), self.sim.lib)
+
+    def _adam_buffers(self):
+        torch = self.torch
+        if self.state is None:
+            self.m, self.v = torch.zeros_like(self.weights), torch.zeros_like(self.weights)
+            self.state = torch.tensor([0.0, 1.0, 1.0], dtype=torch.float64, device=self.device)
+
+    def adam_step(self, lr=3e-4, betas=(0.9, 0.999), eps=1e-8):
+        """One step of torch's Adam (no weight decay, amsgrad or maximize) on ``self.weights`` with ``self.grad``
+        (``fs_adam_dev``).  The learner owns ``m``, ``v`` [P] and ``state`` = float64 ``{t, beta1^t, beta2^t}``, all on the
+        device.  The module's parameters see the step after ``adopt_parameters()``."""
+        self._adam_buffers()
+        self._bind()
+        L.check(self.sim.lib.fs_adam_dev(self.sim._h, self.P, self.weights.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(),
+                                         self.v.data_ptr(), self.state.data_ptr(), float(lr), float(betas[0]), float(betas[1]),
+                                         float(eps)), self.sim.lib)
+
+    def _shard_buffers(self, j, K, R):
+        """Intermediates of shard ``j`` of ``update()``, allocated once per shape."""
+        torch = self.torch
+        buf = self._cache.get((j, K, R))
+        if buf is None:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            buf = dict(logp=torch.empty(K * R, **f32), val=torch.empty(K * R, **f32), last_val=torch.empty(R, **f32),
+                       adv=torch.empty(K, R, **f32), ret=torch.empty(K, R, **f32),
+                       adv64=torch.empty(K * R, dtype=torch.float64, device=self.device))
+            self._cache[(j, K, R)] = buf
+        return buf
+
+    def update(self, shards, epochs=4, clip=0.2, vf_coef=0.5, gamma=0.999, lam=0.97, lr=3e-4, betas=(0.9, 0.999), eps=1e-8,
+               group=None):
+        """One PPO update over ``shards`` = [(obs [K+1, R, D], act [K, R(, A)], rew [K, R], done [K, R] uint8)], the whole of
+        train_vec.ppo_update on the learner's stream: per shard eval (two launches), gae and the statistics; the
+        all-reduce of the three sums (in a data-parallel run); finish; per epoch the gradient over the shards (kernel and
+        reduction), the all-reduce of the packed gradient, Adam.  One shard and 4 epochs: 2 + 1 + 1 + 1 + 4 x 3 = 17
+        launches.  No host synchronisation; no allocation after the first call at a shape (contiguous float32 / uint8
+        shards as the rollouts return them), so the call can be captured into a graph after one eager call ON the capture
+        stream (that call binds the handle to the stream -- fs_set_stream synchronises -- and makes every buffer, the
+        library's scratch for the statistics included).  The parameters must have been adopted (``adopt_parameters()``):
+        Adam moves ``self.weights``."""
+        import torch.distributed as dist
+        torch, lib, h = self.torch, self.sim.lib, self.sim._h
+        if self._stats is None:
+            self._stats, self._mean_std_n = self._f64(3), self._f64(3)
+        if not self._adopted:
+            raise RuntimeError("DeviceLearner.update: call adopt_parameters() first -- Adam moves self.weights, and only "
+                               "adopted parameters are views of them")
+        self._adam_buffers()
+        self._bind()
+        prepared = []
+        for j, (obs, act, rew, done) in enumerate(shards):
+            K, R = int(rew.shape[0]), int(rew.shape[1])
+            n = K * R
+            if done.dtype != torch.uint8 or tuple(done.shape) != (K, R) or done.device != self.device:
+                raise ValueError("DeviceLearner: done must be a uint8 tensor of shape %s on %s" % ((K, R), self.device))
+            obs = self._f32(obs, (K + 1, R, self.D), "obs")
+            o, last = obs[:K].reshape(n, self.D), obs[K]
+            a = self._f32(act.reshape(n, -1), (n, self.A), "act")
+            rew, done = self._f32(rew, (K, R), "rew"), done.contiguous()
+            b = self._shard_buffers(j, K, R)
+            L.check(lib.fs_ppo_eval_dev(h, C.byref(self.struct), n, o.data_ptr(), a.data_ptr(), b["logp"].data_ptr(),
+                                        b["val"].data_ptr()), lib)
+            L.check(lib.fs_ppo_eval_dev(h, C.byref(self.struct), R, last.data_ptr(), None, None, b["last_val"].data_ptr()), lib)
+            L.check(lib.fs_gae_dev(h, K, R, rew.data_ptr(), b["val"].data_ptr(), b["last_val"].data_ptr(), done.data_ptr(),
+                                   float(gamma), float(lam), b["adv"].data_ptr(), b["ret"].data_ptr()), lib)
+            self._adv_stats(n, b["adv"], a, j > 0, b["adv64"], self._stats)
+            self._workspace(n)                               # (grows to the largest shard's need)
+            prepared.append((n, o, a, b))
+        spread = dist.is_available() and dist.is_initialized()
+        if spread:
+            dist.all_reduce(self._stats, op=dist.ReduceOp.SUM, group=group)
+        L.check(lib.fs_adv_finish_dev(h, self._stats.data_ptr(), self._mean_std_n.data_ptr()), lib)
+        for _ in range(epochs):
+            for j, (n, o, a, b) in enumerate(prepared):
+                self._grad_n(n, o, a, b["logp"], b["adv64"], b["ret"], self._mean_std_n, clip, vf_coef, j > 0, self._work)
+            if spread:
+                dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=group)
+            self.adam_step(lr, betas, eps)
         return self.loss

@@ -436,7 +436,7 @@ int fs_add_vehicle(fs_handle h, int replica, int slot, int route, double x, doub
  * "k_rollout_loop<FULL>", "k_rollout_loop<AccelMA>", "k_rollout_loop<FULL,AccelMA>", "k_ring_policy", "k_loop_policy",
  * "k_ring_policy<POMA>", "k_loop_policy<AccelMA>", "k_merge_policy", "k_merge_policy<PO>", "k_merge_policy<PO,WIDE>"
  * (fs_policy_act_dev: "k_policy_act", "k_policy_act_vec", "k_policy_act_wide"; the PPO update's entry points: "k_ppo_eval",
- * "k_gae", "k_ppo_grad"),
+ * "k_gae", "k_ppo_grad", "k_adv_stats", "k_adv_finish", "k_adam"),
  * "k_steps<FAST>", "k_steps<CSET>", "k_steps", "k_steps_ml", "k_steps_open" (also "<mixed>"), "k_steps_wide",
  * "k_merge_queue", "k_drop_queue", "k_obs_mixed"; "" before the first launch).  Diagnostics for tests and bench.py: which
  * configuration class a workload landed in (no reference counterpart).  The string is static.
@@ -546,7 +546,8 @@ int fs_policy_rollout_dev(fs_handle h, const fs_policy* pol, int num_steps, int 
  * estimation, and per epoch the forward pass, the clipped-surrogate loss and autograd's backward pass over a policy and a
  * value network -- as three launches on the handle's stream (kernels: flow_amd/csrc/flowsim_learn.h).  The handle lends its
  * device, its stream and fs_last_error; none of the calls touches the simulation state, none synchronises the host, so a
- * sequence of them can be captured into a graph.  fs_last_kernel reports "k_ppo_eval", "k_gae", "k_ppo_grad".
+ * sequence of them can be captured into a graph.  fs_last_kernel reports "k_ppo_eval", "k_gae", "k_ppo_grad"
+ * (and "k_adv_stats", "k_adv_finish", "k_adam" for the statistics and the optimiser below).
  * Model class (fs_policy's): 1..3 hidden layers of 32 tanh units on obs_dim = 1..160 inputs; the policy's head has act_dim
  * = 1..32 outputs, the MEANS, next to a free log std [act_dim]; the value network is the same trunk with one output.
  * Both weight buffers: float32, device, per layer W [out][in] row-major then b [out].  Everything else -- the head of
@@ -591,6 +592,45 @@ int fs_ppo_grad_dev(fs_handle h, const fs_ppo_model* model, int64_t n, const flo
                     const float* logp_old_dev, const double* adv_dev, const float* ret_dev, const double* mean_std_dev,
                     float clip, float vf_coef, float inv_n_total, int accumulate, float* grad_dev, float* loss_dev,
                     float* work_dev, size_t work_floats);
+
+/* fs_ppo_grad_dev with the sample count on the device: mean_std_n_dev [3] = {mean, std, n} (what fs_adv_finish_dev writes)
+ * replaces mean_std_dev [2] and the host argument inv_n_total; the kernel takes inv_n_total = (float)(1.0 / n), the bits a
+ * host passes for the same n, so with inv_n_total = 1 / n both calls give the same bits.  One kernel body serves both. */
+int fs_ppo_grad_n_dev(fs_handle h, const fs_ppo_model* model, int64_t n, const float* obs_dev, const float* act_dev,
+                      const float* logp_old_dev, const double* adv_dev, const float* ret_dev, const double* mean_std_n_dev,
+                      float clip, float vf_coef, int accumulate, float* grad_dev, float* loss_dev, float* work_dev,
+                      size_t work_floats);
+/* The float64 advantage statistics of ppo_update.  adv_dev [n] float32 (fs_gae_dev's output); act_dev [n, act_dim] or NULL.
+ * A row whose action row holds a NaN is absent (act_dev == NULL: every row is present).  Absent rows are selected out,
+ * not multiplied by zero: nothing of such a row reaches an output, whatever its adv holds.
+ *   adv64_dev [n] = (double)adv of a present row, 0 of an absent one     (the form fs_ppo_grad_dev reads)
+ *   stats_dev [3] = {sum adv, sum adv * adv, count} over the present rows, in double
+ * G = min(512, ceil(n / 1024)) workgroups of 256 lanes: lane t of workgroup b adds rows 256 b + t + 256 G k, k ascending;
+ * the lanes of a workgroup meet in a binary tree (lane t += lane t + half, half = 128 .. 1); the workgroup that finishes
+ * last (an integer ticket) adds the G partial sums: lane t those of workgroups t and t + 256, then the same tree.  The order depends on n alone and there are no float
+ * atomics: the same inputs give the same bits.  accumulate != 0 adds the three sums to what stats_dev holds (several local
+ * shards, in call order).  The first call on a handle allocates a few KB of scratch and synchronises the device once:
+ * make it before a stream capture begins. */
+int fs_adv_stats_dev(fs_handle h, int64_t n, const float* adv_dev, const float* act_dev, int act_dim, int accumulate,
+                     double* adv64_dev, double* stats_dev);
+/* One thread, in double, exactly (no contraction; division and square root correctly rounded)
+ *   n = stats[2];  mean = stats[0] / n;  var = (stats[1] - (n * mean) * mean) / (n - 1);  std = sqrt(var < 0 ? 0 : var)
+ * mean_std_n_dev [3] = {mean, std, n}: ppo_update's formula, bit for bit its float64 result.  A launch of its own because
+ * the data-parallel all-reduce of stats_dev comes between fs_adv_stats_dev and this. */
+int fs_adv_finish_dev(fs_handle h, const double* stats_dev, double* mean_std_n_dev);
+/* One step of torch.optim.Adam (no weight decay, amsgrad or maximize) on packed float32 buffers of num_params elements.
+ * state_dev [3] = {t, beta1^t, beta2^t} in double lives on the device, so that a replayed graph advances it; it starts
+ * as {0, 1, 1}.  Per call, in double:
+ *   t += 1;  p1 *= beta1;  p2 *= beta2;  step = (float)(lr / (1 - p1));  rs = (float)sqrt(1 - p2)
+ * per element, in float32, nothing contracted:
+ *   m = m + (g - m) * (float)(1 - beta1)
+ *   v = v * (float)beta2 + (g * g) * (float)(1 - beta2)
+ *   w = w - step * (m / (sqrtf(v) / rs + (float)eps))
+ * One workgroup of 1024 lanes: every lane reads the state, a barrier follows, lane 0 alone writes it -- no other
+ * workgroup exists that could read the advanced state for the same step.  (num_params is 15 649 at the most for an
+ * fs_ppo_model: sixteen elements per lane.) */
+int fs_adam_dev(fs_handle h, int64_t num_params, float* weights_dev, const float* grad_dev, float* m_dev, float* v_dev,
+                double* state_dev, double lr, double beta1, double beta2, double eps);
 
 /* Append the CURRENT state of one replica to a CSV file (header `time,id,x,speed,lane_number` when the file is new;
  * one row per vehicle, id = slot index, free slots of open networks skipped): the trajectory ("emission") dump of
