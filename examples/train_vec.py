@@ -65,6 +65,31 @@ class GaussianPolicy(nn.Module):
         logp = (-0.5 * ((act - mu) / std) ** 2 - self.log_std - 0.9189385).sum(-1)
         return logp, self.value(obs).squeeze(-1)
 
+    def logp_value_dist(self, obs, act):
+        """``logp_value`` and the distribution itself: (logp, value, means [n, A], log_std [A]) -- what the KL term of
+        ppo_update keeps from its no_grad pass."""
+        mu = self.mu(obs)
+        std = self.log_std.exp()
+        logp = (-0.5 * ((act - mu) / std) ** 2 - self.log_std - 0.9189385).sum(-1)
+        return logp, self.value(obs).squeeze(-1), mu, self.log_std
+
+
+class AdaptiveKL(object):
+    """RLlib's adaptive KL coefficient (``kl_coeff``, ``kl_target``): ``coef`` weighs KL(old || new) in ppo_update's loss
+    and is adapted once per update, after the last epoch, from the mean KL that epoch's gradient pass saw (before its
+    optimiser step): times 1.5 above ``2 target``, times 0.5 below ``0.5 target``."""
+
+    def __init__(self, target=0.02, coef=0.2):
+        self.target, self.coef, self.mean_kl = float(target), float(coef), None
+
+    def adapt(self, mean_kl):
+        self.mean_kl = float(mean_kl)
+        if self.mean_kl > 2.0 * self.target:
+            self.coef *= 1.5
+        elif self.mean_kl < 0.5 * self.target:
+            self.coef *= 0.5
+        return self.coef
+
 
 def gae(rew, val, done, last_val, gamma=0.999, lam=0.97):
     """Generalised advantage estimation over a [K, R] fragment.  ``done`` is the simulator's FLAG BYTE (bit 0: horizon
@@ -82,7 +107,8 @@ def gae(rew, val, done, last_val, gamma=0.999, lam=0.97):
     return adv, adv + val
 
 
-def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None, learner=None):
+def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None, learner=None, kl=None, entropy_coef=0.0, vf_clip=None,
+               vf_coef=0.5):
     """One PPO update over `shards` = [(obs [K+1, R, D], act [K, R, A], rew [K, R], done [K, R])]: the shards this
     process holds (one per rank in data-parallel runs, all of them in a single process).  Every quantity that couples the
     shards is a SUM: the advantage statistics and the gradient -- summed over the local shards here, over the ranks by
@@ -92,8 +118,18 @@ def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None, learner=None):
     ``learner`` (flow_amd.utils.device_ppo.DeviceLearner over pi's parameters): the three torch stages -- the no_grad pass,
     gae() and every epoch's forward and backward pass -- run on the library's kernels instead (fs_ppo_eval_dev, fs_gae_dev,
     fs_ppo_grad_dev); the float64 advantage statistics, the all-reduces and opt.step() are the same code.  Without one, the
-    update is torch alone."""
+    update is torch alone.
+    ``kl`` (an AdaptiveKL), ``entropy_coef``, ``vf_clip``: the loss the reference trains with (RLlib's PPO), per present
+    sample and over the global count n
+        -pg + kl.coef KL(old || new) + vf_coef max((v - ret)^2, (v_c - ret)^2) - entropy_coef H
+        KL = sum_c ls - ls_o + (exp(2 ls_o) + (mu_o - mu)^2) / (2 exp(2 ls)) - 0.5,   H = sum_c ls + 0.5 log(2 pi e)
+        v_c = v_o + clamp(v - v_o, -vf_clip, +vf_clip)
+    with mu_o, ls_o, v_o from the no_grad pass (``pi.logp_value_dist``).  ``vf_clip`` None or inf: vfl = (v - ret)^2.
+    After the last epoch ``kl.adapt`` sees that epoch's mean KL (summed over shards and ranks).  With a learner the same
+    loss runs on fs_ppo_eval_dist_dev / fs_ppo_grad_loss_dev.  With the defaults the arithmetic is what it was."""
     from flow_amd.dist import allreduce_gradients, allreduce_sum
+    vclip = vf_clip is not None and 0.0 < float(vf_clip) < float("inf")
+    full = kl is not None or vclip or float(entropy_coef) != 0.0
     prepared, stats = [], None
     if learner is not None:
         learner.sync()
@@ -106,12 +142,22 @@ def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None, learner=None):
         elif learner is None:
             a = torch.where(present[:, None], a, torch.zeros_like(a))
         with torch.no_grad():
-            if learner is not None:                          # (the kernels take the NaN rows as they are: absent)
+            mu_old = ls_old = None
+            if learner is not None and full:
+                logp_old, val, mu_old = learner.evaluate_dist(o, a)
+                ls_old = learner.log_std_param.detach().clone()
+                last_val = learner.evaluate(obs[K], None)[1]
+                adv, ret = learner.gae(rew, val.view(K, R), last_val, done)
+            elif learner is not None:                        # (the kernels take the NaN rows as they are: absent)
                 logp_old, val = learner.evaluate(o, a)
                 last_val = learner.evaluate(obs[K], None)[1]
                 adv, ret = learner.gae(rew, val.view(K, R), last_val, done)
             else:
-                logp_old, val = pi.logp_value(o, a)
+                if full:
+                    logp_old, val, mu_old, ls_old = pi.logp_value_dist(o, a)
+                    mu_old, ls_old = mu_old.detach().clone(), ls_old.detach().clone()
+                else:
+                    logp_old, val = pi.logp_value(o, a)
                 last_val = pi.value(obs[K]).squeeze(-1)
                 adv, ret = gae(rew, val.view(K, R), done, last_val)
             adv = adv.reshape(-1).double()
@@ -121,18 +167,22 @@ def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None, learner=None):
                 m = present.double()
                 st = torch.stack([(adv * m).sum(), (adv * adv * m).sum(), m.sum()])
             stats = st if stats is None else stats + st
-        prepared.append((o, a, logp_old, adv, ret.reshape(-1), present))
+        prepared.append((o, a, logp_old, adv, ret.reshape(-1), present) + ((val.reshape(-1), mu_old, ls_old) if full else ()))
     stats = allreduce_sum(stats, group)
     n = stats[2]
     mean = stats[0] / n
     std = ((stats[1] - n * mean * mean) / (n - 1)).clamp_min(0).sqrt()
     params = list(pi.parameters())
+    if full:
+        _ppo_epochs_full(pi, opt, prepared, params, epochs, clip, group, learner, kl, float(entropy_coef),
+                         float(vf_clip) if vclip else None, vf_coef, mean, std, n)
+        return
     for _ in range(epochs):
         if learner is not None:
             # one launch per shard writes (the first shard) or adds to (the others, in this order) the packed gradient
             # that every parameter's .grad is a view of
             for j, (o, a, logp_old, adv, ret, present) in enumerate(prepared):
-                learner.gradients(o, a, logp_old, adv, ret, mean, std, clip=clip, vf_coef=0.5, n_total=float(n),
+                learner.gradients(o, a, logp_old, adv, ret, mean, std, clip=clip, vf_coef=vf_coef, n_total=float(n),
                                   accumulate=j > 0)
             learner.attach_grads()
         else:
@@ -147,7 +197,7 @@ def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None, learner=None):
                     pg = torch.where(present, pg, torch.zeros_like(pg))
                     vf = torch.where(present, vf, torch.zeros_like(vf))
                 # the GLOBAL mean as a sum of per-shard sums
-                loss = (-pg.sum() + 0.5 * vf.sum()) / float(n)
+                loss = (-pg.sum() + vf_coef * vf.sum()) / float(n)
                 loss.backward()                              # (accumulates over the local shards)
         allreduce_gradients(params, group)
         opt.step()
@@ -155,8 +205,58 @@ def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None, learner=None):
             learner.sync()                                   # the optimiser moved the weights: repack them for the kernels
 
 
+def _ppo_epochs_full(pi, opt, prepared, params, epochs, clip, group, learner, kl, entropy_coef, vf_clip, vf_coef, mean, std, n):
+    """The epochs of ppo_update with the reference's loss terms on (its docstring states the loss)."""
+    import math
+    from flow_amd.dist import allreduce_gradients, allreduce_sum
+    sum_kl = None
+    if learner is not None:
+        mean_std_n = torch.stack([mean, std, n]).to(torch.float64)
+        if kl is not None:
+            learner.kl_state[0].fill_(kl.coef)
+    for _ in range(epochs):
+        if learner is not None:
+            for j, (o, a, logp_old, adv, ret, present, v_old, mu_old, ls_old) in enumerate(prepared):
+                learner.gradients_loss(o, a, logp_old, adv, ret, mean_std_n, mean_old=mu_old, log_std_old=ls_old, val_old=v_old,
+                                       clip=clip, vf_coef=vf_coef, vf_clip=vf_clip, entropy_coef=entropy_coef,
+                                       kl=kl is not None, accumulate=j > 0)
+            learner.attach_grads()
+            sum_kl = learner.loss_sums[2].double()
+        else:
+            opt.zero_grad()
+            sum_kl = None
+            for o, a, logp_old, adv, ret, present, v_old, mu_old, ls_old in prepared:
+                adv_n = ((adv - mean) / (std + 1e-8)).float()
+                logp, v, mu, ls = pi.logp_value_dist(o, a)
+                ratio = (logp - logp_old).exp()
+                per = -torch.min(ratio * adv_n, ratio.clamp(1 - clip, 1 + clip) * adv_n)
+                vfl = (v - ret).pow(2)
+                if vf_clip is not None:
+                    v_c = v_old + (v - v_old).clamp(-vf_clip, vf_clip)
+                    vfl = torch.max(vfl, (v_c - ret).pow(2))
+                per = per + vf_coef * vfl
+                if kl is not None:
+                    kl_s = (ls - ls_old + ((2.0 * ls_old).exp() + (mu_old - mu).pow(2)) / (2.0 * (2.0 * ls).exp()) - 0.5).sum(-1)
+                    per = per + kl.coef * kl_s
+                    shard_kl = (kl_s.detach() if present is None else torch.where(present, kl_s.detach(), torch.zeros_like(kl_s))).sum()
+                    sum_kl = shard_kl if sum_kl is None else sum_kl + shard_kl
+                if entropy_coef != 0.0:
+                    per = per - entropy_coef * (ls + 0.5 * math.log(2.0 * math.pi * math.e)).sum()
+                if present is not None:
+                    per = torch.where(present, per, torch.zeros_like(per))
+                # the GLOBAL mean as a sum of per-shard sums
+                (per.sum() / float(n)).backward()            # (accumulates over the local shards)
+        allreduce_gradients(params, group)
+        opt.step()
+        if learner is not None:
+            learner.sync()
+    if kl is not None:
+        kl.adapt(float(allreduce_sum(sum_kl.double().reshape(1), group)[0]) / float(n))
+
+
 def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epochs=4, lr=3e-4, seed=0, log=print,
-                    rank=0, world=1, shared_agents=False, fuse_action_vector=False, device_update=False, device_adam=False):
+                    rank=0, world=1, shared_agents=False, fuse_action_vector=False, device_update=False, device_adam=False,
+                    kl_target=None, kl_coeff=0.2, entropy_coeff=0.0, vf_clip=None, vf_coef=0.5, clip=0.2):
     """PPO on R replicas of ``flow_params`` with everything in HBM: returns the mean step reward per iteration.
     ``world`` > 1: this process is rank ``rank`` of a data-parallel run (torch.distributed is initialised): it steps its
     block of the R replicas on its own GPU.
@@ -177,7 +277,12 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     as well -- fs_adv_stats_dev, fs_adv_finish_dev, fs_ppo_grad_n_dev, fs_adam_dev), with no host round trip between two
     rollouts; it implies the device update.  The learner is built first and the policy's parameters become views into
     its packed weights before anything is captured; a fused or graph DevicePolicy runs on that same buffer, and no
-    torch.optim.Adam is built.  Off by default."""
+    torch.optim.Adam is built.  Off by default.
+    ``kl_target`` / ``kl_coeff`` / ``entropy_coeff`` / ``vf_clip`` (RLlib's names): the terms of the loss the reference
+    trains with -- the KL penalty with its adaptive coefficient (starting at ``kl_coeff``), the entropy bonus, the clipped
+    value loss (ppo_update states the loss) -- on whichever path the update takes; ``vf_coef`` and ``clip`` are the value
+    loss's weight and the surrogate's clip range.  All off by default.  With a KL target the log shows, per iteration, the
+    mean KL of the update's last epoch and the coefficient after its adaptation."""
     from flow_amd.dist import allreduce_sum, shard_range
     from flow_amd.envs import VecFlowEnv
     local = int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else 0
@@ -251,6 +356,7 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
         from flow_amd.utils.device_ppo import DeviceLearner
         learner = DeviceLearner(vec, [pi.mu[0], pi.mu[2]], pi.mu[4], pi.log_std, [pi.value[0], pi.value[2]], pi.value[4])
         log("update: on the device (k_ppo_eval, k_gae, k_ppo_grad)")
+    kl = AdaptiveKL(kl_target, kl_coeff) if kl_target is not None and not device_adam else None
     history = []
     for it in range(iterations):
         vec.redraw_ring_lengths()                              # pending ring length per replica for its next in-graph reset
@@ -272,16 +378,22 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
         else:
             shard = (obs, act, rew, done)
         if device_adam:
-            learner.update([shard], epochs=epochs, lr=lr)
+            learner.update([shard], epochs=epochs, lr=lr, clip=clip, vf_coef=vf_coef, kl_target=kl_target,
+                           kl_coef_init=kl_coeff, entropy_coef=entropy_coeff, vf_clip=vf_clip)
         else:
-            ppo_update(pi, opt, [shard], epochs=epochs, learner=learner)
+            ppo_update(pi, opt, [shard], epochs=epochs, clip=clip, learner=learner, kl=kl, entropy_coef=entropy_coeff,
+                       vf_clip=vf_clip, vf_coef=vf_coef)
+        kl_log = ""
+        if kl_target is not None:                              # (read after the update: the device's state under device_adam)
+            coef, mean_kl = learner.kl_state.tolist() if device_adam else (kl.coef, kl.mean_kl)
+            kl_log = "  KL %.5f  kl_coeff %.4g" % (mean_kl, coef)
         tot = allreduce_sum(torch.stack([rew.double().sum(), torch.tensor(float(rew.numel()), dtype=torch.float64, device=dev),
                                          (done != 0).sum().double()]))
         mean_rew = float(tot[0] / tot[1])
         history.append(mean_rew)
         if rank == 0:
-            log("iteration %3d  mean step reward %8.4f  rollout %.1f ms (%.2f M env-steps/s per GPU, %d GPU%s)  episodes ended %d"
-                % (it, mean_rew, t_roll * 1e3, K * R / t_roll / 1e6, world, "s" if world > 1 else "", int(tot[2])))
+            log("iteration %3d  mean step reward %8.4f  rollout %.1f ms (%.2f M env-steps/s per GPU, %d GPU%s)  episodes ended %d%s"
+                % (it, mean_rew, t_roll * 1e3, K * R / t_roll / 1e6, world, "s" if world > 1 else "", int(tot[2]), kl_log))
     vec.close()
     return history
 
@@ -308,6 +420,16 @@ def spawn_ranks(gpus, argv):
     raise SystemExit(rc)
 
 
+def add_ppo_loss_flags(ap):
+    """The terms of the reference's PPO loss (RLlib's names), all off by default (train_vec.py and train.py)."""
+    ap.add_argument("--kl_target", type=float, default=None,
+                    help="add the KL penalty KL(old || new) with RLlib's adaptive coefficient towards this mean KL (the reference: 0.02)")
+    ap.add_argument("--kl_coeff", type=float, default=0.2, help="the KL coefficient's initial value (with --kl_target)")
+    ap.add_argument("--entropy_coeff", type=float, default=0.0, help="weight of the entropy bonus")
+    ap.add_argument("--vf_clip", type=float, default=None,
+                    help="clip the value loss: max((v - ret)^2, (v_old + clamp(v - v_old, +-vf_clip) - ret)^2)")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--replicas", type=int, default=1024)
@@ -321,6 +443,7 @@ def main(argv=None):
                     help="run the PPO update on the library's kernels (DeviceLearner) instead of torch")
     ap.add_argument("--device_adam", action="store_true",
                     help="run the whole PPO update, Adam included, on the device (DeviceLearner.update); implies --device_update")
+    add_ppo_loss_flags(ap)
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     force = os.environ.get("TRAIN_FORCE_DIST") == "1"            # the N > 1 code path (RCCL init, all-reduces) with one rank
@@ -338,7 +461,9 @@ def main(argv=None):
     try:
         return train_on_device(ring_flow_params(args.horizon), replicas=args.replicas, fragment=args.fragment,
                                iterations=args.iterations, epochs=args.epochs, lr=args.lr, rank=rank, world=world,
-                               device_update=args.device_update or args.device_adam, device_adam=args.device_adam)
+                               device_update=args.device_update or args.device_adam, device_adam=args.device_adam,
+                               kl_target=args.kl_target, kl_coeff=args.kl_coeff, entropy_coeff=args.entropy_coeff,
+                               vf_clip=args.vf_clip)
     finally:
         if world > 1 or force:
             import torch.distributed as dist

@@ -46,7 +46,8 @@ EXPORTS = ["fs_create", "fs_destroy", "fs_last_error", "fs_abi_version", "fs_obs
            "fs_use_own_stream", "fs_sync", "fs_reset", "fs_reset_dev", "fs_step", "fs_step_dev", "fs_rollout_dev",
            "fs_get_state", "fs_set_state", "fs_add_vehicle", "fs_dump_trajectory", "fs_last_kernel", "fs_policy_act_dev",
            "fs_policy_rollout_dev", "fs_ppo_eval_dev", "fs_gae_dev", "fs_ppo_workspace", "fs_ppo_grad_dev",
-           "fs_ppo_grad_n_dev", "fs_adv_stats_dev", "fs_adv_finish_dev", "fs_adam_dev"]
+           "fs_ppo_grad_n_dev", "fs_adv_stats_dev", "fs_adv_finish_dev", "fs_adam_dev", "fs_ppo_eval_dist_dev",
+           "fs_ppo_loss_workspace", "fs_ppo_grad_loss_dev", "fs_kl_adapt_dev"]
 
 
 class fs_vehicle_spec(C.Structure):
@@ -120,6 +121,11 @@ class fs_ppo_model(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("num_hidden", C.c_int32),
                 ("hidden_width", C.c_int32), ("activation", C.c_int32), ("policy_weights_dev", C.c_void_p),
                 ("log_std_dev", C.c_void_p), ("value_weights_dev", C.c_void_p)]
+
+
+class fs_ppo_loss(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("clip", C.c_float), ("vf_coef", C.c_float), ("vf_clip", C.c_float),
+                ("entropy_coef", C.c_float), ("kl_state_dev", C.c_void_p)]
 
 
 _libs = {}
@@ -203,6 +209,15 @@ def load(path=None):
     lib.fs_adv_finish_dev.restype = C.c_int
     lib.fs_adam_dev.argtypes = [h, C.c_int64, f32p, f32p, f32p, f32p, f64p, C.c_double, C.c_double, C.c_double, C.c_double]
     lib.fs_adam_dev.restype = C.c_int
+    lib.fs_ppo_eval_dist_dev.argtypes = [h, C.POINTER(fs_ppo_model), C.c_int64, f32p, f32p, f32p, f32p, f32p]
+    lib.fs_ppo_eval_dist_dev.restype = C.c_int
+    lib.fs_ppo_loss_workspace.argtypes = [C.POINTER(fs_ppo_model), C.c_int64]
+    lib.fs_ppo_loss_workspace.restype = C.c_size_t
+    lib.fs_ppo_grad_loss_dev.argtypes = [h, C.POINTER(fs_ppo_model), C.POINTER(fs_ppo_loss), C.c_int64, f32p, f32p, f32p, f32p,
+                                         f32p, f32p, f64p, f32p, f64p, C.c_int, f32p, f32p, f32p, C.c_size_t]
+    lib.fs_ppo_grad_loss_dev.restype = C.c_int
+    lib.fs_kl_adapt_dev.argtypes = [h, f32p, f64p, f64p, C.c_double]
+    lib.fs_kl_adapt_dev.restype = C.c_int
     if lib.fs_abi_version() != FS_ABI_VERSION:
         raise FatalFlowError("libflowsim.so ABI %d != binding ABI %d" % (lib.fs_abi_version(), FS_ABI_VERSION))
     _libs[path] = lib

@@ -6,6 +6,8 @@
 #include "flowsim_sim.h"
 #include "flowsim_learn.h"
 
+#include <cmath>
+
 namespace fsim {
 
 int validate(const fs_config* c) {
@@ -620,6 +622,66 @@ int fs_adam_dev(fs_handle h, int64_t num_params, float* weights_dev, const float
   DeviceGuard guard(S(h)->cfg.device);
   S(h)->last_kernel = "k_adam";
   return launch_adam(S(h)->stream, int(num_params), weights_dev, grad_dev, m_dev, v_dev, state_dev, lr, beta1, beta2, eps);
+}
+
+// ---- the reference's PPO loss (KL penalty, clipped value loss, entropy): additive entry points
+int fs_ppo_eval_dist_dev(fs_handle h, const fs_ppo_model* model, int64_t n, const float* obs_dev, const float* act_dev,
+                         float* logp_dev, float* val_dev, float* mean_old_dev) {
+  if (!h || !obs_dev || !act_dev || !logp_dev || !val_dev || !mean_old_dev)
+    return fail(FS_ERR_INVALID, "fs_ppo_eval_dist_dev: NULL argument");
+  if (n < 1 || n > INT32_MAX) return fail(FS_ERR_INVALID, "fs_ppo_eval_dist_dev: n must be 1 .. 2^31 - 1");
+  fs::PpoView pv;
+  if (int rc = ppo_view("fs_ppo_eval_dist_dev", model, true, &pv)) return rc;
+  DeviceGuard guard(S(h)->cfg.device);
+  S(h)->last_kernel = "k_ppo_eval";
+  return launch_ppo_eval_dist(S(h)->stream, pv, n, obs_dev, act_dev, logp_dev, val_dev, mean_old_dev);
+}
+
+size_t fs_ppo_loss_workspace(const fs_ppo_model* model, int64_t n) {
+  fs::PpoView pv;
+  if (n < 1 || n > INT32_MAX || ppo_view("fs_ppo_loss_workspace", model, false, &pv)) return 0;
+  return fs::ppo_loss_work_floats(n, pv.D, pv.A, pv.L);
+}
+
+int fs_ppo_grad_loss_dev(fs_handle h, const fs_ppo_model* model, const fs_ppo_loss* loss, int64_t n, const float* obs_dev,
+                         const float* act_dev, const float* logp_old_dev, const float* mean_old_dev,
+                         const float* log_std_old_dev, const float* val_old_dev, const double* adv_dev, const float* ret_dev,
+                         const double* mean_std_n_dev, int accumulate, float* grad_dev, float* loss_sums_dev, float* work_dev,
+                         size_t work_floats) {
+  if (!h || !obs_dev || !act_dev || !logp_old_dev || !adv_dev || !ret_dev || !mean_std_n_dev || !grad_dev || !loss_sums_dev ||
+      !work_dev)
+    return fail(FS_ERR_INVALID, "fs_ppo_grad_loss_dev: NULL argument");
+  const std::string w = "fs_ppo_grad_loss_dev: fs_ppo_loss: ";
+  if (!loss) return fail(FS_ERR_INVALID, w + "NULL");
+  if (loss->struct_size != sizeof(fs_ppo_loss)) return fail(FS_ERR_INVALID, w + "struct_size mismatch");
+  if (std::isnan(loss->clip) || std::isnan(loss->vf_coef) || std::isnan(loss->vf_clip) || std::isnan(loss->entropy_coef))
+    return fail(FS_ERR_INVALID, w + "a coefficient is NaN");
+  if (loss->clip < 0.0f) return fail(FS_ERR_INVALID, w + "clip must not be negative");
+  const bool vclip = loss->vf_clip > 0.0f && std::isfinite(loss->vf_clip);
+  if (loss->kl_state_dev && (!mean_old_dev || !log_std_old_dev))
+    return fail(FS_ERR_INVALID, w + "the KL term (kl_state_dev) needs mean_old_dev and log_std_old_dev");
+  if (vclip && !val_old_dev) return fail(FS_ERR_INVALID, w + "value clipping (vf_clip > 0) needs val_old_dev");
+  if (n < 1 || n > INT32_MAX) return fail(FS_ERR_INVALID, "fs_ppo_grad_loss_dev: n must be 1 .. 2^31 - 1");
+  fs::PpoView pv;
+  if (int rc = ppo_view("fs_ppo_grad_loss_dev", model, true, &pv)) return rc;
+  if (work_floats < fs::ppo_loss_work_floats(n, pv.D, pv.A, pv.L))
+    return fail(FS_ERR_INVALID, "fs_ppo_grad_loss_dev: work_dev is smaller than fs_ppo_loss_workspace(model, n) floats");
+  const fs::PpoLossArgs x{mean_old_dev, log_std_old_dev, val_old_dev, loss->kl_state_dev, vclip ? loss->vf_clip : 0.0f,
+                          loss->entropy_coef};
+  DeviceGuard guard(S(h)->cfg.device);
+  S(h)->last_kernel = "k_ppo_grad_loss";
+  return launch_ppo_grad_loss(S(h)->stream, pv, x, n, obs_dev, act_dev, logp_old_dev, adv_dev, ret_dev, mean_std_n_dev,
+                              float(1.0 - double(loss->clip)), float(1.0 + double(loss->clip)), loss->vf_coef,
+                              accumulate ? 1 : 0, grad_dev, loss_sums_dev, work_dev);
+}
+
+int fs_kl_adapt_dev(fs_handle h, const float* loss_sums_dev, const double* mean_std_n_dev, double* kl_state_dev,
+                    double kl_target) {
+  if (!h || !loss_sums_dev || !mean_std_n_dev || !kl_state_dev) return fail(FS_ERR_INVALID, "fs_kl_adapt_dev: NULL argument");
+  if (!(kl_target > 0.0) || !std::isfinite(kl_target)) return fail(FS_ERR_INVALID, "fs_kl_adapt_dev: kl_target must be positive and finite");
+  DeviceGuard guard(S(h)->cfg.device);
+  S(h)->last_kernel = "k_kl_adapt";
+  return launch_kl_adapt(S(h)->stream, loss_sums_dev, mean_std_n_dev, kl_state_dev, kl_target);
 }
 
 const char* fs_last_kernel(fs_handle h) { return h ? reinterpret_cast<SimBase*>(h)->last_kernel : ""; }

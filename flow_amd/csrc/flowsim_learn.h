@@ -9,6 +9,9 @@
 //   k_adv_stats  the float64 advantage statistics {sum adv, sum adv^2, count} of the present rows and the float64 copy of adv
 //   k_adv_finish {mean, std, n} of the three sums (one thread; the data-parallel all-reduce of the sums comes before it)
 //   k_adam       torch's Adam on the packed buffers, its step count and the powers of the betas in device memory
+//   k_ppo_grad<true, true>  ("k_ppo_grad_loss") the same launch with RLlib's PPO loss: the KL penalty KL(old || new), the
+//                clipped value loss and the entropy bonus on top of the surrogate, four loss sums {pg, vfl, KL, H}
+//   k_kl_adapt   RLlib's rule for the KL coefficient, one thread, in double: {coef, mean KL} live in device memory
 //
 // Model class (DevicePolicy's): 1..3 hidden layers of 32 tanh units on 1..160 inputs, a head of A <= 32 means with a free
 // log_std [A]; the value network is the same trunk with one output.  Packed weights per network: per layer W [out][in]
@@ -68,6 +71,29 @@ __host__ __device__ constexpr size_t ppo_work_floats(long long n, int D, int A, 
   return size_t(ppo_groups(n, D, A, L)) * size_t(ppo_params(D, A, L) + 2);
 }
 
+// the full-loss form (k_ppo_grad<true, true>): FOUR loss sums behind the gradient, in LDS and in a workgroup's row of the
+// workspace.  The workgroups are ppo_groups' (the two extra floats do not move the count: the order of every sum is the
+// plain form's).
+constexpr int PPO_LOSS_SUMS = 4;
+__host__ __device__ constexpr size_t ppo_grad_loss_lds(int D, int A, int L) {
+  return sizeof(float) * size_t(2 * ppo_net_lds(D, L) + ppo_stage_floats() + round4(ppo_params(D, A, L) + PPO_LOSS_SUMS));
+}
+static_assert(ppo_grad_loss_lds(PPO_MAX_OBS, PPO_MAX_ACT, 3) <= size_t(PPO_LDS_BYTES), "the largest model's gradient fits LDS");
+__host__ __device__ constexpr size_t ppo_loss_work_floats(long long n, int D, int A, int L) {
+  return size_t(ppo_groups(n, D, A, L)) * size_t(ppo_params(D, A, L) + PPO_LOSS_SUMS);
+}
+
+// what the full-loss form reads on top of k_ppo_grad's arguments (all device pointers; a NULL pointer or a zero
+// coefficient switches its term off for the whole launch)
+struct PpoLossArgs {
+  const float* mean_old;       // [n, A]  the policy's means at the time of the rollout      (KL)
+  const float* log_std_old;    // [A]     log_std at the time of the rollout                 (KL)
+  const float* val_old;        // [n]     the value network's output at the time of the rollout (value clipping)
+  const double* kl_state;      // {coef, ..}: NULL = no KL term
+  float vf_clip;               // <= 0: no value clipping
+  float entropy_coef;          // 0: no entropy term
+};
+
 // k_adv_stats: workgroups (a function of n alone) and the handle's scratch [ticket][G x 3 partial sums]
 constexpr int ADV_THREADS = 256, ADV_MAX_GROUPS = 512;
 constexpr size_t ADV_SCRATCH_BYTES = sizeof(double) * (1 + 3 * ADV_MAX_GROUPS);      // [ticket][G x 3 partial sums]
@@ -92,6 +118,13 @@ int launch_ppo_grad(hipStream_t stream, const fs::PpoView& m, long long n, const
 int launch_ppo_grad_n(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act,
                       const float* logp_old, const double* adv, const float* ret, const double* mean_std_n, float lo, float hi,
                       float vf_coef, int accumulate, float* grad, float* loss, float* work);
+// (the full-loss form: loss [4] = {sum pg, sum vfl, sum KL, sum H}; work: ppo_loss_work_floats)
+int launch_ppo_eval_dist(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act, float* logp,
+                         float* val, float* mean_old);
+int launch_ppo_grad_loss(hipStream_t stream, const fs::PpoView& m, const fs::PpoLossArgs& x, long long n, const float* obs,
+                         const float* act, const float* logp_old, const double* adv, const float* ret, const double* mean_std_n,
+                         float lo, float hi, float vf_coef, int accumulate, float* grad, float* loss, float* work);
+int launch_kl_adapt(hipStream_t stream, const float* loss_sums, const double* mean_std_n, double* kl_state, double kl_target);
 // (scratch: fs::ADV_SCRATCH_BYTES of device memory, zero before its first use: the handle owns it)
 int launch_adv_stats(hipStream_t stream, long long n, const float* adv, const float* act, int A, int accumulate, double* adv64,
                      double* stats, double* scratch);
@@ -231,9 +264,11 @@ __device__ __forceinline__ bool ppo_load_act(const float* act, long long s, bool
   return present;
 }
 
+// DIST: the head's means go out as well, mean_out [n, A] (the old distribution of the KL penalty)
+template <bool DIST>
 __global__ __launch_bounds__(64) void k_ppo_eval(PpoView m, long long n, const float* __restrict__ obs,
                                                  const float* __restrict__ act, float* __restrict__ logp_out,
-                                                 float* __restrict__ val_out) {
+                                                 float* __restrict__ val_out, float* __restrict__ mean_out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* pnet = reinterpret_cast<float*>(smem);
   float* vnet = pnet + ppo_net_lds(m.D, m.L);
@@ -253,6 +288,11 @@ __global__ __launch_bounds__(64) void k_ppo_eval(PpoView m, long long n, const f
       net_forward(pnet, m.D, m.L, obs, s0, n, ~0ull, S, lane, h, out);
       const float lp = ppo_logp(out, a, m.log_std, m.A, zc, sd);
       if (valid) logp_out[s] = lp;
+      if (DIST && valid) {
+#pragma unroll
+        for (int c = 0; c < 32; ++c)
+          if (c < m.A) mean_out[size_t(s) * size_t(m.A) + size_t(c)] = out[c];
+      }
     }
     net_forward(vnet, m.D, m.L, obs, s0, n, ~0ull, S, lane, h, out);
     if (valid) val_out[s] = out[0];
@@ -374,12 +414,21 @@ __device__ __forceinline__ void net_backward(const float* net, int D, int L, int
 
 // N_DEV: mean_std is {mean, std, n} and the sample count of the whole update comes from it, inv_n = float(1.0 / n) -- the
 // bits a host passes as inv_n for the same n -- so that nothing between the statistics and the gradient needs the host
-template <bool N_DEV>
+// LOSS (with N_DEV; fs_last_kernel's "k_ppo_grad_loss"): RLlib's PPO loss per present sample,
+//   -pg + kl_coef KL(old || new) + vf_coef max((v - ret)^2, (v_c - ret)^2) - entropy_coef H,   all over n
+//   KL = sum_c ls - ls_o + (exp(2 ls_o) + (mu_o - mu)^2) / (2 exp(2 ls)) - 0.5,   H = sum_c ls + 0.5 log(2 pi e)
+//   v_c = v_o + clamp(v - v_o, -vf_clip, +vf_clip)
+// with kl_coef = float(x.kl_state[0]) read from the device.  Every new term is added where its quantities already sit in
+// registers, each behind a wave-uniform branch on its argument (a term that is off is not computed: nothing is multiplied
+// by zero), and the old means / old value of an absent row are never loaded.  The sums are four: {pg, vfl, KL, H}.
+template <bool N_DEV, bool LOSS = false>
 __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const float* __restrict__ obs,
                                                  const float* __restrict__ act, const float* __restrict__ logp_old,
                                                  const double* __restrict__ adv, const float* __restrict__ ret,
                                                  const double* __restrict__ mean_std, float lo, float hi, float vf_coef,
-                                                 float inv_n, float* __restrict__ work) {
+                                                 float inv_n, float* __restrict__ work, PpoLossArgs x) {
+  static_assert(N_DEV || !LOSS, "the full loss reads its sample count from the device");
+  constexpr int NS = LOSS ? PPO_LOSS_SUMS : 2;               // loss sums behind the gradient
   if (N_DEV) inv_n = float(1.0 / mean_std[2]);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int D = m.D, A = m.A, L = m.L, P = ppo_params(D, A, L);
@@ -387,11 +436,11 @@ __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const f
   float* vnet = pnet + ppo_net_lds(D, L);
   float* S = vnet + ppo_net_lds(D, L);
   float* T = S + 32 * PPO_TS;
-  float* G = T + PPO_TILE * PPO_TT;                          // [P + 2]: the gradient, then the two loss sums
+  float* G = T + PPO_TILE * PPO_TT;                          // [P + NS]: the gradient, then the loss sums
   const int lane = threadIdx.x;
   net_load(m.pw, D, L, A, pnet, lane);
   net_load(m.vw, D, L, 1, vnet, lane);
-  for (int e = lane; e < P + 2; e += 64) G[e] = 0.0f;
+  for (int e = lane; e < P + NS; e += 64) G[e] = 0.0f;
   __syncthreads();
   const int Pp = ppo_net_params(D, L, A);
   const double mean = mean_std[0], scale = mean_std[1] + 1e-8;
@@ -405,6 +454,7 @@ __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const f
     // ---- the policy: logp, the clipped surrogate, its gradient at the means and at log_std
     net_forward(pnet, D, L, obs, s0, n, keep, S, lane, h, out);
     float pg = 0.0f, vf = 0.0f;
+    float kl = 0.0f, ent = 0.0f;                             // (LOSS)
     {
       float zc[32], sd[32];
       const float logp = ppo_logp(out, a, m.log_std, A, zc, sd);
@@ -422,6 +472,33 @@ __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const f
         dz[c] = c < A ? g_logp * (zc[c] / sd[c]) : 0.0f;
         gls[c] = c < A ? g_logp * __builtin_fmaf(zc[c], zc[c], -1.0f) : 0.0f;
       }
+      if constexpr (LOSS) {
+        if (x.kl_state != nullptr) {
+          // d KL / d mu = (mu - mu_o) / exp(2 ls);  d KL / d ls = 1 - (exp(2 ls_o) + (mu_o - mu)^2) / exp(2 ls)
+          const float w = inv_n * float(x.kl_state[0]);
+#pragma unroll
+          for (int c = 0; c < 32; ++c) {
+            if (c < A) {
+              const float ls = m.log_std[c], lso = x.log_std_old[c], so = expf(lso);
+              const float mo = present ? x.mean_old[size_t(s) * size_t(A) + size_t(c)] : 0.0f;
+              const float var = sd[c] * sd[c], d = mo - out[c];
+              const float q = __builtin_fmaf(d, d, so * so) / var;
+              kl += present ? ((ls - lso) + 0.5f * q) - 0.5f : 0.0f;
+              dz[c] = present ? __builtin_fmaf(w, -d / var, dz[c]) : dz[c];
+              gls[c] = present ? __builtin_fmaf(w, 1.0f - q, gls[c]) : gls[c];
+            }
+          }
+        }
+        const bool ent_on = x.entropy_coef != 0.0f;
+        const float we = inv_n * x.entropy_coef;
+#pragma unroll
+        for (int c = 0; c < 32; ++c) {
+          if (c < A) {
+            ent += present ? m.log_std[c] + 1.4189385f : 0.0f;             // 0.5 log(2 pi e)
+            if (ent_on) gls[c] = present ? gls[c] - we : gls[c];           // d (-entropy_coef H) / d ls = -entropy_coef
+          }
+        }
+      }
       __syncthreads();
       stage_dz(gls, T, lane);
       __syncthreads();
@@ -437,26 +514,46 @@ __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const f
 #pragma unroll
       for (int c = 0; c < 32; ++c) dz[c] = 0.0f;
       dz[0] = (vf_coef * inv_n) * (2.0f * err);
+      if constexpr (LOSS) {
+        if (x.vf_clip > 0.0f) {
+          // max((v - ret)^2, (v_c - ret)^2): where the clipped error is the larger one its gradient is the loss's, and that
+          // is zero where the clamp cut (v_c does not move with v)
+          const float vo = present ? x.val_old[s] : 0.0f;
+          const float dv = out[0] - vo;
+          const float cl = dv < -x.vf_clip ? -x.vf_clip : dv > x.vf_clip ? x.vf_clip : dv;
+          const float err_c = present ? (vo + cl) - ret[s] : 0.0f;
+          const float vf_c = err_c * err_c;
+          const bool clipped = vf_c > vf;
+          dz[0] = clipped ? (cl == dv ? (vf_coef * inv_n) * (2.0f * err_c) : 0.0f) : dz[0];
+          vf = clipped ? vf_c : vf;
+        }
+      }
     }
     net_backward(vnet, D, L, 1, obs, s0, n, keep, S, T, lane, h, dz, G + Pp + A);
-    // ---- the two loss sums
+    // ---- the loss sums
     T[lane * PPO_TT + 0] = pg;
     T[lane * PPO_TT + 1] = vf;
+    if constexpr (LOSS) {
+      T[lane * PPO_TT + 2] = kl;
+      T[lane * PPO_TT + 3] = ent;
+    }
     __syncthreads();
-    col_sum(T, 2, G + P, lane);
+    col_sum(T, NS, G + P, lane);
     __syncthreads();
   }
-  float* w = work + size_t(blockIdx.x) * size_t(P + 2);
-  for (int e = lane; e < P + 2; e += 64) w[e] = G[e];
+  float* w = work + size_t(blockIdx.x) * size_t(P + NS);
+  for (int e = lane; e < P + NS; e += 64) w[e] = G[e];
 }
 
-// the partial gradients of the G workgroups, summed in ascending order: grad [P], loss [2] (accumulate: added to what is there)
+// the partial gradients of the G workgroups, summed in ascending order: grad [P], loss [NS] (accumulate: added to what is
+// there); NS = 2 loss sums, PPO_LOSS_SUMS for the full-loss form
+template <int NS>
 __global__ __launch_bounds__(256) void k_ppo_reduce(const float* __restrict__ work, int G, int P, int accumulate,
                                                     float* __restrict__ grad, float* __restrict__ loss) {
   const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= P + 2) return;
+  if (p >= P + NS) return;
   float acc = work[p];
-  for (int g = 1; g < G; ++g) acc += work[size_t(g) * size_t(P + 2) + size_t(p)];
+  for (int g = 1; g < G; ++g) acc += work[size_t(g) * size_t(P + NS) + size_t(p)];
   float* dst = p < P ? grad + p : loss + (p - P);
   *dst = accumulate ? *dst + acc : acc;
 }
@@ -552,6 +649,20 @@ __global__ __launch_bounds__(64) void k_adv_finish(const double* __restrict__ st
   out[2] = n;
 }
 
+// RLlib's rule for the KL coefficient, once per update: one thread, in double, nothing contracted.  sums [4] are the loss
+// sums of the last epoch's gradient pass (sums[2] = sum KL), mean_std_n[2] the sample count; state = {coef, mean KL of this
+// update} lives on the device, so that a replayed graph advances it
+__global__ __launch_bounds__(64) void k_kl_adapt(const float* __restrict__ sums, const double* __restrict__ mean_std_n,
+                                                 double* state, double kl_target) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const double mean_kl = double(sums[2]) / mean_std_n[2];
+  double coef = state[0];
+  if (mean_kl > 2.0 * kl_target) coef = coef * 1.5;
+  else if (mean_kl < 0.5 * kl_target) coef = coef * 0.5;
+  state[0] = coef;
+  state[1] = mean_kl;
+}
+
 // ---- Adam (torch.optim.Adam without weight decay, amsgrad or maximize) on the packed buffers.  state = {t, beta1^t,
 // beta2^t} in double, on the device, so that a graph replay advances it.  ONE workgroup: every lane reads the state, the
 // barrier follows, then lane 0 alone writes it -- no lane of another workgroup exists that could read the new state for the
@@ -590,8 +701,12 @@ inline int ppo_lds_limit() {
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   if (done_dev == dev) return FS_OK;
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_eval), hipFuncAttributeMaxDynamicSharedMemorySize,
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_eval<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               fs::PPO_LDS_BYTES));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_eval<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              fs::PPO_LDS_BYTES));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_grad<true, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, fs::PPO_LDS_BYTES));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_grad<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               fs::PPO_LDS_BYTES));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_grad<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -600,14 +715,26 @@ inline int ppo_lds_limit() {
   return FS_OK;
 }
 
-int launch_ppo_eval(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act, float* logp,
-                    float* val) {
+template <bool DIST>
+static int launch_ppo_eval_any(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act,
+                               float* logp, float* val, float* mean_old) {
   if (int rc = ppo_lds_limit()) return rc;
   const long long tiles = (n + fs::PPO_TILE - 1) / fs::PPO_TILE;
   const int grid = int(tiles < 1024 ? tiles : 1024);
-  hipLaunchKernelGGL(fs::k_ppo_eval, dim3(grid), dim3(64), fs::ppo_eval_lds(m.D, m.L), stream, m, n, obs, act, logp, val);
+  hipLaunchKernelGGL(fs::k_ppo_eval<DIST>, dim3(grid), dim3(64), fs::ppo_eval_lds(m.D, m.L), stream, m, n, obs, act, logp, val,
+                     mean_old);
   HIP_TRY(hipGetLastError());
   return FS_OK;
+}
+
+int launch_ppo_eval(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act, float* logp,
+                    float* val) {
+  return launch_ppo_eval_any<false>(stream, m, n, obs, act, logp, val, nullptr);
+}
+
+int launch_ppo_eval_dist(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act, float* logp,
+                         float* val, float* mean_old) {
+  return launch_ppo_eval_any<true>(stream, m, n, obs, act, logp, val, mean_old);
 }
 
 int launch_gae(hipStream_t stream, int K, long long R, const float* rew, const float* val, const float* last_val,
@@ -626,9 +753,30 @@ static int launch_ppo_grad_any(hipStream_t stream, const fs::PpoView& m, long lo
   if (int rc = ppo_lds_limit()) return rc;
   const int G = fs::ppo_groups(n, m.D, m.A, m.L), P = fs::ppo_params(m.D, m.A, m.L);
   hipLaunchKernelGGL(fs::k_ppo_grad<N_DEV>, dim3(G), dim3(64), fs::ppo_grad_lds(m.D, m.A, m.L), stream, m, n, obs, act,
-                     logp_old, adv, ret, mean_std, lo, hi, vf_coef, inv_n, work);
+                     logp_old, adv, ret, mean_std, lo, hi, vf_coef, inv_n, work, fs::PpoLossArgs{});
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(fs::k_ppo_reduce, dim3((P + 2 + 255) / 256), dim3(256), 0, stream, work, G, P, accumulate, grad, loss);
+  hipLaunchKernelGGL(fs::k_ppo_reduce<2>, dim3((P + 2 + 255) / 256), dim3(256), 0, stream, work, G, P, accumulate, grad, loss);
+  HIP_TRY(hipGetLastError());
+  return FS_OK;
+}
+
+// the full-loss form: the workgroups of the plain form (ppo_groups), four loss sums
+int launch_ppo_grad_loss(hipStream_t stream, const fs::PpoView& m, const fs::PpoLossArgs& x, long long n, const float* obs,
+                         const float* act, const float* logp_old, const double* adv, const float* ret, const double* mean_std_n,
+                         float lo, float hi, float vf_coef, int accumulate, float* grad, float* loss, float* work) {
+  if (int rc = ppo_lds_limit()) return rc;
+  constexpr int NS = fs::PPO_LOSS_SUMS;
+  const int G = fs::ppo_groups(n, m.D, m.A, m.L), P = fs::ppo_params(m.D, m.A, m.L);
+  hipLaunchKernelGGL((fs::k_ppo_grad<true, true>), dim3(G), dim3(64), fs::ppo_grad_loss_lds(m.D, m.A, m.L), stream, m, n, obs,
+                     act, logp_old, adv, ret, mean_std_n, lo, hi, vf_coef, 0.0f, work, x);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(fs::k_ppo_reduce<NS>, dim3((P + NS + 255) / 256), dim3(256), 0, stream, work, G, P, accumulate, grad, loss);
+  HIP_TRY(hipGetLastError());
+  return FS_OK;
+}
+
+int launch_kl_adapt(hipStream_t stream, const float* loss_sums, const double* mean_std_n, double* kl_state, double kl_target) {
+  hipLaunchKernelGGL(fs::k_kl_adapt, dim3(1), dim3(64), 0, stream, loss_sums, mean_std_n, kl_state, kl_target);
   HIP_TRY(hipGetLastError());
   return FS_OK;
 }

@@ -11,6 +11,10 @@ gradient buffer the kernel writes, so ``allreduce_gradients`` and ``opt.step()``
 (``fs_ppo_grad_n_dev``) and Adam on the packed buffers (``fs_adam_dev``) join the three kernels above, so nothing between
 two rollouts needs the host: a fixed sequence of launches that can be captured into a graph.  After
 ``adopt_parameters()`` the module's parameters ARE views into the packed weights, the counterpart of ``attach_grads()``.
+
+The loss the reference trains with (RLlib's PPO: KL penalty with an adaptive coefficient, clipped value loss, entropy
+bonus) is three more entry points -- ``evaluate_dist`` (``fs_ppo_eval_dist_dev``), ``gradients_loss``
+(``fs_ppo_grad_loss_dev``), ``kl_adapt`` (``fs_kl_adapt_dev``) -- and keywords of ``update()``; every term is off by default.
 """
 import ctypes as C
 
@@ -87,6 +91,11 @@ class DeviceLearner(object):
         self._adopted, self._cache = False, {}
         self.m = self.v = self.state = None                                      # Adam's buffers (adam_step)
         self._stats = self._mean_std_n = None
+        # the full loss (gradients_loss): {sum pg, sum vfl, sum KL, sum H} of the last call; {kl_coef, mean KL} (kl_adapt)
+        self.loss_sums = torch.zeros(4, dtype=torch.float32, device=dev)
+        self.kl_state = torch.tensor([0.2, 0.0], dtype=torch.float64, device=dev)   # (update(): kl_coef_init on its first KL call)
+        self._kl_started = False
+        self._work_loss = None
         off = self.n_policy
         self.struct = L.fs_ppo_model(struct_size=C.sizeof(L.fs_ppo_model), obs_dim=D, act_dim=A, num_hidden=self.num_hidden,
                                      hidden_width=WIDTH, activation=0, policy_weights_dev=self.weights.data_ptr(),
@@ -253,6 +262,80 @@ class DeviceLearner(object):
                                                float(clip), float(vf_coef), int(bool(accumulate)), self.grad.data_ptr(),
                                                self.loss.data_ptr(), work.data_ptr(), work.numel()), self.sim.lib)
 
+    # ---- the reference's loss: KL penalty, clipped value loss, entropy (fs_ppo_eval_dist_dev, fs_ppo_grad_loss_dev,
+    # fs_kl_adapt_dev)
+    def evaluate_dist(self, obs, act):
+        """``evaluate()`` that also returns the head's means: ``(logp [n], val [n], mean_old [n, A])``, the old
+        distribution of the KL term (``val`` serves as the old value of the clipped value loss).  ``logp`` and ``val``
+        hold the bits ``evaluate()`` gives."""
+        torch = self.torch
+        n = int(obs.shape[0])
+        obs, act = self._f32(obs, (n, self.D), "obs"), self._f32(act, (n, self.A), "act")
+        logp = torch.empty(n, dtype=torch.float32, device=self.device)
+        val = torch.empty(n, dtype=torch.float32, device=self.device)
+        mean_old = torch.empty(n, self.A, dtype=torch.float32, device=self.device)
+        self._bind()
+        self._eval_dist(n, obs, act, logp, val, mean_old)
+        return logp, val, mean_old
+
+    def _eval_dist(self, n, obs, act, logp, val, mean_old):
+        L.check(self.sim.lib.fs_ppo_eval_dist_dev(self.sim._h, C.byref(self.struct), n, obs.data_ptr(), act.data_ptr(),
+                                                  logp.data_ptr(), val.data_ptr(), mean_old.data_ptr()), self.sim.lib)
+
+    def _loss_workspace(self, n):
+        need = int(self.sim.lib.fs_ppo_loss_workspace(C.byref(self.struct), n))
+        if self._work_loss is None or self._work_loss.numel() < need:
+            self._work_loss = self.torch.empty(need, dtype=self.torch.float32, device=self.device)
+        return self._work_loss
+
+    def gradients_loss(self, obs, act, logp_old, adv, ret, mean_std_n, mean_old=None, log_std_old=None, val_old=None,
+                       clip=0.2, vf_coef=0.5, vf_clip=None, entropy_coef=0.0, kl=False, accumulate=False):
+        """``gradients_n()`` for the reference's loss (include/flowsim.h ``fs_ppo_loss``): per present sample
+        ``-pg + kl_coef KL(old || new) + vf_coef max((v - ret)^2, (v_c - ret)^2) - entropy_coef H`` over the sample count
+        in ``mean_std_n``.  ``kl=True``: the KL term, its coefficient read ON THE DEVICE from ``self.kl_state[0]``
+        (``mean_old [n, A]`` and ``log_std_old [A]`` are then needed); ``vf_clip`` (``None`` / ``inf``: off) needs
+        ``val_old [n]``.  The gradient goes to ``self.grad``, ``{sum pg, sum vfl, sum KL, sum H}`` to ``self.loss_sums``
+        (returned); ``self.loss`` is not touched.  With every term off, ``self.grad`` and ``self.loss_sums[:2]`` hold the
+        bits of ``gradients_n()``."""
+        torch = self.torch
+        n = int(obs.shape[0])
+        obs, act = self._f32(obs, (n, self.D), "obs"), self._f32(act, (n, self.A), "act")
+        logp_old, ret = self._f32(logp_old, (n,), "logp_old"), self._f32(ret, (n,), "ret")
+        if adv.dtype != torch.float64 or tuple(adv.shape) != (n,) or adv.device != self.device:
+            raise ValueError("DeviceLearner: adv must be a float64 tensor of shape (%d,) on %s" % (n, self.device))
+        if mean_std_n.dtype != torch.float64 or mean_std_n.numel() != 3 or mean_std_n.device != self.device:
+            raise ValueError("DeviceLearner: mean_std_n must be a float64 tensor of 3 elements on %s" % self.device)
+        mean_old = None if mean_old is None else self._f32(mean_old, (n, self.A), "mean_old")
+        log_std_old = None if log_std_old is None else self._f32(log_std_old, (self.A,), "log_std_old")
+        val_old = None if val_old is None else self._f32(val_old, (n,), "val_old")
+        work = self._loss_workspace(n)
+        self._bind()
+        self._grad_loss(n, obs, act, logp_old, mean_old, log_std_old, val_old, adv.contiguous(), ret, mean_std_n, clip, vf_coef,
+                        vf_clip, entropy_coef, kl, accumulate, work)
+        return self.loss_sums
+
+    def _grad_loss(self, n, obs, act, logp_old, mean_old, log_std_old, val_old, adv64, ret, mean_std_n, clip, vf_coef, vf_clip,
+                   entropy_coef, kl, accumulate, work):
+        ptr = lambda t: None if t is None else t.data_ptr()                        # noqa: E731
+        loss = L.fs_ppo_loss(struct_size=C.sizeof(L.fs_ppo_loss), clip=float(clip), vf_coef=float(vf_coef),
+                             vf_clip=0.0 if vf_clip is None else float(vf_clip), entropy_coef=float(entropy_coef),
+                             kl_state_dev=self.kl_state.data_ptr() if kl else None)
+        L.check(self.sim.lib.fs_ppo_grad_loss_dev(self.sim._h, C.byref(self.struct), C.byref(loss), n, obs.data_ptr(),
+                                                  act.data_ptr(), logp_old.data_ptr(), ptr(mean_old), ptr(log_std_old),
+                                                  ptr(val_old), adv64.data_ptr(), ret.data_ptr(), mean_std_n.data_ptr(),
+                                                  int(bool(accumulate)), self.grad.data_ptr(), self.loss_sums.data_ptr(),
+                                                  work.data_ptr(), work.numel()), self.sim.lib)
+
+    def kl_adapt(self, kl_target, mean_std_n, loss_sums=None):
+        """RLlib's rule, on the device, in double: ``mean_kl = loss_sums[2] / mean_std_n[2]``; ``self.kl_state[0]`` times
+        1.5 where it exceeds ``2 kl_target``, times 0.5 where it is below ``0.5 kl_target``; ``self.kl_state[1] = mean_kl``.
+        Once per update, after the last epoch's ``gradients_loss`` (and the all-reduce of ``loss_sums``)."""
+        sums = self.loss_sums if loss_sums is None else loss_sums
+        self._bind()
+        L.check(self.sim.lib.fs_kl_adapt_dev(self.sim._h, sums.data_ptr(), mean_std_n.data_ptr(), self.kl_state.data_ptr(),
+                                             float(kl_target)), self.sim.lib)
+        return self.kl_state
+
     def _adam_buffers(self):
         torch = self.torch
         if self.state is None:
@@ -282,7 +365,7 @@ class DeviceLearner(object):
         return buf
 
     def update(self, shards, epochs=4, clip=0.2, vf_coef=0.5, gamma=0.999, lam=0.97, lr=3e-4, betas=(0.9, 0.999), eps=1e-8,
-               group=None):
+               group=None, kl_target=None, kl_coef_init=0.2, entropy_coef=0.0, vf_clip=None):
         """One PPO update over ``shards`` = [(obs [K+1, R, D], act [K, R(, A)], rew [K, R], done [K, R] uint8)], the whole of
         train_vec.ppo_update on the learner's stream: per shard eval (two launches), gae and the statistics; the
         all-reduce of the three sums (in a data-parallel run); finish; per epoch the gradient over the shards (kernel and
@@ -291,7 +374,14 @@ class DeviceLearner(object):
         shards as the rollouts return them), so the call can be captured into a graph after one eager call ON the capture
         stream (that call binds the handle to the stream -- fs_set_stream synchronises -- and makes every buffer, the
         library's scratch for the statistics included).  The parameters must have been adopted (``adopt_parameters()``):
-        Adam moves ``self.weights``."""
+        Adam moves ``self.weights``.
+        ``kl_target`` / ``entropy_coef`` / ``vf_clip``: the reference's loss (``gradients_loss``).  With any of them on,
+        the first eval of a shard is ``evaluate_dist`` (its ``val`` is the old value) followed by one device-to-device
+        copy of ``log_std`` into the shard's ``log_std_old``; every epoch's gradient is ``gradients_loss``; after the last
+        epoch come the all-reduce of ``loss_sums`` (data-parallel runs) and, with ``kl_target`` set, ``kl_adapt``: the
+        coefficient lives in ``self.kl_state`` on the device (``kl_coef_init`` before the first such update), so a
+        replayed graph advances it.  ``self.loss`` is then left alone: the sums are ``self.loss_sums``.  With the
+        defaults the launches are exactly the 17 above."""
         import torch.distributed as dist
         torch, lib, h = self.torch, self.sim.lib, self.sim._h
         if self._stats is None:
@@ -301,6 +391,13 @@ class DeviceLearner(object):
                                "adopted parameters are views of them")
         self._adam_buffers()
         self._bind()
+        kl_on = kl_target is not None
+        vclip_on = vf_clip is not None and 0.0 < float(vf_clip) < float("inf")
+        full = kl_on or vclip_on or float(entropy_coef) != 0.0
+        if kl_on and not self._kl_started:
+            self.kl_state[0].fill_(float(kl_coef_init))       # (the first such call is eager: never inside a capture)
+            self.kl_state[1].fill_(0.0)
+            self._kl_started = True
         prepared = []
         for j, (obs, act, rew, done) in enumerate(shards):
             K, R = int(rew.shape[0]), int(rew.shape[1])
@@ -312,8 +409,16 @@ class DeviceLearner(object):
             a = self._f32(act.reshape(n, -1), (n, self.A), "act")
             rew, done = self._f32(rew, (K, R), "rew"), done.contiguous()
             b = self._shard_buffers(j, K, R)
-            L.check(lib.fs_ppo_eval_dev(h, C.byref(self.struct), n, o.data_ptr(), a.data_ptr(), b["logp"].data_ptr(),
-                                        b["val"].data_ptr()), lib)
+            if full:
+                if "mean_old" not in b:
+                    b["mean_old"] = torch.empty(n, self.A, dtype=torch.float32, device=self.device)
+                    b["log_std_old"] = torch.empty(self.A, dtype=torch.float32, device=self.device)
+                self._eval_dist(n, o, a, b["logp"], b["val"], b["mean_old"])
+                b["log_std_old"].copy_(self.weights[self.n_policy:self.n_policy + self.A])
+                self._loss_workspace(n)
+            else:
+                L.check(lib.fs_ppo_eval_dev(h, C.byref(self.struct), n, o.data_ptr(), a.data_ptr(), b["logp"].data_ptr(),
+                                            b["val"].data_ptr()), lib)
             L.check(lib.fs_ppo_eval_dev(h, C.byref(self.struct), R, last.data_ptr(), None, None, b["last_val"].data_ptr()), lib)
             L.check(lib.fs_gae_dev(h, K, R, rew.data_ptr(), b["val"].data_ptr(), b["last_val"].data_ptr(), done.data_ptr(),
                                    float(gamma), float(lam), b["adv"].data_ptr(), b["ret"].data_ptr()), lib)
@@ -326,8 +431,19 @@ class DeviceLearner(object):
         L.check(lib.fs_adv_finish_dev(h, self._stats.data_ptr(), self._mean_std_n.data_ptr()), lib)
         for _ in range(epochs):
             for j, (n, o, a, b) in enumerate(prepared):
-                self._grad_n(n, o, a, b["logp"], b["adv64"], b["ret"], self._mean_std_n, clip, vf_coef, j > 0, self._work)
+                if full:
+                    self._grad_loss(n, o, a, b["logp"], b["mean_old"], b["log_std_old"], b["val"], b["adv64"], b["ret"],
+                                    self._mean_std_n, clip, vf_coef, vf_clip if vclip_on else None, entropy_coef, kl_on,
+                                    j > 0, self._work_loss)
+                else:
+                    self._grad_n(n, o, a, b["logp"], b["adv64"], b["ret"], self._mean_std_n, clip, vf_coef, j > 0, self._work)
             if spread:
                 dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=group)
             self.adam_step(lr, betas, eps)
+        if full:
+            if spread:
+                dist.all_reduce(self.loss_sums, op=dist.ReduceOp.SUM, group=group)
+            if kl_on:
+                self.kl_adapt(kl_target, self._mean_std_n)
+            return self.loss_sums
         return self.loss

@@ -632,6 +632,57 @@ int fs_adv_finish_dev(fs_handle h, const double* stats_dev, double* mean_std_n_d
 int fs_adam_dev(fs_handle h, int64_t num_params, float* weights_dev, const float* grad_dev, float* m_dev, float* v_dev,
                 double* state_dev, double lr, double beta1, double beta2, double eps);
 
+/* ---- the reference's PPO loss: KL penalty, clipped value loss, entropy --------
+ * The loss RLlib's PPO optimises (the reference's examples/train.py trains with it), per present sample, over the sample
+ * count n of the whole update:
+ *   -pg + kl_coef KL + vf_coef vfl - entropy_coef H
+ *   pg  = as in fs_ppo_grad_dev
+ *   KL  = sum_c ls - ls_o + (exp(2 ls_o) + (mu_o - mu)^2) / (2 exp(2 ls)) - 0.5        (old || new, diagonal Gaussians)
+ *   H   = sum_c ls + 0.5 log(2 pi e)
+ *   vfl = max((v - ret)^2, (v_c - ret)^2),   v_c = v_o + clamp(v - v_o, -vf_clip, +vf_clip)
+ * mu, ls: the head's means and the free log std now; mu_o, ls_o, v_o: means, log std and value at the time of the rollout.
+ * clip: the surrogate's (>= 0).  vf_clip <= 0 or not finite: no value clipping, vfl = (v - ret)^2.  entropy_coef == 0: no
+ * entropy term.  kl_state_dev == NULL: no KL term; otherwise kl_state_dev [2] = {kl_coef, mean KL of the last update} in
+ * double ON THE DEVICE -- the kernel reads the coefficient there and fs_kl_adapt_dev advances it, so a replayed graph
+ * trains with the adapted value.  A term that is off is selected out, not multiplied by zero, and its inputs are not read.
+ * A wrong struct_size, a NaN among the coefficients or clip < 0: FS_ERR_INVALID, with a message that names fs_ppo_loss. */
+typedef struct fs_ppo_loss {
+  uint32_t struct_size;               /* sizeof(fs_ppo_loss) */
+  float clip;                         /* the surrogate's clip range */
+  float vf_coef;
+  float vf_clip;                      /* <= 0 or not finite: off */
+  float entropy_coef;                 /* 0: off */
+  const double* kl_state_dev;         /* {kl_coef, mean KL}, device; NULL: off */
+} fs_ppo_loss;
+
+/* fs_ppo_eval_dev that also writes the head's means, mean_old_dev [n, A]: the no_grad pass of an update whose loss has the
+ * KL term (val_dev then serves as v_o).  act_dev, logp_dev and mean_old_dev must not be NULL.  logp_dev and val_dev hold
+ * the bits fs_ppo_eval_dev gives.  fs_last_kernel reports "k_ppo_eval". */
+int fs_ppo_eval_dist_dev(fs_handle h, const fs_ppo_model* model, int64_t n, const float* obs_dev, const float* act_dev,
+                         float* logp_dev, float* val_dev, float* mean_old_dev);
+/* Floats of work_dev that fs_ppo_grad_loss_dev needs: the workgroups of fs_ppo_workspace times (P + 4) -- four loss sums
+ * behind a partial gradient instead of two (0: the model or n is not valid). */
+size_t fs_ppo_loss_workspace(const fs_ppo_model* model, int64_t n);
+/* fs_ppo_grad_n_dev for the loss above: grad_dev [P] as there, loss_sums_dev [4] = {sum pg, sum vfl, sum KL, sum H} over the
+ * present samples (sum KL is 0 without the KL term).  mean_old_dev [n, A], log_std_old_dev [A]: may be NULL only without a KL term; val_old_dev
+ * [n]: may be NULL only without value clipping.  Nothing of an absent row (a NaN in its action row) reaches an output, its
+ * mean_old and val_old included.  The mapping, the workgroup count and so the order of every sum are fs_ppo_grad_dev's:
+ * with every term off, grad_dev and loss_sums_dev[0..1] hold the bits of fs_ppo_grad_n_dev.  fs_last_kernel reports
+ * "k_ppo_grad_loss". */
+int fs_ppo_grad_loss_dev(fs_handle h, const fs_ppo_model* model, const fs_ppo_loss* loss, int64_t n, const float* obs_dev,
+                         const float* act_dev, const float* logp_old_dev, const float* mean_old_dev,
+                         const float* log_std_old_dev, const float* val_old_dev, const double* adv_dev, const float* ret_dev,
+                         const double* mean_std_n_dev, int accumulate, float* grad_dev, float* loss_sums_dev, float* work_dev,
+                         size_t work_floats);
+/* RLlib's adaptive KL coefficient, once per update, after the last epoch (and after the data-parallel all-reduce of
+ * loss_sums_dev).  One thread, in double, nothing contracted:
+ *   mean_kl = (double)loss_sums[2] / mean_std_n[2]
+ *   coef *= 1.5 if mean_kl > 2.0 kl_target;   coef *= 0.5 if mean_kl < 0.5 kl_target
+ *   kl_state = {coef, mean_kl}
+ * kl_target must be positive and finite.  fs_last_kernel reports "k_kl_adapt". */
+int fs_kl_adapt_dev(fs_handle h, const float* loss_sums_dev, const double* mean_std_n_dev, double* kl_state_dev,
+                    double kl_target);
+
 /* Append the CURRENT state of one replica to a CSV file (header `time,id,x,speed,lane_number` when the file is new;
  * one row per vehicle, id = slot index, free slots of open networks skipped): the trajectory ("emission") dump of
  * flow/core/kernel/simulation/traci.py:95-101 (SUMO's --emission-output) for callers without the Python layer;
