@@ -48,25 +48,28 @@ def parse_args(args):
                              '(DeviceLearner.update); implies --device_update')
     parser.add_argument('--epochs', type=int, default=4, help='device: passes over a rollout fragment per update')
     from train_vec import add_ppo_loss_flags
-    add_ppo_loss_flags(parser)                              # --kl_target --kl_coeff --entropy_coeff --vf_clip: all off by default
+    add_ppo_loss_flags(parser)              # --kl_target --kl_coeff --entropy_coeff --vf_clip --sgd_minibatch_size: all off by default
     parser.add_argument('--reference_ppo', action='store_true',
                         help='device: the loss and settings the reference trains with (RLlib PPO as its train.py sets it '
                              'up): --kl_target 0.02 --kl_coeff 0.2 --vf_clip 10 --epochs 10, vf_loss_coeff 1.0, '
-                             'clip_param 0.3.  Not reproduced: RLlib\'s minibatches of 128 (every epoch is one full-batch '
-                             'step here) and its head of 2 x act_dim outputs (the log std is a free parameter here)')
+                             'clip_param 0.3.  With --sgd_minibatch_size 128 --device_adam on top, every epoch is a '
+                             'shuffled pass of minibatch steps: the reference\'s optimisation.  Not reproduced: its head '
+                             'of 2 x act_dim outputs (the log std is a free parameter here)')
     return parser.parse_known_args(args)[0]
 
 
 def ppo_loss_settings(flags):
     """train_on_device's loss keywords from the flags.  --reference_ppo: what the reference's train.py hands RLlib
     (kl_target 0.02, num_sgd_iter 10) on top of RLlib's PPO defaults (kl_coeff 0.2, vf_clip_param 10, vf_loss_coeff 1.0,
-    clip_param 0.3, entropy_coeff 0); gamma 0.999 and lambda 0.97 are train_on_device's already.  Not reproduced:
-    sgd_minibatch_size 128 (an epoch is ONE step over the whole fragment here) and the head of 2 act_dim outputs."""
+    clip_param 0.3, entropy_coeff 0); gamma 0.999 and lambda 0.97 are train_on_device's already.  --reference_ppo keeps
+    its meaning: the minibatches are a flag of their own, and ``--reference_ppo --sgd_minibatch_size 128 --device_adam`` is
+    the reference's optimisation (num_sgd_iter passes of sgd_minibatch_size samples).  Not reproduced: the head of
+    2 act_dim outputs."""
     if flags.reference_ppo:
         return dict(kl_target=0.02, kl_coeff=0.2, vf_clip=10.0, epochs=10, vf_coef=1.0, clip=0.3,
-                    entropy_coeff=flags.entropy_coeff)
+                    entropy_coeff=flags.entropy_coeff, sgd_minibatch_size=flags.sgd_minibatch_size)
     return dict(kl_target=flags.kl_target, kl_coeff=flags.kl_coeff, vf_clip=flags.vf_clip, epochs=flags.epochs,
-                entropy_coeff=flags.entropy_coeff)
+                entropy_coeff=flags.entropy_coeff, sgd_minibatch_size=flags.sgd_minibatch_size)
 
 
 def load_experiment(name):

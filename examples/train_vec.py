@@ -108,7 +108,7 @@ def gae(rew, val, done, last_val, gamma=0.999, lam=0.97):
 
 
 def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None, learner=None, kl=None, entropy_coef=0.0, vf_clip=None,
-               vf_coef=0.5):
+               vf_coef=0.5, minibatch=None, shuffle_seed=0, epoch0=0):
     """One PPO update over `shards` = [(obs [K+1, R, D], act [K, R, A], rew [K, R], done [K, R])]: the shards this
     process holds (one per rank in data-parallel runs, all of them in a single process).  Every quantity that couples the
     shards is a SUM: the advantage statistics and the gradient -- summed over the local shards here, over the ranks by
@@ -126,8 +126,16 @@ def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None, learner=None, kl
         v_c = v_o + clamp(v - v_o, -vf_clip, +vf_clip)
     with mu_o, ls_o, v_o from the no_grad pass (``pi.logp_value_dist``).  ``vf_clip`` None or inf: vfl = (v - ret)^2.
     After the last epoch ``kl.adapt`` sees that epoch's mean KL (summed over shards and ranks).  With a learner the same
-    loss runs on fs_ppo_eval_dist_dev / fs_ppo_grad_loss_dev.  With the defaults the arithmetic is what it was."""
+    loss runs on fs_ppo_eval_dist_dev / fs_ppo_grad_loss_dev.  With the defaults the arithmetic is what it was.
+    ``minibatch`` (RLlib's ``sgd_minibatch_size``, a per-shard size B; None: everything above): an epoch is a shuffled
+    pass of minibatch steps, the way RLlib's do_minibatch_sgd makes ``num_sgd_iter`` passes (_ppo_epochs_minibatch states
+    the semantics; it is the definition DeviceLearner.update(minibatch=) is tested against).  Epoch e of this call draws
+    ``epoch_permutation(shuffle_seed, epoch0 + e, n)``.  With a ``learner`` (the --device_update path, torch's Adam) this is
+    not built: use --device_adam, where the whole step is one launch."""
     from flow_amd.dist import allreduce_gradients, allreduce_sum
+    if minibatch is not None and learner is not None:
+        raise NotImplementedError("ppo_update(learner=..., minibatch=...): minibatch steps around torch's Adam (--device_update) "
+                                  "are not built; --device_adam runs them on the device (DeviceLearner.update(minibatch=))")
     vclip = vf_clip is not None and 0.0 < float(vf_clip) < float("inf")
     full = kl is not None or vclip or float(entropy_coef) != 0.0
     prepared, stats = [], None
@@ -173,6 +181,11 @@ def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None, learner=None, kl
     mean = stats[0] / n
     std = ((stats[1] - n * mean * mean) / (n - 1)).clamp_min(0).sqrt()
     params = list(pi.parameters())
+    if minibatch is not None:
+        _ppo_epochs_minibatch(pi, opt, prepared, params, epochs, clip, group, kl, float(entropy_coef),
+                              float(vf_clip) if vclip else None, vf_coef, mean, std, n, full, int(minibatch), shuffle_seed,
+                              epoch0)
+        return
     if full:
         _ppo_epochs_full(pi, opt, prepared, params, epochs, clip, group, learner, kl, float(entropy_coef),
                          float(vf_clip) if vclip else None, vf_coef, mean, std, n)
@@ -254,9 +267,75 @@ def _ppo_epochs_full(pi, opt, prepared, params, epochs, clip, group, learner, kl
         kl.adapt(float(allreduce_sum(sum_kl.double().reshape(1), group)[0]) / float(n))
 
 
+def _ppo_epochs_minibatch(pi, opt, prepared, params, epochs, clip, group, kl, entropy_coef, vf_clip, vf_coef, mean, std, n, full,
+                          B, shuffle_seed, epoch0):
+    """The epochs of ppo_update as shuffled passes of minibatch steps -- the definition of ``minibatch=B``:
+    * the advantages stay standardised by (mean, std) of the WHOLE batch, and logp_old, mu_old, ls_old, v_old by the one
+      no_grad pass before the first epoch; kl.coef stays constant through the update;
+    * epoch e permutes a shard's n rows with perm = epoch_permutation(shuffle_seed, epoch0 + e, n); minibatch k is rows
+      perm[kB : (k + 1)B] (the last one kept when it is short), ceil(n / B) steps per epoch in ascending k; with several
+      shards (of equal n: ValueError otherwise) step k takes those rows of EVERY shard;
+    * one step: ppo_update's loss (the terms on or off) summed over the minibatch's present rows of all shards and ranks,
+      divided by THEIR count c -- not by n --, its gradient, one optimiser step; c == 0: no step at all;
+    * after the last epoch kl.adapt sees (the sum of that epoch's minibatches' per-sample KL, each evaluated before its
+      own step) / n."""
+    import math
+    from flow_amd.dist import allreduce_gradients, allreduce_sum
+    from flow_amd.utils.device_ppo import epoch_permutation
+    sizes = sorted(set(int(p[0].shape[0]) for p in prepared))
+    if len(sizes) != 1:
+        raise ValueError("ppo_update(minibatch=): the shards must hold the same number of samples (got %s)" % sizes)
+    n_rows = sizes[0]
+    if B < 1:
+        raise ValueError("ppo_update(minibatch=): the minibatch size must be at least 1 (got %d)" % B)
+    sum_kl = None
+    for e in range(epochs):
+        perm = torch.as_tensor(epoch_permutation(shuffle_seed, epoch0 + e, n_rows), device=prepared[0][0].device)
+        sum_kl = torch.zeros((), dtype=torch.float64, device=prepared[0][0].device)
+        for k in range(-(-n_rows // B)):
+            idx = perm[k * B:(k + 1) * B]
+            opt.zero_grad()
+            total, count = None, 0.0
+            for shard in prepared:
+                o, a, logp_old, adv, ret, present = (None if t is None else t[idx] for t in shard[:6])
+                adv_n = ((adv - mean) / (std + 1e-8)).float()
+                if full:
+                    v_old, mu_old, ls_old = shard[6][idx], shard[7][idx], shard[8]
+                    logp, v, mu, ls = pi.logp_value_dist(o, a)
+                else:
+                    logp, v = pi.logp_value(o, a)
+                ratio = (logp - logp_old).exp()
+                per = -torch.min(ratio * adv_n, ratio.clamp(1 - clip, 1 + clip) * adv_n)
+                vfl = (v - ret).pow(2)
+                if vf_clip is not None:
+                    v_c = v_old + (v - v_old).clamp(-vf_clip, vf_clip)
+                    vfl = torch.max(vfl, (v_c - ret).pow(2))
+                per = per + vf_coef * vfl
+                if kl is not None:
+                    kl_s = (ls - ls_old + ((2.0 * ls_old).exp() + (mu_old - mu).pow(2)) / (2.0 * (2.0 * ls).exp()) - 0.5).sum(-1)
+                    per = per + kl.coef * kl_s
+                    kl_d = kl_s.detach()
+                    sum_kl = sum_kl + (kl_d if present is None else torch.where(present, kl_d, torch.zeros_like(kl_d))).sum().double()
+                if entropy_coef != 0.0:
+                    per = per - entropy_coef * (ls + 0.5 * math.log(2.0 * math.pi * math.e)).sum()
+                if present is not None:
+                    per = torch.where(present, per, torch.zeros_like(per))
+                total = per.sum() if total is None else total + per.sum()
+                count += float(idx.numel()) if present is None else float(present.sum())
+            count = float(allreduce_sum(torch.tensor([count], dtype=torch.float64, device=idx.device), group)[0])
+            if count == 0.0:
+                continue                                     # (nobody present: no step, the optimiser's state untouched)
+            (total / count).backward()                       # the minibatch's own mean, as a sum of per-shard sums
+            allreduce_gradients(params, group)
+            opt.step()
+    if kl is not None and sum_kl is not None:                # (no epoch: no KL was seen, the coefficient stays)
+        kl.adapt(float(allreduce_sum(sum_kl.reshape(1), group)[0]) / float(n))
+
+
 def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epochs=4, lr=3e-4, seed=0, log=print,
                     rank=0, world=1, shared_agents=False, fuse_action_vector=False, device_update=False, device_adam=False,
-                    kl_target=None, kl_coeff=0.2, entropy_coeff=0.0, vf_clip=None, vf_coef=0.5, clip=0.2):
+                    kl_target=None, kl_coeff=0.2, entropy_coeff=0.0, vf_clip=None, vf_coef=0.5, clip=0.2,
+                    sgd_minibatch_size=None):
     """PPO on R replicas of ``flow_params`` with everything in HBM: returns the mean step reward per iteration.
     ``world`` > 1: this process is rank ``rank`` of a data-parallel run (torch.distributed is initialised): it steps its
     block of the R replicas on its own GPU.
@@ -282,7 +361,12 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     trains with -- the KL penalty with its adaptive coefficient (starting at ``kl_coeff``), the entropy bonus, the clipped
     value loss (ppo_update states the loss) -- on whichever path the update takes; ``vf_coef`` and ``clip`` are the value
     loss's weight and the surrogate's clip range.  All off by default.  With a KL target the log shows, per iteration, the
-    mean KL of the update's last epoch and the coefficient after its adaptation."""
+    mean KL of the update's last epoch and the coefficient after its adaptation.
+    ``sgd_minibatch_size`` (RLlib's name; None: one optimiser step per epoch over the whole fragment): every epoch is a
+    shuffled pass of minibatch steps of this many samples (ppo_update(minibatch=) states the semantics).  With
+    ``device_adam`` a step runs on the device (DeviceLearner.update(minibatch=)); the torch update runs the same steps in
+    torch; ``device_update`` alone (torch's Adam around the kernels) does not build them and says so.  The epochs of
+    iteration ``it`` draw the permutations of epochs ``it * epochs ..`` on both paths."""
     from flow_amd.dist import allreduce_sum, shard_range
     from flow_amd.envs import VecFlowEnv
     local = int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else 0
@@ -379,10 +463,12 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
             shard = (obs, act, rew, done)
         if device_adam:
             learner.update([shard], epochs=epochs, lr=lr, clip=clip, vf_coef=vf_coef, kl_target=kl_target,
-                           kl_coef_init=kl_coeff, entropy_coef=entropy_coeff, vf_clip=vf_clip)
+                           kl_coef_init=kl_coeff, entropy_coef=entropy_coeff, vf_clip=vf_clip, minibatch=sgd_minibatch_size,
+                           shuffle_seed=seed)
         else:
             ppo_update(pi, opt, [shard], epochs=epochs, clip=clip, learner=learner, kl=kl, entropy_coef=entropy_coeff,
-                       vf_clip=vf_clip, vf_coef=vf_coef)
+                       vf_clip=vf_clip, vf_coef=vf_coef, minibatch=sgd_minibatch_size, shuffle_seed=seed,
+                       epoch0=it * epochs)
         kl_log = ""
         if kl_target is not None:                              # (read after the update: the device's state under device_adam)
             coef, mean_kl = learner.kl_state.tolist() if device_adam else (kl.coef, kl.mean_kl)
@@ -428,6 +514,9 @@ def add_ppo_loss_flags(ap):
     ap.add_argument("--entropy_coeff", type=float, default=0.0, help="weight of the entropy bonus")
     ap.add_argument("--vf_clip", type=float, default=None,
                     help="clip the value loss: max((v - ret)^2, (v_old + clamp(v - v_old, +-vf_clip) - ret)^2)")
+    ap.add_argument("--sgd_minibatch_size", type=int, default=None,
+                    help="make every epoch a shuffled pass of minibatch steps of this many samples (the reference: 128); on "
+                         "the device with --device_adam.  Default: one step per epoch over the whole fragment")
 
 
 def main(argv=None):
@@ -463,7 +552,7 @@ def main(argv=None):
                                iterations=args.iterations, epochs=args.epochs, lr=args.lr, rank=rank, world=world,
                                device_update=args.device_update or args.device_adam, device_adam=args.device_adam,
                                kl_target=args.kl_target, kl_coeff=args.kl_coeff, entropy_coeff=args.entropy_coeff,
-                               vf_clip=args.vf_clip)
+                               vf_clip=args.vf_clip, sgd_minibatch_size=args.sgd_minibatch_size)
     finally:
         if world > 1 or force:
             import torch.distributed as dist

@@ -47,7 +47,11 @@ EXPORTS = ["fs_create", "fs_destroy", "fs_last_error", "fs_abi_version", "fs_obs
            "fs_get_state", "fs_set_state", "fs_add_vehicle", "fs_dump_trajectory", "fs_last_kernel", "fs_policy_act_dev",
            "fs_policy_rollout_dev", "fs_ppo_eval_dev", "fs_gae_dev", "fs_ppo_workspace", "fs_ppo_grad_dev",
            "fs_ppo_grad_n_dev", "fs_adv_stats_dev", "fs_adv_finish_dev", "fs_adam_dev", "fs_ppo_eval_dist_dev",
-           "fs_ppo_loss_workspace", "fs_ppo_grad_loss_dev", "fs_kl_adapt_dev"]
+           "fs_ppo_loss_workspace", "fs_ppo_grad_loss_dev", "fs_kl_adapt_dev", "fs_ppo_perm_host",
+           "fs_ppo_minibatch_workspace", "fs_ppo_minibatch_dev", "fs_ppo_mb_finish_dev"]
+# fs_ppo_minibatch.mode / .flags
+FS_MB_STEP, FS_MB_PARTIAL = 0, 1
+FS_MB_ACCUMULATE, FS_MB_FIRST, FS_MB_LAST = 1, 2, 4
 
 
 class fs_vehicle_spec(C.Structure):
@@ -126,6 +130,14 @@ class fs_ppo_model(C.Structure):
 class fs_ppo_loss(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("clip", C.c_float), ("vf_coef", C.c_float), ("vf_clip", C.c_float),
                 ("entropy_coef", C.c_float), ("kl_state_dev", C.c_void_p)]
+
+
+class fs_ppo_minibatch(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
+                ("batch", C.c_int64), ("index", C.c_int64), ("seed", C.c_uint64), ("epoch_dev", C.c_void_p),
+                ("count_dev", C.c_void_p), ("weights_dev", C.c_void_p), ("m_dev", C.c_void_p), ("v_dev", C.c_void_p),
+                ("state_dev", C.c_void_p), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double)]
 
 
 _libs = {}
@@ -218,6 +230,17 @@ def load(path=None):
     lib.fs_ppo_grad_loss_dev.restype = C.c_int
     lib.fs_kl_adapt_dev.argtypes = [h, f32p, f64p, f64p, C.c_double]
     lib.fs_kl_adapt_dev.restype = C.c_int
+    lib.fs_ppo_perm_host.argtypes = [C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p]
+    lib.fs_ppo_perm_host.restype = C.c_int
+    lib.fs_ppo_minibatch_workspace.argtypes = [C.POINTER(fs_ppo_model), C.c_int64]
+    lib.fs_ppo_minibatch_workspace.restype = C.c_size_t
+    lib.fs_ppo_minibatch_dev.argtypes = [h, C.POINTER(fs_ppo_model), C.POINTER(fs_ppo_loss), C.POINTER(fs_ppo_minibatch),
+                                         C.c_int64, f32p, f32p, f32p, f32p, f32p, f32p, f64p, f32p, f64p, f32p, f32p, f32p,
+                                         C.c_size_t]
+    lib.fs_ppo_minibatch_dev.restype = C.c_int
+    lib.fs_ppo_mb_finish_dev.argtypes = [h, C.c_int64, f32p, f32p, f32p, f32p, f64p, f64p, C.c_void_p, C.c_int, C.c_double,
+                                         C.c_double, C.c_double, C.c_double]
+    lib.fs_ppo_mb_finish_dev.restype = C.c_int
     if lib.fs_abi_version() != FS_ABI_VERSION:
         raise FatalFlowError("libflowsim.so ABI %d != binding ABI %d" % (lib.fs_abi_version(), FS_ABI_VERSION))
     _libs[path] = lib

@@ -643,15 +643,10 @@ size_t fs_ppo_loss_workspace(const fs_ppo_model* model, int64_t n) {
   return fs::ppo_loss_work_floats(n, pv.D, pv.A, pv.L);
 }
 
-int fs_ppo_grad_loss_dev(fs_handle h, const fs_ppo_model* model, const fs_ppo_loss* loss, int64_t n, const float* obs_dev,
-                         const float* act_dev, const float* logp_old_dev, const float* mean_old_dev,
-                         const float* log_std_old_dev, const float* val_old_dev, const double* adv_dev, const float* ret_dev,
-                         const double* mean_std_n_dev, int accumulate, float* grad_dev, float* loss_sums_dev, float* work_dev,
-                         size_t work_floats) {
-  if (!h || !obs_dev || !act_dev || !logp_old_dev || !adv_dev || !ret_dev || !mean_std_n_dev || !grad_dev || !loss_sums_dev ||
-      !work_dev)
-    return fail(FS_ERR_INVALID, "fs_ppo_grad_loss_dev: NULL argument");
-  const std::string w = "fs_ppo_grad_loss_dev: fs_ppo_loss: ";
+// fs_ppo_loss and the old distribution's pointers -> the kernels' PpoLossArgs (refusals name fs_ppo_loss)
+static int ppo_loss_args(const char* who, const fs_ppo_loss* loss, const float* mean_old_dev, const float* log_std_old_dev,
+                         const float* val_old_dev, fs::PpoLossArgs* out) {
+  const std::string w = std::string(who) + ": fs_ppo_loss: ";
   if (!loss) return fail(FS_ERR_INVALID, w + "NULL");
   if (loss->struct_size != sizeof(fs_ppo_loss)) return fail(FS_ERR_INVALID, w + "struct_size mismatch");
   if (std::isnan(loss->clip) || std::isnan(loss->vf_coef) || std::isnan(loss->vf_clip) || std::isnan(loss->entropy_coef))
@@ -661,13 +656,26 @@ int fs_ppo_grad_loss_dev(fs_handle h, const fs_ppo_model* model, const fs_ppo_lo
   if (loss->kl_state_dev && (!mean_old_dev || !log_std_old_dev))
     return fail(FS_ERR_INVALID, w + "the KL term (kl_state_dev) needs mean_old_dev and log_std_old_dev");
   if (vclip && !val_old_dev) return fail(FS_ERR_INVALID, w + "value clipping (vf_clip > 0) needs val_old_dev");
+  *out = fs::PpoLossArgs{mean_old_dev, log_std_old_dev, val_old_dev, loss->kl_state_dev, vclip ? loss->vf_clip : 0.0f,
+                         loss->entropy_coef};
+  return FS_OK;
+}
+
+int fs_ppo_grad_loss_dev(fs_handle h, const fs_ppo_model* model, const fs_ppo_loss* loss, int64_t n, const float* obs_dev,
+                         const float* act_dev, const float* logp_old_dev, const float* mean_old_dev,
+                         const float* log_std_old_dev, const float* val_old_dev, const double* adv_dev, const float* ret_dev,
+                         const double* mean_std_n_dev, int accumulate, float* grad_dev, float* loss_sums_dev, float* work_dev,
+                         size_t work_floats) {
+  if (!h || !obs_dev || !act_dev || !logp_old_dev || !adv_dev || !ret_dev || !mean_std_n_dev || !grad_dev || !loss_sums_dev ||
+      !work_dev)
+    return fail(FS_ERR_INVALID, "fs_ppo_grad_loss_dev: NULL argument");
+  fs::PpoLossArgs x;
+  if (int rc = ppo_loss_args("fs_ppo_grad_loss_dev", loss, mean_old_dev, log_std_old_dev, val_old_dev, &x)) return rc;
   if (n < 1 || n > INT32_MAX) return fail(FS_ERR_INVALID, "fs_ppo_grad_loss_dev: n must be 1 .. 2^31 - 1");
   fs::PpoView pv;
   if (int rc = ppo_view("fs_ppo_grad_loss_dev", model, true, &pv)) return rc;
   if (work_floats < fs::ppo_loss_work_floats(n, pv.D, pv.A, pv.L))
     return fail(FS_ERR_INVALID, "fs_ppo_grad_loss_dev: work_dev is smaller than fs_ppo_loss_workspace(model, n) floats");
-  const fs::PpoLossArgs x{mean_old_dev, log_std_old_dev, val_old_dev, loss->kl_state_dev, vclip ? loss->vf_clip : 0.0f,
-                          loss->entropy_coef};
   DeviceGuard guard(S(h)->cfg.device);
   S(h)->last_kernel = "k_ppo_grad_loss";
   return launch_ppo_grad_loss(S(h)->stream, pv, x, n, obs_dev, act_dev, logp_old_dev, adv_dev, ret_dev, mean_std_n_dev,
@@ -682,6 +690,92 @@ int fs_kl_adapt_dev(fs_handle h, const float* loss_sums_dev, const double* mean_
   DeviceGuard guard(S(h)->cfg.device);
   S(h)->last_kernel = "k_kl_adapt";
   return launch_kl_adapt(S(h)->stream, loss_sums_dev, mean_std_n_dev, kl_state_dev, kl_target);
+}
+
+// ---- minibatch SGD: one launch per step (k_ppo_minibatch), the chain's finish (k_mb_finish), the permutation on the host
+static_assert(FS_MB_STEP == fs::MB_STEP && FS_MB_PARTIAL == fs::MB_PARTIAL && FS_MB_ACCUMULATE == fs::MB_ACCUMULATE &&
+              FS_MB_FIRST == fs::MB_FIRST && FS_MB_LAST == fs::MB_LAST, "include/flowsim.h and flowsim_learn.h agree");
+int fs_ppo_perm_host(uint64_t seed, uint64_t epoch, int64_t n, int64_t* out) {
+  if (!out) return fail(FS_ERR_INVALID, "fs_ppo_perm_host: NULL argument");
+  if (n < 1 || n > INT32_MAX) return fail(FS_ERR_INVALID, "fs_ppo_perm_host: n must be 1 .. 2^31 - 1");
+  const fs::PermKey k = fs::perm_key(seed, epoch, uint32_t(n));
+  for (int64_t i = 0; i < n; ++i) out[i] = int64_t(fs::perm_at(k, uint32_t(i)));
+  return FS_OK;
+}
+
+size_t fs_ppo_minibatch_workspace(const fs_ppo_model* model, int64_t batch) {
+  fs::PpoView pv;
+  if (batch < 1 || batch > INT32_MAX || ppo_view("fs_ppo_minibatch_workspace", model, false, &pv)) return 0;
+  return fs::ppo_mb_work_floats(batch, pv.D, pv.A, pv.L);
+}
+
+int fs_ppo_minibatch_dev(fs_handle h, const fs_ppo_model* model, const fs_ppo_loss* loss, const fs_ppo_minibatch* mb, int64_t n,
+                         const float* obs_dev, const float* act_dev, const float* logp_old_dev, const float* mean_old_dev,
+                         const float* log_std_old_dev, const float* val_old_dev, const double* adv_dev, const float* ret_dev,
+                         const double* mean_std_n_dev, float* grad_dev, float* loss_sums_dev, float* work_dev,
+                         size_t work_floats) {
+  const std::string w = "fs_ppo_minibatch_dev: fs_ppo_minibatch: ";
+  if (!mb) return fail(FS_ERR_INVALID, w + "NULL");
+  if (mb->struct_size != sizeof(fs_ppo_minibatch)) return fail(FS_ERR_INVALID, w + "struct_size mismatch");
+  if (mb->mode != FS_MB_STEP && mb->mode != FS_MB_PARTIAL) return fail(FS_ERR_INVALID, w + "mode must be FS_MB_STEP or FS_MB_PARTIAL");
+  if (mb->flags & ~(FS_MB_ACCUMULATE | FS_MB_FIRST | FS_MB_LAST)) return fail(FS_ERR_INVALID, w + "unknown flags");
+  if (mb->batch < 1 || mb->batch > INT32_MAX) return fail(FS_ERR_INVALID, w + "batch (B) must be 1 .. 2^31 - 1");
+  if (n < 1 || n > INT32_MAX) return fail(FS_ERR_INVALID, "fs_ppo_minibatch_dev: n must be 1 .. 2^31 - 1");
+  if (mb->index < 0 || mb->index > (n - 1) / mb->batch) return fail(FS_ERR_INVALID, w + "index (k) must be 0 .. ceil(n / batch) - 1");
+  if (!mb->epoch_dev) return fail(FS_ERR_INVALID, w + "epoch_dev is NULL");
+  fs::PpoView pv;
+  if (int rc = ppo_view("fs_ppo_minibatch_dev", model, true, &pv)) return rc;
+  if (mb->mode == FS_MB_STEP) {
+    if (!mb->state_dev) return fail(FS_ERR_INVALID, w + "state_dev is NULL (FS_MB_STEP applies Adam)");
+    if (!mb->m_dev) return fail(FS_ERR_INVALID, w + "m_dev is NULL (FS_MB_STEP applies Adam)");
+    if (!mb->v_dev) return fail(FS_ERR_INVALID, w + "v_dev is NULL (FS_MB_STEP applies Adam)");
+    if (!mb->weights_dev) return fail(FS_ERR_INVALID, w + "weights_dev is NULL (FS_MB_STEP applies Adam)");
+    if (mb->flags & FS_MB_ACCUMULATE) return fail(FS_ERR_INVALID, w + "FS_MB_ACCUMULATE needs FS_MB_PARTIAL (a step has one shard)");
+    const int Pp = fs::ppo_net_params(pv.D, pv.L, pv.A);
+    if (pv.pw != mb->weights_dev || pv.log_std != mb->weights_dev + Pp || pv.vw != mb->weights_dev + Pp + pv.A)
+      return fail(FS_ERR_INVALID, w + "weights_dev must be the packed buffer [policy][log_std A][value] that fs_ppo_model points into");
+  } else if (!mb->count_dev) {
+    return fail(FS_ERR_INVALID, w + "count_dev is NULL (FS_MB_PARTIAL leaves the count there)");
+  }
+  fs::PpoLossArgs x;
+  if (int rc = ppo_loss_args("fs_ppo_minibatch_dev", loss, mean_old_dev, log_std_old_dev, val_old_dev, &x)) return rc;
+  if (!h || !obs_dev || !act_dev || !logp_old_dev || !adv_dev || !ret_dev || !mean_std_n_dev || !grad_dev || !loss_sums_dev ||
+      !work_dev)
+    return fail(FS_ERR_INVALID, "fs_ppo_minibatch_dev: NULL argument");
+  if (work_floats < fs::ppo_mb_work_floats(mb->batch, pv.D, pv.A, pv.L))
+    return fail(FS_ERR_INVALID, "fs_ppo_minibatch_dev: work_dev is smaller than fs_ppo_minibatch_workspace(model, batch) floats");
+  SimBase* s = S(h);
+  DeviceGuard guard(s->cfg.device);
+  if (!s->d_mb_ticket) {
+    // the first call on a handle allocates (and synchronises the device once): make it outside a stream capture
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, 64));
+    s->allocs.push_back(p);
+    HIP_TRY(hipMemset(p, 0, 64));
+    HIP_TRY(hipDeviceSynchronize());
+    s->d_mb_ticket = static_cast<unsigned*>(p);
+  }
+  const fs::PpoMbArgs a{mb->seed, reinterpret_cast<unsigned long long*>(mb->epoch_dev), mb->batch, mb->index,
+                        mb->mode == FS_MB_STEP ? fs::MB_STEP : fs::MB_PARTIAL, mb->flags, s->d_mb_ticket, grad_dev, loss_sums_dev,
+                        mb->count_dev, mb->weights_dev, mb->m_dev, mb->v_dev, mb->state_dev, mb->lr, mb->beta1, mb->beta2, mb->eps};
+  s->last_kernel = "k_ppo_minibatch";
+  return launch_ppo_minibatch(s->stream, pv, x, a, n, obs_dev, act_dev, logp_old_dev, adv_dev, ret_dev, mean_std_n_dev,
+                              float(1.0 - double(loss->clip)), float(1.0 + double(loss->clip)), loss->vf_coef, work_dev);
+}
+
+int fs_ppo_mb_finish_dev(fs_handle h, int64_t num_params, float* weights_dev, float* grad_dev, float* m_dev, float* v_dev,
+                         double* state_dev, const double* count_dev, uint64_t* epoch_dev, int flags, double lr, double beta1,
+                         double beta2, double eps) {
+  if (!state_dev) return fail(FS_ERR_INVALID, "fs_ppo_mb_finish_dev: state_dev is NULL");
+  if (!m_dev) return fail(FS_ERR_INVALID, "fs_ppo_mb_finish_dev: m_dev is NULL");
+  if (!v_dev) return fail(FS_ERR_INVALID, "fs_ppo_mb_finish_dev: v_dev is NULL");
+  if (!h || !weights_dev || !grad_dev || !count_dev || !epoch_dev) return fail(FS_ERR_INVALID, "fs_ppo_mb_finish_dev: NULL argument");
+  if (num_params < 1 || num_params > INT32_MAX) return fail(FS_ERR_INVALID, "fs_ppo_mb_finish_dev: num_params must be 1 .. 2^31 - 1");
+  if (flags & ~FS_MB_LAST) return fail(FS_ERR_INVALID, "fs_ppo_mb_finish_dev: flags may hold FS_MB_LAST alone");
+  DeviceGuard guard(S(h)->cfg.device);
+  S(h)->last_kernel = "k_mb_finish";
+  return launch_mb_finish(S(h)->stream, int(num_params), weights_dev, grad_dev, m_dev, v_dev, state_dev, count_dev,
+                          reinterpret_cast<unsigned long long*>(epoch_dev), flags, lr, beta1, beta2, eps);
 }
 
 const char* fs_last_kernel(fs_handle h) { return h ? reinterpret_cast<SimBase*>(h)->last_kernel : ""; }

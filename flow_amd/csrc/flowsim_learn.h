@@ -12,6 +12,10 @@
 //   k_ppo_grad<true, true>  ("k_ppo_grad_loss") the same launch with RLlib's PPO loss: the KL penalty KL(old || new), the
 //                clipped value loss and the entropy bonus on top of the surrogate, four loss sums {pg, vfl, KL, H}
 //   k_kl_adapt   RLlib's rule for the KL coefficient, one thread, in double: {coef, mean KL} live in device memory
+//   k_ppo_grad<true, true, true>  ("k_ppo_minibatch") ONE minibatch step of a shuffled epoch in one launch: the rows are
+//                gathered through a computed permutation, the last workgroup to finish reduces the partials, divides by
+//                the minibatch's own count and applies Adam (MB_STEP), or leaves the raw sums for k_mb_finish (MB_PARTIAL)
+//   k_mb_finish  the divide and Adam of the MB_PARTIAL chain (several shards or ranks), one workgroup like k_adam
 //
 // Model class (DevicePolicy's): 1..3 hidden layers of 32 tanh units on 1..160 inputs, a head of A <= 32 means with a free
 // log_std [A]; the value network is the same trunk with one output.  Packed weights per network: per layer W [out][in]
@@ -94,6 +98,87 @@ struct PpoLossArgs {
   float entropy_coef;          // 0: no entropy term
 };
 
+// ---- minibatches (k_ppo_minibatch, k_mb_finish).  An epoch is a shuffled pass: minibatch k of size B is rows
+// perm[kB .. min((k + 1) B, n)) of the shard, and perm is COMPUTED, never stored: a balanced Feistel network of 4 rounds
+// over the smallest even number of bits that holds n - 1 (at least 2), round function murmur3's fmix32 of (right half +
+// round key), keys = fmix32 chains of (seed, epoch, round), cycle-walked -- re-applied until the value is < n.  The network
+// is a bijection of its domain of at most 4 n values and the start is < n, so the walk comes back below n (it returns to
+// its start at the latest); it takes under 4 passes on average.  32-bit integer operations only: the host (fs_ppo_perm_host),
+// the kernel and numpy (flow_amd.utils.device_ppo.epoch_permutation) give the same values.
+__host__ __device__ inline uint32_t fmix32(uint32_t h) {
+  h ^= h >> 16;
+  h *= 0x85ebca6bu;
+  h ^= h >> 13;
+  h *= 0xc2b2ae35u;
+  h ^= h >> 16;
+  return h;
+}
+
+struct PermKey {
+  uint32_t key[4];
+  uint32_t n, half, mask;      // the domain is [0, 2^(2 half)), mask = 2^half - 1
+};
+
+__host__ __device__ inline PermKey perm_key(unsigned long long seed, unsigned long long epoch, uint32_t n) {
+  PermKey k;
+  uint32_t bits = 0;
+  while (bits < 32 && (n - 1u) >> bits) ++bits;               // bits of n - 1 (n >= 1)
+  k.half = bits < 2 ? 1u : (bits + 1u) / 2u;
+  k.mask = (1u << k.half) - 1u;
+  k.n = n;
+  uint32_t b = fmix32(uint32_t(seed) + 0x9e3779b9u);
+  b = fmix32(b ^ uint32_t(seed >> 32));
+  b = fmix32(b + uint32_t(epoch));
+  b = fmix32(b ^ uint32_t(epoch >> 32));
+  for (uint32_t r = 0; r < 4; ++r) k.key[r] = fmix32(b + 0x9e3779b9u * (r + 1u));
+  return k;
+}
+
+// perm[i], i < n
+__host__ __device__ inline uint32_t perm_at(const PermKey& k, uint32_t i) {
+  uint32_t x = i;
+  do {
+    uint32_t l = x >> k.half, r = x & k.mask;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int q = 0; q < 4; ++q) {
+      const uint32_t f = fmix32(r + k.key[q]) & k.mask;
+      const uint32_t nl = r;
+      r = l ^ f;
+      l = nl;
+    }
+    x = (l << k.half) | r;
+  } while (x >= k.n);
+  return x;
+}
+
+// workgroups of k_ppo_minibatch: ppo_groups of a batch of B samples -- a function of (B, D, A, L) alone, the short last
+// minibatch of an epoch included (its spare workgroups write zero partials)
+__host__ __device__ constexpr int ppo_mb_groups(long long B, int D, int A, int L) { return ppo_groups(B, D, A, L); }
+// 4-byte words of the workspace of one fs_ppo_minibatch_dev call: G partials [P + 4], then G integer counts
+__host__ __device__ constexpr size_t ppo_mb_work_floats(long long B, int D, int A, int L) {
+  return size_t(ppo_mb_groups(B, D, A, L)) * size_t(ppo_params(D, A, L) + PPO_LOSS_SUMS + 1);
+}
+
+constexpr int MB_STEP = 0, MB_PARTIAL = 1;                           // the tail's modes
+constexpr int MB_ACCUMULATE = 1, MB_FIRST = 2, MB_LAST = 4;          // flags
+
+// what the minibatch form reads and writes on top of the full-loss form's arguments
+struct PpoMbArgs {
+  unsigned long long seed;
+  unsigned long long* epoch;   // the learner's epoch counter (device)
+  long long B, k;              // minibatch k of B rows
+  int mode, flags;
+  unsigned* ticket;            // the handle's (zero between launches)
+  float* grad;                 // [P]
+  float* loss_sums;            // [4]
+  double* count;               // [1] (MB_PARTIAL)
+  float *w, *m, *v;            // [P] the packed weights and Adam's moments (MB_STEP)
+  double* state;               // Adam's {t, beta1^t, beta2^t}
+  double lr, beta1, beta2, eps;
+};
+
 // k_adv_stats: workgroups (a function of n alone) and the handle's scratch [ticket][G x 3 partial sums]
 constexpr int ADV_THREADS = 256, ADV_MAX_GROUPS = 512;
 constexpr size_t ADV_SCRATCH_BYTES = sizeof(double) * (1 + 3 * ADV_MAX_GROUPS);      // [ticket][G x 3 partial sums]
@@ -125,6 +210,12 @@ int launch_ppo_grad_loss(hipStream_t stream, const fs::PpoView& m, const fs::Ppo
                          const float* act, const float* logp_old, const double* adv, const float* ret, const double* mean_std_n,
                          float lo, float hi, float vf_coef, int accumulate, float* grad, float* loss, float* work);
 int launch_kl_adapt(hipStream_t stream, const float* loss_sums, const double* mean_std_n, double* kl_state, double kl_target);
+// (the minibatch form, fs_last_kernel's "k_ppo_minibatch", and the finish of the PARTIAL chain, "k_mb_finish")
+int launch_ppo_minibatch(hipStream_t stream, const fs::PpoView& m, const fs::PpoLossArgs& x, const fs::PpoMbArgs& mb, long long n,
+                         const float* obs, const float* act, const float* logp_old, const double* adv, const float* ret,
+                         const double* mean_std_n, float lo, float hi, float vf_coef, float* work);
+int launch_mb_finish(hipStream_t stream, int P, float* w, float* grad, float* m, float* v, double* state, const double* count,
+                     unsigned long long* epoch, int flags, double lr, double beta1, double beta2, double eps);
 // (scratch: fs::ADV_SCRATCH_BYTES of device memory, zero before its first use: the handle owns it)
 int launch_adv_stats(hipStream_t stream, long long n, const float* adv, const float* act, int A, int accumulate, double* adv64,
                      double* stats, double* scratch);
@@ -176,15 +267,24 @@ __device__ __forceinline__ void layer_acc(const float* wt, const float* S, int n
 }
 
 // inputs [c0, c0 + 32) of the tile's observations -> S [input][sample]: coalesced rows of 32 floats; a sample beyond n,
-// or one that `keep` (a lane mask of the tile) leaves out, is staged as zeros
+// or one that `keep` (a lane mask of the tile) leaves out, is staged as zeros.  GATHER (the minibatch form): sample s of the
+// tile is row `row` of lane s -- the lanes hand their rows round with a ds_bpermute -- and a negative row is a lane beyond
+// the minibatch's end
+template <bool GATHER = false>
 __device__ __forceinline__ void stage_obs(const float* obs, long long s0, long long n, int D, int c0, unsigned long long keep,
-                                          float* S, int lane) {
+                                          float* S, int lane, int row = 0) {
   const int i = lane & 31, col = c0 + i;
 #pragma unroll 4
   for (int r = 0; r < 32; ++r) {
     const int s = 2 * r + (lane >> 5);
-    const bool ok = s0 + s < n && col < D && ((keep >> s) & 1ull);
-    S[i * PPO_TS + s] = ok ? obs[size_t(s0 + s) * size_t(D) + size_t(col)] : 0.0f;
+    if constexpr (GATHER) {
+      const int rs = __shfl(row, s, 64);
+      const bool ok = rs >= 0 && col < D && ((keep >> s) & 1ull);
+      S[i * PPO_TS + s] = ok ? obs[size_t(rs) * size_t(D) + size_t(col)] : 0.0f;
+    } else {
+      const bool ok = s0 + s < n && col < D && ((keep >> s) & 1ull);
+      S[i * PPO_TS + s] = ok ? obs[size_t(s0 + s) * size_t(D) + size_t(col)] : 0.0f;
+    }
   }
 }
 
@@ -195,14 +295,16 @@ __device__ __forceinline__ void stage_units(const float (&h)[32], float* S, int 
 
 // THE forward pass of one network on one tile: h[l] = the lane's activations of hidden layer l (l < L), out = the head's 32
 // padded outputs.  Ends without a barrier: S holds the lane's own column.
+template <bool GATHER = false>
 __device__ __forceinline__ void net_forward(const float* net, int D, int L, const float* obs, long long s0, long long n,
-                                            unsigned long long keep, float* S, int lane, float (&h)[3][32], float (&out)[32]) {
+                                            unsigned long long keep, float* S, int lane, float (&h)[3][32], float (&out)[32],
+                                            int row = 0) {
   float z[32];
 #pragma unroll
   for (int u = 0; u < 32; ++u) z[u] = net[32 * D + u];
   for (int c0 = 0; c0 < D; c0 += 32) {
     __syncthreads();                                       // (the last readers of S are done)
-    stage_obs(obs, s0, n, D, c0, keep, S, lane);
+    stage_obs<GATHER>(obs, s0, n, D, c0, keep, S, lane, row);
     __syncthreads();
     layer_acc(net + c0 * 32, S, D - c0 < 32 ? D - c0 : 32, lane, z);
   }
@@ -393,9 +495,10 @@ __device__ __forceinline__ void back_layer(const float* net, int D, int L, int n
 
 // the backward pass of one network on one tile: dz = the loss's gradient at the head's 32 padded outputs (zero for the
 // samples that do not count); G = the network's gradient in LDS (packed layout)
+template <bool GATHER = false>
 __device__ __forceinline__ void net_backward(const float* net, int D, int L, int n_out, const float* obs, long long s0,
                                              long long n, unsigned long long keep, float* S, float* T, int lane,
-                                             const float (&h)[3][32], float (&dz)[32], float* G) {
+                                             const float (&h)[3][32], float (&dz)[32], float* G, int row = 0) {
   if (L >= 3) back_layer<3>(net, D, L, n_out, S, T, lane, h, dz, G);
   if (L >= 2) back_layer<2>(net, D, L, n_out, S, T, lane, h, dz, G);
   back_layer<1>(net, D, L, n_out, S, T, lane, h, dz, G);
@@ -405,7 +508,7 @@ __device__ __forceinline__ void net_backward(const float* net, int D, int L, int
   col_sum(T, 32, G + 32 * D, lane);
   for (int c0 = 0; c0 < D; c0 += 32) {
     __syncthreads();
-    stage_obs(obs, s0, n, D, c0, keep, S, lane);
+    stage_obs<GATHER>(obs, s0, n, D, c0, keep, S, lane, row);
     __syncthreads();
     grad_block(T, S, D - c0 < 32 ? D - c0 : 32, 32, G, D, c0, lane);
   }
@@ -421,15 +524,43 @@ __device__ __forceinline__ void net_backward(const float* net, int D, int L, int
 // with kl_coef = float(x.kl_state[0]) read from the device.  Every new term is added where its quantities already sit in
 // registers, each behind a wave-uniform branch on its argument (a term that is off is not computed: nothing is multiplied
 // by zero), and the old means / old value of an absent row are never loaded.  The sums are four: {pg, vfl, KL, H}.
-template <bool N_DEV, bool LOSS = false>
+// MB (with LOSS; fs_last_kernel's "k_ppo_minibatch"): ONE minibatch step in one launch.  The tile's 64 rows are
+//   perm(seed, epoch, k B + 64 t + lane)
+// and every per-row read goes through them (a lane beyond the minibatch's end is a lane beyond n: staged zeros, zero seeds);
+// the lane arithmetic runs with inv_n = 1 -- every term is linear in it -- and each workgroup counts its present rows as an
+// integer.  A workgroup writes its partial [P + 4] and its count, then draws an integer ticket (k_adv_stats's pattern: an
+// agent-scope release before the ticket, an acquire after it); the workgroup that draws the LAST ticket runs the tail
+// (mb_tail), every other one exits: nobody ever waits for anybody.
+struct PpoNoMb {};
+template <bool MB>
+struct PpoMbOf { typedef PpoNoMb type; };
+template <>
+struct PpoMbOf<true> { typedef PpoMbArgs type; };
+
+__device__ __forceinline__ void mb_tail(const PpoMbArgs& mb, float* work, int G, int P, int lane);
+
+template <bool N_DEV, bool LOSS = false, bool MB = false>
 __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const float* __restrict__ obs,
                                                  const float* __restrict__ act, const float* __restrict__ logp_old,
                                                  const double* __restrict__ adv, const float* __restrict__ ret,
                                                  const double* __restrict__ mean_std, float lo, float hi, float vf_coef,
-                                                 float inv_n, float* __restrict__ work, PpoLossArgs x) {
+                                                 float inv_n, float* __restrict__ work, PpoLossArgs x,
+                                                 typename PpoMbOf<MB>::type mb) {
   static_assert(N_DEV || !LOSS, "the full loss reads its sample count from the device");
+  static_assert(LOSS || !MB, "the minibatch form is a form of the full loss");
   constexpr int NS = LOSS ? PPO_LOSS_SUMS : 2;               // loss sums behind the gradient
-  if (N_DEV) inv_n = float(1.0 / mean_std[2]);
+  if constexpr (!MB) {
+    if (N_DEV) inv_n = float(1.0 / mean_std[2]);
+  }
+  long long mb_begin = 0, mb_end = 0;                        // (MB) the minibatch's positions in the permutation
+  [[maybe_unused]] PermKey pk;
+  [[maybe_unused]] unsigned cnt = 0;                         // (MB) present rows of this workgroup's tiles
+  if constexpr (MB) {
+    inv_n = 1.0f;
+    pk = perm_key(mb.seed, *mb.epoch, uint32_t(n));
+    mb_begin = mb.k * mb.B;
+    mb_end = mb_begin + mb.B < n ? mb_begin + mb.B : n;
+  }
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int D = m.D, A = m.A, L = m.L, P = ppo_params(D, A, L);
   float* pnet = reinterpret_cast<float*>(smem);
@@ -444,15 +575,23 @@ __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const f
   __syncthreads();
   const int Pp = ppo_net_params(D, L, A);
   const double mean = mean_std[0], scale = mean_std[1] + 1e-8;
-  const long long tiles = (n + PPO_TILE - 1) / PPO_TILE;
+  const long long tiles = ((MB ? mb_end - mb_begin : n) + PPO_TILE - 1) / PPO_TILE;
   for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
-    const long long s0 = t * PPO_TILE, s = s0 + lane;
-    const bool valid = s < n;
+    long long s0 = t * PPO_TILE, s = s0 + lane;
+    bool valid = s < n;
+    int row = 0;                                             // (MB) the lane's row, -1 beyond the minibatch's end
+    if constexpr (MB) {
+      const long long at = mb_begin + s;
+      valid = at < mb_end;
+      row = valid ? int(perm_at(pk, uint32_t(valid ? at : 0))) : -1;
+      s = row;
+    }
     float a[32], h[3][32], out[32], dz[32];
     const bool present = ppo_load_act(act, s, valid, A, a) && valid;
     const unsigned long long keep = __ballot(present);
+    if constexpr (MB) cnt += unsigned(__popcll(keep));
     // ---- the policy: logp, the clipped surrogate, its gradient at the means and at log_std
-    net_forward(pnet, D, L, obs, s0, n, keep, S, lane, h, out);
+    net_forward<MB>(pnet, D, L, obs, s0, n, keep, S, lane, h, out, row);
     float pg = 0.0f, vf = 0.0f;
     float kl = 0.0f, ent = 0.0f;                             // (LOSS)
     {
@@ -505,9 +644,9 @@ __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const f
       col_sum(T, A, G + Pp, lane);
       __syncthreads();
     }
-    net_backward(pnet, D, L, A, obs, s0, n, keep, S, T, lane, h, dz, G);
+    net_backward<MB>(pnet, D, L, A, obs, s0, n, keep, S, T, lane, h, dz, G, row);
     // ---- the value network: (v - ret)^2
-    net_forward(vnet, D, L, obs, s0, n, keep, S, lane, h, out);
+    net_forward<MB>(vnet, D, L, obs, s0, n, keep, S, lane, h, out, row);
     {
       const float err = present ? out[0] - ret[s] : 0.0f;
       vf = err * err;
@@ -529,7 +668,7 @@ __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const f
         }
       }
     }
-    net_backward(vnet, D, L, 1, obs, s0, n, keep, S, T, lane, h, dz, G + Pp + A);
+    net_backward<MB>(vnet, D, L, 1, obs, s0, n, keep, S, T, lane, h, dz, G + Pp + A, row);
     // ---- the loss sums
     T[lane * PPO_TT + 0] = pg;
     T[lane * PPO_TT + 1] = vf;
@@ -543,6 +682,22 @@ __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const f
   }
   float* w = work + size_t(blockIdx.x) * size_t(P + NS);
   for (int e = lane; e < P + NS; e += 64) w[e] = G[e];
+  if constexpr (MB) {
+    const int groups = gridDim.x;
+    unsigned* counts = reinterpret_cast<unsigned*>(work + size_t(groups) * size_t(P + NS));
+    if (lane == 0) counts[blockIdx.x] = cnt;
+    // the wave's stores are out (release, agent scope) before lane 0 draws the ticket; the last workgroup to draw sees every
+    // partial (acquire).  Nobody waits: a workgroup that is not last is done.
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    unsigned drawn = 0;
+    if (lane == 0) drawn = __hip_atomic_fetch_add(mb.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    drawn = unsigned(__builtin_amdgcn_readfirstlane(int(drawn)));
+    if (drawn != unsigned(groups - 1)) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    mb_tail(mb, work, groups, P, lane);
+  }
 }
 
 // the partial gradients of the G workgroups, summed in ascending order: grad [P], loss [NS] (accumulate: added to what is
@@ -669,26 +824,118 @@ __global__ __launch_bounds__(64) void k_kl_adapt(const float* __restrict__ sums,
 // old step.  P is at most ppo_params(160, 32, 3) = 15 649: sixteen elements per lane.
 constexpr int ADAM_THREADS = 1024;
 
-__global__ __launch_bounds__(ADAM_THREADS) void k_adam(int P, float* __restrict__ w, const float* __restrict__ g,
-                                                        float* __restrict__ m, float* __restrict__ v, double* state, double lr,
-                                                        double beta1, double beta2, double eps) {
+// (the operation sequence is written once: k_adam, k_mb_finish and the tail of k_ppo_minibatch run these two)
+struct AdamCoef {
+  float step, rs, c1, b2, c2, e;
+};
+
+// every lane of the ONE workgroup reads the state, the barrier follows, then lane 0 alone writes it
+__device__ __forceinline__ AdamCoef adam_advance(double* state, double lr, double beta1, double beta2, double eps, int tid) {
   const double t = state[0] + 1.0, p1 = state[1] * beta1, p2 = state[2] * beta2;
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if (tid == 0) {
     state[0] = t;
     state[1] = p1;
     state[2] = p2;
   }
-  const float step = float(lr / (1.0 - p1)), rs = float(sqrt(1.0 - p2));
-  const float c1 = float(1.0 - beta1), b2 = float(beta2), c2 = float(1.0 - beta2), e = float(eps);
-  for (int i = threadIdx.x; i < P; i += ADAM_THREADS) {
-    const float gi = g[i];
-    const float mi = m[i] + (gi - m[i]) * c1;
-    const float vi = v[i] * b2 + (gi * gi) * c2;
-    m[i] = mi;
-    v[i] = vi;
-    w[i] = w[i] - step * (mi / (sqrtf(vi) / rs + e));
+  return AdamCoef{float(lr / (1.0 - p1)), float(sqrt(1.0 - p2)), float(1.0 - beta1), float(beta2), float(1.0 - beta2),
+                  float(eps)};
+}
+
+__device__ __forceinline__ void adam_element(const AdamCoef& c, float* w, float gi, float* m, float* v, int i) {
+  const float mi = m[i] + (gi - m[i]) * c.c1;
+  const float vi = v[i] * c.b2 + (gi * gi) * c.c2;
+  m[i] = mi;
+  v[i] = vi;
+  w[i] = w[i] - c.step * (mi / (sqrtf(vi) / c.rs + c.e));
+}
+
+__global__ __launch_bounds__(ADAM_THREADS) void k_adam(int P, float* __restrict__ w, const float* __restrict__ g,
+                                                        float* __restrict__ m, float* __restrict__ v, double* state, double lr,
+                                                        double beta1, double beta2, double eps) {
+  const AdamCoef c = adam_advance(state, lr, beta1, beta2, eps, threadIdx.x);
+  for (int i = threadIdx.x; i < P; i += ADAM_THREADS) adam_element(c, w, g[i], m, v, i);
+}
+
+// ---- the end of a minibatch step: the mean's gradient and one Adam step.  grad [P] holds the RAW sums of the step (all
+// shards, all ranks), c the count of its present rows.  Exactly
+//   g[p] = grad[p] * (float)(1.0 / (double)c);   grad[p] = g[p];   then k_adam's sequence with g
+// and with c == 0 nothing at all: no step, Adam's t, m, v and the weights untouched, grad left as it is (exact zeros).
+// MB_LAST: the epoch counter advances (whether or not a step was made).  ONE workgroup of NT lanes.
+template <int NT>
+__device__ __forceinline__ void mb_finish(int P, float* __restrict__ w, float* __restrict__ grad, float* __restrict__ m,
+                                          float* __restrict__ v, double* state, double c,
+                                          unsigned long long* epoch, int flags, double lr, double beta1, double beta2,
+                                          double eps, int tid) {
+  if (tid == 0 && (flags & MB_LAST)) *epoch = *epoch + 1ull;
+  if (c == 0.0) return;
+  const float scale = float(1.0 / c);
+  const AdamCoef k = adam_advance(state, lr, beta1, beta2, eps, tid);
+#pragma unroll 4
+  for (int i = tid; i < P; i += NT) {
+    const float g = grad[i] * scale;
+    grad[i] = g;
+    adam_element(k, w, g, m, v, i);
   }
+}
+
+__global__ __launch_bounds__(ADAM_THREADS) void k_mb_finish(int P, float* w, float* grad, float* m, float* v, double* state,
+                                                             const double* count, unsigned long long* epoch, int flags,
+                                                             double lr, double beta1, double beta2, double eps) {
+  mb_finish<ADAM_THREADS>(P, w, grad, m, v, state, count[0], epoch, flags, lr, beta1, beta2, eps, threadIdx.x);
+}
+
+// the tail of k_ppo_minibatch: ONE wave, the workgroup that drew the last ticket.  The G partials are added in ascending
+// workgroup order (k_ppo_reduce's order; lane l takes elements l, l + 64, ..), the G counts as integers.  The raw sums go to
+// grad (MB_ACCUMULATE: are added to it) and to loss_sums (added unless this is the epoch's first minibatch of the first
+// shard: MB_FIRST without MB_ACCUMULATE overwrites).  MB_PARTIAL ends there, with the count in count[0]; MB_STEP goes on to
+// mb_finish -- each lane re-reads the elements it wrote itself.  Writing the weights here is safe: every other workgroup
+// finished net_load (and read the epoch counter) long before it wrote its partial, and that came before its ticket.
+__device__ __forceinline__ void mb_tail(const PpoMbArgs& mb, float* work, int G, int P, int lane) {
+  constexpr int NS = PPO_LOSS_SUMS;
+  const unsigned* counts = reinterpret_cast<const unsigned*>(work + size_t(G) * size_t(P + NS));
+  unsigned c = 0;
+  for (int g = 0; g < G; ++g) c += counts[g];
+  const bool acc = (mb.flags & MB_ACCUMULATE) != 0, add_sums = acc || (mb.flags & MB_FIRST) == 0;
+  // (one wave has to keep many loads in flight to get through G (P + 4) floats: a lane carries four elements and loads
+  // eight workgroups' values of each before it adds them -- in ascending workgroup order, element by element)
+  const int W = P + NS;
+  for (int p0 = lane; p0 < W; p0 += 256) {
+    float a[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a[j] = p0 + 64 * j < W ? work[p0 + 64 * j] : 0.0f;
+    int g = 1;
+    for (; g + 8 <= G; g += 8) {
+      float x[8][4];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x[u][j] = p0 + 64 * j < W ? work[size_t(g + u) * size_t(W) + size_t(p0 + 64 * j)] : 0.0f;
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a[j] += x[u][j];
+    }
+    for (; g < G; ++g)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) a[j] += p0 + 64 * j < W ? work[size_t(g) * size_t(W) + size_t(p0 + 64 * j)] : 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int p = p0 + 64 * j;
+      if (p < P) {
+        mb.grad[p] = acc ? mb.grad[p] + a[j] : a[j];
+      } else if (p < W) {
+        float* dst = mb.loss_sums + (p - P);
+        *dst = add_sums ? *dst + a[j] : a[j];
+      }
+    }
+  }
+  if (lane == 0) __hip_atomic_store(mb.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (mb.mode == MB_PARTIAL) {
+    if (lane == 0) mb.count[0] = acc ? mb.count[0] + double(c) : double(c);
+    return;
+  }
+  mb_finish<64>(P, mb.w, mb.grad, mb.m, mb.v, mb.state, double(c), mb.epoch, mb.flags, mb.lr, mb.beta1, mb.beta2, mb.eps, lane);
 }
 
 }  // namespace fs
@@ -706,6 +953,8 @@ inline int ppo_lds_limit() {
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_eval<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               fs::PPO_LDS_BYTES));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_grad<true, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, fs::PPO_LDS_BYTES));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_grad<true, true, true>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, fs::PPO_LDS_BYTES));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_grad<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               fs::PPO_LDS_BYTES));
@@ -753,7 +1002,7 @@ static int launch_ppo_grad_any(hipStream_t stream, const fs::PpoView& m, long lo
   if (int rc = ppo_lds_limit()) return rc;
   const int G = fs::ppo_groups(n, m.D, m.A, m.L), P = fs::ppo_params(m.D, m.A, m.L);
   hipLaunchKernelGGL(fs::k_ppo_grad<N_DEV>, dim3(G), dim3(64), fs::ppo_grad_lds(m.D, m.A, m.L), stream, m, n, obs, act,
-                     logp_old, adv, ret, mean_std, lo, hi, vf_coef, inv_n, work, fs::PpoLossArgs{});
+                     logp_old, adv, ret, mean_std, lo, hi, vf_coef, inv_n, work, fs::PpoLossArgs{}, fs::PpoNoMb{});
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(fs::k_ppo_reduce<2>, dim3((P + 2 + 255) / 256), dim3(256), 0, stream, work, G, P, accumulate, grad, loss);
   HIP_TRY(hipGetLastError());
@@ -768,9 +1017,30 @@ int launch_ppo_grad_loss(hipStream_t stream, const fs::PpoView& m, const fs::Ppo
   constexpr int NS = fs::PPO_LOSS_SUMS;
   const int G = fs::ppo_groups(n, m.D, m.A, m.L), P = fs::ppo_params(m.D, m.A, m.L);
   hipLaunchKernelGGL((fs::k_ppo_grad<true, true>), dim3(G), dim3(64), fs::ppo_grad_loss_lds(m.D, m.A, m.L), stream, m, n, obs,
-                     act, logp_old, adv, ret, mean_std_n, lo, hi, vf_coef, 0.0f, work, x);
+                     act, logp_old, adv, ret, mean_std_n, lo, hi, vf_coef, 0.0f, work, x, fs::PpoNoMb{});
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(fs::k_ppo_reduce<NS>, dim3((P + NS + 255) / 256), dim3(256), 0, stream, work, G, P, accumulate, grad, loss);
+  HIP_TRY(hipGetLastError());
+  return FS_OK;
+}
+
+// one minibatch step: the full-loss form's arguments and mb (work: ppo_mb_work_floats(mb.B, ..) words).  The LDS is the
+// full-loss form's, under its static_assert
+int launch_ppo_minibatch(hipStream_t stream, const fs::PpoView& m, const fs::PpoLossArgs& x, const fs::PpoMbArgs& mb, long long n,
+                         const float* obs, const float* act, const float* logp_old, const double* adv, const float* ret,
+                         const double* mean_std_n, float lo, float hi, float vf_coef, float* work) {
+  if (int rc = ppo_lds_limit()) return rc;
+  const int G = fs::ppo_mb_groups(mb.B, m.D, m.A, m.L);
+  hipLaunchKernelGGL((fs::k_ppo_grad<true, true, true>), dim3(G), dim3(64), fs::ppo_grad_loss_lds(m.D, m.A, m.L), stream, m, n,
+                     obs, act, logp_old, adv, ret, mean_std_n, lo, hi, vf_coef, 0.0f, work, x, mb);
+  HIP_TRY(hipGetLastError());
+  return FS_OK;
+}
+
+int launch_mb_finish(hipStream_t stream, int P, float* w, float* grad, float* m, float* v, double* state, const double* count,
+                     unsigned long long* epoch, int flags, double lr, double beta1, double beta2, double eps) {
+  hipLaunchKernelGGL(fs::k_mb_finish, dim3(1), dim3(fs::ADAM_THREADS), 0, stream, P, w, grad, m, v, state, count, epoch, flags,
+                     lr, beta1, beta2, eps);
   HIP_TRY(hipGetLastError());
   return FS_OK;
 }

@@ -101,6 +101,7 @@ struct SimBase {
   bool no_mask_skip = false;    // FLOWSIM_NO_MASK_SKIP=1: a masked k_steps_open / k_steps_wide launch steps every wave (A/B, tests)
   bool no_queue = false;        // FLOWSIM_NO_QUEUE=1: keep k_steps_open / k_steps_wide for the open networks (tests)
   double* d_adv_scratch = nullptr;  // k_adv_stats: ticket and partial sums (flowsim_learn.h), allocated by its first launch
+  unsigned* d_mb_ticket = nullptr;  // k_ppo_minibatch: the ticket its workgroups draw (zero between launches), allocated by its first launch
   int* d_qflag = nullptr;       // k_drop_queue: bit 0 = a path held more than its 64 lanes (the launch's results are invalid)
   bool qflag_armed = false;     // a queue-order launch ran since the flag was last read
   // after a stream synchronisation: did a queue-order launch overflow a path?  (sticky: the handle is unusable then)

@@ -23,6 +23,48 @@ from flow_amd import _lib as L
 MAX_OBS, MAX_ACT, WIDTH = 160, 32, 32
 
 
+def _fmix32(h):
+    """murmur3's finaliser on uint32 arrays (wrapping arithmetic)."""
+    import numpy as np
+    h = h ^ (h >> np.uint32(16))
+    h = h * np.uint32(0x85ebca6b)
+    h = h ^ (h >> np.uint32(13))
+    h = h * np.uint32(0xc2b2ae35)
+    return h ^ (h >> np.uint32(16))
+
+
+def epoch_permutation(seed, epoch, n):
+    """The permutation of ``[0, n)`` that epoch ``epoch`` of a minibatch update with ``shuffle_seed=seed`` walks through
+    (int64 [n]): minibatch ``k`` of size ``B`` is rows ``perm[k B : (k + 1) B]``.  A numpy restatement of ``perm_at`` in
+    flow_amd/csrc/flowsim_learn.h -- a 4-round balanced Feistel network on the smallest even number of bits that holds
+    ``n - 1``, round function fmix32(right half + key), keys from fmix32 of (seed, epoch, round), cycle-walked until the
+    value is below ``n`` -- with the values of the kernel (k_ppo_minibatch) and of ``fs_ppo_perm_host``.  No GPU, no
+    library."""
+    import numpy as np
+    n, seed, epoch = int(n), int(seed) & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1)
+    if not 1 <= n <= 2 ** 31 - 1:
+        raise ValueError("epoch_permutation: n must be 1 .. 2^31 - 1")
+    u = np.uint32
+    with np.errstate(over="ignore"):
+        bits = (n - 1).bit_length()
+        half = 1 if bits < 2 else (bits + 1) // 2
+        mask = u((1 << half) - 1)
+        b = _fmix32(u(seed & 0xffffffff) + u(0x9e3779b9))
+        b = _fmix32(b ^ u(seed >> 32))
+        b = _fmix32(b + u(epoch & 0xffffffff))
+        b = _fmix32(b ^ u(epoch >> 32))
+        keys = [_fmix32(b + u(0x9e3779b9) * u(r + 1)) for r in range(4)]
+        x = np.arange(n, dtype=np.uint32)
+        todo = np.ones(n, dtype=bool)
+        while todo.any():
+            l, r = x[todo] >> u(half), x[todo] & mask
+            for key in keys:
+                l, r = r, l ^ (_fmix32(r + key) & mask)
+            x[todo] = (l << u(half)) | r
+            todo[todo] = x[todo] >= u(n)
+    return x.astype(np.int64)
+
+
 def _check_trunk(who, hidden, head, n_out, what):
     if not 1 <= len(hidden) <= 3:
         raise NotImplementedError("DeviceLearner (fs_ppo_model): %s has %d hidden layers; 1..3 are built" % (who, len(hidden)))
@@ -96,6 +138,12 @@ class DeviceLearner(object):
         self.kl_state = torch.tensor([0.2, 0.0], dtype=torch.float64, device=dev)   # (update(): kl_coef_init on its first KL call)
         self._kl_started = False
         self._work_loss = None
+        # minibatch SGD (minibatch_step, update(minibatch=)): the epoch counter the kernel's permutation reads -- the bits of
+        # a uint64, on the device next to Adam's state so that a replayed graph draws fresh permutations -- and the count of
+        # present rows of a step made of PARTIAL launches
+        self.mb_epoch = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.mb_count = torch.zeros(1, dtype=torch.float64, device=dev)
+        self._work_mb, self._work_mbs = None, {}
         off = self.n_policy
         self.struct = L.fs_ppo_model(struct_size=C.sizeof(L.fs_ppo_model), obs_dim=D, act_dim=A, num_hidden=self.num_hidden,
                                      hidden_width=WIDTH, activation=0, policy_weights_dev=self.weights.data_ptr(),
@@ -336,6 +384,91 @@ class DeviceLearner(object):
                                              float(kl_target)), self.sim.lib)
         return self.kl_state
 
+    # ---- minibatch SGD: one launch per step (fs_ppo_minibatch_dev), the chain's finish (fs_ppo_mb_finish_dev)
+    def _mb_workspace(self, batch):
+        """The workspace of minibatch steps of ``batch`` rows: one buffer per size, made once and KEPT -- a graph captured
+        at one batch size holds its buffer's address, so a later call at a larger size must not free it."""
+        need = int(self.sim.lib.fs_ppo_minibatch_workspace(C.byref(self.struct), int(batch)))
+        if need not in self._work_mbs:
+            self._work_mbs[need] = self.torch.empty(max(need, 1), dtype=self.torch.float32, device=self.device)
+        self._work_mb = self._work_mbs[need]
+        return self._work_mb
+
+    def minibatch_step(self, obs, act, logp_old, adv, ret, mean_std_n, batch, index, shuffle_seed=0, mean_old=None,
+                       log_std_old=None, val_old=None, clip=0.2, vf_coef=0.5, vf_clip=None, entropy_coef=0.0, kl=False,
+                       partial=False, accumulate=False, first=None, last=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-8):
+        """ONE minibatch step of a shuffled epoch in one launch (``fs_ppo_minibatch_dev``): minibatch ``index`` of size
+        ``batch`` of the ``n`` rows, i.e. rows ``epoch_permutation(shuffle_seed, self.mb_epoch, n)[index * batch :
+        (index + 1) * batch]`` -- gathered inside the kernel --, the loss of ``gradients_loss`` over them divided by the
+        minibatch's own count of present rows, its gradient into ``self.grad``, and one Adam step on ``self.weights``
+        (``m``, ``v``, ``state`` as ``adam_step`` keeps them).  The raw loss sums are added to ``self.loss_sums``
+        (``first``: overwrite; default: ``index == 0``); ``last`` (default: the epoch's last minibatch) advances
+        ``self.mb_epoch``.  A minibatch without a present row makes no step.  ``adv`` is the raw float64 advantage and
+        ``mean_std_n`` its statistics over the whole batch.
+        ``partial=True``: the launch only reduces -- raw sums into ``self.grad`` / ``self.loss_sums``, the count into
+        ``self.mb_count`` (``accumulate=True``: a later shard of the same step, added) -- and ``mb_finish()`` ends the step
+        once every shard (and rank) is in.  One shard without ``partial`` gives the bits of ``partial`` + ``mb_finish``."""
+        torch = self.torch
+        n = int(obs.shape[0])
+        obs, act = self._f32(obs, (n, self.D), "obs"), self._f32(act, (n, self.A), "act")
+        logp_old, ret = self._f32(logp_old, (n,), "logp_old"), self._f32(ret, (n,), "ret")
+        if adv.dtype != torch.float64 or tuple(adv.shape) != (n,) or adv.device != self.device:
+            raise ValueError("DeviceLearner: adv must be a float64 tensor of shape (%d,) on %s" % (n, self.device))
+        if mean_std_n.dtype != torch.float64 or mean_std_n.numel() != 3 or mean_std_n.device != self.device:
+            raise ValueError("DeviceLearner: mean_std_n must be a float64 tensor of 3 elements on %s" % self.device)
+        mean_old = None if mean_old is None else self._f32(mean_old, (n, self.A), "mean_old")
+        log_std_old = None if log_std_old is None else self._f32(log_std_old, (self.A,), "log_std_old")
+        val_old = None if val_old is None else self._f32(val_old, (n,), "val_old")
+        batch, index = int(batch), int(index)
+        steps = -(-n // max(batch, 1))
+        self._adam_buffers()
+        work = self._mb_workspace(batch)
+        self._bind()
+        self._mb_step(n, obs, act, logp_old, mean_old, log_std_old, val_old, adv.contiguous(), ret, mean_std_n, batch, index,
+                      shuffle_seed, clip, vf_coef, vf_clip, entropy_coef, kl, partial, accumulate,
+                      index == 0 if first is None else first, index == steps - 1 if last is None else last, lr, betas, eps, work)
+        return self.loss_sums
+
+    def _mb_step(self, n, obs, act, logp_old, mean_old, log_std_old, val_old, adv64, ret, mean_std_n, batch, index, seed, clip,
+                 vf_coef, vf_clip, entropy_coef, kl, partial, accumulate, first, last, lr, betas, eps, work):
+        ptr = lambda t: None if t is None else t.data_ptr()                        # noqa: E731
+        loss = L.fs_ppo_loss(struct_size=C.sizeof(L.fs_ppo_loss), clip=float(clip), vf_coef=float(vf_coef),
+                             vf_clip=0.0 if vf_clip is None else float(vf_clip), entropy_coef=float(entropy_coef),
+                             kl_state_dev=self.kl_state.data_ptr() if kl else None)
+        flags = (L.FS_MB_ACCUMULATE if accumulate else 0) | (L.FS_MB_FIRST if first else 0) | (L.FS_MB_LAST if last else 0)
+        mb = L.fs_ppo_minibatch(struct_size=C.sizeof(L.fs_ppo_minibatch), mode=L.FS_MB_PARTIAL if partial else L.FS_MB_STEP,
+                                flags=flags, batch=batch, index=index, seed=int(seed) & (2 ** 64 - 1),
+                                epoch_dev=self.mb_epoch.data_ptr(), count_dev=self.mb_count.data_ptr(),
+                                weights_dev=self.weights.data_ptr(), m_dev=self.m.data_ptr(), v_dev=self.v.data_ptr(),
+                                state_dev=self.state.data_ptr(), lr=float(lr), beta1=float(betas[0]), beta2=float(betas[1]),
+                                eps=float(eps))
+        L.check(self.sim.lib.fs_ppo_minibatch_dev(self.sim._h, C.byref(self.struct), C.byref(loss), C.byref(mb), n,
+                                                  obs.data_ptr(), act.data_ptr(), logp_old.data_ptr(), ptr(mean_old),
+                                                  ptr(log_std_old), ptr(val_old), adv64.data_ptr(), ret.data_ptr(),
+                                                  mean_std_n.data_ptr(), self.grad.data_ptr(), self.loss_sums.data_ptr(),
+                                                  work.data_ptr(), work.numel()), self.sim.lib)
+
+    def mb_finish(self, last=False, lr=3e-4, betas=(0.9, 0.999), eps=1e-8):
+        """The end of a step made of ``minibatch_step(partial=True)`` launches (``fs_ppo_mb_finish_dev``): ``self.grad``
+        (raw sums) times ``float(1 / self.mb_count)``, then ``adam_step``'s sequence; no step where the count is 0.
+        ``last=True`` advances ``self.mb_epoch``."""
+        self._adam_buffers()
+        self._bind()
+        L.check(self.sim.lib.fs_ppo_mb_finish_dev(self.sim._h, self.P, self.weights.data_ptr(), self.grad.data_ptr(),
+                                                  self.m.data_ptr(), self.v.data_ptr(), self.state.data_ptr(),
+                                                  self.mb_count.data_ptr(), self.mb_epoch.data_ptr(),
+                                                  L.FS_MB_LAST if last else 0, float(lr), float(betas[0]), float(betas[1]),
+                                                  float(eps)), self.sim.lib)
+
+    @staticmethod
+    def minibatch_fused(batch, D, A, num_hidden):
+        """Does ``update(minibatch=batch)`` make a one-shard step as ONE launch (True) or as the chain PARTIAL +
+        ``mb_finish`` (False)?  A rule on (B, D, A, L) alone, from profiles/ppo_minibatch_bench.json (DESIGN.md 4.3
+        "Minibatches"): at (3, 1), (25, 5) and (141, 20), each at B = 128, 1024 and 4096, the chain took 0.93 .. 0.97 of the
+        one launch's time, the ranges apart at all nine points -- Adam by the one wave of the tail costs more than a second
+        launch of 1024 lanes -- so the rule is the chain, everywhere.  Both give the same bits."""
+        return False
+
     def _adam_buffers(self):
         torch = self.torch
         if self.state is None:
@@ -365,7 +498,8 @@ class DeviceLearner(object):
         return buf
 
     def update(self, shards, epochs=4, clip=0.2, vf_coef=0.5, gamma=0.999, lam=0.97, lr=3e-4, betas=(0.9, 0.999), eps=1e-8,
-               group=None, kl_target=None, kl_coef_init=0.2, entropy_coef=0.0, vf_clip=None):
+               group=None, kl_target=None, kl_coef_init=0.2, entropy_coef=0.0, vf_clip=None, minibatch=None, shuffle_seed=0,
+               fused=None):
         """One PPO update over ``shards`` = [(obs [K+1, R, D], act [K, R(, A)], rew [K, R], done [K, R] uint8)], the whole of
         train_vec.ppo_update on the learner's stream: per shard eval (two launches), gae and the statistics; the
         all-reduce of the three sums (in a data-parallel run); finish; per epoch the gradient over the shards (kernel and
@@ -381,7 +515,20 @@ class DeviceLearner(object):
         epoch come the all-reduce of ``loss_sums`` (data-parallel runs) and, with ``kl_target`` set, ``kl_adapt``: the
         coefficient lives in ``self.kl_state`` on the device (``kl_coef_init`` before the first such update), so a
         replayed graph advances it.  ``self.loss`` is then left alone: the sums are ``self.loss_sums``.  With the
-        defaults the launches are exactly the 17 above."""
+        defaults the launches are exactly the 17 above.
+        ``minibatch`` (a per-shard size B; ``None``: everything above, launch for launch): an epoch is a shuffled pass of
+        ``ceil(n / B)`` minibatch steps (``minibatch_step`` states one step), each ONE launch for one shard in one process
+        (``fused=True``: 5 + epochs x ceil(n / B) launches, plus the copy and ``kl_adapt`` with the loss terms on) or the
+        chain of two, PARTIAL + ``mb_finish`` (what the rule ``minibatch_fused`` picks: it measured faster); for several
+        shards (of equal n: ``ValueError`` otherwise) or ranks, one PARTIAL launch per shard, the all-reduces of the raw
+        sums and of the count, and ``mb_finish``.  The statistics, the old distribution and the KL coefficient stay those of
+        the update's start; ``loss_sums`` accumulate over an epoch's minibatches, so ``kl_adapt`` sees the last epoch's
+        mean KL, each minibatch's evaluated before its own step.  The permutations are
+        ``epoch_permutation(shuffle_seed, self.mb_epoch, n)``; ``self.mb_epoch`` advances on the device with every epoch.
+        ``epochs=0`` makes the prelude alone: no step, and no ``kl_adapt`` either (no KL was seen; ``loss_sums`` is left).
+        ``fused`` (``None``: the rule ``minibatch_fused``) picks the one-launch step or the chain for one shard in one
+        process -- the same bits either way (scripts/bench_ppo_minibatch.py times both).
+        Returns ``self.loss_sums``."""
         import torch.distributed as dist
         torch, lib, h = self.torch, self.sim.lib, self.sim._h
         if self._stats is None:
@@ -394,6 +541,15 @@ class DeviceLearner(object):
         kl_on = kl_target is not None
         vclip_on = vf_clip is not None and 0.0 < float(vf_clip) < float("inf")
         full = kl_on or vclip_on or float(entropy_coef) != 0.0
+        if minibatch is not None:
+            minibatch = int(minibatch)
+            if minibatch < 1:
+                raise ValueError("DeviceLearner.update: minibatch must be at least 1 (got %d)" % minibatch)
+            sizes = set(int(s[2].shape[0]) * int(s[2].shape[1]) for s in shards)
+            if len(sizes) != 1:
+                raise ValueError("DeviceLearner.update: minibatch steps take rows [kB, (k + 1)B) of every shard's own "
+                                 "permutation, so the shards must hold the same number of samples (got %s)" % sorted(sizes))
+            work_mb = self._mb_workspace(minibatch)
         if kl_on and not self._kl_started:
             self.kl_state[0].fill_(float(kl_coef_init))       # (the first such call is eager: never inside a capture)
             self.kl_state[1].fill_(0.0)
@@ -429,6 +585,32 @@ class DeviceLearner(object):
         if spread:
             dist.all_reduce(self._stats, op=dist.ReduceOp.SUM, group=group)
         L.check(lib.fs_adv_finish_dev(h, self._stats.data_ptr(), self._mean_std_n.data_ptr()), lib)
+        if minibatch is not None:
+            n = prepared[0][0]
+            steps = -(-n // minibatch)
+            if fused is None:
+                fused = self.minibatch_fused(minibatch, self.D, self.A, self.num_hidden)
+            chain = spread or len(prepared) > 1 or not fused
+            for _ in range(epochs):
+                for k in range(steps):
+                    for j, (n, o, a, b) in enumerate(prepared):
+                        self._mb_step(n, o, a, b["logp"], b.get("mean_old") if full else None,
+                                      b.get("log_std_old") if full else None, b["val"] if full else None, b["adv64"],
+                                      b["ret"], self._mean_std_n, minibatch, k, shuffle_seed, clip, vf_coef,
+                                      vf_clip if vclip_on else None, entropy_coef, kl_on, chain, j > 0, k == 0,
+                                      k == steps - 1, lr, betas, eps, work_mb)
+                    if chain:
+                        if spread:
+                            dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=group)
+                            dist.all_reduce(self.mb_count, op=dist.ReduceOp.SUM, group=group)
+                        self.mb_finish(k == steps - 1, lr, betas, eps)
+            if epochs < 1:                                   # (no epoch: no KL was seen, the coefficient stays -- ppo_update's rule)
+                return self.loss_sums
+            if spread:
+                dist.all_reduce(self.loss_sums, op=dist.ReduceOp.SUM, group=group)
+            if kl_on:
+                self.kl_adapt(kl_target, self._mean_std_n)
+            return self.loss_sums
         for _ in range(epochs):
             for j, (n, o, a, b) in enumerate(prepared):
                 if full:

@@ -683,6 +683,71 @@ int fs_ppo_grad_loss_dev(fs_handle h, const fs_ppo_model* model, const fs_ppo_lo
 int fs_kl_adapt_dev(fs_handle h, const float* loss_sums_dev, const double* mean_std_n_dev, double* kl_state_dev,
                     double kl_target);
 
+/* ---- minibatch SGD: an epoch is a shuffled pass of minibatch steps ---------------
+ * Epoch e of an update permutes the shard's n rows with perm(seed, e, n); minibatch k of size B is rows
+ * perm[k B .. min((k + 1) B, n)), the last one kept when it is short; ceil(n / B) steps per epoch, in ascending k.  One step:
+ * the loss above (every term on or off) over the minibatch's present rows, divided by the minibatch's OWN count c of present
+ * rows, its gradient, one Adam step; c == 0 makes no step (Adam's t, m, v and the weights untouched).  The advantages stay
+ * standardised by mean_std_n_dev (whole batch, once per update; its n is not read here), the old distribution and the KL
+ * coefficient stay those of the update's start.
+ * perm is computed, never stored: a balanced Feistel network of 4 rounds over the smallest even number of bits that holds
+ * n - 1 (at least 2), round function murmur3's fmix32 of (right half + round key), round keys from fmix32 of (seed, epoch,
+ * round), cycle-walked (re-applied until the value is < n).  32-bit integer operations only: fs_ppo_perm_host, the kernel
+ * and flow_amd.utils.device_ppo.epoch_permutation give the same values.
+ * fs_ppo_perm_host needs no handle and no GPU: out [n] = perm(seed, epoch, n). */
+int fs_ppo_perm_host(uint64_t seed, uint64_t epoch, int64_t n, int64_t* out);
+
+enum { FS_MB_STEP = 0, FS_MB_PARTIAL = 1 };                          /* fs_ppo_minibatch.mode */
+enum { FS_MB_ACCUMULATE = 1, FS_MB_FIRST = 2, FS_MB_LAST = 4 };      /* fs_ppo_minibatch.flags */
+typedef struct fs_ppo_minibatch {
+  uint32_t struct_size;               /* sizeof(fs_ppo_minibatch) */
+  int32_t mode;                       /* FS_MB_STEP: reduce, divide, Adam in the launch; FS_MB_PARTIAL: reduce only */
+  int32_t flags;                      /* FS_MB_ACCUMULATE (PARTIAL): a later shard of the step -- sums and count are added
+                                       * FS_MB_FIRST: the epoch's first minibatch -- loss_sums_dev is overwritten, not added to
+                                       * FS_MB_LAST (STEP): the epoch's last minibatch -- *epoch_dev advances */
+  int32_t reserved;
+  int64_t batch;                      /* B >= 1 (a per-shard size) */
+  int64_t index;                      /* k: 0 .. ceil(n / B) - 1 */
+  uint64_t seed;
+  uint64_t* epoch_dev;                /* the epoch counter, device: read by the launch, so a replayed graph draws fresh
+                                       * permutations */
+  double* count_dev;                  /* PARTIAL: [1] the step's count of present rows (double, so that it all-reduces) */
+  float* weights_dev;                 /* STEP: the packed buffer [policy][log_std A][value] fs_ppo_model points into */
+  float* m_dev;                       /* STEP: Adam's moments [P] and state [3], as in fs_adam_dev */
+  float* v_dev;
+  double* state_dev;
+  double lr, beta1, beta2, eps;       /* STEP */
+} fs_ppo_minibatch;
+
+/* 4-byte words of work_dev that fs_ppo_minibatch_dev needs: G (P + 4) partial sums and G integer counts, G = the workgroups
+ * of fs_ppo_workspace for a batch of `batch` samples -- a function of (batch, model) alone (0: not valid). */
+size_t fs_ppo_minibatch_workspace(const fs_ppo_model* model, int64_t batch);
+/* One minibatch step in ONE launch (fs_last_kernel: "k_ppo_minibatch"); the arguments are fs_ppo_grad_loss_dev's, the rows
+ * are gathered through perm inside the kernel.  Tile t (64 positions of the minibatch) goes to workgroup t mod G; the lane
+ * arithmetic runs with 1 in the place of 1 / n (every term is linear in it); a workgroup writes its partial [P + 4] and its
+ * integer count of present rows to work_dev and draws an integer ticket; the workgroup that draws the last one adds the G
+ * partials in ascending workgroup order -- no float atomics, no workgroup ever waits for another -- and
+ *   FS_MB_STEP     c = the sum of the counts;  g[p] = sum[p] * (float)(1.0 / (double)c);  grad_dev[p] = g[p];  the raw loss
+ *                  sums are added to loss_sums_dev (FS_MB_FIRST: overwrite it);  fs_adam_dev's sequence with g on
+ *                  weights_dev, m_dev, v_dev, state_dev;  c == 0: grad_dev = the sums (exact zeros), no Adam step
+ *   FS_MB_PARTIAL  grad_dev, loss_sums_dev, count_dev[0] receive the raw sums and (double)c (FS_MB_ACCUMULATE: they are
+ *                  added); fs_ppo_mb_finish_dev follows once every shard is in and the ranks have all-reduced them.
+ * FS_MB_STEP on one shard gives the bits of FS_MB_PARTIAL + fs_ppo_mb_finish_dev.  Nothing of an absent row (a NaN in its
+ * action row) reaches an output.  Refused before anything launches, by name: a model outside fs_ppo_model's class, batch < 1,
+ * an index beyond the epoch, a NULL epoch_dev, and in FS_MB_STEP a NULL state_dev, m_dev, v_dev or weights_dev.  The first
+ * call on a handle allocates the ticket and synchronises the device once: make it before a stream capture begins. */
+int fs_ppo_minibatch_dev(fs_handle h, const fs_ppo_model* model, const fs_ppo_loss* loss, const fs_ppo_minibatch* mb, int64_t n,
+                         const float* obs_dev, const float* act_dev, const float* logp_old_dev, const float* mean_old_dev,
+                         const float* log_std_old_dev, const float* val_old_dev, const double* adv_dev, const float* ret_dev,
+                         const double* mean_std_n_dev, float* grad_dev, float* loss_sums_dev, float* work_dev,
+                         size_t work_floats);
+/* The end of a step made of FS_MB_PARTIAL launches (fs_last_kernel: "k_mb_finish"), one workgroup like fs_adam_dev:
+ *   c = count_dev[0];  c == 0: nothing;  otherwise g[p] = grad_dev[p] * (float)(1.0 / c);  grad_dev[p] = g[p];  fs_adam_dev's
+ *   sequence with g.  flags: FS_MB_LAST advances *epoch_dev (with or without a step). */
+int fs_ppo_mb_finish_dev(fs_handle h, int64_t num_params, float* weights_dev, float* grad_dev, float* m_dev, float* v_dev,
+                         double* state_dev, const double* count_dev, uint64_t* epoch_dev, int flags, double lr, double beta1,
+                         double beta2, double eps);
+
 /* Append the CURRENT state of one replica to a CSV file (header `time,id,x,speed,lane_number` when the file is new;
  * one row per vehicle, id = slot index, free slots of open networks skipped): the trajectory ("emission") dump of
  * flow/core/kernel/simulation/traci.py:95-101 (SUMO's --emission-output) for callers without the Python layer;
