@@ -47,14 +47,16 @@ def parse_args(args):
                         help='device: run the whole PPO update, Adam included, on the device with no host round trip '
                              '(DeviceLearner.update); implies --device_update')
     parser.add_argument('--epochs', type=int, default=4, help='device: passes over a rollout fragment per update')
-    from train_vec import add_ppo_loss_flags
+    from train_vec import add_model_flags, add_ppo_loss_flags
     add_ppo_loss_flags(parser)              # --kl_target --kl_coeff --entropy_coeff --vf_clip --sgd_minibatch_size: all off by default
+    add_model_flags(parser)                 # --net_log_std: off by default
     parser.add_argument('--reference_ppo', action='store_true',
                         help='device: the loss and settings the reference trains with (RLlib PPO as its train.py sets it '
                              'up): --kl_target 0.02 --kl_coeff 0.2 --vf_clip 10 --epochs 10, vf_loss_coeff 1.0, '
                              'clip_param 0.3.  With --sgd_minibatch_size 128 --device_adam on top, every epoch is a '
-                             'shuffled pass of minibatch steps: the reference\'s optimisation.  Not reproduced: its head '
-                             'of 2 x act_dim outputs (the log std is a free parameter here)')
+                             'shuffled pass of minibatch steps: the reference\'s optimisation; --net_log_std on top of '
+                             'that gives the policy the reference\'s head of 2 x act_dim outputs (without it the log std '
+                             'is a free parameter)')
     return parser.parse_known_args(args)[0]
 
 
@@ -63,8 +65,8 @@ def ppo_loss_settings(flags):
     (kl_target 0.02, num_sgd_iter 10) on top of RLlib's PPO defaults (kl_coeff 0.2, vf_clip_param 10, vf_loss_coeff 1.0,
     clip_param 0.3, entropy_coeff 0); gamma 0.999 and lambda 0.97 are train_on_device's already.  --reference_ppo keeps
     its meaning: the minibatches are a flag of their own, and ``--reference_ppo --sgd_minibatch_size 128 --device_adam`` is
-    the reference's optimisation (num_sgd_iter passes of sgd_minibatch_size samples).  Not reproduced: the head of
-    2 act_dim outputs."""
+    the reference's optimisation (num_sgd_iter passes of sgd_minibatch_size samples); the reference's model, the head of
+    2 act_dim outputs, is the flag --net_log_std (train_device passes it on)."""
     if flags.reference_ppo:
         return dict(kl_target=0.02, kl_coeff=0.2, vf_clip=10.0, epochs=10, vf_coef=1.0, clip=0.3,
                     entropy_coeff=flags.entropy_coeff, sgd_minibatch_size=flags.sgd_minibatch_size)
@@ -125,7 +127,7 @@ def train_device(submodule, flags, multiagent=False):
     return train_on_device(fp, replicas=flags.replicas, fragment=flags.rollout_size, iterations=flags.num_steps,
                            shared_agents=multiagent, fuse_action_vector=flags.fuse_policy and not multiagent,
                            device_update=flags.device_update or flags.device_adam, device_adam=flags.device_adam,
-                           **ppo_loss_settings(flags))
+                           net_log_std=flags.net_log_std, **ppo_loss_settings(flags))
 
 
 def main(args):

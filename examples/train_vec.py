@@ -46,20 +46,41 @@ def ring_flow_params(horizon):
 
 
 class GaussianPolicy(nn.Module):
-    def __init__(self, obs_dim, act_dim, hidden=32):
+    """``net_log_std`` (RLlib's default model, ``free_log_std: false`` -- what the reference trains): the last layer of
+    ``self.mu`` has ``2 * act_dim`` outputs, the means and then the log stds (RLlib's DiagGaussian order, DevicePolicy's),
+    so the standard deviation depends on the observation, and there is no ``log_std`` parameter.  The log-std rows start
+    with zero weights and bias -0.5: the first rollout samples as the free form does at its start."""
+
+    def __init__(self, obs_dim, act_dim, hidden=32, net_log_std=False):
         super().__init__()
+        self.net_log_std, self.act_dim = bool(net_log_std), act_dim
         self.mu = nn.Sequential(nn.Linear(obs_dim, hidden), nn.Tanh(), nn.Linear(hidden, hidden), nn.Tanh(),
-                                nn.Linear(hidden, act_dim))
+                                nn.Linear(hidden, 2 * act_dim if net_log_std else act_dim))
         self.value = nn.Sequential(nn.Linear(obs_dim, hidden), nn.Tanh(), nn.Linear(hidden, hidden), nn.Tanh(),
                                    nn.Linear(hidden, 1))
-        self.log_std = nn.Parameter(torch.full((act_dim,), -0.5))
+        if net_log_std:
+            with torch.no_grad():
+                self.mu[4].weight[act_dim:].zero_()
+                self.mu[4].bias[act_dim:].fill_(-0.5)
+        else:
+            self.log_std = nn.Parameter(torch.full((act_dim,), -0.5))
+
+    def _dist(self, obs):
+        """(means, log stds) [n, A] of the head of 2 A outputs."""
+        out = self.mu(obs)
+        return out[..., :self.act_dim], out[..., self.act_dim:]
 
     def act(self, obs):                       # what the captured graph runs every step
         with torch.no_grad():
+            if self.net_log_std:
+                mu, ls = self._dist(obs)
+                return mu + torch.randn_like(mu) * ls.exp()
             mu = self.mu(obs)
             return mu + torch.randn_like(mu) * self.log_std.exp()
 
     def logp_value(self, obs, act):
+        if self.net_log_std:
+            return self.logp_value_dist(obs, act)[:2]
         mu = self.mu(obs)
         std = self.log_std.exp()
         logp = (-0.5 * ((act - mu) / std) ** 2 - self.log_std - 0.9189385).sum(-1)
@@ -67,7 +88,11 @@ class GaussianPolicy(nn.Module):
 
     def logp_value_dist(self, obs, act):
         """``logp_value`` and the distribution itself: (logp, value, means [n, A], log_std [A]) -- what the KL term of
-        ppo_update keeps from its no_grad pass."""
+        ppo_update keeps from its no_grad pass.  ``net_log_std``: the log stds are per sample, [n, A]."""
+        if self.net_log_std:
+            mu, ls = self._dist(obs)
+            logp = (-0.5 * ((act - mu) / ls.exp()) ** 2 - ls - 0.9189385).sum(-1)
+            return logp, self.value(obs).squeeze(-1), mu, ls
         mu = self.mu(obs)
         std = self.log_std.exp()
         logp = (-0.5 * ((act - mu) / std) ** 2 - self.log_std - 0.9189385).sum(-1)
@@ -125,6 +150,8 @@ def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None, learner=None, kl
         KL = sum_c ls - ls_o + (exp(2 ls_o) + (mu_o - mu)^2) / (2 exp(2 ls)) - 0.5,   H = sum_c ls + 0.5 log(2 pi e)
         v_c = v_o + clamp(v - v_o, -vf_clip, +vf_clip)
     with mu_o, ls_o, v_o from the no_grad pass (``pi.logp_value_dist``).  ``vf_clip`` None or inf: vfl = (v - ret)^2.
+    A policy whose log stds come from the network (``GaussianPolicy(net_log_std=True)``) hands over ls and ls_o per sample,
+    [n, A]: the same formulas, H = sum_c ls[s, c] + 0.5 log(2 pi e) per sample.
     After the last epoch ``kl.adapt`` sees that epoch's mean KL (summed over shards and ranks).  With a learner the same
     loss runs on fs_ppo_eval_dist_dev / fs_ppo_grad_loss_dev.  With the defaults the arithmetic is what it was.
     ``minibatch`` (RLlib's ``sgd_minibatch_size``, a per-shard size B; None: everything above): an epoch is a shuffled
@@ -133,6 +160,10 @@ def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None, learner=None, kl
     ``epoch_permutation(shuffle_seed, epoch0 + e, n)``.  With a ``learner`` (the --device_update path, torch's Adam) this is
     not built: use --device_adam, where the whole step is one launch."""
     from flow_amd.dist import allreduce_gradients, allreduce_sum
+    if learner is not None and getattr(learner, "net_log_std", False):
+        raise NotImplementedError("ppo_update(learner=...) with the 2A-output head (net_log_std): the gradient around torch's "
+                                  "Adam (--device_update, fs_ppo_grad_dev) is not built for it; --device_adam runs the whole "
+                                  "update on the device (DeviceLearner.update)")
     if minibatch is not None and learner is not None:
         raise NotImplementedError("ppo_update(learner=..., minibatch=...): minibatch steps around torch's Adam (--device_update) "
                                   "are not built; --device_adam runs them on the device (DeviceLearner.update(minibatch=))")
@@ -218,9 +249,16 @@ def ppo_update(pi, opt, shards, epochs=4, clip=0.2, group=None, learner=None, kl
             learner.sync()                                   # the optimiser moved the weights: repack them for the kernels
 
 
+def _entropy(ls):
+    """H of the diagonal Gaussian: sum_c ls + 0.5 log(2 pi e) -- one number for the free log_std [A], one per sample for
+    log stds from the network [n, A]."""
+    import math
+    h = ls + 0.5 * math.log(2.0 * math.pi * math.e)
+    return h.sum() if ls.dim() == 1 else h.sum(-1)
+
+
 def _ppo_epochs_full(pi, opt, prepared, params, epochs, clip, group, learner, kl, entropy_coef, vf_clip, vf_coef, mean, std, n):
     """The epochs of ppo_update with the reference's loss terms on (its docstring states the loss)."""
-    import math
     from flow_amd.dist import allreduce_gradients, allreduce_sum
     sum_kl = None
     if learner is not None:
@@ -254,7 +292,7 @@ def _ppo_epochs_full(pi, opt, prepared, params, epochs, clip, group, learner, kl
                     shard_kl = (kl_s.detach() if present is None else torch.where(present, kl_s.detach(), torch.zeros_like(kl_s))).sum()
                     sum_kl = shard_kl if sum_kl is None else sum_kl + shard_kl
                 if entropy_coef != 0.0:
-                    per = per - entropy_coef * (ls + 0.5 * math.log(2.0 * math.pi * math.e)).sum()
+                    per = per - entropy_coef * _entropy(ls)
                 if present is not None:
                     per = torch.where(present, per, torch.zeros_like(per))
                 # the GLOBAL mean as a sum of per-shard sums
@@ -279,7 +317,6 @@ def _ppo_epochs_minibatch(pi, opt, prepared, params, epochs, clip, group, kl, en
       divided by THEIR count c -- not by n --, its gradient, one optimiser step; c == 0: no step at all;
     * after the last epoch kl.adapt sees (the sum of that epoch's minibatches' per-sample KL, each evaluated before its
       own step) / n."""
-    import math
     from flow_amd.dist import allreduce_gradients, allreduce_sum
     from flow_amd.utils.device_ppo import epoch_permutation
     sizes = sorted(set(int(p[0].shape[0]) for p in prepared))
@@ -301,6 +338,8 @@ def _ppo_epochs_minibatch(pi, opt, prepared, params, epochs, clip, group, kl, en
                 adv_n = ((adv - mean) / (std + 1e-8)).float()
                 if full:
                     v_old, mu_old, ls_old = shard[6][idx], shard[7][idx], shard[8]
+                    if ls_old.dim() > 1:                     # (log stds from the network: per sample)
+                        ls_old = ls_old[idx]
                     logp, v, mu, ls = pi.logp_value_dist(o, a)
                 else:
                     logp, v = pi.logp_value(o, a)
@@ -317,7 +356,7 @@ def _ppo_epochs_minibatch(pi, opt, prepared, params, epochs, clip, group, kl, en
                     kl_d = kl_s.detach()
                     sum_kl = sum_kl + (kl_d if present is None else torch.where(present, kl_d, torch.zeros_like(kl_d))).sum().double()
                 if entropy_coef != 0.0:
-                    per = per - entropy_coef * (ls + 0.5 * math.log(2.0 * math.pi * math.e)).sum()
+                    per = per - entropy_coef * _entropy(ls)
                 if present is not None:
                     per = torch.where(present, per, torch.zeros_like(per))
                 total = per.sum() if total is None else total + per.sum()
@@ -335,7 +374,7 @@ def _ppo_epochs_minibatch(pi, opt, prepared, params, epochs, clip, group, kl, en
 def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epochs=4, lr=3e-4, seed=0, log=print,
                     rank=0, world=1, shared_agents=False, fuse_action_vector=False, device_update=False, device_adam=False,
                     kl_target=None, kl_coeff=0.2, entropy_coeff=0.0, vf_clip=None, vf_coef=0.5, clip=0.2,
-                    sgd_minibatch_size=None):
+                    sgd_minibatch_size=None, net_log_std=False):
     """PPO on R replicas of ``flow_params`` with everything in HBM: returns the mean step reward per iteration.
     ``world`` > 1: this process is rank ``rank`` of a data-parallel run (torch.distributed is initialised): it steps its
     block of the R replicas on its own GPU.
@@ -366,8 +405,16 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     shuffled pass of minibatch steps of this many samples (ppo_update(minibatch=) states the semantics).  With
     ``device_adam`` a step runs on the device (DeviceLearner.update(minibatch=)); the torch update runs the same steps in
     torch; ``device_update`` alone (torch's Adam around the kernels) does not build them and says so.  The epochs of
-    iteration ``it`` draw the permutations of epochs ``it * epochs ..`` on both paths."""
+    iteration ``it`` draw the permutations of epochs ``it * epochs ..`` on both paths.
+    ``net_log_std``: the policy's head has 2 x act_dim outputs, the means and the log stds (``GaussianPolicy(net_log_std=
+    True)``: RLlib's default model, the reference's).  The torch update takes it, and so does ``device_adam`` -- the learner
+    is ``DeviceLearner(net_log_std=True)`` and a fused or graph DevicePolicy reads its buffer through ``share`` --;
+    ``device_update`` alone (the host-n gradient around torch's Adam) does not build it and says so.  Off by default."""
     from flow_amd.dist import allreduce_sum, shard_range
+    if net_log_std and device_update and not device_adam:
+        raise NotImplementedError("train_on_device(net_log_std=True, device_update=True): the 2A-output head is not built for "
+                                  "the device update around torch's Adam (fs_ppo_grad_dev); add device_adam (--device_adam), "
+                                  "which runs the whole update on the device")
     from flow_amd.envs import VecFlowEnv
     local = int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else 0
     dev = torch.device("cuda", local)
@@ -379,11 +426,14 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     if shared_agents and (vec.act_dim < 1 or vec.obs_dim % vec.act_dim):
         raise ValueError("shared_agents: the observation (%d) is not one block per action column (%d)" % (vec.obs_dim, vec.act_dim))
     k_ag = vec.obs_dim // n_ag
-    pi = GaussianPolicy(k_ag if shared_agents else vec.obs_dim, 1 if shared_agents else vec.act_dim).to(dev)
+    pi = GaussianPolicy(k_ag if shared_agents else vec.obs_dim, 1 if shared_agents else vec.act_dim,
+                        net_log_std=net_log_std).to(dev)
+    free_log_std = None if net_log_std else pi.log_std
     learner, opt = None, None
     if device_adam:
         from flow_amd.utils.device_ppo import DeviceLearner
-        learner = DeviceLearner(vec, [pi.mu[0], pi.mu[2]], pi.mu[4], pi.log_std, [pi.value[0], pi.value[2]], pi.value[4])
+        learner = DeviceLearner(vec, [pi.mu[0], pi.mu[2]], pi.mu[4], free_log_std, [pi.value[0], pi.value[2]], pi.value[4],
+                                net_log_std=net_log_std)
         learner.adopt_parameters()                             # (before the rollout graph captures the parameters' addresses)
     else:
         opt = torch.optim.Adam(pi.parameters(), lr=lr)
@@ -398,9 +448,9 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     try:
         from flow_amd.utils.device_policy import DevicePolicy
         if fuse_action_vector and not shared_agents:
-            fused = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=pi.log_std, seed=seed, act_dim=vec.act_dim)
+            fused = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=free_log_std, seed=seed, act_dim=vec.act_dim)
         else:
-            fused = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=pi.log_std, seed=seed)
+            fused = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=free_log_std, seed=seed)
         if device_adam:
             fused.share(learner)                               # the rollout kernels read the buffer the learner's Adam writes
         vec.reset()
@@ -519,6 +569,14 @@ def add_ppo_loss_flags(ap):
                          "the device with --device_adam.  Default: one step per epoch over the whole fragment")
 
 
+def add_model_flags(ap):
+    """The policy head's form (train_vec.py and train.py)."""
+    ap.add_argument("--net_log_std", action="store_true",
+                    help="the policy's head has 2 x act_dim outputs, the means and the log stds (RLlib's default model, "
+                         "free_log_std: false -- the reference's), instead of a free log_std parameter; on the device with "
+                         "--device_adam")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--replicas", type=int, default=1024)
@@ -533,6 +591,7 @@ def main(argv=None):
     ap.add_argument("--device_adam", action="store_true",
                     help="run the whole PPO update, Adam included, on the device (DeviceLearner.update); implies --device_update")
     add_ppo_loss_flags(ap)
+    add_model_flags(ap)
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     force = os.environ.get("TRAIN_FORCE_DIST") == "1"            # the N > 1 code path (RCCL init, all-reduces) with one rank
@@ -552,7 +611,8 @@ def main(argv=None):
                                iterations=args.iterations, epochs=args.epochs, lr=args.lr, rank=rank, world=world,
                                device_update=args.device_update or args.device_adam, device_adam=args.device_adam,
                                kl_target=args.kl_target, kl_coeff=args.kl_coeff, entropy_coeff=args.entropy_coeff,
-                               vf_clip=args.vf_clip, sgd_minibatch_size=args.sgd_minibatch_size)
+                               vf_clip=args.vf_clip, sgd_minibatch_size=args.sgd_minibatch_size,
+                               net_log_std=args.net_log_std)
     finally:
         if world > 1 or force:
             import torch.distributed as dist

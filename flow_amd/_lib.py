@@ -122,6 +122,7 @@ class fs_policy(C.Structure):
 
 
 class fs_ppo_model(C.Structure):
+    # (log_std_dev None / NULL: the policy's head has 2 x act_dim outputs, the means and then the log stds)
     _fields_ = [("struct_size", C.c_uint32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("num_hidden", C.c_int32),
                 ("hidden_width", C.c_int32), ("activation", C.c_int32), ("policy_weights_dev", C.c_void_p),
                 ("log_std_dev", C.c_void_p), ("value_weights_dev", C.c_void_p)]

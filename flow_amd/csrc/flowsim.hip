@@ -505,7 +505,11 @@ int fs_policy_rollout_dev(fs_handle h, const fs_policy* pol, int num_steps, int 
 }
 
 // ---- the PPO update on the device (flowsim_learn.h): the handle lends its device, its stream and fs_last_error
-static int ppo_view(const char* who, const fs_ppo_model* m, bool need_policy, fs::PpoView* out) {
+// the head of 2 A outputs, fs_policy's convention: no free log_std (log_std_dev == NULL), rows A .. 2A-1 are the log stds
+static bool ppo_head_ls(const fs_ppo_model* m) { return m && m->struct_size == sizeof(fs_ppo_model) && !m->log_std_dev; }
+
+// (free_head_only: the caller's kernel is not built for the head of 2 A outputs -- fs_ppo_grad_dev, the host-n gradient)
+static int ppo_view(const char* who, const fs_ppo_model* m, bool need_policy, fs::PpoView* out, bool free_head_only = false) {
   const std::string w = std::string(who) + ": fs_ppo_model: ";
   if (!m) return fail(FS_ERR_INVALID, w + "NULL");
   if (m->struct_size != sizeof(fs_ppo_model)) return fail(FS_ERR_INVALID, w + "struct_size mismatch");
@@ -516,8 +520,9 @@ static int ppo_view(const char* who, const fs_ppo_model* m, bool need_policy, fs
   if (m->num_hidden < 1 || m->num_hidden > 3 || m->hidden_width != 32)
     return fail(FS_ERR_UNSUPPORTED, w + "1..3 hidden layers of 32 units");
   if (m->activation != 0) return fail(FS_ERR_UNSUPPORTED, w + "activation must be 0 (tanh)");
-  if (need_policy && !m->log_std_dev)
-    return fail(FS_ERR_UNSUPPORTED, w + "the head of 2 A outputs (no free log_std) is not built: log_std_dev is NULL");
+  if (need_policy && free_head_only && !m->log_std_dev)
+    return fail(FS_ERR_UNSUPPORTED, w + "the head of 2 A outputs (no free log_std: log_std_dev is NULL) is not built for the "
+                                        "gradient with the sample count from the host; fs_ppo_grad_n_dev takes it");
   if (!m->value_weights_dev || (need_policy && !m->policy_weights_dev)) return fail(FS_ERR_INVALID, w + "NULL weights");
   *out = fs::PpoView{m->policy_weights_dev, m->log_std_dev, m->value_weights_dev, m->obs_dim, m->act_dim, m->num_hidden};
   return FS_OK;
@@ -530,7 +535,7 @@ int fs_ppo_eval_dev(fs_handle h, const fs_ppo_model* model, int64_t n, const flo
   fs::PpoView pv;
   if (int rc = ppo_view("fs_ppo_eval_dev", model, act_dev != nullptr, &pv)) return rc;
   DeviceGuard guard(S(h)->cfg.device);
-  S(h)->last_kernel = "k_ppo_eval";
+  S(h)->last_kernel = act_dev && ppo_net_ls(pv) ? "k_ppo_eval_ls" : "k_ppo_eval";
   return launch_ppo_eval(S(h)->stream, pv, n, obs_dev, act_dev, logp_dev, val_dev);
 }
 
@@ -548,18 +553,22 @@ int fs_gae_dev(fs_handle h, int num_steps, int64_t num_cols, const float* rew_de
 size_t fs_ppo_workspace(const fs_ppo_model* model, int64_t n) {
   fs::PpoView pv;
   if (n < 1 || n > INT32_MAX || ppo_view("fs_ppo_workspace", model, false, &pv)) return 0;
-  return fs::ppo_work_floats(n, pv.D, pv.A, pv.L);
+  return fs::ppo_work_floats(n, pv.D, pv.A, pv.L, ppo_head_ls(model));
 }
 
 int fs_ppo_grad_dev(fs_handle h, const fs_ppo_model* model, int64_t n, const float* obs_dev, const float* act_dev,
                     const float* logp_old_dev, const double* adv_dev, const float* ret_dev, const double* mean_std_dev,
                     float clip, float vf_coef, float inv_n_total, int accumulate, float* grad_dev, float* loss_dev,
                     float* work_dev, size_t work_floats) {
+  if (ppo_head_ls(model)) {                                  // (refused from the model alone, whatever else is passed)
+    fs::PpoView none;
+    if (int rc = ppo_view("fs_ppo_grad_dev", model, true, &none, true)) return rc;
+  }
   if (!h || !obs_dev || !act_dev || !logp_old_dev || !adv_dev || !ret_dev || !mean_std_dev || !grad_dev || !loss_dev || !work_dev)
     return fail(FS_ERR_INVALID, "fs_ppo_grad_dev: NULL argument");
   if (n < 1 || n > INT32_MAX) return fail(FS_ERR_INVALID, "fs_ppo_grad_dev: n must be 1 .. 2^31 - 1");
   fs::PpoView pv;
-  if (int rc = ppo_view("fs_ppo_grad_dev", model, true, &pv)) return rc;
+  if (int rc = ppo_view("fs_ppo_grad_dev", model, true, &pv, true)) return rc;
   if (work_floats < fs::ppo_work_floats(n, pv.D, pv.A, pv.L))
     return fail(FS_ERR_INVALID, "fs_ppo_grad_dev: work_dev is smaller than fs_ppo_workspace(model, n) floats");
   DeviceGuard guard(S(h)->cfg.device);
@@ -579,10 +588,10 @@ int fs_ppo_grad_n_dev(fs_handle h, const fs_ppo_model* model, int64_t n, const f
   if (n < 1 || n > INT32_MAX) return fail(FS_ERR_INVALID, "fs_ppo_grad_n_dev: n must be 1 .. 2^31 - 1");
   fs::PpoView pv;
   if (int rc = ppo_view("fs_ppo_grad_n_dev", model, true, &pv)) return rc;
-  if (work_floats < fs::ppo_work_floats(n, pv.D, pv.A, pv.L))
+  if (work_floats < fs::ppo_work_floats(n, pv.D, pv.A, pv.L, ppo_net_ls(pv)))
     return fail(FS_ERR_INVALID, "fs_ppo_grad_n_dev: work_dev is smaller than fs_ppo_workspace(model, n) floats");
   DeviceGuard guard(S(h)->cfg.device);
-  S(h)->last_kernel = "k_ppo_grad";
+  S(h)->last_kernel = ppo_net_ls(pv) ? "k_ppo_grad_ls" : "k_ppo_grad";
   return launch_ppo_grad_n(S(h)->stream, pv, n, obs_dev, act_dev, logp_old_dev, adv_dev, ret_dev, mean_std_n_dev,
                            float(1.0 - double(clip)), float(1.0 + double(clip)), vf_coef, accumulate ? 1 : 0, grad_dev,
                            loss_dev, work_dev);
@@ -633,27 +642,33 @@ int fs_ppo_eval_dist_dev(fs_handle h, const fs_ppo_model* model, int64_t n, cons
   fs::PpoView pv;
   if (int rc = ppo_view("fs_ppo_eval_dist_dev", model, true, &pv)) return rc;
   DeviceGuard guard(S(h)->cfg.device);
-  S(h)->last_kernel = "k_ppo_eval";
+  S(h)->last_kernel = ppo_net_ls(pv) ? "k_ppo_eval_ls" : "k_ppo_eval";
   return launch_ppo_eval_dist(S(h)->stream, pv, n, obs_dev, act_dev, logp_dev, val_dev, mean_old_dev);
 }
 
 size_t fs_ppo_loss_workspace(const fs_ppo_model* model, int64_t n) {
   fs::PpoView pv;
   if (n < 1 || n > INT32_MAX || ppo_view("fs_ppo_loss_workspace", model, false, &pv)) return 0;
-  return fs::ppo_loss_work_floats(n, pv.D, pv.A, pv.L);
+  return fs::ppo_loss_work_floats(n, pv.D, pv.A, pv.L, ppo_head_ls(model));
 }
 
-// fs_ppo_loss and the old distribution's pointers -> the kernels' PpoLossArgs (refusals name fs_ppo_loss)
+// fs_ppo_loss and the old distribution's pointers -> the kernels' PpoLossArgs (refusals name fs_ppo_loss).  head_ls (the
+// head of 2 A outputs): the old log stds travel in mean_old_dev [n, 2A] and log_std_old_dev must be NULL
 static int ppo_loss_args(const char* who, const fs_ppo_loss* loss, const float* mean_old_dev, const float* log_std_old_dev,
-                         const float* val_old_dev, fs::PpoLossArgs* out) {
+                         const float* val_old_dev, fs::PpoLossArgs* out, bool head_ls) {
   const std::string w = std::string(who) + ": fs_ppo_loss: ";
+  if (head_ls && log_std_old_dev)
+    return fail(FS_ERR_INVALID, std::string(who) + ": log_std_old_dev must be NULL with the head of 2 A outputs (fs_ppo_model's "
+                                "log_std_dev is NULL): mean_old_dev holds [n, 2A], a row's means and then its log stds");
   if (!loss) return fail(FS_ERR_INVALID, w + "NULL");
   if (loss->struct_size != sizeof(fs_ppo_loss)) return fail(FS_ERR_INVALID, w + "struct_size mismatch");
   if (std::isnan(loss->clip) || std::isnan(loss->vf_coef) || std::isnan(loss->vf_clip) || std::isnan(loss->entropy_coef))
     return fail(FS_ERR_INVALID, w + "a coefficient is NaN");
   if (loss->clip < 0.0f) return fail(FS_ERR_INVALID, w + "clip must not be negative");
   const bool vclip = loss->vf_clip > 0.0f && std::isfinite(loss->vf_clip);
-  if (loss->kl_state_dev && (!mean_old_dev || !log_std_old_dev))
+  if (loss->kl_state_dev && head_ls && !mean_old_dev)
+    return fail(FS_ERR_INVALID, w + "the KL term (kl_state_dev) needs mean_old_dev [n, 2A]");
+  if (loss->kl_state_dev && !head_ls && (!mean_old_dev || !log_std_old_dev))
     return fail(FS_ERR_INVALID, w + "the KL term (kl_state_dev) needs mean_old_dev and log_std_old_dev");
   if (vclip && !val_old_dev) return fail(FS_ERR_INVALID, w + "value clipping (vf_clip > 0) needs val_old_dev");
   *out = fs::PpoLossArgs{mean_old_dev, log_std_old_dev, val_old_dev, loss->kl_state_dev, vclip ? loss->vf_clip : 0.0f,
@@ -666,18 +681,21 @@ int fs_ppo_grad_loss_dev(fs_handle h, const fs_ppo_model* model, const fs_ppo_lo
                          const float* log_std_old_dev, const float* val_old_dev, const double* adv_dev, const float* ret_dev,
                          const double* mean_std_n_dev, int accumulate, float* grad_dev, float* loss_sums_dev, float* work_dev,
                          size_t work_floats) {
+  fs::PpoLossArgs x;
+  if (ppo_head_ls(model) && log_std_old_dev)                 // (refused from the arguments alone: the message is ppo_loss_args')
+    return ppo_loss_args("fs_ppo_grad_loss_dev", loss, mean_old_dev, log_std_old_dev, val_old_dev, &x, true);
   if (!h || !obs_dev || !act_dev || !logp_old_dev || !adv_dev || !ret_dev || !mean_std_n_dev || !grad_dev || !loss_sums_dev ||
       !work_dev)
     return fail(FS_ERR_INVALID, "fs_ppo_grad_loss_dev: NULL argument");
-  fs::PpoLossArgs x;
-  if (int rc = ppo_loss_args("fs_ppo_grad_loss_dev", loss, mean_old_dev, log_std_old_dev, val_old_dev, &x)) return rc;
+  if (int rc = ppo_loss_args("fs_ppo_grad_loss_dev", loss, mean_old_dev, log_std_old_dev, val_old_dev, &x, ppo_head_ls(model)))
+    return rc;
   if (n < 1 || n > INT32_MAX) return fail(FS_ERR_INVALID, "fs_ppo_grad_loss_dev: n must be 1 .. 2^31 - 1");
   fs::PpoView pv;
   if (int rc = ppo_view("fs_ppo_grad_loss_dev", model, true, &pv)) return rc;
-  if (work_floats < fs::ppo_loss_work_floats(n, pv.D, pv.A, pv.L))
+  if (work_floats < fs::ppo_loss_work_floats(n, pv.D, pv.A, pv.L, ppo_net_ls(pv)))
     return fail(FS_ERR_INVALID, "fs_ppo_grad_loss_dev: work_dev is smaller than fs_ppo_loss_workspace(model, n) floats");
   DeviceGuard guard(S(h)->cfg.device);
-  S(h)->last_kernel = "k_ppo_grad_loss";
+  S(h)->last_kernel = ppo_net_ls(pv) ? "k_ppo_grad_loss_ls" : "k_ppo_grad_loss";
   return launch_ppo_grad_loss(S(h)->stream, pv, x, n, obs_dev, act_dev, logp_old_dev, adv_dev, ret_dev, mean_std_n_dev,
                               float(1.0 - double(loss->clip)), float(1.0 + double(loss->clip)), loss->vf_coef,
                               accumulate ? 1 : 0, grad_dev, loss_sums_dev, work_dev);
@@ -706,7 +724,7 @@ int fs_ppo_perm_host(uint64_t seed, uint64_t epoch, int64_t n, int64_t* out) {
 size_t fs_ppo_minibatch_workspace(const fs_ppo_model* model, int64_t batch) {
   fs::PpoView pv;
   if (batch < 1 || batch > INT32_MAX || ppo_view("fs_ppo_minibatch_workspace", model, false, &pv)) return 0;
-  return fs::ppo_mb_work_floats(batch, pv.D, pv.A, pv.L);
+  return fs::ppo_mb_work_floats(batch, pv.D, pv.A, pv.L, ppo_head_ls(model));
 }
 
 int fs_ppo_minibatch_dev(fs_handle h, const fs_ppo_model* model, const fs_ppo_loss* loss, const fs_ppo_minibatch* mb, int64_t n,
@@ -732,17 +750,21 @@ int fs_ppo_minibatch_dev(fs_handle h, const fs_ppo_model* model, const fs_ppo_lo
     if (!mb->weights_dev) return fail(FS_ERR_INVALID, w + "weights_dev is NULL (FS_MB_STEP applies Adam)");
     if (mb->flags & FS_MB_ACCUMULATE) return fail(FS_ERR_INVALID, w + "FS_MB_ACCUMULATE needs FS_MB_PARTIAL (a step has one shard)");
     const int Pp = fs::ppo_net_params(pv.D, pv.L, pv.A);
-    if (pv.pw != mb->weights_dev || pv.log_std != mb->weights_dev + Pp || pv.vw != mb->weights_dev + Pp + pv.A)
+    if (ppo_net_ls(pv)) {
+      if (pv.pw != mb->weights_dev || pv.vw != mb->weights_dev + fs::ppo_net_params(pv.D, pv.L, 2 * pv.A))
+        return fail(FS_ERR_INVALID, w + "weights_dev must be the packed buffer [policy][value] that fs_ppo_model points into");
+    } else if (pv.pw != mb->weights_dev || pv.log_std != mb->weights_dev + Pp || pv.vw != mb->weights_dev + Pp + pv.A)
       return fail(FS_ERR_INVALID, w + "weights_dev must be the packed buffer [policy][log_std A][value] that fs_ppo_model points into");
   } else if (!mb->count_dev) {
     return fail(FS_ERR_INVALID, w + "count_dev is NULL (FS_MB_PARTIAL leaves the count there)");
   }
   fs::PpoLossArgs x;
-  if (int rc = ppo_loss_args("fs_ppo_minibatch_dev", loss, mean_old_dev, log_std_old_dev, val_old_dev, &x)) return rc;
+  if (int rc = ppo_loss_args("fs_ppo_minibatch_dev", loss, mean_old_dev, log_std_old_dev, val_old_dev, &x, ppo_net_ls(pv)))
+    return rc;
   if (!h || !obs_dev || !act_dev || !logp_old_dev || !adv_dev || !ret_dev || !mean_std_n_dev || !grad_dev || !loss_sums_dev ||
       !work_dev)
     return fail(FS_ERR_INVALID, "fs_ppo_minibatch_dev: NULL argument");
-  if (work_floats < fs::ppo_mb_work_floats(mb->batch, pv.D, pv.A, pv.L))
+  if (work_floats < fs::ppo_mb_work_floats(mb->batch, pv.D, pv.A, pv.L, ppo_net_ls(pv)))
     return fail(FS_ERR_INVALID, "fs_ppo_minibatch_dev: work_dev is smaller than fs_ppo_minibatch_workspace(model, batch) floats");
   SimBase* s = S(h);
   DeviceGuard guard(s->cfg.device);
@@ -758,7 +780,7 @@ int fs_ppo_minibatch_dev(fs_handle h, const fs_ppo_model* model, const fs_ppo_lo
   const fs::PpoMbArgs a{mb->seed, reinterpret_cast<unsigned long long*>(mb->epoch_dev), mb->batch, mb->index,
                         mb->mode == FS_MB_STEP ? fs::MB_STEP : fs::MB_PARTIAL, mb->flags, s->d_mb_ticket, grad_dev, loss_sums_dev,
                         mb->count_dev, mb->weights_dev, mb->m_dev, mb->v_dev, mb->state_dev, mb->lr, mb->beta1, mb->beta2, mb->eps};
-  s->last_kernel = "k_ppo_minibatch";
+  s->last_kernel = ppo_net_ls(pv) ? "k_ppo_minibatch_ls" : "k_ppo_minibatch";
   return launch_ppo_minibatch(s->stream, pv, x, a, n, obs_dev, act_dev, logp_old_dev, adv_dev, ret_dev, mean_std_n_dev,
                               float(1.0 - double(loss->clip)), float(1.0 + double(loss->clip)), loss->vf_coef, work_dev);
 }

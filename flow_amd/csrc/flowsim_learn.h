@@ -16,10 +16,14 @@
 //                gathered through a computed permutation, the last workgroup to finish reduces the partials, divides by
 //                the minibatch's own count and applies Adam (MB_STEP), or leaves the raw sums for k_mb_finish (MB_PARTIAL)
 //   k_mb_finish  the divide and Adam of the MB_PARTIAL chain (several shards or ranks), one workgroup like k_adam
+//   NET_LS       one more flag of k_ppo_eval and of the three device-n forms of k_ppo_grad (fs_last_kernel's "k_ppo_eval_ls",
+//                "k_ppo_grad_ls", "k_ppo_grad_loss_ls", "k_ppo_minibatch_ls"): the head of 2 A outputs, whose rows A .. 2A-1
+//                are the log stds -- a function of the observation -- and no free log_std (PpoView::log_std == NULL)
 //
 // Model class (DevicePolicy's): 1..3 hidden layers of 32 tanh units on 1..160 inputs, a head of A <= 32 means with a free
-// log_std [A]; the value network is the same trunk with one output.  Packed weights per network: per layer W [out][in]
-// row-major, then b [out] (fs_policy's layout).
+// log_std [A] -- or (NET_LS) a head of 2 A rows, the A means and then the A log stds: RLlib's DiagGaussian order --; the
+// value network is the same trunk with one output.  Packed weights per network: per layer W [out][in] row-major, then
+// b [out] (fs_policy's layout).
 //
 // Mapping: a workgroup is ONE wave and a lane is ONE sample of a 64-sample tile; tile t belongs to workgroup t mod G and a
 // workgroup takes its tiles in ascending order.  G depends on (n, D, A, layers) alone (ppo_groups), and so does the order
@@ -46,52 +50,63 @@ constexpr int PPO_LDS_BYTES = 160 * 1024;
 
 struct PpoView {
   const float* pw;         // policy weights (packed)
-  const float* log_std;    // [A]
+  const float* log_std;    // [A]; NULL: the head has 2 A rows, the log stds come from rows A .. 2A-1 (NET_LS)
   const float* vw;         // value weights (packed)
   int D, A, L;
 };
 
-// packed parameter counts: a network with n_out outputs; the whole gradient [policy][log_std A][value]
+// packed parameter counts: a network with n_out outputs; the whole gradient [policy][log_std A][value], or with the head of
+// 2 A rows (ls) [policy with its 2A-row head][value]: no log_std slot
 __host__ __device__ constexpr int ppo_net_params(int D, int L, int n_out) { return 32 * D + 32 + (L - 1) * 1056 + 33 * n_out; }
-__host__ __device__ constexpr int ppo_params(int D, int A, int L) { return ppo_net_params(D, L, A) + A + ppo_net_params(D, L, 1); }
-// the LDS copy of a network: [input][unit] per layer, the head padded to 32 units
+__host__ __device__ constexpr int ppo_params(int D, int A, int L, bool ls = false) {
+  return ls ? ppo_net_params(D, L, 2 * A) + ppo_net_params(D, L, 1) : ppo_net_params(D, L, A) + A + ppo_net_params(D, L, 1);
+}
+// the LDS copy of a network: [input][unit] per layer, the head padded to 32 units; the head of 2 A rows is TWO such blocks,
+// rows 0 .. A-1 (means) and rows A .. 2A-1 (log stds), each padded with zeros: 1056 floats more in the policy network's copy
 __host__ __device__ constexpr int ppo_net_lds(int D, int L) { return 32 * D + 32 + L * 1056; }
+__host__ __device__ constexpr int ppo_nets_lds(int D, int L, bool ls) { return 2 * ppo_net_lds(D, L) + (ls ? 1056 : 0); }
 __host__ __device__ constexpr int ppo_stage_floats() { return 32 * PPO_TS + PPO_TILE * PPO_TT; }
 __host__ __device__ constexpr int round4(int x) { return (x + 3) & ~3; }
-__host__ __device__ constexpr size_t ppo_eval_lds(int D, int L) { return sizeof(float) * size_t(2 * ppo_net_lds(D, L) + ppo_stage_floats()); }
-__host__ __device__ constexpr size_t ppo_grad_lds(int D, int A, int L) {
-  return sizeof(float) * size_t(2 * ppo_net_lds(D, L) + ppo_stage_floats() + round4(ppo_params(D, A, L) + 2));
+__host__ __device__ constexpr size_t ppo_eval_lds(int D, int L, bool ls = false) {
+  return sizeof(float) * size_t(ppo_nets_lds(D, L, ls) + ppo_stage_floats());
+}
+__host__ __device__ constexpr size_t ppo_grad_lds(int D, int A, int L, bool ls = false) {
+  return sizeof(float) * size_t(ppo_nets_lds(D, L, ls) + ppo_stage_floats() + round4(ppo_params(D, A, L, ls) + 2));
 }
 // workgroups of k_ppo_grad: one per tile up to what the chip holds at once (256 CUs, as many workgroups per CU as their LDS
-// allows, four at the most) -- a function of (n, D, A, L) alone
-__host__ __device__ constexpr int ppo_groups(long long n, int D, int A, int L) {
+// allows, four at the most) -- a function of (n, D, A, L) and the head's form alone
+__host__ __device__ constexpr int ppo_groups(long long n, int D, int A, int L, bool ls = false) {
   const long long tiles = (n + PPO_TILE - 1) / PPO_TILE;
-  const int per_cu = int(size_t(PPO_LDS_BYTES) / ppo_grad_lds(D, A, L));
+  const int per_cu = int(size_t(PPO_LDS_BYTES) / ppo_grad_lds(D, A, L, ls));
   const long long cap = 256LL * (per_cu > 4 ? 4 : per_cu < 1 ? 1 : per_cu);
   return int(tiles < cap ? (tiles < 1 ? 1 : tiles) : cap);
 }
 // floats of the partial-gradient workspace of one fs_ppo_grad_dev call
-__host__ __device__ constexpr size_t ppo_work_floats(long long n, int D, int A, int L) {
-  return size_t(ppo_groups(n, D, A, L)) * size_t(ppo_params(D, A, L) + 2);
+__host__ __device__ constexpr size_t ppo_work_floats(long long n, int D, int A, int L, bool ls = false) {
+  return size_t(ppo_groups(n, D, A, L, ls)) * size_t(ppo_params(D, A, L, ls) + 2);
 }
 
 // the full-loss form (k_ppo_grad<true, true>): FOUR loss sums behind the gradient, in LDS and in a workgroup's row of the
 // workspace.  The workgroups are ppo_groups' (the two extra floats do not move the count: the order of every sum is the
 // plain form's).
 constexpr int PPO_LOSS_SUMS = 4;
-__host__ __device__ constexpr size_t ppo_grad_loss_lds(int D, int A, int L) {
-  return sizeof(float) * size_t(2 * ppo_net_lds(D, L) + ppo_stage_floats() + round4(ppo_params(D, A, L) + PPO_LOSS_SUMS));
+__host__ __device__ constexpr size_t ppo_grad_loss_lds(int D, int A, int L, bool ls = false) {
+  return sizeof(float) * size_t(ppo_nets_lds(D, L, ls) + ppo_stage_floats() + round4(ppo_params(D, A, L, ls) + PPO_LOSS_SUMS));
 }
 static_assert(ppo_grad_loss_lds(PPO_MAX_OBS, PPO_MAX_ACT, 3) <= size_t(PPO_LDS_BYTES), "the largest model's gradient fits LDS");
-__host__ __device__ constexpr size_t ppo_loss_work_floats(long long n, int D, int A, int L) {
-  return size_t(ppo_groups(n, D, A, L)) * size_t(ppo_params(D, A, L) + PPO_LOSS_SUMS);
+static_assert(ppo_params(PPO_MAX_OBS, PPO_MAX_ACT, 3, true) == 16673 && ppo_grad_loss_lds(PPO_MAX_OBS, PPO_MAX_ACT, 3, true) == 155040 &&
+              ppo_grad_loss_lds(PPO_MAX_OBS, PPO_MAX_ACT, 3, true) <= size_t(PPO_LDS_BYTES),
+              "the largest model with the head of 2 A rows fits LDS");
+__host__ __device__ constexpr size_t ppo_loss_work_floats(long long n, int D, int A, int L, bool ls = false) {
+  return size_t(ppo_groups(n, D, A, L, ls)) * size_t(ppo_params(D, A, L, ls) + PPO_LOSS_SUMS);
 }
 
 // what the full-loss form reads on top of k_ppo_grad's arguments (all device pointers; a NULL pointer or a zero
 // coefficient switches its term off for the whole launch)
 struct PpoLossArgs {
   const float* mean_old;       // [n, A]  the policy's means at the time of the rollout      (KL)
-  const float* log_std_old;    // [A]     log_std at the time of the rollout                 (KL)
+                               // (NET_LS: [n, 2A], a row's A means and then its A log stds, as k_ppo_eval<true, true> writes it)
+  const float* log_std_old;    // [A]     log_std at the time of the rollout                 (KL; NET_LS: not read)
   const float* val_old;        // [n]     the value network's output at the time of the rollout (value clipping)
   const double* kl_state;      // {coef, ..}: NULL = no KL term
   float vf_clip;               // <= 0: no value clipping
@@ -155,10 +170,12 @@ __host__ __device__ inline uint32_t perm_at(const PermKey& k, uint32_t i) {
 
 // workgroups of k_ppo_minibatch: ppo_groups of a batch of B samples -- a function of (B, D, A, L) alone, the short last
 // minibatch of an epoch included (its spare workgroups write zero partials)
-__host__ __device__ constexpr int ppo_mb_groups(long long B, int D, int A, int L) { return ppo_groups(B, D, A, L); }
+__host__ __device__ constexpr int ppo_mb_groups(long long B, int D, int A, int L, bool ls = false) {
+  return ppo_groups(B, D, A, L, ls);
+}
 // 4-byte words of the workspace of one fs_ppo_minibatch_dev call: G partials [P + 4], then G integer counts
-__host__ __device__ constexpr size_t ppo_mb_work_floats(long long B, int D, int A, int L) {
-  return size_t(ppo_mb_groups(B, D, A, L)) * size_t(ppo_params(D, A, L) + PPO_LOSS_SUMS + 1);
+__host__ __device__ constexpr size_t ppo_mb_work_floats(long long B, int D, int A, int L, bool ls = false) {
+  return size_t(ppo_mb_groups(B, D, A, L, ls)) * size_t(ppo_params(D, A, L, ls) + PPO_LOSS_SUMS + 1);
 }
 
 constexpr int MB_STEP = 0, MB_PARTIAL = 1;                           // the tail's modes
@@ -191,6 +208,8 @@ __host__ __device__ constexpr int adv_groups(long long n) {
 }  // namespace fs
 
 namespace fsim {
+// the head of 2 A rows: a model with policy weights and no free log_std (fs_ppo_model's log_std_dev == NULL)
+inline bool ppo_net_ls(const fs::PpoView& m) { return m.pw != nullptr && m.log_std == nullptr; }
 // (defined in the learn_f32 part: flowsim_part.hip with -DFS_PART_LEARN=1)
 int launch_ppo_eval(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act, float* logp,
                     float* val);
@@ -237,6 +256,9 @@ __device__ __forceinline__ float ppo_tanh(float z) {                     // (flo
 // then b [32]; the head's units >= n_out are zero
 __device__ __forceinline__ int ppo_layer_off(int D, int l) { return l == 0 ? 0 : 32 * D + 32 + (l - 1) * 1056; }
 
+// NET_LS: the head has 2 n_out rows and becomes two blocks, rows 0 .. n_out-1 at ppo_layer_off(D, L) and rows n_out ..
+// 2 n_out-1 behind it (+ 1056), each Wt [32][32] then b [32] with the units >= n_out zero
+template <bool NET_LS = false>
 __device__ __forceinline__ void net_load(const float* w, int D, int L, int n_out, float* lds, int lane) {
   for (int e = lane; e < 32 * D; e += 64) lds[(e % D) * 32 + e / D] = w[e];
   if (lane < 32) lds[32 * D + lane] = w[32 * D + lane];
@@ -244,6 +266,16 @@ __device__ __forceinline__ void net_load(const float* w, int D, int L, int n_out
   for (int l = 1; l <= L; ++l) {
     float* q = lds + ppo_layer_off(D, l);
     const int rows = l < L ? 32 : n_out;
+    if constexpr (NET_LS) {
+      if (l == L) {
+        for (int blk = 0; blk < 2; ++blk, q += 1056) {
+          const float* wb = w + blk * rows * 32;
+          for (int e = lane; e < 1024; e += 64) q[(e & 31) * 32 + (e >> 5)] = (e >> 5) < rows ? wb[e] : 0.0f;
+          if (lane < 32) q[1024 + lane] = lane < rows ? w[2 * rows * 32 + blk * rows + lane] : 0.0f;
+        }
+        break;
+      }
+    }
     for (int e = lane; e < 1024; e += 64) q[(e & 31) * 32 + (e >> 5)] = (e >> 5) < rows ? w[e] : 0.0f;
     if (lane < 32) q[1024 + lane] = lane < rows ? w[rows * 32 + lane] : 0.0f;
     w += rows * 33;
@@ -331,9 +363,20 @@ __device__ __forceinline__ void net_forward(const float* net, int D, int L, cons
   layer_acc(q, S, 32, lane, out);
 }
 
+// the second block of the head of 2 A rows (NET_LS): ls = the lane's 32 padded log stds, one more layer_acc over the hidden
+// column that net_forward left in S (the lane's own column: no barrier between the two)
+__device__ __forceinline__ void head_log_std(const float* net, int D, int L, const float* S, int lane, float (&ls)[32]) {
+  const float* q = net + ppo_layer_off(D, L) + 1056;
+#pragma unroll
+  for (int u = 0; u < 32; ++u) ls[u] = q[1024 + u];
+  layer_acc(q, S, 32, lane, ls);
+}
+
 // log-probability of the lane's action row under the Gaussian head (train_vec.GaussianPolicy.logp_value): zc = the
-// standardised actions, inv_std = exp(-log_std) is not used: the division is the reference's
-__device__ __forceinline__ float ppo_logp(const float (&mu)[32], const float (&a)[32], const float* log_std, int A,
+// standardised actions, inv_std = exp(-log_std) is not used: the division is the reference's.  log_std [c]: the free
+// parameter in memory, or (NET_LS) the lane's registers
+template <typename LS>
+__device__ __forceinline__ float ppo_logp(const float (&mu)[32], const float (&a)[32], const LS& log_std, int A,
                                           float (&zc)[32], float (&sd)[32]) {
   float logp = 0.0f;
 #pragma unroll
@@ -367,16 +410,17 @@ __device__ __forceinline__ bool ppo_load_act(const float* act, long long s, bool
 }
 
 // DIST: the head's means go out as well, mean_out [n, A] (the old distribution of the KL penalty)
-template <bool DIST>
+// NET_LS (act != NULL): the head of 2 A rows; DIST then writes mean_out [n, 2A], a row's A means and then its A log stds
+template <bool DIST, bool NET_LS = false>
 __global__ __launch_bounds__(64) void k_ppo_eval(PpoView m, long long n, const float* __restrict__ obs,
                                                  const float* __restrict__ act, float* __restrict__ logp_out,
                                                  float* __restrict__ val_out, float* __restrict__ mean_out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* pnet = reinterpret_cast<float*>(smem);
-  float* vnet = pnet + ppo_net_lds(m.D, m.L);
+  float* vnet = pnet + ppo_net_lds(m.D, m.L) + (NET_LS ? 1056 : 0);
   float* S = vnet + ppo_net_lds(m.D, m.L);
   const int lane = threadIdx.x;
-  if (act != nullptr) net_load(m.pw, m.D, m.L, m.A, pnet, lane);
+  if (act != nullptr) net_load<NET_LS>(m.pw, m.D, m.L, m.A, pnet, lane);
   net_load(m.vw, m.D, m.L, 1, vnet, lane);
   __syncthreads();
   const long long tiles = (n + PPO_TILE - 1) / PPO_TILE;
@@ -388,12 +432,29 @@ __global__ __launch_bounds__(64) void k_ppo_eval(PpoView m, long long n, const f
       float a[32], zc[32], sd[32];
       ppo_load_act(act, s, valid, m.A, a);
       net_forward(pnet, m.D, m.L, obs, s0, n, ~0ull, S, lane, h, out);
-      const float lp = ppo_logp(out, a, m.log_std, m.A, zc, sd);
-      if (valid) logp_out[s] = lp;
-      if (DIST && valid) {
+      if constexpr (NET_LS) {
+        float ls[32];
+        head_log_std(pnet, m.D, m.L, S, lane, ls);
+        const float lp = ppo_logp(out, a, ls, m.A, zc, sd);
+        if (valid) logp_out[s] = lp;
+        if (DIST && valid) {
+          float* row = mean_out + size_t(s) * size_t(2 * m.A);
 #pragma unroll
-        for (int c = 0; c < 32; ++c)
-          if (c < m.A) mean_out[size_t(s) * size_t(m.A) + size_t(c)] = out[c];
+          for (int c = 0; c < 32; ++c) {
+            if (c < m.A) {
+              row[c] = out[c];
+              row[m.A + c] = ls[c];
+            }
+          }
+        }
+      } else {
+        const float lp = ppo_logp(out, a, m.log_std, m.A, zc, sd);
+        if (valid) logp_out[s] = lp;
+        if (DIST && valid) {
+#pragma unroll
+          for (int c = 0; c < 32; ++c)
+            if (c < m.A) mean_out[size_t(s) * size_t(m.A) + size_t(c)] = out[c];
+        }
       }
     }
     net_forward(vnet, m.D, m.L, obs, s0, n, ~0ull, S, lane, h, out);
@@ -462,46 +523,77 @@ __device__ __forceinline__ void stage_dz(const float (&dz)[32], float* T, int la
   for (int q = 0; q < 8; ++q) t4[q] = make_float4(dz[4 * q], dz[4 * q + 1], dz[4 * q + 2], dz[4 * q + 3]);
 }
 
+// sum_u Wt[i][u] dz[u] of one block of 32 units (q: the layer's LDS copy): four strided partial sums, (a0 + a1) + (a2 + a3)
+__device__ __forceinline__ float back_dot(const float* q, int i, const float (&dz)[32]) {
+  const float4* w4 = reinterpret_cast<const float4*>(q + i * 32);
+  float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float4 w = w4[k];
+    a0 = __builtin_fmaf(w.x, dz[4 * k + 0], a0);
+    a1 = __builtin_fmaf(w.y, dz[4 * k + 1], a1);
+    a2 = __builtin_fmaf(w.z, dz[4 * k + 2], a2);
+    a3 = __builtin_fmaf(w.w, dz[4 * k + 3], a3);
+  }
+  return (a0 + a1) + (a2 + a3);
+}
+
+// (NET_LS) what the backward pass takes on top of dz: the loss's gradient at the 32 padded log-std outputs of the head
+struct PpoNoLs {};
+template <bool NET_LS>
+struct PpoLsOf { typedef PpoNoLs type; };
+template <>
+struct PpoLsOf<true> { typedef float type[32]; };
+
 // one layer of the backward pass (LYR = 1 .. L; the head when LYR == L): its weight and bias gradients from dz and its input
-// h[LYR-1], then dz of the layer below: (Wt dz) (1 - h^2), through the lane's own column of S
-template <int LYR>
+// h[LYR-1], then dz of the layer below: (Wt dz) (1 - h^2), through the lane's own column of S.
+// NET_LS, at the head (n_out = A rows per block): block 0 (rows 0 .. A-1 of the packed head, bias 2A 32 ..) from dz exactly
+// as above, then block 1 (rows A .. 2A-1, bias 2A 32 + A ..) from dz1 over the same staged h; the gradient at the last hidden
+// layer is (block 0's sum) + (block 1's sum), each sum in back_dot's order
+template <int LYR, bool NET_LS = false>
 __device__ __forceinline__ void back_layer(const float* net, int D, int L, int n_out, float* S, float* T, int lane,
-                                           const float (&h)[3][32], float (&dz)[32], float* G) {
+                                           const float (&h)[3][32], float (&dz)[32], float* G,
+                                           const typename PpoLsOf<NET_LS>::type& dz1) {
   const float* q = net + ppo_layer_off(D, LYR);
   const int rows = LYR < L ? 32 : n_out;
+  const bool two = NET_LS && LYR == L;
   float* g = G + 32 * D + 32 + (LYR - 1) * 1056;
   stage_units(h[LYR - 1], S, lane);
   stage_dz(dz, T, lane);
   __syncthreads();
   grad_block(T, S, 32, rows, g, 32, 0, lane);
-  col_sum(T, rows, g + rows * 32, lane);
+  col_sum(T, rows, g + (two ? 2 * rows : rows) * 32, lane);
   __syncthreads();
-  for (int i = 0; i < 32; ++i) {
-    const float4* w4 = reinterpret_cast<const float4*>(q + i * 32);
-    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float4 w = w4[k];
-      a0 = __builtin_fmaf(w.x, dz[4 * k + 0], a0);
-      a1 = __builtin_fmaf(w.y, dz[4 * k + 1], a1);
-      a2 = __builtin_fmaf(w.z, dz[4 * k + 2], a2);
-      a3 = __builtin_fmaf(w.w, dz[4 * k + 3], a3);
+  if constexpr (NET_LS) {
+    if (two) {
+      stage_dz(dz1, T, lane);
+      __syncthreads();
+      grad_block(T, S, 32, rows, g + rows * 32, 32, 0, lane);
+      col_sum(T, rows, g + 2 * rows * 32 + rows, lane);
+      __syncthreads();
     }
-    S[i * PPO_TS + lane] = (a0 + a1) + (a2 + a3);
+  }
+  for (int i = 0; i < 32; ++i) {
+    float back = back_dot(q, i, dz);
+    if constexpr (NET_LS) {
+      if (two) back += back_dot(q + 1056, i, dz1);
+    }
+    S[i * PPO_TS + lane] = back;
   }
 #pragma unroll
   for (int u = 0; u < 32; ++u) dz[u] = S[u * PPO_TS + lane] * __builtin_fmaf(-h[LYR - 1][u], h[LYR - 1][u], 1.0f);
 }
 
 // the backward pass of one network on one tile: dz = the loss's gradient at the head's 32 padded outputs (zero for the
-// samples that do not count); G = the network's gradient in LDS (packed layout)
-template <bool GATHER = false>
+// samples that do not count); G = the network's gradient in LDS (packed layout); NET_LS: dz1, back_layer's
+template <bool GATHER = false, bool NET_LS = false>
 __device__ __forceinline__ void net_backward(const float* net, int D, int L, int n_out, const float* obs, long long s0,
                                              long long n, unsigned long long keep, float* S, float* T, int lane,
-                                             const float (&h)[3][32], float (&dz)[32], float* G, int row = 0) {
-  if (L >= 3) back_layer<3>(net, D, L, n_out, S, T, lane, h, dz, G);
-  if (L >= 2) back_layer<2>(net, D, L, n_out, S, T, lane, h, dz, G);
-  back_layer<1>(net, D, L, n_out, S, T, lane, h, dz, G);
+                                             const float (&h)[3][32], float (&dz)[32], float* G,
+                                             const typename PpoLsOf<NET_LS>::type& dz1, int row = 0) {
+  if (L >= 3) back_layer<3, NET_LS>(net, D, L, n_out, S, T, lane, h, dz, G, dz1);
+  if (L >= 2) back_layer<2, NET_LS>(net, D, L, n_out, S, T, lane, h, dz, G, dz1);
+  back_layer<1, NET_LS>(net, D, L, n_out, S, T, lane, h, dz, G, dz1);
   // layer 0: the bias, then the weights by chunks of 32 inputs
   stage_dz(dz, T, lane);
   __syncthreads();
@@ -539,7 +631,11 @@ struct PpoMbOf<true> { typedef PpoMbArgs type; };
 
 __device__ __forceinline__ void mb_tail(const PpoMbArgs& mb, float* work, int G, int P, int lane);
 
-template <bool N_DEV, bool LOSS = false, bool MB = false>
+// NET_LS (with N_DEV; fs_last_kernel's "..._ls" names): the head of 2 A rows.  The lane's log stds are 32 more registers
+// (head_log_std), read where the free form reads m.log_std[c]; the old distribution x.mean_old is [n, 2A] and the old log
+// stds are read like the old means, column by column and never for an absent row; the per-sample gradient at the log stds
+// is not column-summed into a log_std slot but goes down the network as dz of the head's second block (back_layer).
+template <bool N_DEV, bool LOSS = false, bool MB = false, bool NET_LS = false>
 __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const float* __restrict__ obs,
                                                  const float* __restrict__ act, const float* __restrict__ logp_old,
                                                  const double* __restrict__ adv, const float* __restrict__ ret,
@@ -548,6 +644,7 @@ __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const f
                                                  typename PpoMbOf<MB>::type mb) {
   static_assert(N_DEV || !LOSS, "the full loss reads its sample count from the device");
   static_assert(LOSS || !MB, "the minibatch form is a form of the full loss");
+  static_assert(N_DEV || !NET_LS, "the head of 2 A rows is built for the device-n forms");
   constexpr int NS = LOSS ? PPO_LOSS_SUMS : 2;               // loss sums behind the gradient
   if constexpr (!MB) {
     if (N_DEV) inv_n = float(1.0 / mean_std[2]);
@@ -562,18 +659,19 @@ __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const f
     mb_end = mb_begin + mb.B < n ? mb_begin + mb.B : n;
   }
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int D = m.D, A = m.A, L = m.L, P = ppo_params(D, A, L);
+  const int D = m.D, A = m.A, L = m.L, P = ppo_params(D, A, L, NET_LS);
   float* pnet = reinterpret_cast<float*>(smem);
-  float* vnet = pnet + ppo_net_lds(D, L);
+  float* vnet = pnet + ppo_net_lds(D, L) + (NET_LS ? 1056 : 0);
   float* S = vnet + ppo_net_lds(D, L);
   float* T = S + 32 * PPO_TS;
   float* G = T + PPO_TILE * PPO_TT;                          // [P + NS]: the gradient, then the loss sums
   const int lane = threadIdx.x;
-  net_load(m.pw, D, L, A, pnet, lane);
+  net_load<NET_LS>(m.pw, D, L, A, pnet, lane);
   net_load(m.vw, D, L, 1, vnet, lane);
   for (int e = lane; e < P + NS; e += 64) G[e] = 0.0f;
   __syncthreads();
-  const int Pp = ppo_net_params(D, L, A);
+  const int Pp = ppo_net_params(D, L, NET_LS ? 2 * A : A);   // the policy's part; the value network's follows (after log_std [A])
+  const int Pv = NET_LS ? Pp : Pp + A;
   const double mean = mean_std[0], scale = mean_std[1] + 1e-8;
   const long long tiles = ((MB ? mb_end - mb_begin : n) + PPO_TILE - 1) / PPO_TILE;
   for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
@@ -594,9 +692,17 @@ __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const f
     net_forward<MB>(pnet, D, L, obs, s0, n, keep, S, lane, h, out, row);
     float pg = 0.0f, vf = 0.0f;
     float kl = 0.0f, ent = 0.0f;                             // (LOSS)
+    float gls[32];                                           // the loss's gradient at the log stds, per sample
     {
       float zc[32], sd[32];
-      const float logp = ppo_logp(out, a, m.log_std, A, zc, sd);
+      [[maybe_unused]] float lsr[32];                        // (NET_LS) the lane's log stds
+      float logp;
+      if constexpr (NET_LS) {
+        head_log_std(pnet, D, L, S, lane, lsr);
+        logp = ppo_logp(out, a, lsr, A, zc, sd);
+      } else {
+        logp = ppo_logp(out, a, m.log_std, A, zc, sd);
+      }
       const float adv_n = present ? float((adv[s] - mean) / scale) : 0.0f;
       const float ratio = present ? expf(logp - logp_old[s]) : 1.0f;
       const float clamped = ratio < lo ? lo : ratio > hi ? hi : ratio;
@@ -605,7 +711,6 @@ __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const f
       // d(-pg / n_total) / d logp: the unclipped branch is live inside [lo, hi] (both branches are it) or where it is the smaller
       const bool live = present && ((ratio >= lo && ratio <= hi) || s1 < s2);
       const float g_logp = live ? (-inv_n * adv_n) * ratio : 0.0f;
-      float gls[32];
 #pragma unroll
       for (int c = 0; c < 32; ++c) {
         dz[c] = c < A ? g_logp * (zc[c] / sd[c]) : 0.0f;
@@ -618,8 +723,18 @@ __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const f
 #pragma unroll
           for (int c = 0; c < 32; ++c) {
             if (c < A) {
-              const float ls = m.log_std[c], lso = x.log_std_old[c], so = expf(lso);
-              const float mo = present ? x.mean_old[size_t(s) * size_t(A) + size_t(c)] : 0.0f;
+              float ls, lso, mo;
+              if constexpr (NET_LS) {
+                const float* old = x.mean_old + size_t(s) * size_t(2 * A);
+                ls = lsr[c];
+                lso = present ? old[A + c] : 0.0f;
+                mo = present ? old[c] : 0.0f;
+              } else {
+                ls = m.log_std[c];
+                lso = x.log_std_old[c];
+                mo = present ? x.mean_old[size_t(s) * size_t(A) + size_t(c)] : 0.0f;
+              }
+              const float so = expf(lso);
               const float var = sd[c] * sd[c], d = mo - out[c];
               const float q = __builtin_fmaf(d, d, so * so) / var;
               kl += present ? ((ls - lso) + 0.5f * q) - 0.5f : 0.0f;
@@ -633,18 +748,24 @@ __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const f
 #pragma unroll
         for (int c = 0; c < 32; ++c) {
           if (c < A) {
-            ent += present ? m.log_std[c] + 1.4189385f : 0.0f;             // 0.5 log(2 pi e)
+            float ls;
+            if constexpr (NET_LS) ls = lsr[c];
+            else ls = m.log_std[c];
+            ent += present ? ls + 1.4189385f : 0.0f;                       // 0.5 log(2 pi e)
             if (ent_on) gls[c] = present ? gls[c] - we : gls[c];           // d (-entropy_coef H) / d ls = -entropy_coef
           }
         }
       }
-      __syncthreads();
-      stage_dz(gls, T, lane);
-      __syncthreads();
-      col_sum(T, A, G + Pp, lane);
-      __syncthreads();
+      if constexpr (!NET_LS) {
+        __syncthreads();
+        stage_dz(gls, T, lane);
+        __syncthreads();
+        col_sum(T, A, G + Pp, lane);
+        __syncthreads();
+      }
     }
-    net_backward<MB>(pnet, D, L, A, obs, s0, n, keep, S, T, lane, h, dz, G, row);
+    if constexpr (NET_LS) net_backward<MB, true>(pnet, D, L, A, obs, s0, n, keep, S, T, lane, h, dz, G, gls, row);
+    else net_backward<MB>(pnet, D, L, A, obs, s0, n, keep, S, T, lane, h, dz, G, PpoNoLs{}, row);
     // ---- the value network: (v - ret)^2
     net_forward<MB>(vnet, D, L, obs, s0, n, keep, S, lane, h, out, row);
     {
@@ -668,7 +789,7 @@ __global__ __launch_bounds__(64) void k_ppo_grad(PpoView m, long long n, const f
         }
       }
     }
-    net_backward<MB>(vnet, D, L, 1, obs, s0, n, keep, S, T, lane, h, dz, G + Pp + A, row);
+    net_backward<MB>(vnet, D, L, 1, obs, s0, n, keep, S, T, lane, h, dz, G + Pv, PpoNoLs{}, row);
     // ---- the loss sums
     T[lane * PPO_TT + 0] = pg;
     T[lane * PPO_TT + 1] = vf;
@@ -960,6 +1081,17 @@ inline int ppo_lds_limit() {
                               fs::PPO_LDS_BYTES));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_grad<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               fs::PPO_LDS_BYTES));
+  // the head of 2 A rows (NET_LS)
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_eval<false, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, fs::PPO_LDS_BYTES));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_eval<true, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, fs::PPO_LDS_BYTES));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_grad<true, false, false, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, fs::PPO_LDS_BYTES));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_grad<true, true, false, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, fs::PPO_LDS_BYTES));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fs::k_ppo_grad<true, true, true, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, fs::PPO_LDS_BYTES));
   done_dev = dev;
   return FS_OK;
 }
@@ -970,8 +1102,12 @@ static int launch_ppo_eval_any(hipStream_t stream, const fs::PpoView& m, long lo
   if (int rc = ppo_lds_limit()) return rc;
   const long long tiles = (n + fs::PPO_TILE - 1) / fs::PPO_TILE;
   const int grid = int(tiles < 1024 ? tiles : 1024);
-  hipLaunchKernelGGL(fs::k_ppo_eval<DIST>, dim3(grid), dim3(64), fs::ppo_eval_lds(m.D, m.L), stream, m, n, obs, act, logp, val,
-                     mean_old);
+  if (fsim::ppo_net_ls(m) && act != nullptr)                 // (values alone, act == NULL: the policy is not read)
+    hipLaunchKernelGGL((fs::k_ppo_eval<DIST, true>), dim3(grid), dim3(64), fs::ppo_eval_lds(m.D, m.L, true), stream, m, n, obs,
+                       act, logp, val, mean_old);
+  else
+    hipLaunchKernelGGL(fs::k_ppo_eval<DIST>, dim3(grid), dim3(64), fs::ppo_eval_lds(m.D, m.L), stream, m, n, obs, act, logp,
+                       val, mean_old);
   HIP_TRY(hipGetLastError());
   return FS_OK;
 }
@@ -994,15 +1130,24 @@ int launch_gae(hipStream_t stream, int K, long long R, const float* rew, const f
   return FS_OK;
 }
 
-// the two forms of the gradient launch: inv_n from the host, or n from the device (mean_std [3])
+// the two forms of the gradient launch: inv_n from the host, or n from the device (mean_std [3]); the head of 2 A rows
+// (m.log_std == NULL) is built for the second alone
 template <bool N_DEV>
 static int launch_ppo_grad_any(hipStream_t stream, const fs::PpoView& m, long long n, const float* obs, const float* act,
                                const float* logp_old, const double* adv, const float* ret, const double* mean_std, float lo,
                                float hi, float vf_coef, float inv_n, int accumulate, float* grad, float* loss, float* work) {
   if (int rc = ppo_lds_limit()) return rc;
-  const int G = fs::ppo_groups(n, m.D, m.A, m.L), P = fs::ppo_params(m.D, m.A, m.L);
-  hipLaunchKernelGGL(fs::k_ppo_grad<N_DEV>, dim3(G), dim3(64), fs::ppo_grad_lds(m.D, m.A, m.L), stream, m, n, obs, act,
-                     logp_old, adv, ret, mean_std, lo, hi, vf_coef, inv_n, work, fs::PpoLossArgs{}, fs::PpoNoMb{});
+  const bool ls = N_DEV && fsim::ppo_net_ls(m);
+  const int G = fs::ppo_groups(n, m.D, m.A, m.L, ls), P = fs::ppo_params(m.D, m.A, m.L, ls);
+  if constexpr (N_DEV) {
+    if (ls)
+      hipLaunchKernelGGL((fs::k_ppo_grad<true, false, false, true>), dim3(G), dim3(64), fs::ppo_grad_lds(m.D, m.A, m.L, true),
+                         stream, m, n, obs, act, logp_old, adv, ret, mean_std, lo, hi, vf_coef, inv_n, work, fs::PpoLossArgs{},
+                         fs::PpoNoMb{});
+  }
+  if (!ls)
+    hipLaunchKernelGGL(fs::k_ppo_grad<N_DEV>, dim3(G), dim3(64), fs::ppo_grad_lds(m.D, m.A, m.L), stream, m, n, obs, act,
+                       logp_old, adv, ret, mean_std, lo, hi, vf_coef, inv_n, work, fs::PpoLossArgs{}, fs::PpoNoMb{});
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(fs::k_ppo_reduce<2>, dim3((P + 2 + 255) / 256), dim3(256), 0, stream, work, G, P, accumulate, grad, loss);
   HIP_TRY(hipGetLastError());
@@ -1015,9 +1160,14 @@ int launch_ppo_grad_loss(hipStream_t stream, const fs::PpoView& m, const fs::Ppo
                          float lo, float hi, float vf_coef, int accumulate, float* grad, float* loss, float* work) {
   if (int rc = ppo_lds_limit()) return rc;
   constexpr int NS = fs::PPO_LOSS_SUMS;
-  const int G = fs::ppo_groups(n, m.D, m.A, m.L), P = fs::ppo_params(m.D, m.A, m.L);
-  hipLaunchKernelGGL((fs::k_ppo_grad<true, true>), dim3(G), dim3(64), fs::ppo_grad_loss_lds(m.D, m.A, m.L), stream, m, n, obs,
-                     act, logp_old, adv, ret, mean_std_n, lo, hi, vf_coef, 0.0f, work, x, fs::PpoNoMb{});
+  const bool ls = fsim::ppo_net_ls(m);
+  const int G = fs::ppo_groups(n, m.D, m.A, m.L, ls), P = fs::ppo_params(m.D, m.A, m.L, ls);
+  if (ls)
+    hipLaunchKernelGGL((fs::k_ppo_grad<true, true, false, true>), dim3(G), dim3(64), fs::ppo_grad_loss_lds(m.D, m.A, m.L, true),
+                       stream, m, n, obs, act, logp_old, adv, ret, mean_std_n, lo, hi, vf_coef, 0.0f, work, x, fs::PpoNoMb{});
+  else
+    hipLaunchKernelGGL((fs::k_ppo_grad<true, true>), dim3(G), dim3(64), fs::ppo_grad_loss_lds(m.D, m.A, m.L), stream, m, n, obs,
+                       act, logp_old, adv, ret, mean_std_n, lo, hi, vf_coef, 0.0f, work, x, fs::PpoNoMb{});
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(fs::k_ppo_reduce<NS>, dim3((P + NS + 255) / 256), dim3(256), 0, stream, work, G, P, accumulate, grad, loss);
   HIP_TRY(hipGetLastError());
@@ -1030,9 +1180,14 @@ int launch_ppo_minibatch(hipStream_t stream, const fs::PpoView& m, const fs::Ppo
                          const float* obs, const float* act, const float* logp_old, const double* adv, const float* ret,
                          const double* mean_std_n, float lo, float hi, float vf_coef, float* work) {
   if (int rc = ppo_lds_limit()) return rc;
-  const int G = fs::ppo_mb_groups(mb.B, m.D, m.A, m.L);
-  hipLaunchKernelGGL((fs::k_ppo_grad<true, true, true>), dim3(G), dim3(64), fs::ppo_grad_loss_lds(m.D, m.A, m.L), stream, m, n,
-                     obs, act, logp_old, adv, ret, mean_std_n, lo, hi, vf_coef, 0.0f, work, x, mb);
+  const bool ls = fsim::ppo_net_ls(m);
+  const int G = fs::ppo_mb_groups(mb.B, m.D, m.A, m.L, ls);
+  if (ls)
+    hipLaunchKernelGGL((fs::k_ppo_grad<true, true, true, true>), dim3(G), dim3(64), fs::ppo_grad_loss_lds(m.D, m.A, m.L, true),
+                       stream, m, n, obs, act, logp_old, adv, ret, mean_std_n, lo, hi, vf_coef, 0.0f, work, x, mb);
+  else
+    hipLaunchKernelGGL((fs::k_ppo_grad<true, true, true>), dim3(G), dim3(64), fs::ppo_grad_loss_lds(m.D, m.A, m.L), stream, m, n,
+                       obs, act, logp_old, adv, ret, mean_std_n, lo, hi, vf_coef, 0.0f, work, x, mb);
   HIP_TRY(hipGetLastError());
   return FS_OK;
 }

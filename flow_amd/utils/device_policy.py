@@ -46,11 +46,18 @@ class DevicePolicy(object):
         """Run on the storage of ``learner`` (a ``flow_amd.utils.device_ppo.DeviceLearner`` over the same network): the
         struct's ``weights_dev`` and ``log_std_dev`` point into ``learner.weights`` -- [policy weights][log_std A][value
         weights], the policy's part in this class's own layout -- so the rollout kernels read the very buffer the
-        learner's Adam writes, and ``sync()`` has nothing to do.  Only the free-``log_std`` form can share, and the layer
-        shapes must be the learner's.  Share before a graph captures the policy (``vec.capture``)."""
-        if self.ls is None:
+        learner's Adam writes, and ``sync()`` has nothing to do.  The head's form must be the learner's -- the free
+        ``log_std`` with a free-``log_std`` learner, the head of 2 x act_dim outputs with a ``net_log_std=True`` learner
+        (``weights_dev`` is then the learner's policy part, [policy with its 2A-row head], and ``log_std_dev`` stays NULL)
+        -- and so must the layer shapes.  Share before a graph captures the policy (``vec.capture``)."""
+        net_ls = bool(getattr(learner, "net_log_std", False))
+        if self.ls is None and not net_ls:
             raise NotImplementedError("DevicePolicy.share: the head of 2 x act_dim outputs (no free log_std) cannot share a "
                                       "DeviceLearner's storage: its packed weights hold the act_dim means next to log_std")
+        if self.ls is not None and net_ls:
+            raise NotImplementedError("DevicePolicy.share: a policy with a free log_std cannot share the storage of a "
+                                      "DeviceLearner(net_log_std=True): its packed weights hold the head of 2 x act_dim "
+                                      "outputs and no log_std")
         mine = (self.hidden[0].in_features, len(self.hidden), self.act_dim)
         theirs = (learner.D, learner.num_hidden, learner.A)
         if mine != theirs:
@@ -61,8 +68,11 @@ class DevicePolicy(object):
                              % (learner.weights.device, learner.n_policy, self.buf.numel(), self.buf.device))
         self.shared = learner
         self.buf = learner.weights[:learner.n_policy]
-        self.ls = learner.weights[learner.n_policy:learner.n_policy + self.act_dim]
         self.struct.weights_dev = self.buf.data_ptr()
+        if net_ls:                                           # (the log stds are rows A .. 2A-1 of the head: no slot, NULL)
+            self.struct.log_std_dev = None
+            return self
+        self.ls = learner.weights[learner.n_policy:learner.n_policy + self.act_dim]
         self.struct.log_std_dev = self.ls.data_ptr()
         return self
 

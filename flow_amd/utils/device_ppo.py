@@ -78,26 +78,43 @@ def _check_trunk(who, hidden, head, n_out, what):
 
 class DeviceLearner(object):
     """``policy_hidden`` / ``value_hidden``: the ``nn.Linear`` layers of the two trunks (1..3 each, the same number, 32
-    units, tanh between them); ``policy_head``: 32 -> A means (1 <= A <= 32) next to the free ``log_std`` [A];
+    units, tanh between them); ``policy_head``: 32 -> A means (1 <= A <= 32) next to the free ``log_std`` [A] -- or, with
+    the keyword ``net_log_std=True`` and ``log_std=None``, 32 -> 2 A outputs, the A means and then the A log stds (RLlib's
+    ``free_log_std: false``; every method but ``gradients()``, the host-n form, takes it);
     ``value_head``: 32 -> 1.  The observation has 1..160 values.  Anything else is refused here, by name, before the device
     is touched.  ``sim_or_vec``: a float32 ``FlowSim`` or ``VecFlowEnv`` -- it lends its device and its stream (the
     simulation state is never touched).  ``sync()`` repacks the current parameter values (after every optimiser step)."""
 
-    def __init__(self, sim_or_vec, policy_hidden, policy_head, log_std, value_hidden, value_head):
+    def __init__(self, sim_or_vec, policy_hidden, policy_head, log_std, value_hidden, value_head, net_log_std=False):
         import torch
         self.torch = torch
         self.p_hidden, self.p_head, self.log_std_param = list(policy_hidden), policy_head, log_std
         self.v_hidden, self.v_head = list(value_hidden), value_head
-        if log_std is None:
-            raise NotImplementedError("DeviceLearner (fs_ppo_model): the 2A-output head (means and log stds from the "
-                                      "network, no free log_std) is not built")
-        A = int(log_std.numel())
-        if not 1 <= A <= MAX_ACT:
-            raise NotImplementedError("DeviceLearner (fs_ppo_model): act_dim A = %d; 1..32 are built" % A)
-        if policy_head.out_features == 2 * A:
-            raise NotImplementedError("DeviceLearner (fs_ppo_model): the 2A-output head (%d outputs for A = %d) is not "
-                                      "built: the head gives the A means next to the free log_std" % (2 * A, A))
-        _check_trunk("the policy network", self.p_hidden, policy_head, A, "the head gives the A = %d means" % A)
+        self.net_log_std = bool(net_log_std)
+        if self.net_log_std:
+            # the head of 2 A outputs (RLlib's free_log_std: false): rows 0 .. A-1 the means, rows A .. 2A-1 the log stds
+            if log_std is not None:
+                raise NotImplementedError("DeviceLearner (fs_ppo_model): net_log_std=True is the 2A-output head, whose log "
+                                          "stds come from the network: log_std must be None (got %d values)" % log_std.numel())
+            if policy_head.out_features % 2:
+                raise NotImplementedError("DeviceLearner (fs_ppo_model): net_log_std=True needs a head of 2 A outputs, the "
+                                          "means and then the log stds; %d outputs is odd" % policy_head.out_features)
+            A = policy_head.out_features // 2
+            if not 1 <= A <= MAX_ACT:
+                raise NotImplementedError("DeviceLearner (fs_ppo_model): act_dim A = %d; 1..32 are built" % A)
+            _check_trunk("the policy network", self.p_hidden, policy_head, 2 * A,
+                         "the head gives the A = %d means and the A log stds" % A)
+        else:
+            if log_std is None:
+                raise NotImplementedError("DeviceLearner (fs_ppo_model): the 2A-output head (means and log stds from the "
+                                          "network, no free log_std) is not built")
+            A = int(log_std.numel())
+            if not 1 <= A <= MAX_ACT:
+                raise NotImplementedError("DeviceLearner (fs_ppo_model): act_dim A = %d; 1..32 are built" % A)
+            if policy_head.out_features == 2 * A:
+                raise NotImplementedError("DeviceLearner (fs_ppo_model): the 2A-output head (%d outputs for A = %d) is not "
+                                          "built: the head gives the A means next to the free log_std" % (2 * A, A))
+            _check_trunk("the policy network", self.p_hidden, policy_head, A, "the head gives the A = %d means" % A)
         _check_trunk("the value network", self.v_hidden, value_head, 1, "the value head has 1 output")
         if len(self.v_hidden) != len(self.p_hidden):
             raise NotImplementedError("DeviceLearner (fs_ppo_model): the two trunks have %d and %d hidden layers; the same "
@@ -110,7 +127,8 @@ class DeviceLearner(object):
         for l in self.p_hidden + [policy_head]:
             self.params += [l.weight, l.bias]
         self.n_policy = sum(p.numel() for p in self.params)
-        self.params.append(log_std)
+        if not self.net_log_std:
+            self.params.append(log_std)
         for l in self.v_hidden + [value_head]:
             self.params += [l.weight, l.bias]
         if any(p.dtype != torch.float32 for p in self.params):
@@ -125,7 +143,8 @@ class DeviceLearner(object):
             raise NotImplementedError("DeviceLearner: a float32 handle lends its stream (float64 / mixed learners are not built)")
         self.device, self.D, self.A, self.num_hidden = dev, D, A, len(self.p_hidden)
         self.P = sum(p.numel() for p in self.params)
-        self.weights = torch.zeros(self.P, dtype=torch.float32, device=dev)      # [policy][log_std A][value]
+        self.weights = torch.zeros(self.P, dtype=torch.float32, device=dev)      # [policy][log_std A][value]; net_log_std:
+        #                                                                          [policy with its 2A-row head][value]
         self.grad = torch.zeros(self.P, dtype=torch.float32, device=dev)         # the same layout
         self.loss = torch.zeros(2, dtype=torch.float32, device=dev)              # {sum pg, sum vf} of the last gradients()
         self._mean_std = torch.zeros(2, dtype=torch.float64, device=dev)
@@ -145,10 +164,11 @@ class DeviceLearner(object):
         self.mb_count = torch.zeros(1, dtype=torch.float64, device=dev)
         self._work_mb, self._work_mbs = None, {}
         off = self.n_policy
+        self.n_dist = 2 * A if self.net_log_std else A       # columns of the old distribution (evaluate_dist's mean_old)
         self.struct = L.fs_ppo_model(struct_size=C.sizeof(L.fs_ppo_model), obs_dim=D, act_dim=A, num_hidden=self.num_hidden,
                                      hidden_width=WIDTH, activation=0, policy_weights_dev=self.weights.data_ptr(),
-                                     log_std_dev=self.weights.data_ptr() + 4 * off,
-                                     value_weights_dev=self.weights.data_ptr() + 4 * (off + A))
+                                     log_std_dev=None if self.net_log_std else self.weights.data_ptr() + 4 * off,
+                                     value_weights_dev=self.weights.data_ptr() + 4 * (off + (0 if self.net_log_std else A)))
         self.sync()
 
     def sync(self):
@@ -232,6 +252,10 @@ class DeviceLearner(object):
         ``attach_grads()``), its two sums ``{sum pg, sum vf}`` into ``self.loss`` (returned).  ``adv`` is the RAW float64
         advantage; ``mean`` / ``std`` its float64 statistics (0-dim tensors or numbers); ``n_total`` the sample count of
         the whole update (all shards, all ranks).  ``accumulate=True`` adds to what both buffers hold."""
+        if self.net_log_std:
+            raise NotImplementedError("DeviceLearner.gradients (fs_ppo_grad_dev): the gradient with the sample count from the "
+                                      "host is not built for the 2A-output head (net_log_std=True); gradients_n / "
+                                      "gradients_loss / update take it")
         torch = self.torch
         n = int(obs.shape[0])
         obs, act = self._f32(obs, (n, self.D), "obs"), self._f32(act, (n, self.A), "act")
@@ -315,13 +339,15 @@ class DeviceLearner(object):
     def evaluate_dist(self, obs, act):
         """``evaluate()`` that also returns the head's means: ``(logp [n], val [n], mean_old [n, A])``, the old
         distribution of the KL term (``val`` serves as the old value of the clipped value loss).  ``logp`` and ``val``
-        hold the bits ``evaluate()`` gives."""
+        hold the bits ``evaluate()`` gives.  ``net_log_std``: ``mean_old`` is ``[n, 2A]``, a row's A means and then its A
+        log stds -- the whole old distribution, which ``gradients_loss`` / ``minibatch_step`` take as ``mean_old`` with
+        ``log_std_old=None``."""
         torch = self.torch
         n = int(obs.shape[0])
         obs, act = self._f32(obs, (n, self.D), "obs"), self._f32(act, (n, self.A), "act")
         logp = torch.empty(n, dtype=torch.float32, device=self.device)
         val = torch.empty(n, dtype=torch.float32, device=self.device)
-        mean_old = torch.empty(n, self.A, dtype=torch.float32, device=self.device)
+        mean_old = torch.empty(n, self.n_dist, dtype=torch.float32, device=self.device)
         self._bind()
         self._eval_dist(n, obs, act, logp, val, mean_old)
         return logp, val, mean_old
@@ -353,7 +379,7 @@ class DeviceLearner(object):
             raise ValueError("DeviceLearner: adv must be a float64 tensor of shape (%d,) on %s" % (n, self.device))
         if mean_std_n.dtype != torch.float64 or mean_std_n.numel() != 3 or mean_std_n.device != self.device:
             raise ValueError("DeviceLearner: mean_std_n must be a float64 tensor of 3 elements on %s" % self.device)
-        mean_old = None if mean_old is None else self._f32(mean_old, (n, self.A), "mean_old")
+        mean_old = None if mean_old is None else self._f32(mean_old, (n, self.n_dist), "mean_old")
         log_std_old = None if log_std_old is None else self._f32(log_std_old, (self.A,), "log_std_old")
         val_old = None if val_old is None else self._f32(val_old, (n,), "val_old")
         work = self._loss_workspace(n)
@@ -416,7 +442,7 @@ class DeviceLearner(object):
             raise ValueError("DeviceLearner: adv must be a float64 tensor of shape (%d,) on %s" % (n, self.device))
         if mean_std_n.dtype != torch.float64 or mean_std_n.numel() != 3 or mean_std_n.device != self.device:
             raise ValueError("DeviceLearner: mean_std_n must be a float64 tensor of 3 elements on %s" % self.device)
-        mean_old = None if mean_old is None else self._f32(mean_old, (n, self.A), "mean_old")
+        mean_old = None if mean_old is None else self._f32(mean_old, (n, self.n_dist), "mean_old")
         log_std_old = None if log_std_old is None else self._f32(log_std_old, (self.A,), "log_std_old")
         val_old = None if val_old is None else self._f32(val_old, (n,), "val_old")
         batch, index = int(batch), int(index)
@@ -567,10 +593,11 @@ class DeviceLearner(object):
             b = self._shard_buffers(j, K, R)
             if full:
                 if "mean_old" not in b:
-                    b["mean_old"] = torch.empty(n, self.A, dtype=torch.float32, device=self.device)
-                    b["log_std_old"] = torch.empty(self.A, dtype=torch.float32, device=self.device)
+                    b["mean_old"] = torch.empty(n, self.n_dist, dtype=torch.float32, device=self.device)
+                    b["log_std_old"] = None if self.net_log_std else torch.empty(self.A, dtype=torch.float32, device=self.device)
                 self._eval_dist(n, o, a, b["logp"], b["val"], b["mean_old"])
-                b["log_std_old"].copy_(self.weights[self.n_policy:self.n_policy + self.A])
+                if not self.net_log_std:                     # (net_log_std: the old log stds are columns A .. 2A-1 of mean_old)
+                    b["log_std_old"].copy_(self.weights[self.n_policy:self.n_policy + self.A])
                 self._loss_workspace(n)
             else:
                 L.check(lib.fs_ppo_eval_dev(h, C.byref(self.struct), n, o.data_ptr(), a.data_ptr(), b["logp"].data_ptr(),

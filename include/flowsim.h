@@ -550,9 +550,16 @@ int fs_policy_rollout_dev(fs_handle h, const fs_policy* pol, int num_steps, int 
  * (and "k_adv_stats", "k_adv_finish", "k_adam" for the statistics and the optimiser below).
  * Model class (fs_policy's): 1..3 hidden layers of 32 tanh units on obs_dim = 1..160 inputs; the policy's head has act_dim
  * = 1..32 outputs, the MEANS, next to a free log std [act_dim]; the value network is the same trunk with one output.
- * Both weight buffers: float32, device, per layer W [out][in] row-major then b [out].  Everything else -- the head of
- * 2 act_dim outputs (log_std_dev == NULL), another width or activation, obs_dim / act_dim out of range -- is refused with
- * FS_ERR_UNSUPPORTED and a message that names fs_ppo_model. */
+ * Both weight buffers: float32, device, per layer W [out][in] row-major then b [out].
+ * log_std_dev == NULL (fs_policy's convention) selects the head of 2 act_dim outputs instead: the policy's last layer has
+ * 2 A rows, rows 0 .. A-1 the means and rows A .. 2A-1 the log stds (RLlib's DiagGaussian order), so the standard deviation
+ * depends on the observation and there is no free log std.  The packed parameters are then [policy with its 2A-row head]
+ * [value weights] -- P = 2 (32 D + 32 + (num_hidden - 1) 1056) + 66 A + 33 -- and every sum's order depends on the head's
+ * form as well.  fs_ppo_eval_dev, fs_ppo_eval_dist_dev, fs_ppo_grad_n_dev, fs_ppo_grad_loss_dev, fs_ppo_minibatch_dev,
+ * fs_ppo_mb_finish_dev and the three workspace functions take it (fs_last_kernel: "k_ppo_eval_ls", "k_ppo_grad_ls",
+ * "k_ppo_grad_loss_ls", "k_ppo_minibatch_ls"); fs_ppo_grad_dev, the gradient with the sample count from the host, refuses it.
+ * Everything else -- another width or activation, obs_dim / act_dim out of range -- is refused with FS_ERR_UNSUPPORTED and a
+ * message that names fs_ppo_model. */
 typedef struct fs_ppo_model {
   uint32_t struct_size;               /* sizeof(fs_ppo_model) */
   int32_t obs_dim;                    /* D: 1..160 */
@@ -560,8 +567,8 @@ typedef struct fs_ppo_model {
   int32_t num_hidden;                 /* 1..3 hidden layers ... */
   int32_t hidden_width;               /* ... of 32 units each */
   int32_t activation;                 /* 0 = tanh */
-  const float* policy_weights_dev;    /* [32 D + 32][(num_hidden - 1) x 1056][33 A] */
-  const float* log_std_dev;           /* [A] */
+  const float* policy_weights_dev;    /* [32 D + 32][(num_hidden - 1) x 1056][33 A]   (log_std_dev == NULL: [.. 33 x 2A]) */
+  const float* log_std_dev;           /* [A]; NULL: the head has 2 A outputs, rows A .. 2A-1 are the log stds */
   const float* value_weights_dev;     /* [32 D + 32][(num_hidden - 1) x 1056][33] */
 } fs_ppo_model;
 
@@ -657,7 +664,9 @@ typedef struct fs_ppo_loss {
 
 /* fs_ppo_eval_dev that also writes the head's means, mean_old_dev [n, A]: the no_grad pass of an update whose loss has the
  * KL term (val_dev then serves as v_o).  act_dev, logp_dev and mean_old_dev must not be NULL.  logp_dev and val_dev hold
- * the bits fs_ppo_eval_dev gives.  fs_last_kernel reports "k_ppo_eval". */
+ * the bits fs_ppo_eval_dev gives.  fs_last_kernel reports "k_ppo_eval".
+ * The head of 2 act_dim outputs (model->log_std_dev == NULL): mean_old_dev is [n, 2A], the A means and then the A log stds
+ * of the row -- the whole old distribution; fs_last_kernel reports "k_ppo_eval_ls". */
 int fs_ppo_eval_dist_dev(fs_handle h, const fs_ppo_model* model, int64_t n, const float* obs_dev, const float* act_dev,
                          float* logp_dev, float* val_dev, float* mean_old_dev);
 /* Floats of work_dev that fs_ppo_grad_loss_dev needs: the workgroups of fs_ppo_workspace times (P + 4) -- four loss sums
@@ -668,7 +677,11 @@ size_t fs_ppo_loss_workspace(const fs_ppo_model* model, int64_t n);
  * [n]: may be NULL only without value clipping.  Nothing of an absent row (a NaN in its action row) reaches an output, its
  * mean_old and val_old included.  The mapping, the workgroup count and so the order of every sum are fs_ppo_grad_dev's:
  * with every term off, grad_dev and loss_sums_dev[0..1] hold the bits of fs_ppo_grad_n_dev.  fs_last_kernel reports
- * "k_ppo_grad_loss". */
+ * "k_ppo_grad_loss".
+ * The head of 2 act_dim outputs (model->log_std_dev == NULL): the old log stds are per sample and travel in mean_old_dev
+ * [n, 2A] as fs_ppo_eval_dist_dev writes it; log_std_old_dev must be NULL (anything else: FS_ERR_INVALID, by name).  KL and
+ * H are the formulas above with ls and ls_o of the sample.  fs_last_kernel reports "k_ppo_grad_loss_ls".  The same holds
+ * for fs_ppo_minibatch_dev ("k_ppo_minibatch_ls"). */
 int fs_ppo_grad_loss_dev(fs_handle h, const fs_ppo_model* model, const fs_ppo_loss* loss, int64_t n, const float* obs_dev,
                          const float* act_dev, const float* logp_old_dev, const float* mean_old_dev,
                          const float* log_std_old_dev, const float* val_old_dev, const double* adv_dev, const float* ret_dev,
@@ -712,7 +725,8 @@ typedef struct fs_ppo_minibatch {
   uint64_t* epoch_dev;                /* the epoch counter, device: read by the launch, so a replayed graph draws fresh
                                        * permutations */
   double* count_dev;                  /* PARTIAL: [1] the step's count of present rows (double, so that it all-reduces) */
-  float* weights_dev;                 /* STEP: the packed buffer [policy][log_std A][value] fs_ppo_model points into */
+  float* weights_dev;                 /* STEP: the packed buffer [policy][log_std A][value] fs_ppo_model points into
+                                       * (the head of 2 act_dim outputs: [policy][value]) */
   float* m_dev;                       /* STEP: Adam's moments [P] and state [3], as in fs_adam_dev */
   float* v_dev;
   double* state_dev;
