@@ -15,6 +15,8 @@ N_ROLLOUTS = 4
 N_CPUS = 2
 N_HUMANS = 13
 N_AVS = 1
+# the reference's POLICY_GRAPHS / policies_to_train: each agent maps to a policy of its own (policy_mapping_fn = identity)
+POLICIES_TO_TRAIN = ["av", "adversary"]
 
 vehicles = VehicleParams()
 for veh_id, controller, count in (("human", (IDMController, {"noise": 0.2}), N_HUMANS), ("rl", (RLController, {}), N_AVS)):

@@ -46,6 +46,10 @@ def parse_args(args):
     parser.add_argument('--device_adam', action='store_true',
                         help='device: run the whole PPO update, Adam included, on the device with no host round trip '
                              '(DeviceLearner.update); implies --device_update')
+    parser.add_argument('--train_adversary', action='store_true',
+                        help='device: train BOTH policies of an adversarial experiment (adversarial_figure_eight: the av '
+                             'and the adversary that perturbs its accelerations, opposite rewards) -- one fused two-policy '
+                             'rollout per fragment, one update per policy; without it such an experiment is refused')
     parser.add_argument('--epochs', type=int, default=4, help='device: passes over a rollout fragment per update')
     from train_vec import add_model_flags, add_ppo_loss_flags
     add_ppo_loss_flags(parser)              # --kl_target --kl_coeff --entropy_coeff --vf_clip --sgd_minibatch_size: all off by default
@@ -130,6 +134,17 @@ def train_device(submodule, flags, multiagent=False):
                            net_log_std=flags.net_log_std, **ppo_loss_settings(flags))
 
 
+def train_adversary(submodule, flags):
+    """--train_adversary: the two policies of an adversarial experiment ('av' and 'adversary', opposite rewards)."""
+    from train_vec import train_adversarial_on_device
+    fp = submodule.flow_params
+    fp['sim'].render = False
+    return train_adversarial_on_device(fp, replicas=flags.replicas, fragment=flags.rollout_size, iterations=flags.num_steps,
+                                       device_update=flags.device_update or flags.device_adam,
+                                       device_adam=flags.device_adam, net_log_std=flags.net_log_std,
+                                       **ppo_loss_settings(flags))
+
+
 def main(args):
     flags = parse_args(args)
     submodule, multiagent = load_experiment(flags.exp_config)
@@ -138,12 +153,18 @@ def main(args):
     if flags.rl_trainer.lower() == "device":
         # multi-agent experiments whose agents share the policy 'av' (multiagent_ring / _figure_eight / _merge: one
         # observation block and one action column per agent) train that ONE policy; adversarial_figure_eight has two
-        # policies with opposite rewards: not this loop
-        if multiagent and len(getattr(submodule, "POLICIES_TO_TRAIN", ["av"])) > 1:
-            raise ValueError("--rl_trainer device trains one shared policy; %s trains %s"
-                             % (flags.exp_config, submodule.POLICIES_TO_TRAIN))
-        if multiagent and flags.exp_config.startswith("adversarial"):
-            raise ValueError("--rl_trainer device trains one shared policy; adversarial experiments train two")
+        # policies with opposite rewards: not this loop, but train_adversarial_on_device's behind --train_adversary
+        two = multiagent and (len(getattr(submodule, "POLICIES_TO_TRAIN", ["av"])) > 1
+                              or flags.exp_config.startswith("adversarial"))
+        if flags.train_adversary:
+            if not two:
+                raise ValueError("--train_adversary trains the two policies of an adversarial experiment "
+                                 "(adversarial_figure_eight); %s trains one" % flags.exp_config)
+            return train_adversary(submodule, flags)
+        if two:
+            raise ValueError("--rl_trainer device trains one shared policy; %s trains %s: add --train_adversary to train "
+                             "both (one fused two-policy rollout, one update per policy)"
+                             % (flags.exp_config, getattr(submodule, "POLICIES_TO_TRAIN", "two")))
         return train_device(submodule, flags, multiagent)
     raise ValueError("rl_trainer should be either 'device' or 'rllib'.")
 

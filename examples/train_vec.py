@@ -534,6 +534,113 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     return history
 
 
+def update_adversarial(rollout, update_av, update_adversary):
+    """The update step of train_adversarial_on_device: ``rollout`` is what ``VecFlowEnv.policy_pair_rollout`` returns,
+    ``(obs, act [2, K, R], logp, rew, done)``.  The av learns from ``(obs, act[0], rew, done)``, the adversary from
+    ``(obs, act[1], -rew, done)`` -- the same observations, its own samples, the opposite reward
+    (multiagent/ring/accel.py:50-52).  ``update_av`` / ``update_adversary``: callables on one shard, each a per-policy
+    update (``ppo_update`` or ``DeviceLearner.update`` with that policy's own optimiser state)."""
+    obs, act, _, rew, done = rollout
+    update_av((obs, act[0].unsqueeze(-1), rew, done))
+    update_adversary((obs, act[1].unsqueeze(-1), -rew, done))
+
+
+def train_adversarial_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epochs=4, lr=3e-4, seed=0, log=print,
+                                device_update=False, device_adam=False, kl_target=None, kl_coeff=0.2, entropy_coeff=0.0,
+                                vf_clip=None, vf_coef=0.5, clip=0.2, sgd_minibatch_size=None, net_log_std=False):
+    """PPO on TWO policies with opposite rewards (the reference's adversarial_figure_eight.py: POLICY_GRAPHS 'av' and
+    'adversary', policy_mapping_fn the identity): both read AccelEnv's observation, each draws an action, the RL vehicle
+    receives ``av + perturb_weight * adversary``.  One fragment is ONE launch (``VecFlowEnv.policy_pair_rollout``:
+    k_loop_policy<Adversarial>), followed by one update per policy (``update_adversarial``).  Returns the av's mean step
+    reward per iteration (the adversary's is its negation).
+    The two ``GaussianPolicy(obs_dim, 1)`` start from different torch seeds and sample with different seeds.  The loss
+    and model keywords are ``train_on_device``'s, applied to both policies, and so are the three update paths -- torch
+    ``ppo_update`` with an optimiser per policy, ``device_update``, ``device_adam`` (a ``DeviceLearner`` per policy,
+    adopted, its ``DevicePolicy`` sharing its weights) -- each a per-policy call.  One process, one GPU; a handle the
+    pair kernel refuses raises NotImplementedError with the library's message (there is no captured-graph fallback).
+    The observation row is the kernel's AccelEnv order ``[v..., x...]``, where the reference's adversarial state
+    interleaves ``[v_i, x_i]``: a fixed permutation of the first layer's inputs, irrelevant to training from scratch."""
+    if net_log_std and device_update and not device_adam:
+        raise NotImplementedError("train_adversarial_on_device(net_log_std=True, device_update=True): the 2A-output head is "
+                                  "not built for the device update around torch's Adam (fs_ppo_grad_dev); add device_adam "
+                                  "(--device_adam), which runs the whole update on the device")
+    from flow_amd.envs import VecFlowEnv
+    from flow_amd.utils.device_policy import DevicePolicy
+    from flow_amd.utils.device_ppo import DeviceLearner
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    vec = VecFlowEnv(flow_params, num_replicas=replicas, device=0)
+    if vec.act_dim != 1:
+        raise ValueError("train_adversarial_on_device: two policies drive ONE action column; this environment has %d" % vec.act_dim)
+
+    class Side(object):                                        # one policy with its optimiser state
+        pass
+    sides = []
+    for j, name in enumerate(("av", "adversary")):
+        sd = Side()
+        sd.name = name
+        torch.manual_seed(seed + 7919 * j)                     # different initial weights
+        sd.pi = pi = GaussianPolicy(vec.obs_dim, 1, net_log_std=net_log_std).to(dev)
+        free_log_std = None if net_log_std else pi.log_std
+        sd.learner, sd.opt, sd.kl = None, None, None
+        if device_adam:
+            sd.learner = DeviceLearner(vec, [pi.mu[0], pi.mu[2]], pi.mu[4], free_log_std, [pi.value[0], pi.value[2]],
+                                       pi.value[4], net_log_std=net_log_std)
+            sd.learner.adopt_parameters()
+        else:
+            sd.opt = torch.optim.Adam(pi.parameters(), lr=lr)
+            if device_update:
+                sd.learner = DeviceLearner(vec, [pi.mu[0], pi.mu[2]], pi.mu[4], pi.log_std, [pi.value[0], pi.value[2]],
+                                           pi.value[4])
+            if kl_target is not None:
+                sd.kl = AdaptiveKL(kl_target, kl_coeff)
+        sd.policy = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=free_log_std, seed=seed + 104729 * j)
+        if device_adam:
+            sd.policy.share(sd.learner)
+        sides.append(sd)
+    av, adv = sides
+    vec.reset()
+    vec.policy_pair_rollout(av.policy, adv.policy, 1, reset_done=True)      # (probe: raises with the library's message)
+    weight = float(vec.env.env_params.additional_params['perturb_weight'])
+    log("rollout: fused two-policy + step kernel (%s); the vehicle receives av + %g * adversary" % (vec.sim.last_kernel, weight))
+    vec.reset()
+    if device_adam:
+        log("update: on the device, Adam included, one DeviceLearner per policy (k_ppo_eval, k_gae, k_adv_stats, "
+            "k_adv_finish, k_ppo_grad, k_adam)")
+    elif device_update:
+        log("update: on the device, one DeviceLearner per policy (k_ppo_eval, k_gae, k_ppo_grad)")
+    K, R = fragment, replicas
+    history = []
+    for it in range(iterations):
+        def updater(sd):
+            if device_adam:
+                return lambda shard: sd.learner.update([shard], epochs=epochs, lr=lr, clip=clip, vf_coef=vf_coef,
+                                                       kl_target=kl_target, kl_coef_init=kl_coeff, entropy_coef=entropy_coeff,
+                                                       vf_clip=vf_clip, minibatch=sgd_minibatch_size, shuffle_seed=seed)
+            return lambda shard: ppo_update(sd.pi, sd.opt, [shard], epochs=epochs, clip=clip, learner=sd.learner, kl=sd.kl,
+                                            entropy_coef=entropy_coeff, vf_clip=vf_clip, vf_coef=vf_coef,
+                                            minibatch=sgd_minibatch_size, shuffle_seed=seed, epoch0=it * epochs)
+        t0 = time.perf_counter()
+        av.policy.sync()                                       # the optimisers moved the weights: repack them for the kernel
+        adv.policy.sync()
+        rollout = vec.policy_pair_rollout(av.policy, adv.policy, K, reset_done=True)
+        torch.cuda.synchronize(dev)
+        t_roll = time.perf_counter() - t0
+        update_adversarial(rollout, updater(av), updater(adv))
+        kl_log = ""
+        if kl_target is not None:                              # (read after the updates: the device's state under device_adam)
+            for sd in sides:
+                coef, mean_kl = sd.learner.kl_state.tolist() if device_adam else (sd.kl.coef, sd.kl.mean_kl)
+                kl_log += "  %s KL %.5f  kl_coeff %.4g" % (sd.name, mean_kl, coef)
+        rew, done = rollout[3], rollout[4]
+        mean_rew = float(rew.double().mean())
+        history.append(mean_rew)
+        log("iteration %3d  mean step reward %8.4f  rollout %.1f ms (%.2f M env-steps/s per GPU, 1 GPU)  episodes ended %d%s"
+            % (it, mean_rew, t_roll * 1e3, K * R / t_roll / 1e6, int((done != 0).sum()), kl_log))
+    vec.close()
+    return history
+
+
 def spawn_ranks(gpus, argv):
     """--gpus N without a launcher: start the N ranks as child processes.  Nothing in THIS process has touched a GPU
     (torch.cuda.device_count() does not initialise it); never an exec of a process that has."""

@@ -48,7 +48,8 @@ EXPORTS = ["fs_create", "fs_destroy", "fs_last_error", "fs_abi_version", "fs_obs
            "fs_policy_rollout_dev", "fs_ppo_eval_dev", "fs_gae_dev", "fs_ppo_workspace", "fs_ppo_grad_dev",
            "fs_ppo_grad_n_dev", "fs_adv_stats_dev", "fs_adv_finish_dev", "fs_adam_dev", "fs_ppo_eval_dist_dev",
            "fs_ppo_loss_workspace", "fs_ppo_grad_loss_dev", "fs_kl_adapt_dev", "fs_ppo_perm_host",
-           "fs_ppo_minibatch_workspace", "fs_ppo_minibatch_dev", "fs_ppo_mb_finish_dev"]
+           "fs_ppo_minibatch_workspace", "fs_ppo_minibatch_dev", "fs_ppo_mb_finish_dev", "fs_policy_pair_act_dev",
+           "fs_policy_pair_rollout_dev"]
 # fs_ppo_minibatch.mode / .flags
 FS_MB_STEP, FS_MB_PARTIAL = 0, 1
 FS_MB_ACCUMULATE, FS_MB_FIRST, FS_MB_LAST = 1, 2, 4
@@ -203,6 +204,11 @@ def load(path=None):
     lib.fs_policy_act_dev.restype = C.c_int
     lib.fs_policy_rollout_dev.argtypes = [h, C.POINTER(fs_policy), C.c_int, C.c_int, f32p, f32p, f32p, f32p, u8p]
     lib.fs_policy_rollout_dev.restype = C.c_int
+    lib.fs_policy_pair_act_dev.argtypes = [h, C.POINTER(fs_policy), C.POINTER(fs_policy), C.c_float, f32p, f32p, f32p, f32p]
+    lib.fs_policy_pair_act_dev.restype = C.c_int
+    lib.fs_policy_pair_rollout_dev.argtypes = [h, C.POINTER(fs_policy), C.POINTER(fs_policy), C.c_float, C.c_int, C.c_int,
+                                               f32p, f32p, f32p, f32p, u8p]
+    lib.fs_policy_pair_rollout_dev.restype = C.c_int
     f64p = C.c_void_p
     lib.fs_ppo_eval_dev.argtypes = [h, C.POINTER(fs_ppo_model), C.c_int64, f32p, f32p, f32p, f32p]
     lib.fs_ppo_eval_dev.restype = C.c_int

@@ -504,6 +504,26 @@ int fs_policy_rollout_dev(fs_handle h, const fs_policy* pol, int num_steps, int 
   return S(h)->launch_policy(pol, num_steps, reset_done ? 1 : 0, nullptr, obs_dev, act_dev, logp_dev, rew_dev, done_dev);
 }
 
+int fs_policy_pair_act_dev(fs_handle h, const fs_policy* av, const fs_policy* adversary, float perturb_weight,
+                           const float* obs_dev, float* act_dev, float* logp_dev, float* cmd_dev) {
+  if (!h || !av || !adversary || !obs_dev || !act_dev || !logp_dev || !cmd_dev)
+    return fail(FS_ERR_INVALID, "fs_policy_pair_act_dev: NULL argument");
+  DeviceGuard guard(S(h)->cfg.device);
+  return S(h)->launch_policy_pair(av, adversary, perturb_weight, 0, 0, obs_dev, nullptr, act_dev, logp_dev, cmd_dev, nullptr,
+                                  nullptr);
+}
+
+int fs_policy_pair_rollout_dev(fs_handle h, const fs_policy* av, const fs_policy* adversary, float perturb_weight,
+                               int num_steps, int reset_done, float* obs_dev, float* act_dev, float* logp_dev,
+                               float* rew_dev, uint8_t* done_dev) {
+  if (!h || !av || !adversary || !obs_dev || !act_dev || !logp_dev || !rew_dev || !done_dev)
+    return fail(FS_ERR_INVALID, "fs_policy_pair_rollout_dev: NULL argument");
+  if (num_steps < 1) return fail(FS_ERR_INVALID, "fs_policy_pair_rollout_dev: num_steps < 1");
+  DeviceGuard guard(S(h)->cfg.device);
+  return S(h)->launch_policy_pair(av, adversary, perturb_weight, num_steps, reset_done ? 1 : 0, nullptr, obs_dev, act_dev,
+                                  logp_dev, nullptr, rew_dev, done_dev);
+}
+
 // ---- the PPO update on the device (flowsim_learn.h): the handle lends its device, its stream and fs_last_error
 // the head of 2 A outputs, fs_policy's convention: no free log_std (log_std_dev == NULL), rows A .. 2A-1 are the log stds
 static bool ppo_head_ls(const fs_ppo_model* m) { return m && m->struct_size == sizeof(fs_ppo_model) && !m->log_std_dev; }

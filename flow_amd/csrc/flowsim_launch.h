@@ -331,4 +331,30 @@ namespace fsim {
     }
   }
 
+  // two policies on the AccelEnv head's one RL vehicle: k_policy_pair_act (obs == nullptr) or k_loop_policy_pair, in
+  // k_loop_policy's instantiation for this handle
+  template <typename T>
+  int Sim<T>::launch_policy_pair16(const fs::PolicyView& pv, const fs::PolicyView& pv2, float pw, int num_steps,
+                                   int reset_done, const float* obs_in, float* obs, float* act, float* logp, float* cmd,
+                                   float* rew, uint8_t* done) {
+    if constexpr (std::is_same<T, float>::value) {
+      if (obs == nullptr) {
+        last_kernel = "k_policy_pair_act";
+        hipLaunchKernelGGL(fs::k_policy_pair_act<16>, dim3((dv.R * 16 + 255) / 256), dim3(256), 0, stream, pv, pv2, pw, dv.R,
+                           dv.rep0, obs_in, act, logp, cmd);
+        return launched();
+      }
+      const bool fastc = loop_delta4 && loop_fastc_ok();
+      const auto k = fastc ? &fs::k_loop_policy_pair<true, true>
+                           : loop_delta4 ? &fs::k_loop_policy_pair<true, false> : &fs::k_loop_policy_pair<false, false>;
+      last_kernel = "k_loop_policy<Adversarial>";
+      const int waves = (dv.R + 3) / 4;
+      hipLaunchKernelGGL(k, dim3((waves + 3) / 4), dim3(256), 0, stream, dv, pv, pv2, pw, num_steps, reset_done, obs, act,
+                         logp, rew, done);
+      return launched();
+    } else {
+      return fail(FS_ERR_UNSUPPORTED, "fs_policy_pair: k_loop_policy_pair is a float32 kernel");
+    }
+  }
+
 }  // namespace fsim

@@ -16,10 +16,11 @@
 // stopped).
 //
 // The network is written ONCE: policy_layer is the 32-input layer, policy_trunk the layer sequence (narrow or WIDE first
-// layer, then the hidden layers), policy_load_trunk its weights' way into LDS.  All eight kernels that evaluate a policy
+// layer, then the hidden layers), policy_load_trunk its weights' way into LDS.  All ten kernels that evaluate a policy
 // call that trunk -- the eager k_policy_act, k_policy_act_vec and k_policy_act_wide (fs_policy_act_dev; the last with a
 // first layer of more than 32 inputs, policy_wide_layer1, which is policy_layer over chunks), the fused k_ring_policy,
-// k_loop_policy, k_merge_queue<POLICY>, k_merge_policy and k_merge_wide_policy (flowsim_queue.h) -- through policy_eval
+// k_loop_policy, k_merge_queue<POLICY>, k_merge_policy and k_merge_wide_policy (flowsim_queue.h), and the two-policy
+// pair k_policy_pair_act / k_loop_policy_pair (fs_policy_pair_*: two networks on one RL vehicle) -- through policy_eval
 // (the trunk and the two-output Gaussian head), policy_vec_act (the trunk and the action-vector head) or policy_wide_act
 // (the same head behind a first layer of more than 32 inputs), so a fragment is bit-identical to
 // eager stepping by construction (tests/test_policy_gpu.py and its siblings).  Every operation is an explicit fma /
@@ -762,17 +763,37 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
 // the policy: obs [K+1, R, 6 n_ag], act / logp [K, R, n_ag], the shared desired-velocity reward, no crash
 // (tests/test_policy_ma_gpu.py).  Agent c's six values sit on two lanes -- its RL vehicle's (four) and its follower's (two,
 // k_rollout_loop's flush_obs) -- and are gathered from registers into policy_wide_inputs' layout for in_dim = 6.
-template <int HEAD, bool DELTA4, bool FASTC>
-__global__ __launch_bounds__(256) void k_loop_policy(DevView<float> s, PolicyView pv, int num_steps, int reset_done,
-                                                     float* __restrict__ obs, float* __restrict__ act,
-                                                     float* __restrict__ logp, float* __restrict__ rew,
-                                                     uint8_t* __restrict__ done) {
+//
+// The body is written ONCE, loop_policy_body: k_loop_policy calls it with PAIR = false, k_loop_policy_pair (below) with
+// HEAD 0 and PAIR = true.  PAIR (two policies, one RL vehicle: AdversarialAccelEnv on the figure eight) adds, all of it
+// under `if constexpr (PAIR)`: the adversary's PolicyView pv2 with its LDS copy PL2 and the weight pw; its evaluation on
+// the same o0, o1 registers; its draw from Philox column 0x40000000 + 1 (act_draws1) at the replica's counter, keyed by
+// ITS seed; the RL lane's command a = fmaf(pw, a_adv, a_av); the stores into the planes of act / logp [2, K, R] (plane 0
+// the av, plane 1 the adversary).  The reward of HEAD 0 does not read the action: rew is the av's, the adversary's its
+// negation.  The views are taken by value and the LDS is declared in the body, as the kernel had them: with references
+// and the tables handed in as pointers k_loop_policy<0, true, true> came out one AGPR larger (tests/test_codegen.py).
+template <bool PAIR>
+struct PairLds {           // the adversary's LDS copy (PAIR), or nothing
+  PolicyLds L;
+};
+template <>
+struct PairLds<false> {};
+
+template <int HEAD, bool DELTA4, bool FASTC, bool PAIR>
+__device__ __forceinline__ void loop_policy_body(const DevView<float> s, const PolicyView pv, const PolicyView pv2,
+                                                 float pw, int num_steps, int reset_done, float* __restrict__ obs,
+                                                 float* __restrict__ act, float* __restrict__ logp,
+                                                 float* __restrict__ rew, uint8_t* __restrict__ done) {
   typedef float T;
   typedef float X;
   constexpr int SEG = 16, RPW = 4;
+  static_assert(!PAIR || HEAD == 0, "loop_policy_body: two policies drive the AccelEnv head's one RL vehicle");
+  // (the LDS of the kernel this body is inlined into: every instantiation has ONE caller)
   __shared__ X tab_start[FS_MAX_SEGMENTS + 2], tab_fs[FS_MAX_SEGMENTS + 2], tab_sl[FS_MAX_SEGMENTS + 2];
   __shared__ PolicyLds PL;
+  __shared__ PairLds<PAIR> PL2;
   policy_load(pv, &PL, threadIdx.x, blockDim.x);
+  if constexpr (PAIR) policy_load(pv2, &PL2.L, threadIdx.x, blockDim.x);
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int seg = lane / SEG;
@@ -966,6 +987,16 @@ __global__ __launch_bounds__(256) void k_loop_policy(DevView<float> s, PolicyVie
         act[size_t(step) * R + rr] = a;
         logp[size_t(step) * R + rr] = lp;
       }
+      if constexpr (PAIR) {                              // the adversary: the same observation, its own network and stream
+        float mu2, ls2, a2, lp2;
+        policy_eval<SEG, true>(pv2, &PL2.L, i, o0, o1, 0.0f, mu2, ls2);
+        policy_sample(pv2, s.rep0 + uint32_t(rr), pctr, mu2, ls2, a2, lp2, &act_draws1, 1u);
+        if (rvalid && i == 0) {
+          act[(size_t(num_steps) + step) * R + rr] = a2;
+          logp[(size_t(num_steps) + step) * R + rr] = lp2;
+        }
+        a = __builtin_fmaf(pw, a2, a);                   // (k_policy_pair_act's cmd: THE combination)
+      }
     }
     pctr += 1u;
     // ---- Env.step: k_rollout_loop's step ---------------------------------------------------------------------------
@@ -1095,6 +1126,65 @@ __global__ __launch_bounds__(256) void k_loop_policy(DevView<float> s, PolicyVie
       if (any_noise) s.noise_ctr[rr] = nctr;
     }
   }
+}
+
+template <int HEAD, bool DELTA4, bool FASTC>
+__global__ __launch_bounds__(256) void k_loop_policy(DevView<float> s, PolicyView pv, int num_steps, int reset_done,
+                                                     float* __restrict__ obs, float* __restrict__ act,
+                                                     float* __restrict__ logp, float* __restrict__ rew,
+                                                     uint8_t* __restrict__ done) {
+  loop_policy_body<HEAD, DELTA4, FASTC, false>(s, pv, pv, 0.0f, num_steps, reset_done, obs, act, logp, rew, done);
+}
+
+// ---- TWO policies on one RL vehicle (AdversarialAccelEnv on the figure eight: the reference's adversarial_figure_eight.py
+// maps the agents 'av' and 'adversary' to a policy each) ---------------------------------------------------------------
+// Both networks read the replica's observation; the av draws from the single-agent stream (column 0x40000000, its seed),
+// the adversary from column 0x40000000 + 1 keyed by ITS seed (equal seeds still give independent draws), both at the
+// replica's counter -- the handle's, shared by the two policies (pv.ctr == pv2.ctr), advancing by ONE per step.  The
+// vehicle receives cmd = fmaf(perturb_weight, a_adv, a_av): the one float32 expression that defines the combination
+// (flow/envs/multiagent/adversarial_accel.py: av_action + perturb_weight * adv_action); clipping stays where fs_step_dev
+// does it.
+
+// eager form: obs [R, in_dim] -> act / logp [2, R] (plane 0 the av, plane 1 the adversary), cmd [R]; a row of 16 lanes is
+// one replica, as in k_policy_act
+template <int ROW>     // (a template so that every object of the library may include this header)
+__global__ __launch_bounds__(256) void k_policy_pair_act(PolicyView pv, PolicyView pv2, float pw, int R, uint32_t rep0,
+                                                         const float* __restrict__ obs, float* __restrict__ act,
+                                                         float* __restrict__ logp, float* __restrict__ cmd) {
+  __shared__ PolicyLds L, L2;
+  policy_load(pv, &L, threadIdx.x, blockDim.x);
+  policy_load(pv2, &L2, threadIdx.x, blockDim.x);
+  const int lane = threadIdx.x & 63, j = lane & 15;
+  const int r = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+  const int rr = r < R ? r : R - 1;
+  const uint32_t c0 = pv.ctr[rr];
+  float ia, ib;
+  policy_wide_inputs(obs + size_t(rr) * pv.in_dim, pv.in_dim, j, ia, ib);
+  float mu, ls, a, lp, mu2, ls2, a2, lp2;
+  policy_eval<ROW, true>(pv, &L, j, ia, ib, 0.0f, mu, ls);
+  policy_eval<ROW, true>(pv2, &L2, j, ia, ib, 0.0f, mu2, ls2);
+  policy_sample(pv, rep0 + uint32_t(rr), c0, mu, ls, a, lp, nullptr, 0u);
+  policy_sample(pv2, rep0 + uint32_t(rr), c0, mu2, ls2, a2, lp2, nullptr, 1u);
+  if (r < R && j == 0) {
+    act[r] = a;
+    act[size_t(R) + r] = a2;
+    logp[r] = lp;
+    logp[size_t(R) + r] = lp2;
+    cmd[r] = __builtin_fmaf(pw, a2, a);
+    pv.ctr[r] = c0 + 1u;
+  }
+}
+
+// fused form: K x (pair act -> Env.step(cmd) [-> reset of a finished episode]) on a segment-table loop, AccelEnv head:
+// loop_policy_body<0, ., ., PAIR>; the mapping is k_loop_policy's (a row of 16 lanes per replica, four replicas per wave,
+// 16 per workgroup).  obs [K+1, R, 2 N], act / logp [2, K, R], rew / done [K, R].  LDS: two PolicyLds and the segment
+// tables, about 28 KB per workgroup.
+template <bool DELTA4, bool FASTC>
+__global__ __launch_bounds__(256) void k_loop_policy_pair(DevView<float> s, PolicyView pv, PolicyView pv2, float pw,
+                                                          int num_steps, int reset_done, float* __restrict__ obs,
+                                                          float* __restrict__ act, float* __restrict__ logp,
+                                                          float* __restrict__ rew, uint8_t* __restrict__ done) {
+  loop_policy_body<0, DELTA4, FASTC, true>(s, pv, pv2, pw, num_steps, reset_done, obs, act, logp, rew, done);
 }
 
 }  // namespace fs

@@ -130,6 +130,10 @@ struct SimBase {
   // policy in the loop (flowsim_policy.h): obs == nullptr selects the eager form (act only)
   virtual int launch_policy(const fs_policy* pol, int num_steps, int reset_done, const float* obs_in, float* obs,
                             float* act, float* logp, float* rew, uint8_t* done) = 0;
+  // two policies on one RL vehicle (fs_policy_pair_*): obs == nullptr selects the eager form (act, logp, cmd)
+  virtual int launch_policy_pair(const fs_policy* av, const fs_policy* adv, float pw, int num_steps, int reset_done,
+                                 const float* obs_in, float* obs, float* act, float* logp, float* cmd, float* rew,
+                                 uint8_t* done) = 0;
   uint32_t* d_pol_ctr = nullptr;   // [R] actions sampled so far per replica (the policy's draw counters)
   virtual int get_state(int field, void* dst, size_t bytes) = 0;
   virtual int set_state(int field, const void* src, size_t bytes) = 0;
@@ -868,16 +872,59 @@ struct Sim : SimBase {
                           float* rew, uint8_t* done);
   int launch_policy_loop16(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act, float* logp,
                            float* rew, uint8_t* done);
+  // ---- launch_policy's checks and set-up that fs_policy_pair shares (launch_policy_pair below) ----
+  // the model class every policy kernel evaluates
+  const char* policy_model_why(const fs_policy* pol) const {
+    if (pol->num_hidden < 1 || pol->num_hidden > 3 || pol->hidden_width != 32 || pol->activation != 0)
+      return "fs_policy model (1..3 hidden layers of 32 tanh units)";
+    if (!pol->weights_dev) return "fs_policy.weights_dev (NULL)";
+    return nullptr;
+  }
+  // ONE RL vehicle on a segment-table loop (k_loop_policy): why this handle / policy is not built, or nullptr.  po_ok:
+  // the WaveAttenuationPOEnv head counts (not for two policies); fragment_resets: a fused launch that resets in place
+  const char* policy_loop_why(const fs_policy* pol, bool po_ok, bool fragment_resets) const {
+    const bool po = po_ok && dv.env == FS_ENV_WAVE_ATTENUATION_PO, accel = dv.env == FS_ENV_ACCEL && !dv.evaluate;
+    if (!std::is_same<T, float>::value || mixed) return "precision (f32 on segment-table loops)";
+    if (seg != 16 || dv.N < 2) return "num_vehicles (2..16: a row of 16 lanes per replica)";
+    if (!(po || accel) || dv.num_rl != 1)
+      return po_ok ? "env (WaveAttenuationPOEnv or AccelEnv with one RL vehicle)" : "env (AccelEnv with one RL vehicle)";
+    if (pol->obs_dim != (po ? 3 : 2 * dv.N)) return "fs_policy.obs_dim (the environment's observation)";
+    if (!(dv.flags & fs::FLAG_IDM_SET) || (dv.flags & fs::FLAG_HAS_FAILSAFE) || dv.sims_per_step != 1 ||
+        dv.integrator != FS_EULER || dv.track_aux || dv.sort_vehicles || dv.obs_perm != nullptr || !loop_div_ok ||
+        (fragment_resets && cfg.warmup_steps != 0))
+      return "configuration (what k_rollout_loop steps: IDM / RL / Sim vehicles, Euler, track_aux = 0; resets inside a "
+             "fragment: warmup_steps = 0)";
+    return nullptr;
+  }
+  // the draw counters [R]: allocated (zero) by the first policy launch of the handle
+  int policy_counters() {
+    if (d_pol_ctr) return FS_OK;
+    int rc = dev_alloc(&d_pol_ctr, size_t(dv.R));
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(d_pol_ctr, 0, size_t(dv.R) * sizeof(uint32_t), stream));
+    return FS_OK;
+  }
+  // the kernels' view of a policy with ONE action column (the action-vector heads scale n_out)
+  fs::PolicyView policy_view(const fs_policy* pol) const {
+    fs::PolicyView pv;
+    pv.w = pol->weights_dev;
+    pv.log_std = pol->log_std_dev;
+    pv.ctr = d_pol_ctr;
+    pv.in_dim = pol->obs_dim;
+    pv.num_hidden = pol->num_hidden;
+    pv.n_out = pol->log_std_dev ? 1 : 2;
+    pv.seed_lo = uint32_t(pol->seed & 0xFFFFFFFFull);
+    pv.seed_hi = uint32_t(pol->seed >> 32);
+    return pv;
+  }
   int launch_policy(const fs_policy* pol, int num_steps, int reset_done, const float* obs_in, float* obs, float* act,
                     float* logp, float* rew, uint8_t* done) override {
     if (!pol || pol->struct_size != sizeof(fs_policy)) return fail(FS_ERR_INVALID, "fs_policy: struct_size mismatch");
     const bool f32_or_mixed = mixed || std::is_same<T, float>::value;
     const bool loop = dv.nseg > 0;                       // a segment-table loop (figure eight) or a ring
     const bool ma = dv.env == FS_ENV_WAVE_ATTENUATION_PO_MA || dv.env == FS_ENV_ACCEL_PO_MA || dv.env == FS_ENV_MERGE_MA;
-    const char* why = nullptr;
-    if (pol->num_hidden < 1 || pol->num_hidden > 3 || pol->hidden_width != 32 || pol->activation != 0)
-      why = "fs_policy model (1..3 hidden layers of 32 tanh units)";
-    else if (!pol->weights_dev) why = "fs_policy.weights_dev (NULL)";
+    const char* why = policy_model_why(pol);
+    if (why) {}                                          // (the model class: every head's first check)
     else if (dv.env == FS_ENV_MERGE_PO) {                // ONE network: the whole observation -> num_rl action columns
       if (!std::is_same<T, float>::value || mixed)
         why = "precision (FS_ENV_MERGE_PO is FS_F32 / FS_F16S only: FS_MIXED / FS_F64 handles are not built)";
@@ -947,18 +994,7 @@ struct Sim : SimBase {
                          (dv.N % 2) != 0))
         why = "configuration (what k_ring_pair steps: single-lane ring of IDM / RL vehicles, Euler, track_aux = 0)";
     }
-    else if (loop) {
-      const bool po = dv.env == FS_ENV_WAVE_ATTENUATION_PO, accel = dv.env == FS_ENV_ACCEL && !dv.evaluate;
-      if (!std::is_same<T, float>::value || mixed) why = "precision (f32 on segment-table loops)";
-      else if (seg != 16 || dv.N < 2) why = "num_vehicles (2..16: a row of 16 lanes per replica)";
-      else if (!(po || accel) || dv.num_rl != 1) why = "env (WaveAttenuationPOEnv or AccelEnv with one RL vehicle)";
-      else if (pol->obs_dim != (po ? 3 : 2 * dv.N)) why = "fs_policy.obs_dim (the environment's observation)";
-      else if (!(dv.flags & fs::FLAG_IDM_SET) || (dv.flags & fs::FLAG_HAS_FAILSAFE) || dv.sims_per_step != 1 ||
-               dv.integrator != FS_EULER || dv.track_aux || dv.sort_vehicles || dv.obs_perm != nullptr || !loop_div_ok ||
-               (obs != nullptr && reset_done && cfg.warmup_steps != 0))
-        why = "configuration (what k_rollout_loop steps: IDM / RL / Sim vehicles, Euler, track_aux = 0; resets inside a "
-              "fragment: warmup_steps = 0)";
-    }
+    else if (loop) why = policy_loop_why(pol, true, obs != nullptr && reset_done);
     else if (!f32_or_mixed) why = "precision (f32 or mixed)";
     else if (seg != 32) why = "num_vehicles (18..32: a row of 16 lanes per replica)";
     else if (dv.env != FS_ENV_WAVE_ATTENUATION_PO || dv.num_rl != 1) why = "env (WaveAttenuationPOEnv with one RL vehicle)";
@@ -973,21 +1009,9 @@ struct Sim : SimBase {
         msg += " (FS_ENV_BOTTLENECK_DV)";                // (the checks shared by every head: model class, weights)
       return fail(FS_ERR_UNSUPPORTED, msg);
     }
-    if (!d_pol_ctr) {
-      int rc = dev_alloc(&d_pol_ctr, size_t(dv.R));
-      if (rc) return rc;
-      HIP_TRY(hipMemsetAsync(d_pol_ctr, 0, size_t(dv.R) * sizeof(uint32_t), stream));
-    }
-    fs::PolicyView pv;
-    pv.w = pol->weights_dev;
-    pv.log_std = pol->log_std_dev;
-    pv.ctr = d_pol_ctr;
-    pv.in_dim = pol->obs_dim;
-    pv.num_hidden = pol->num_hidden;
-    pv.n_out = pol->log_std_dev ? 1 : 2;
+    if (int rc = policy_counters()) return rc;
+    fs::PolicyView pv = policy_view(pol);
     if (dv.env == FS_ENV_MERGE_PO || dv.env == FS_ENV_BOTTLENECK_DV) pv.n_out *= dv.num_rl;  // the action-vector heads: num_rl means [and num_rl log stds]
-    pv.seed_lo = uint32_t(pol->seed & 0xFFFFFFFFull);
-    pv.seed_hi = uint32_t(pol->seed >> 32);
     if constexpr (std::is_same<T, float>::value) {
       const bool po_wide = dv.env == FS_ENV_MERGE_PO && dv.num_rl > fs::FS_POLICY_VEC_MAX;   // 35 .. 160 inputs
       if (dv.env == FS_ENV_MERGE_PO && obs == nullptr && !po_wide) return launch_policy_act_vec(pv, obs_in, act, logp);
@@ -999,6 +1023,31 @@ struct Sim : SimBase {
     if (obs == nullptr) return launch_policy_act(pv, ma ? dv.num_rl : 1, obs_in, act, logp);      // eager: the policy alone
     if (loop) return launch_policy_loop16(pv, num_steps, reset_done, obs, act, logp, rew, done);
     return launch_policy_row16(pv, num_steps, reset_done, obs, act, logp, rew, done);
+  }
+
+  // two policies, one RL vehicle (fs_policy_pair_act_dev / fs_policy_pair_rollout_dev; flowsim_policy.h k_policy_pair_act,
+  // k_loop_policy_pair): what launch_policy's loop branch takes for the AccelEnv head, for BOTH policies; obs == nullptr
+  // selects the eager form (act, logp, cmd)
+  int launch_policy_pair16(const fs::PolicyView& pv, const fs::PolicyView& pv2, float pw, int num_steps, int reset_done,
+                           const float* obs_in, float* obs, float* act, float* logp, float* cmd, float* rew, uint8_t* done);
+  int launch_policy_pair(const fs_policy* av, const fs_policy* adv, float pw, int num_steps, int reset_done,
+                         const float* obs_in, float* obs, float* act, float* logp, float* cmd, float* rew,
+                         uint8_t* done) override {
+    if (!av || !adv || av->struct_size != sizeof(fs_policy) || adv->struct_size != sizeof(fs_policy))
+      return fail(FS_ERR_INVALID, "fs_policy_pair: fs_policy struct_size mismatch");
+    if (!std::isfinite(pw)) return fail(FS_ERR_INVALID, "fs_policy_pair: perturb_weight is not finite");
+    const bool resets = obs != nullptr && reset_done;
+    const char *why = nullptr, *who = "";
+    if (dv.nseg == 0) why = "network (a segment-table loop: the figure eight; rings and the open networks take one policy)";
+    for (const fs_policy* pol : {av, adv}) {
+      if (why) break;
+      who = pol == av ? "av: " : "adversary: ";
+      if ((why = policy_model_why(pol)) == nullptr) why = policy_loop_why(pol, false, resets);
+    }
+    if (why) return fail(FS_ERR_UNSUPPORTED, std::string("fs_policy_pair: not built for this handle: ") + who + why);
+    if (int rc = policy_counters()) return rc;
+    return launch_policy_pair16(policy_view(av), policy_view(adv), pw, num_steps, reset_done, obs_in, obs, act, logp, cmd,
+                                rew, done);
   }
 
   int launch_reset(const uint8_t* mask) override {

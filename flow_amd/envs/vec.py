@@ -439,6 +439,69 @@ class VecFlowEnv(object):
         self.sim.policy_rollout_dev(policy.struct, K, out[0], out[1], out[2], out[3], out[4], reset_done=reset_done)
         return out
 
+    def _pair_weight(self, what, av, adversary, weight):
+        for name, pol in (("av", av), ("adversary", adversary)):
+            if pol.act_dim != 1:
+                raise ValueError("VecFlowEnv.%s: the %s policy has act_dim = %d; each of the two policies emits the one "
+                                 "action column of the RL vehicle" % (what, name, pol.act_dim))
+        if weight is None:
+            weight = self.env.env_params.additional_params.get('perturb_weight')
+            if weight is None:
+                raise ValueError("VecFlowEnv.%s: no weight given and env_params.additional_params has no 'perturb_weight' "
+                                 "(AdversarialAccelEnv's: the vehicle receives av + perturb_weight * adversary)" % what)
+        return float(weight)
+
+    def policy_pair_act(self, av, adversary, weight=None, obs=None, out=None):
+        """ONE evaluation of two policies (``DevicePolicy`` objects with ``act_dim == 1``) on the same observation, in one
+        kernel launch (``fs_policy_pair_act_dev``, k_policy_pair_act): the reference's AdversarialAccelEnv, whose agents
+        'av' and 'adversary' map to a policy each.  Returns ``(act [2, R], logp [2, R], cmd [R])``: plane 0 the av's
+        sample, plane 1 the adversary's (its own Philox column, keyed by its own seed), and the command the vehicle
+        receives, ``cmd = av + weight * adversary`` (one float32 fma) -- what ``step(cmd.unsqueeze(-1))`` takes.
+        ``weight=None`` reads ``env_params.additional_params['perturb_weight']``.  Every call advances the replicas' draw
+        counters by one."""
+        torch, R = self.torch, self.num_envs
+        self.use_current_stream()
+        weight = self._pair_weight("policy_pair_act", av, adversary, weight)
+        obs = self._obs if obs is None else self._check(obs, (R, self.obs_dim), torch.float32)
+        if out is None:
+            out = (torch.empty((2, R), dtype=torch.float32, device=self.device),
+                   torch.empty((2, R), dtype=torch.float32, device=self.device),
+                   torch.empty((R,), dtype=torch.float32, device=self.device))
+        else:
+            self._check(out[0], (2, R), torch.float32)
+            self._check(out[1], (2, R), torch.float32)
+            self._check(out[2], (R,), torch.float32)
+        self.sim.policy_pair_act_dev(av.struct, adversary.struct, weight, obs, out[0], out[1], out[2])
+        return out
+
+    def policy_pair_rollout(self, av, adversary, num_steps, reset_done=False, weight=None, out=None):
+        """``num_steps`` x (two policies -> ``av + weight * adversary`` -> Env.step [-> Env.reset of finished episodes])
+        in ONE kernel launch (``fs_policy_pair_rollout_dev``, k_loop_policy<Adversarial>).  Returns device tensors
+        ``(obs [K+1, R, obs_dim], act [2, K, R], logp [2, K, R], rew [K, R], done [K, R])``: ``act[0]`` / ``logp[0]`` are
+        the av's, ``act[1]`` / ``logp[1]`` the adversary's (each a contiguous ``[K, R]`` tensor), ``rew`` is the av's
+        reward and the adversary's is ``-rew``.  Built for AccelEnv with one RL vehicle on the figure eight
+        (AdversarialAccelEnv); any other handle raises NotImplementedError naming fs_policy_pair.  The observation row is
+        the kernel's AccelEnv order ``[v..., x...]``; the reference's adversarial state interleaves ``[v_i, x_i]`` -- a
+        fixed permutation of the first layer's inputs."""
+        torch, R, K = self.torch, self.num_envs, int(num_steps)
+        self.use_current_stream()
+        weight = self._pair_weight("policy_pair_rollout", av, adversary, weight)
+        if out is None:
+            out = (torch.empty((K + 1, R, self.obs_dim), dtype=torch.float32, device=self.device),
+                   torch.empty((2, K, R), dtype=torch.float32, device=self.device),
+                   torch.empty((2, K, R), dtype=torch.float32, device=self.device),
+                   torch.empty((K, R), dtype=torch.float32, device=self.device),
+                   torch.empty((K, R), dtype=torch.uint8, device=self.device))
+        else:
+            self._check(out[0], (K + 1, R, self.obs_dim), torch.float32)
+            self._check(out[1], (2, K, R), torch.float32)
+            self._check(out[2], (2, K, R), torch.float32)
+            self._check(out[3], (K, R), torch.float32)
+            self._check(out[4], (K, R), torch.uint8)
+        self.sim.policy_pair_rollout_dev(av.struct, adversary.struct, weight, K, out[0], out[1], out[2], out[3], out[4],
+                                         reset_done=reset_done)
+        return out
+
     # ---- host-side inspection
     def get_state(self, field):
         return self.sim.get_state(field)

@@ -286,6 +286,19 @@ class FlowSim:
         L.check(self.lib.fs_policy_rollout_dev(self._h, C.byref(pol), int(num_steps), int(bool(reset_done)), _ptr(obs),
                                                _ptr(act), _ptr(logp), _ptr(rew), _ptr(done)), self.lib)
 
+    def policy_pair_act_dev(self, av, adversary, weight, obs, act, logp, cmd):
+        """Two policies on the one RL vehicle of an AccelEnv handle (fs_policy_pair_act_dev): act / logp [2, R] (plane 0
+        the av, plane 1 the adversary) and the command cmd [R] = fmaf(weight, a_adversary, a_av) for obs [R, obs_dim]."""
+        L.check(self.lib.fs_policy_pair_act_dev(self._h, C.byref(av), C.byref(adversary), float(weight), _ptr(obs),
+                                                _ptr(act), _ptr(logp), _ptr(cmd)), self.lib)
+
+    def policy_pair_rollout_dev(self, av, adversary, weight, num_steps, obs, act, logp, rew, done, reset_done=False):
+        """obs [K+1, R, obs_dim]; act / logp [2, K, R] (agent-major planes); rew / done [K, R]: the av's reward, the
+        adversary's is its negation (fs_policy_pair_rollout_dev)."""
+        L.check(self.lib.fs_policy_pair_rollout_dev(self._h, C.byref(av), C.byref(adversary), float(weight), int(num_steps),
+                                                    int(bool(reset_done)), _ptr(obs), _ptr(act), _ptr(logp), _ptr(rew),
+                                                    _ptr(done)), self.lib)
+
     # ------------------------------------------------------------------ state access
     def _field_shape(self, field):
         if field in (L.FS_FIELD_TIME,):

@@ -434,7 +434,8 @@ int fs_add_vehicle(fs_handle h, int replica, int slot, int route, double x, doub
 /* Family of the step kernel the handle's last fs_step / fs_rollout / fs_policy_rollout launch chose ("k_rollout_pair" with
  * "+speed_mode" and / or "+noise", "k_rollout_idm", "k_ring_pair<Accel | PO | POMA | AccelMA>", "k_rollout_loop",
  * "k_rollout_loop<FULL>", "k_rollout_loop<AccelMA>", "k_rollout_loop<FULL,AccelMA>", "k_ring_policy", "k_loop_policy",
- * "k_ring_policy<POMA>", "k_loop_policy<AccelMA>", "k_merge_policy", "k_merge_policy<PO>", "k_merge_policy<PO,WIDE>"
+ * "k_ring_policy<POMA>", "k_loop_policy<AccelMA>", "k_merge_policy", "k_merge_policy<PO>", "k_merge_policy<PO,WIDE>",
+ * "k_loop_policy<Adversarial>" (fs_policy_pair_rollout_dev; fs_policy_pair_act_dev: "k_policy_pair_act")
  * (fs_policy_act_dev: "k_policy_act", "k_policy_act_vec", "k_policy_act_wide"; the PPO update's entry points: "k_ppo_eval",
  * "k_gae", "k_ppo_grad", "k_adv_stats", "k_adv_finish", "k_adam"),
  * "k_steps<FAST>", "k_steps<CSET>", "k_steps", "k_steps_ml", "k_steps_open" (also "<mixed>"), "k_steps_wide",
@@ -540,6 +541,39 @@ int fs_policy_act_dev(fs_handle h, const fs_policy* pol, const float* obs_dev, f
  * logp_dev [K, R]), rew_dev [K, R], done_dev [K, R] (flags as in fs_rollout_dev). */
 int fs_policy_rollout_dev(fs_handle h, const fs_policy* pol, int num_steps, int reset_done, float* obs_dev,
                           float* act_dev, float* logp_dev, float* rew_dev, uint8_t* done_dev);
+
+/* ---- two policies, one RL vehicle (fs_policy_pair) ----------------------------
+ * The reference's adversarial experiment (examples/exp_configs/rl/multiagent/adversarial_figure_eight.py:
+ * AdversarialAccelEnv, 13 IDM vehicles + ONE RL vehicle on the figure eight) maps its two agents to a policy each: 'av'
+ * and 'adversary' read the SAME observation (AccelEnv's, 2 N values), each draws an action, the vehicle receives
+ * av + perturb_weight * adversary, and the adversary's reward is the negation of the av's.  Two fs_policy structs (the
+ * model class above; they may differ in num_hidden and in the form of their head) drive the one action column of an
+ * FS_ENV_ACCEL handle:
+ *   act / logp   agent-major planes: plane 0 the av, plane 1 the adversary (each agent's [K, R] is contiguous: a learner
+ *                takes it without a copy)
+ *   draws        the av: Philox column 0x40000000 (the single-agent stream) keyed by ITS seed; the adversary: column
+ *                0x40000000 + 1 keyed by ITS seed (equal seeds still give independent draws); both at the replica's
+ *                counter -- the handle's, shared by the two policies and by fs_policy_act_dev --, which advances by ONE per
+ *                call / step
+ *   cmd          fmaf(perturb_weight, a_adversary, a_av), float32: THE combination.  fs_step_dev takes cmd [R] as its action
+ *                column; clipping stays where fs_step_dev does it (act holds the samples)
+ *   rew          the av's reward (desired velocity: it does not read the action); the adversary's is -rew
+ * fs_policy_pair_act_dev ("k_policy_pair_act"): obs_dev [R, 2 N] -> act_dev / logp_dev [2, R], cmd_dev [R]; one launch, no
+ * host synchronisation.  fs_policy_pair_rollout_dev ("k_loop_policy<Adversarial>"): obs_dev [K+1, R, 2 N], act_dev /
+ * logp_dev [2, K, R], rew_dev / done_dev [K, R], reset_done as in fs_policy_rollout_dev.  A fragment equals
+ * K x (fs_policy_pair_act_dev, fs_step_dev(cmd), fs_reset_dev(done)) bit for bit, and with perturb_weight = 0 its obs,
+ * plane 0, rew and done are fs_policy_rollout_dev(av)'s.
+ * Accepted: what fs_policy_rollout_dev takes for the AccelEnv head on a segment-table loop -- FS_F32, FS_ENV_ACCEL without
+ * evaluate, num_rl = 1, 2..16 vehicles, the configuration k_rollout_loop steps, warmup_steps = 0 when a fragment resets --
+ * with obs_dim = 2 N for BOTH policies.  Everything else -- rings and open networks, other heads, other precisions -- is
+ * FS_ERR_UNSUPPORTED, refused before anything launches, with a message that names fs_policy_pair; a perturb_weight that
+ * is not finite is FS_ERR_INVALID. */
+int fs_policy_pair_act_dev(fs_handle h, const fs_policy* av, const fs_policy* adversary, float perturb_weight,
+                           const float* obs_dev /*[R, D]*/, float* act_dev /*[2, R]*/, float* logp_dev /*[2, R]*/,
+                           float* cmd_dev /*[R]*/);
+int fs_policy_pair_rollout_dev(fs_handle h, const fs_policy* av, const fs_policy* adversary, float perturb_weight,
+                               int num_steps, int reset_done, float* obs_dev /*[K+1, R, D]*/, float* act_dev /*[2, K, R]*/,
+                               float* logp_dev /*[2, K, R]*/, float* rew_dev /*[K, R]*/, uint8_t* done_dev /*[K, R]*/);
 
 /* ---- the PPO update on the device ---------------------------------------------
  * What examples/train_vec.py ppo_update runs in torch between two rollouts -- the no_grad pass, generalised advantage
