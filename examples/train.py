@@ -34,7 +34,8 @@ def parse_args(args):
     parser.add_argument('--num_cpus', type=int, default=1, help='rollout workers (rllib only)')
     parser.add_argument('--num_steps', type=int, default=20, help='training iterations')
     parser.add_argument('--rollout_size', type=int, default=100, help='env steps per rollout fragment')
-    parser.add_argument('--checkpoint_path', type=str, default=None, help='rllib: checkpoint to restore')
+    parser.add_argument('--checkpoint_path', type=str, default=None,
+                        help='rllib: checkpoint to restore (device: --checkpoint_dir / --restore)')
     parser.add_argument('--replicas', type=int, default=1024, help='device: environment replicas in the handle')
     parser.add_argument('--fuse_policy', action='store_true',
                         help='device: roll an action-vector policy (singleagent_merge) out through the fused policy + '
@@ -51,7 +52,8 @@ def parse_args(args):
                              'and the adversary that perturbs its accelerations, opposite rewards) -- one fused two-policy '
                              'rollout per fragment, one update per policy; without it such an experiment is refused')
     parser.add_argument('--epochs', type=int, default=4, help='device: passes over a rollout fragment per update')
-    from train_vec import add_model_flags, add_ppo_loss_flags
+    from train_vec import add_checkpoint_flags, add_model_flags, add_ppo_loss_flags
+    add_checkpoint_flags(parser)            # --checkpoint_dir --checkpoint_freq --restore --episode_stats: all off by default
     add_ppo_loss_flags(parser)              # --kl_target --kl_coeff --entropy_coeff --vf_clip --sgd_minibatch_size: all off by default
     add_model_flags(parser)                 # --net_log_std: off by default
     parser.add_argument('--reference_ppo', action='store_true',
@@ -76,6 +78,12 @@ def ppo_loss_settings(flags):
                     entropy_coeff=flags.entropy_coeff, sgd_minibatch_size=flags.sgd_minibatch_size)
     return dict(kl_target=flags.kl_target, kl_coeff=flags.kl_coeff, vf_clip=flags.vf_clip, epochs=flags.epochs,
                 entropy_coeff=flags.entropy_coeff, sgd_minibatch_size=flags.sgd_minibatch_size)
+
+
+def checkpoint_settings(flags):
+    """train_on_device's checkpoint and log keywords from the flags (all off by default)."""
+    return dict(checkpoint_dir=flags.checkpoint_dir, checkpoint_freq=flags.checkpoint_freq, restore=flags.restore,
+                episode_stats=flags.episode_stats)
 
 
 def load_experiment(name):
@@ -131,7 +139,7 @@ def train_device(submodule, flags, multiagent=False):
     return train_on_device(fp, replicas=flags.replicas, fragment=flags.rollout_size, iterations=flags.num_steps,
                            shared_agents=multiagent, fuse_action_vector=flags.fuse_policy and not multiagent,
                            device_update=flags.device_update or flags.device_adam, device_adam=flags.device_adam,
-                           net_log_std=flags.net_log_std, **ppo_loss_settings(flags))
+                           net_log_std=flags.net_log_std, **checkpoint_settings(flags), **ppo_loss_settings(flags))
 
 
 def train_adversary(submodule, flags):
@@ -142,7 +150,7 @@ def train_adversary(submodule, flags):
     return train_adversarial_on_device(fp, replicas=flags.replicas, fragment=flags.rollout_size, iterations=flags.num_steps,
                                        device_update=flags.device_update or flags.device_adam,
                                        device_adam=flags.device_adam, net_log_std=flags.net_log_std,
-                                       **ppo_loss_settings(flags))
+                                       **checkpoint_settings(flags), **ppo_loss_settings(flags))
 
 
 def main(args):

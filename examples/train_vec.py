@@ -70,13 +70,14 @@ class GaussianPolicy(nn.Module):
         out = self.mu(obs)
         return out[..., :self.act_dim], out[..., self.act_dim:]
 
-    def act(self, obs):                       # what the captured graph runs every step
+    def act(self, obs, explore=True):         # what the captured graph runs every step
+        """A sample of the action distribution; ``explore=False``: its mean (evaluation without exploration noise)."""
         with torch.no_grad():
             if self.net_log_std:
                 mu, ls = self._dist(obs)
-                return mu + torch.randn_like(mu) * ls.exp()
+                return mu + torch.randn_like(mu) * ls.exp() if explore else mu
             mu = self.mu(obs)
-            return mu + torch.randn_like(mu) * self.log_std.exp()
+            return mu + torch.randn_like(mu) * self.log_std.exp() if explore else mu
 
     def logp_value(self, obs, act):
         if self.net_log_std:
@@ -371,10 +372,164 @@ def _ppo_epochs_minibatch(pi, opt, prepared, params, epochs, clip, group, kl, en
         kl.adapt(float(allreduce_sum(sum_kl.reshape(1), group)[0]) / float(n))
 
 
+def model_descriptor(pi):
+    """``(obs_dim, act_dim, num_hidden, net_log_std)`` of a GaussianPolicy: DeviceLearner.descriptor()'s tuple."""
+    return (int(pi.mu[0].in_features), int(pi.act_dim), sum(isinstance(m, nn.Linear) for m in pi.mu) - 1, bool(pi.net_log_std))
+
+
+def policy_state(pi, opt=None, kl=None, learner=None):
+    """What one policy carries from one update to the next, as plain CPU tensors and numbers.  ``learner`` with
+    ``device_adam`` (no ``opt``): ``DeviceLearner.state_dict()`` -- packed weights, Adam's m / v / {t, beta1^t, beta2^t},
+    the KL state, the minibatch epoch counter.  Otherwise (torch, --device_update): ``opt.state_dict()`` and AdaptiveKL's
+    two numbers.  ``pi.state_dict()`` is kept on every path: the model alone can be loaded anywhere."""
+    cpu = lambda v: v.detach().to("cpu").clone() if torch.is_tensor(v) else v     # noqa: E731
+    out = dict(descriptor=list(model_descriptor(pi)), pi={k: cpu(v) for k, v in pi.state_dict().items()})
+    if learner is not None and opt is None:
+        out["learner"] = learner.state_dict()
+    else:
+        sd = opt.state_dict()
+        out["opt"] = dict(state={k: {n: cpu(v) for n, v in st.items()} for k, st in sd["state"].items()},
+                          param_groups=sd["param_groups"])
+        out["kl"] = None if kl is None else [float(kl.coef), None if kl.mean_kl is None else float(kl.mean_kl)]
+    return out
+
+
+def restore_policy(entry, pi, opt=None, kl=None, learner=None, log=print, name="policy", model_only=False):
+    """Load ``entry`` (a ``policy_state``) in place: the model always; the optimiser state, the KL coefficient and the
+    epoch counter where the checkpoint was written on THIS update path (``learner`` without ``opt``: device_adam;
+    ``opt``: torch's Adam, with or without the device update) -- onto another path the log says that they were dropped.
+    ``model_only`` (evaluation): nothing but the model is wanted.  A model of another shape is refused by name."""
+    from flow_amd.utils.device_ppo import check_descriptor
+    check_descriptor("restore_policy (%s)" % name, entry["descriptor"], model_descriptor(pi))
+    device_adam = learner is not None and opt is None
+    if device_adam and "learner" in entry and not model_only:
+        learner.load_state_dict(entry["learner"])            # (in place: pi's adopted parameters are views of it)
+        return True
+    with torch.no_grad():
+        pi.load_state_dict(entry["pi"])                       # (copies in place: adopted views stay views)
+    if learner is not None:
+        learner.sync()
+    if model_only:
+        return False
+    if opt is not None and "opt" in entry:
+        opt.load_state_dict(entry["opt"])
+        if kl is not None and entry.get("kl") is not None:
+            kl.coef, kl.mean_kl = entry["kl"][0], entry["kl"][1]
+        return True
+    log("restore: %s: the checkpoint was written on another update path (%s): the model is loaded, the optimiser state, "
+        "the KL coefficient and the epoch counter were dropped" % (name, "device_adam" if "learner" in entry else "torch Adam"))
+    return False
+
+
+def save_checkpoint(directory, iteration, flow_params, policies, seed=0, update_path="torch", model=None):
+    """``directory/checkpoint_<iteration>/``: ``state.pt`` -- a ``torch.save`` of plain tensors and numbers:
+    ``policies`` ({name: policy_state(...)}: one entry, 'av', or the adversarial trainer's two), ``iteration``, ``seed``,
+    ``update_path`` ('torch', 'device_update' or 'device_adam') and ``model`` (how the trainer was called: shared_agents,
+    fuse_action_vector, adversarial) -- and ``params.json``, the flow params through FlowParamsEncoder, as the reference
+    puts next to its checkpoints.  Returns the checkpoint's path."""
+    import json
+    from flow_amd.utils.rllib import FlowParamsEncoder
+    path = os.path.join(str(directory), "checkpoint_%d" % int(iteration))
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, "params.json"), "w") as f:
+        json.dump(flow_params, f, cls=FlowParamsEncoder, sort_keys=True, indent=4)
+    torch.save(dict(iteration=int(iteration), seed=int(seed), update_path=str(update_path), model=dict(model or {}),
+                    policies=policies), os.path.join(path, "state.pt"))
+    return path
+
+
+def load_checkpoint(path):
+    """What ``save_checkpoint`` wrote at ``path`` (a ``checkpoint_<iteration>`` directory): the dict of ``state.pt`` with
+    ``flow_params`` (``params.json`` through ``get_flow_params``) next to it."""
+    from flow_amd.utils.rllib import get_flow_params
+    state = torch.load(os.path.join(str(path), "state.pt"), map_location="cpu", weights_only=True)
+    state["flow_params"] = get_flow_params(os.path.join(str(path), "params.json"))
+    return state
+
+
+def add_checkpoint_flags(ap):
+    """Checkpoints and the episode statistics of the log (train_vec.py and train.py), all off by default."""
+    ap.add_argument("--checkpoint_dir", type=str, default=None,
+                    help="write checkpoint_<iteration>/ (state.pt, params.json) here every --checkpoint_freq iterations and at the end")
+    ap.add_argument("--checkpoint_freq", type=int, default=None, help="iterations between checkpoints (with --checkpoint_dir)")
+    ap.add_argument("--restore", type=str, default=None,
+                    help="a checkpoint_<iteration> directory: continue at iteration + 1 with its weights, optimiser state, KL "
+                         "coefficient and epoch counter (the environments start from a reset, the sampling streams from their seeds)")
+    ap.add_argument("--episode_stats", action="store_true",
+                    help="append RLlib's episode_reward_mean / min / max, episode_len_mean and episodes (of the episodes that "
+                         "ended in the iteration's fragment) to the iteration line (k_episode_stats)")
+
+
+def _checkpoint_due(it, last, freq):
+    return it == last or (freq is not None and freq > 0 and (it + 1) % freq == 0)
+
+
+def choose_rollout(vec, pi, fragment, seed, log, shared_agents=False, fuse_action_vector=False, learner=None, world=1,
+                   rank=0, greedy=False):
+    """How a fragment of ``fragment`` closed-loop steps runs for this environment and model -- train_on_device's choice,
+    which examples/evaluate.py shares: ``(fused, graph, graph_policy)``, exactly one of ``fused`` (a DevicePolicy for
+    ``vec.policy_rollout``) and ``graph`` (a StepGraph, begun after a reset) set.  ``learner``: a DeviceLearner whose
+    buffer a DevicePolicy shares (device_adam).  ``greedy``: the mean action instead of a sample -- ``fs_policy.greedy`` in
+    the kernels, ``pi.act(obs, explore=False)`` around the torch module."""
+    n_ag = vec.act_dim if shared_agents else 1
+    k_ag = vec.obs_dim // n_ag
+    free_log_std = None if pi.net_log_std else pi.log_std
+    device_adam = learner is not None
+    # the rollout: ONE kernel per fragment where the library has the fused policy + step form for this experiment and
+    # model (fs_policy_rollout_dev: rings / the figure eight with one RL vehicle, the multi-agent ring, figure eight and
+    # merge -- its actions applied -- with their agents sharing the policy, 1..3 hidden layers of 32 tanh units);
+    # otherwise K single steps around the torch policy captured as one HIP graph.  (Shared agents: the network's input is
+    # one agent's block, k_ag values; on the merge an agent whose RL slot is empty has a NaN action, which ppo_update
+    # leaves out.)
+    fused, graph, graph_policy = None, None, None
+    shared = "; one policy shared by %d agents per replica" % n_ag if shared_agents else ""
+    try:
+        from flow_amd.utils.device_policy import DevicePolicy
+        if fuse_action_vector and not shared_agents:
+            fused = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=free_log_std, seed=seed, act_dim=vec.act_dim, greedy=greedy)
+        else:
+            fused = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=free_log_std, seed=seed, greedy=greedy)
+        if device_adam:
+            fused.share(learner)                               # the rollout kernels read the buffer the learner's Adam writes
+        vec.reset()
+        vec.policy_rollout(fused, 1, reset_done=True)           # (probe: raises NotImplementedError when not built)
+        kernel = vec.sim.last_kernel
+        vec.reset()
+        log("rollout: fused policy + step kernel (%s)%s" % (kernel, shared))
+    except NotImplementedError as e:
+        why = e
+        graph_policy, fused = (fused if fuse_action_vector and not shared_agents else None), None
+        if graph_policy is not None:
+            # no fused kernel for this head (BottleneckDesiredVelocityEnv): the library's eager policy kernel, where it is
+            # built, goes into the captured fragment in the torch module's place -- one launch per step instead of ten-odd
+            try:
+                vec.reset()
+                vec.policy_act(graph_policy)                   # (probe)
+                kernel = vec.sim.last_kernel
+                graph = vec.capture(fragment, policy=graph_policy, reset_done=True)
+                graph.begin(vec.reset())
+                log("rollout: HIP graph of %d single steps around the policy kernel (%s)" % (fragment, kernel))
+            except NotImplementedError:
+                graph_policy = None
+    if fused is None and graph is None:
+        log("rollout: HIP graph of %d single steps around the torch policy (%s)%s" % (fragment, why, shared))
+        if world > 1:
+            torch.manual_seed(seed + 1000 * (rank + 1))       # the graph's torch.randn: another stream per rank
+        R_ = vec.num_envs
+
+        def act_shared(obs):                                   # [R, agents * k] -> [R, agents]: every agent its own sample
+            return pi.act(obs.view(R_ * n_ag, k_ag), explore=not greedy).view(R_, n_ag)
+        graph = vec.capture(fragment, policy=act_shared if shared_agents else (lambda obs: pi.act(obs, explore=not greedy)) if greedy else pi.act,
+                            reset_done=True)
+        graph.begin(vec.reset())
+    return fused, graph, graph_policy
+
+
 def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epochs=4, lr=3e-4, seed=0, log=print,
                     rank=0, world=1, shared_agents=False, fuse_action_vector=False, device_update=False, device_adam=False,
                     kl_target=None, kl_coeff=0.2, entropy_coeff=0.0, vf_clip=None, vf_coef=0.5, clip=0.2,
-                    sgd_minibatch_size=None, net_log_std=False):
+                    sgd_minibatch_size=None, net_log_std=False, checkpoint_dir=None, checkpoint_freq=None, restore=None,
+                    episode_stats=False, on_episodes=None):
     """PPO on R replicas of ``flow_params`` with everything in HBM: returns the mean step reward per iteration.
     ``world`` > 1: this process is rank ``rank`` of a data-parallel run (torch.distributed is initialised): it steps its
     block of the R replicas on its own GPU.
@@ -409,7 +564,16 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     ``net_log_std``: the policy's head has 2 x act_dim outputs, the means and the log stds (``GaussianPolicy(net_log_std=
     True)``: RLlib's default model, the reference's).  The torch update takes it, and so does ``device_adam`` -- the learner
     is ``DeviceLearner(net_log_std=True)`` and a fused or graph DevicePolicy reads its buffer through ``share`` --;
-    ``device_update`` alone (the host-n gradient around torch's Adam) does not build it and says so.  Off by default."""
+    ``device_update`` alone (the host-n gradient around torch's Adam) does not build it and says so.  Off by default.
+    ``checkpoint_dir`` / ``checkpoint_freq``: rank 0 writes ``save_checkpoint`` every ``checkpoint_freq`` iterations and
+    after the last one.  ``restore`` (a ``checkpoint_<iteration>`` directory): the weights, the optimiser state, the KL
+    coefficient and the epoch counter are loaded (``restore_policy``) and ``iterations`` more iterations run, numbered
+    from ``iteration + 1``; the environments start from a reset and the sampling streams from their seeds, so the run is
+    not the uninterrupted run's bit for bit -- the update is.  ``episode_stats``: the iteration line ends with RLlib's
+    ``episode_reward_mean / min / max``, ``episode_len_mean`` and ``episodes`` over the episodes that ended in the
+    iteration's fragment (``VecFlowEnv.episode_stats``: one launch per fragment; the shared reward on the multi-agent
+    heads); ``on_episodes`` (a callable) then receives ``(iteration, summary dict)`` of every iteration.  All off by
+    default: the line, the history and every launch are then what they were."""
     from flow_amd.dist import allreduce_sum, shard_range
     if net_log_std and device_update and not device_adam:
         raise NotImplementedError("train_on_device(net_log_std=True, device_update=True): the 2A-output head is not built for "
@@ -437,52 +601,9 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
         learner.adopt_parameters()                             # (before the rollout graph captures the parameters' addresses)
     else:
         opt = torch.optim.Adam(pi.parameters(), lr=lr)
-    # the rollout: ONE kernel per fragment where the library has the fused policy + step form for this experiment and
-    # model (fs_policy_rollout_dev: rings / the figure eight with one RL vehicle, the multi-agent ring, figure eight and
-    # merge -- its actions applied -- with their agents sharing the policy, 1..3 hidden layers of 32 tanh units);
-    # otherwise K single steps around the torch policy captured as one HIP graph.  (Shared agents: the network's input is
-    # one agent's block, k_ag values; on the merge an agent whose RL slot is empty has a NaN action, which ppo_update
-    # leaves out.)
-    fused, graph, graph_policy = None, None, None
-    shared = "; one policy shared by %d agents per replica" % n_ag if shared_agents else ""
-    try:
-        from flow_amd.utils.device_policy import DevicePolicy
-        if fuse_action_vector and not shared_agents:
-            fused = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=free_log_std, seed=seed, act_dim=vec.act_dim)
-        else:
-            fused = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=free_log_std, seed=seed)
-        if device_adam:
-            fused.share(learner)                               # the rollout kernels read the buffer the learner's Adam writes
-        vec.reset()
-        vec.policy_rollout(fused, 1, reset_done=True)           # (probe: raises NotImplementedError when not built)
-        kernel = vec.sim.last_kernel
-        vec.reset()
-        log("rollout: fused policy + step kernel (%s)%s" % (kernel, shared))
-    except NotImplementedError as e:
-        why = e
-        graph_policy, fused = (fused if fuse_action_vector and not shared_agents else None), None
-        if graph_policy is not None:
-            # no fused kernel for this head (BottleneckDesiredVelocityEnv): the library's eager policy kernel, where it is
-            # built, goes into the captured fragment in the torch module's place -- one launch per step instead of ten-odd
-            try:
-                vec.reset()
-                vec.policy_act(graph_policy)                   # (probe)
-                kernel = vec.sim.last_kernel
-                graph = vec.capture(fragment, policy=graph_policy, reset_done=True)
-                graph.begin(vec.reset())
-                log("rollout: HIP graph of %d single steps around the policy kernel (%s)" % (fragment, kernel))
-            except NotImplementedError:
-                graph_policy = None
-    if fused is None and graph is None:
-        log("rollout: HIP graph of %d single steps around the torch policy (%s)%s" % (fragment, why, shared))
-        if world > 1:
-            torch.manual_seed(seed + 1000 * (rank + 1))       # the graph's torch.randn: another stream per rank
-        R_ = hi - lo
-
-        def act_shared(obs):                                   # [R, agents * k] -> [R, agents]: every agent its own sample
-            return pi.act(obs.view(R_ * n_ag, k_ag)).view(R_, n_ag)
-        graph = vec.capture(fragment, policy=act_shared if shared_agents else pi.act, reset_done=True)
-        graph.begin(vec.reset())
+    fused, graph, graph_policy = choose_rollout(vec, pi, fragment, seed, log, shared_agents=shared_agents,
+                                                fuse_action_vector=fuse_action_vector, learner=learner if device_adam else None,
+                                                world=world, rank=rank)
     K, R = fragment, hi - lo
     if device_adam:
         log("update: on the device, Adam included (k_ppo_eval, k_gae, k_adv_stats, k_adv_finish, k_ppo_grad, k_adam)")
@@ -491,8 +612,16 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
         learner = DeviceLearner(vec, [pi.mu[0], pi.mu[2]], pi.mu[4], pi.log_std, [pi.value[0], pi.value[2]], pi.value[4])
         log("update: on the device (k_ppo_eval, k_gae, k_ppo_grad)")
     kl = AdaptiveKL(kl_target, kl_coeff) if kl_target is not None and not device_adam else None
+    update_path = "device_adam" if device_adam else "device_update" if device_update else "torch"
+    start = 0
+    if restore is not None:
+        ck = load_checkpoint(restore)
+        restore_policy(ck["policies"]["av"], pi, opt, kl, learner, log=log if rank == 0 else (lambda *a: None), name="av")
+        start = int(ck["iteration"]) + 1
+        if rank == 0:
+            log("restore: %s (iteration %d, written on %s): continuing at iteration %d" % (restore, ck["iteration"], ck["update_path"], start))
     history = []
-    for it in range(iterations):
+    for it in range(start, start + iterations):
         vec.redraw_ring_lengths()                              # pending ring length per replica for its next in-graph reset
         vec.redraw_inflow_rates()                              # ... pending total inflow (reset_inflow; a no-op without it)
         t0 = time.perf_counter()
@@ -527,9 +656,22 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
                                          (done != 0).sum().double()]))
         mean_rew = float(tot[0] / tot[1])
         history.append(mean_rew)
+        ep_log = ""
+        if episode_stats:                                      # (the episodes that ended in this fragment; carries kept)
+            from flow_amd.utils import episode_stats as es
+            summary = es.summarize(es.allreduce(vec.episode_stats(rew, done, reset=it == start, accumulate=False)))
+            if on_episodes is not None:
+                on_episodes(it, summary)
+            ep_log = es.log_suffix(summary)
         if rank == 0:
-            log("iteration %3d  mean step reward %8.4f  rollout %.1f ms (%.2f M env-steps/s per GPU, %d GPU%s)  episodes ended %d%s"
-                % (it, mean_rew, t_roll * 1e3, K * R / t_roll / 1e6, world, "s" if world > 1 else "", int(tot[2]), kl_log))
+            log("iteration %3d  mean step reward %8.4f  rollout %.1f ms (%.2f M env-steps/s per GPU, %d GPU%s)  episodes ended %d%s%s"
+                % (it, mean_rew, t_roll * 1e3, K * R / t_roll / 1e6, world, "s" if world > 1 else "", int(tot[2]), kl_log, ep_log))
+            if checkpoint_dir is not None and _checkpoint_due(it, start + iterations - 1, checkpoint_freq):
+                path = save_checkpoint(checkpoint_dir, it, flow_params, dict(av=policy_state(pi, opt, kl, learner)), seed=seed,
+                                       update_path=update_path,
+                                       model=dict(shared_agents=bool(shared_agents), fuse_action_vector=bool(fuse_action_vector),
+                                                  adversarial=False))
+                log("checkpoint: %s" % path)
     vec.close()
     return history
 
@@ -547,7 +689,9 @@ def update_adversarial(rollout, update_av, update_adversary):
 
 def train_adversarial_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epochs=4, lr=3e-4, seed=0, log=print,
                                 device_update=False, device_adam=False, kl_target=None, kl_coeff=0.2, entropy_coeff=0.0,
-                                vf_clip=None, vf_coef=0.5, clip=0.2, sgd_minibatch_size=None, net_log_std=False):
+                                vf_clip=None, vf_coef=0.5, clip=0.2, sgd_minibatch_size=None, net_log_std=False,
+                                checkpoint_dir=None, checkpoint_freq=None, restore=None, episode_stats=False,
+                                on_episodes=None):
     """PPO on TWO policies with opposite rewards (the reference's adversarial_figure_eight.py: POLICY_GRAPHS 'av' and
     'adversary', policy_mapping_fn the identity): both read AccelEnv's observation, each draws an action, the RL vehicle
     receives ``av + perturb_weight * adversary``.  One fragment is ONE launch (``VecFlowEnv.policy_pair_rollout``:
@@ -559,7 +703,9 @@ def train_adversarial_on_device(flow_params, replicas=1024, fragment=100, iterat
     adopted, its ``DevicePolicy`` sharing its weights) -- each a per-policy call.  One process, one GPU; a handle the
     pair kernel refuses raises NotImplementedError with the library's message (there is no captured-graph fallback).
     The observation row is the kernel's AccelEnv order ``[v..., x...]``, where the reference's adversarial state
-    interleaves ``[v_i, x_i]``: a fixed permutation of the first layer's inputs, irrelevant to training from scratch."""
+    interleaves ``[v_i, x_i]``: a fixed permutation of the first layer's inputs, irrelevant to training from scratch.
+    ``checkpoint_dir`` / ``checkpoint_freq`` / ``restore`` / ``episode_stats`` / ``on_episodes``: ``train_on_device``'s; a checkpoint holds
+    both policies ('av' and 'adversary'), and the episode statistics are the av's (the adversary's return is the negation)."""
     if net_log_std and device_update and not device_adam:
         raise NotImplementedError("train_adversarial_on_device(net_log_std=True, device_update=True): the 2A-output head is "
                                   "not built for the device update around torch's Adam (fs_ppo_grad_dev); add device_adam "
@@ -610,8 +756,16 @@ def train_adversarial_on_device(flow_params, replicas=1024, fragment=100, iterat
     elif device_update:
         log("update: on the device, one DeviceLearner per policy (k_ppo_eval, k_gae, k_ppo_grad)")
     K, R = fragment, replicas
+    update_path = "device_adam" if device_adam else "device_update" if device_update else "torch"
+    start = 0
+    if restore is not None:
+        ck = load_checkpoint(restore)
+        for sd in sides:
+            restore_policy(ck["policies"][sd.name], sd.pi, sd.opt, sd.kl, sd.learner, log=log, name=sd.name)
+        start = int(ck["iteration"]) + 1
+        log("restore: %s (iteration %d, written on %s): continuing at iteration %d" % (restore, ck["iteration"], ck["update_path"], start))
     history = []
-    for it in range(iterations):
+    for it in range(start, start + iterations):
         def updater(sd):
             if device_adam:
                 return lambda shard: sd.learner.update([shard], epochs=epochs, lr=lr, clip=clip, vf_coef=vf_coef,
@@ -635,8 +789,21 @@ def train_adversarial_on_device(flow_params, replicas=1024, fragment=100, iterat
         rew, done = rollout[3], rollout[4]
         mean_rew = float(rew.double().mean())
         history.append(mean_rew)
-        log("iteration %3d  mean step reward %8.4f  rollout %.1f ms (%.2f M env-steps/s per GPU, 1 GPU)  episodes ended %d%s"
-            % (it, mean_rew, t_roll * 1e3, K * R / t_roll / 1e6, int((done != 0).sum()), kl_log))
+        ep_log = ""
+        if episode_stats:                                      # (the av's return; the adversary's is its negation)
+            from flow_amd.utils import episode_stats as es
+            summary = es.summarize(vec.episode_stats(rew, done, reset=it == start, accumulate=False))
+            if on_episodes is not None:
+                on_episodes(it, summary)
+            ep_log = es.log_suffix(summary)
+        log("iteration %3d  mean step reward %8.4f  rollout %.1f ms (%.2f M env-steps/s per GPU, 1 GPU)  episodes ended %d%s%s"
+            % (it, mean_rew, t_roll * 1e3, K * R / t_roll / 1e6, int((done != 0).sum()), kl_log, ep_log))
+        if checkpoint_dir is not None and _checkpoint_due(it, start + iterations - 1, checkpoint_freq):
+            path = save_checkpoint(checkpoint_dir, it, flow_params,
+                                   {sd.name: policy_state(sd.pi, sd.opt, sd.kl, sd.learner) for sd in sides}, seed=seed,
+                                   update_path=update_path,
+                                   model=dict(shared_agents=False, fuse_action_vector=False, adversarial=True))
+            log("checkpoint: %s" % path)
     vec.close()
     return history
 
@@ -699,6 +866,7 @@ def main(argv=None):
                     help="run the whole PPO update, Adam included, on the device (DeviceLearner.update); implies --device_update")
     add_ppo_loss_flags(ap)
     add_model_flags(ap)
+    add_checkpoint_flags(ap)
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     force = os.environ.get("TRAIN_FORCE_DIST") == "1"            # the N > 1 code path (RCCL init, all-reduces) with one rank
@@ -719,7 +887,8 @@ def main(argv=None):
                                device_update=args.device_update or args.device_adam, device_adam=args.device_adam,
                                kl_target=args.kl_target, kl_coeff=args.kl_coeff, entropy_coeff=args.entropy_coeff,
                                vf_clip=args.vf_clip, sgd_minibatch_size=args.sgd_minibatch_size,
-                               net_log_std=args.net_log_std)
+                               net_log_std=args.net_log_std, checkpoint_dir=args.checkpoint_dir,
+                               checkpoint_freq=args.checkpoint_freq, restore=args.restore, episode_stats=args.episode_stats)
     finally:
         if world > 1 or force:
             import torch.distributed as dist

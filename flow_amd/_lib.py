@@ -49,7 +49,7 @@ EXPORTS = ["fs_create", "fs_destroy", "fs_last_error", "fs_abi_version", "fs_obs
            "fs_ppo_grad_n_dev", "fs_adv_stats_dev", "fs_adv_finish_dev", "fs_adam_dev", "fs_ppo_eval_dist_dev",
            "fs_ppo_loss_workspace", "fs_ppo_grad_loss_dev", "fs_kl_adapt_dev", "fs_ppo_perm_host",
            "fs_ppo_minibatch_workspace", "fs_ppo_minibatch_dev", "fs_ppo_mb_finish_dev", "fs_policy_pair_act_dev",
-           "fs_policy_pair_rollout_dev"]
+           "fs_policy_pair_rollout_dev", "fs_episode_stats_dev"]
 # fs_ppo_minibatch.mode / .flags
 FS_MB_STEP, FS_MB_PARTIAL = 0, 1
 FS_MB_ACCUMULATE, FS_MB_FIRST, FS_MB_LAST = 1, 2, 4
@@ -118,8 +118,8 @@ class fs_config(C.Structure):
 
 class fs_policy(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("obs_dim", C.c_int32), ("num_hidden", C.c_int32),
-                ("hidden_width", C.c_int32), ("activation", C.c_int32), ("weights_dev", C.c_void_p),
-                ("log_std_dev", C.c_void_p), ("seed", C.c_uint64)]
+                ("hidden_width", C.c_int32), ("activation", C.c_int32), ("greedy", C.c_int32),
+                ("weights_dev", C.c_void_p), ("log_std_dev", C.c_void_p), ("seed", C.c_uint64)]
 
 
 class fs_ppo_model(C.Structure):
@@ -224,6 +224,8 @@ def load(path=None):
     lib.fs_ppo_grad_n_dev.restype = C.c_int
     lib.fs_adv_stats_dev.argtypes = [h, C.c_int64, f32p, f32p, C.c_int, C.c_int, f64p, f64p]
     lib.fs_adv_stats_dev.restype = C.c_int
+    lib.fs_episode_stats_dev.argtypes = [h, C.c_int, f32p, u8p, f64p, C.c_void_p, f64p, C.c_int]
+    lib.fs_episode_stats_dev.restype = C.c_int
     lib.fs_adv_finish_dev.argtypes = [h, f64p, f64p]
     lib.fs_adv_finish_dev.restype = C.c_int
     lib.fs_adam_dev.argtypes = [h, C.c_int64, f32p, f32p, f32p, f32p, f64p, C.c_double, C.c_double, C.c_double, C.c_double]

@@ -637,6 +637,27 @@ int fs_adv_stats_dev(fs_handle h, int64_t n, const float* adv_dev, const float* 
   return launch_adv_stats(s->stream, n, adv_dev, act_dev, act_dim, accumulate ? 1 : 0, adv64_dev, stats_dev, s->d_adv_scratch);
 }
 
+int fs_episode_stats_dev(fs_handle h, int num_steps, const float* rew_dev, const uint8_t* done_dev, double* run_ret_dev,
+                         int32_t* run_len_dev, double* stats_dev, int accumulate) {
+  if (!h || !rew_dev || !done_dev || !run_ret_dev || !run_len_dev || !stats_dev)
+    return fail(FS_ERR_INVALID, "fs_episode_stats_dev: NULL argument");
+  if (num_steps < 1) return fail(FS_ERR_INVALID, "fs_episode_stats_dev: num_steps must be at least 1");
+  SimBase* s = S(h);
+  DeviceGuard guard(s->cfg.device);
+  if (!s->d_ep_scratch) {
+    // the first call on a handle allocates (and synchronises the device once): make it outside a stream capture
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, fs::EP_SCRATCH_BYTES));
+    s->allocs.push_back(p);
+    HIP_TRY(hipMemset(p, 0, fs::EP_SCRATCH_BYTES));
+    HIP_TRY(hipDeviceSynchronize());
+    s->d_ep_scratch = static_cast<double*>(p);
+  }
+  s->last_kernel = "k_episode_stats";
+  return launch_episode_stats(s->stream, num_steps, (long long)s->cfg.num_replicas, rew_dev, done_dev, run_ret_dev, run_len_dev,
+                              stats_dev, accumulate ? 1 : 0, s->d_ep_scratch);
+}
+
 int fs_adv_finish_dev(fs_handle h, const double* stats_dev, double* mean_std_n_dev) {
   if (!h || !stats_dev || !mean_std_n_dev) return fail(FS_ERR_INVALID, "fs_adv_finish_dev: NULL argument");
   DeviceGuard guard(S(h)->cfg.device);

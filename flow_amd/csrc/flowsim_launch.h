@@ -315,7 +315,11 @@ namespace fsim {
                                    float* logp, float* rew, uint8_t* done) {
     if constexpr (std::is_same<T, float>::value) {
       const bool fastc = loop_delta4 && loop_fastc_ok();
+      // (fs_policy.greedy picks the instantiation on this family: flowsim_policy.h policy_sample)
       auto kernel = [&](auto H) {
+        if (pv.greedy)
+          return fastc ? &fs::k_greedy_loop_policy<H, true, true>
+                       : loop_delta4 ? &fs::k_greedy_loop_policy<H, true, false> : &fs::k_greedy_loop_policy<H, false, false>;
         return fastc ? &fs::k_loop_policy<H, true, true>
                      : loop_delta4 ? &fs::k_loop_policy<H, true, false> : &fs::k_loop_policy<H, false, false>;
       };

@@ -205,6 +205,15 @@ __host__ __device__ constexpr int adv_groups(long long n) {
   return int(g < 1 ? 1 : g > ADV_MAX_GROUPS ? ADV_MAX_GROUPS : g);
 }
 
+// k_episode_stats: workgroups (a function of R alone) and the handle's scratch [ticket][G x EP_STATS partials]
+constexpr int EP_THREADS = 256, EP_MAX_GROUPS = 512, EP_STATS = 8, EP_AHEAD = 8;
+constexpr size_t EP_SCRATCH_BYTES = sizeof(double) * (1 + EP_STATS * EP_MAX_GROUPS);
+
+__host__ __device__ constexpr int ep_groups(long long R) {
+  const long long g = (R + EP_THREADS - 1) / EP_THREADS;                             // one replica per lane before G saturates
+  return int(g < 1 ? 1 : g > EP_MAX_GROUPS ? EP_MAX_GROUPS : g);
+}
+
 }  // namespace fs
 
 namespace fsim {
@@ -239,6 +248,9 @@ int launch_mb_finish(hipStream_t stream, int P, float* w, float* grad, float* m,
 int launch_adv_stats(hipStream_t stream, long long n, const float* adv, const float* act, int A, int accumulate, double* adv64,
                      double* stats, double* scratch);
 int launch_adv_finish(hipStream_t stream, const double* stats, double* mean_std_n);
+// (scratch: fs::EP_SCRATCH_BYTES of device memory, zero before its first use: the handle owns it)
+int launch_episode_stats(hipStream_t stream, int K, long long R, const float* rew, const uint8_t* done, double* run_ret,
+                         int32_t* run_len, double* stats, int accumulate, double* scratch);
 int launch_adam(hipStream_t stream, int P, float* w, const float* g, float* m, float* v, double* state, double lr, double beta1,
                 double beta2, double eps);
 }  // namespace fsim
@@ -913,6 +925,111 @@ __global__ __launch_bounds__(ADV_THREADS) void k_adv_stats(long long n, const fl
   if (t == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- the episode statistics {episodes, sum ret, sum ret^2, min ret, max ret, sum len, min len, max len} of a fragment's
+// rew / done [K, R].  G = ep_groups(R) workgroups of EP_THREADS lanes; lane t of workgroup b walks replicas
+// r = b EP_THREADS + t + j G EP_THREADS, j ascending, each over k = 0 .. K-1 with the replica's carries (run_ret += rew in
+// double, run_len += 1; done != 0 emits the episode into the lane's partials -- sums added, min / max combined, in that
+// (j, k) order -- and zeroes the carries), and writes the carries back.  Then k_adv_stats's scheme: the lanes of a workgroup meet
+// in a binary tree over LDS (lane t (+)= lane t + half, half = 128 .. 1; (+) = add, fmin or fmax per statistic), lane 0
+// writes the workgroup's partials and draws an integer ticket, the workgroup that draws the last one combines the G
+// partials (lane t those of workgroups t and t + EP_THREADS, then the same tree) and resets the ticket.  The order of
+// every sum depends on (K, R) alone.  A lane without an episode contributes {0, 0, 0, +inf, -inf, 0, +inf, -inf}.
+__device__ __forceinline__ double ep_combine(int k, double a, double b) {
+  return (k == 3 || k == 6) ? fmin(a, b) : (k == 4 || k == 7) ? fmax(a, b) : a + b;
+}
+
+__device__ __forceinline__ void ep_tree(double (*red)[EP_THREADS], int t) {
+  for (int half = EP_THREADS / 2; half >= 1; half >>= 1) {
+    if (t < half) {
+#pragma unroll
+      for (int k = 0; k < EP_STATS; ++k) red[k][t] = ep_combine(k, red[k][t], red[k][t + half]);
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(EP_THREADS) void k_episode_stats(int K, long long R, const float* __restrict__ rew,
+                                                              const uint8_t* __restrict__ done,
+                                                              double* __restrict__ run_ret, int32_t* __restrict__ run_len,
+                                                              double* __restrict__ stats, int accumulate, double* scratch) {
+  __shared__ double red[EP_STATS][EP_THREADS];
+  __shared__ int is_last;
+  const int t = threadIdx.x, G = gridDim.x;
+  const double inf = __builtin_inf();
+  double p[EP_STATS] = {0.0, 0.0, 0.0, inf, -inf, 0.0, inf, -inf};
+  for (long long r = (long long)blockIdx.x * EP_THREADS + t; r < R; r += (long long)G * EP_THREADS) {
+    double ret = run_ret[r];
+    int32_t len = run_len[r];
+    // (EP_AHEAD steps' loads in flight together -- the walk is a chain of dependent adds, not of dependent loads --; the
+    // loads past K - 1 repeat the last step's address and are not used)
+    for (int k0 = 0; k0 < K; k0 += EP_AHEAD) {
+      float rw[EP_AHEAD];
+      uint8_t dn[EP_AHEAD];
+#pragma unroll
+      for (int j = 0; j < EP_AHEAD; ++j) {
+        const int k = k0 + j < K ? k0 + j : K - 1;
+        const size_t i = size_t(k) * size_t(R) + size_t(r);
+        rw[j] = rew[i];
+        dn[j] = done[i];
+      }
+#pragma unroll
+      for (int j = 0; j < EP_AHEAD; ++j) {
+        if (k0 + j < K) {
+          ret += double(rw[j]);
+          len += 1;
+          if (dn[j] != 0) {
+            const double l = double(len);
+            p[0] += 1.0;
+            p[1] += ret;
+            p[2] += ret * ret;
+            p[3] = fmin(p[3], ret);
+            p[4] = fmax(p[4], ret);
+            p[5] += l;
+            p[6] = fmin(p[6], l);
+            p[7] = fmax(p[7], l);
+            ret = 0.0;
+            len = 0;
+          }
+        }
+      }
+    }
+    run_ret[r] = ret;
+    run_len[r] = len;
+  }
+#pragma unroll
+  for (int k = 0; k < EP_STATS; ++k) red[k][t] = p[k];
+  __syncthreads();
+  ep_tree(red, t);
+  unsigned* ticket = reinterpret_cast<unsigned*>(scratch);
+  double* part = scratch + 1;
+  if (t == 0) {
+    for (int k = 0; k < EP_STATS; ++k) part[EP_STATS * blockIdx.x + k] = red[k][0];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool last = drawn == unsigned(G - 1);
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    is_last = last ? 1 : 0;
+  }
+  __syncthreads();
+  if (is_last == 0) return;
+  // lane t combines the partials of workgroups t, t + EP_THREADS (G <= 2 EP_THREADS), then the same tree
+  double q[EP_STATS] = {0.0, 0.0, 0.0, inf, -inf, 0.0, inf, -inf};
+  for (int g = t; g < G; g += EP_THREADS) {
+#pragma unroll
+    for (int k = 0; k < EP_STATS; ++k) q[k] = ep_combine(k, q[k], part[EP_STATS * g + k]);
+  }
+#pragma unroll
+  for (int k = 0; k < EP_STATS; ++k) red[k][t] = q[k];
+  __syncthreads();
+  ep_tree(red, t);
+  if (t < EP_STATS) stats[t] = accumulate ? ep_combine(t, stats[t], red[t][0]) : red[t][0];
+  if (t == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ppo_update's formula, in double (division and square root are correctly rounded; nothing contracts): a NaN variance
 // (n = 1) stays a NaN, as torch's clamp_min leaves it
 __global__ __launch_bounds__(64) void k_adv_finish(const double* __restrict__ stats, double* __restrict__ out) {
@@ -1224,6 +1341,14 @@ int launch_adv_stats(hipStream_t stream, long long n, const float* adv, const fl
                      double* stats, double* scratch) {
   hipLaunchKernelGGL(fs::k_adv_stats, dim3(fs::adv_groups(n)), dim3(fs::ADV_THREADS), 0, stream, n, adv, act, A, accumulate,
                      adv64, stats, scratch);
+  HIP_TRY(hipGetLastError());
+  return FS_OK;
+}
+
+int launch_episode_stats(hipStream_t stream, int K, long long R, const float* rew, const uint8_t* done, double* run_ret,
+                         int32_t* run_len, double* stats, int accumulate, double* scratch) {
+  hipLaunchKernelGGL(fs::k_episode_stats, dim3(fs::ep_groups(R)), dim3(fs::EP_THREADS), 0, stream, K, R, rew, done, run_ret,
+                     run_len, stats, accumulate, scratch);
   HIP_TRY(hipGetLastError());
   return FS_OK;
 }

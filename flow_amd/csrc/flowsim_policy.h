@@ -37,6 +37,7 @@ struct PolicyView {
   uint32_t* ctr;           // device [R]: actions sampled so far per replica (the draw counter of the policy's stream)
   int in_dim, num_hidden, n_out;
   uint32_t seed_lo, seed_hi;
+  int greedy;              // fs_policy.greedy: policy_sample applies the mean (the draw is still made: the streams advance)
 };
 
 struct alignas(16) PolicyLds {
@@ -225,7 +226,14 @@ __device__ __forceinline__ void policy_eval(const PolicyView& pv, const PolicyLd
 
 // the action: mean + std * g, g the replica's next standard normal draw (Philox block of four per counter / 4, column
 // 0x40000000 + agent: a stream of its own next to the vehicles' noise -- agent 0 is the single-agent stream); log-probability
-// of a 1-d diagonal Gaussian
+// of a 1-d diagonal Gaussian.  pv.greedy (wave-uniform): the mean itself -- a select, fma(sd, 0, mu) would be NaN where sd
+// overflows -- and the density at the mean, the same expression with g = 0; the draw, the counters and the control flow
+// around this call are the sampling path's, so greedy and sampling calls interleave on one stream.
+// GREEDY: -1 reads pv.greedy at run time -- every kernel but the k_loop_policy family.  There the flag is a template
+// parameter (0 / 1) and the launch picks the instantiation from fs_policy.greedy: with one more run-time scalar
+// k_loop_policy<0, false, false> was one register over its recorded total (tests/test_codegen.py), so its sampling
+// instantiations stay the code they were and the greedy ones are kernels of their own (k_greedy_loop_policy).
+template <int GREEDY = -1>
 __device__ __forceinline__ void policy_sample(const PolicyView& pv, uint32_t replica, uint32_t ctr, float mu, float log_std,
                                               float& action, float& logp, NoiseBlock<float>* nzb = nullptr,
                                               uint32_t agent = 0u) {
@@ -234,19 +242,28 @@ __device__ __forceinline__ void policy_sample(const PolicyView& pv, uint32_t rep
   const float g = nzb ? nzb->draw(pv.seed_lo, pv.seed_hi, replica, col, ctr)
                       : gauss<float>(pv.seed_lo, pv.seed_hi, replica, col, ctr);
   const float sd = __builtin_amdgcn_exp2f(log_std * 1.4426950408889634f);
-  action = __builtin_fmaf(sd, g, mu);
-  logp = __builtin_fmaf(-0.5f * g, g, -log_std) - 0.9189385332046727f;
+  const float a_s = __builtin_fmaf(sd, g, mu);
+  const float lp_s = __builtin_fmaf(-0.5f * g, g, -log_std);
+  if constexpr (GREEDY == 0) {
+    action = a_s;
+    logp = lp_s - 0.9189385332046727f;
+  } else {
+    const bool greedy = GREEDY == 1 || pv.greedy != 0;
+    action = greedy ? mu : a_s;
+    logp = (greedy ? -log_std : lp_s) - 0.9189385332046727f;
+  }
 }
 
 // a fused kernel's draw for agent c of a shared policy: agents 0 and 1 keep their Philox block over four steps (one
 // NoiseBlock each, six registers), agents from 2 on draw with gauss() -- the same bits either way (NoiseBlock::draw is
 // gauss()); a block per agent for every agent would be an array indexed by the run-time agent: scratch memory
+template <int GREEDY = -1>
 __device__ __forceinline__ void policy_sample_agent(const PolicyView& pv, uint32_t replica, uint32_t ctr, int c, float mu,
                                                     float log_std, float& action, float& logp, NoiseBlock<float>& nzb0,
                                                     NoiseBlock<float>& nzb1) {
-  if (c == 0) policy_sample(pv, replica, ctr, mu, log_std, action, logp, &nzb0, 0u);          // (wave-uniform)
-  else if (c == 1) policy_sample(pv, replica, ctr, mu, log_std, action, logp, &nzb1, 1u);
-  else policy_sample(pv, replica, ctr, mu, log_std, action, logp, nullptr, uint32_t(c));
+  if (c == 0) policy_sample<GREEDY>(pv, replica, ctr, mu, log_std, action, logp, &nzb0, 0u);          // (wave-uniform)
+  else if (c == 1) policy_sample<GREEDY>(pv, replica, ctr, mu, log_std, action, logp, &nzb1, 1u);
+  else policy_sample<GREEDY>(pv, replica, ctr, mu, log_std, action, logp, nullptr, uint32_t(c));
 }
 
 // an agent without a vehicle (FS_ENV_MERGE_MA: its column's RL slot is empty): no command (fs_step_dev reads NaN as
@@ -779,7 +796,7 @@ struct PairLds {           // the adversary's LDS copy (PAIR), or nothing
 template <>
 struct PairLds<false> {};
 
-template <int HEAD, bool DELTA4, bool FASTC, bool PAIR>
+template <int HEAD, bool DELTA4, bool FASTC, bool PAIR, int GREEDY>
 __device__ __forceinline__ void loop_policy_body(const DevView<float> s, const PolicyView pv, const PolicyView pv2,
                                                  float pw, int num_steps, int reset_done, float* __restrict__ obs,
                                                  float* __restrict__ act, float* __restrict__ logp,
@@ -972,7 +989,7 @@ __device__ __forceinline__ void loop_policy_body(const DevView<float> s, const P
         const float ib = i == 0 ? b0 : (i == 1 ? b1 : (i == 2 ? b2 : 0.0f));
         float ac;
         policy_eval<SEG, true>(pv, &PL, i, ia, ib, 0.0f, mu, ls);
-        policy_sample_agent(pv, s.rep0 + uint32_t(rr), pctr, c, mu, ls, ac, lp, act_draws, act_draws1);
+        policy_sample_agent<GREEDY>(pv, s.rep0 + uint32_t(rr), pctr, c, mu, ls, ac, lp, act_draws, act_draws1);
         if (rvalid && i == 0) {
           act[(size_t(step) * R + rr) * n_ag + c] = ac;
           logp[(size_t(step) * R + rr) * n_ag + c] = lp;
@@ -982,7 +999,7 @@ __device__ __forceinline__ void loop_policy_body(const DevView<float> s, const P
     } else {
       if (HEAD == 1) policy_eval<SEG>(pv, &PL, i, o0, o1, o2, mu, ls);
       else policy_eval<SEG, true>(pv, &PL, i, o0, o1, 0.0f, mu, ls);
-      policy_sample(pv, s.rep0 + uint32_t(rr), pctr, mu, ls, a, lp, &act_draws);
+      policy_sample<GREEDY>(pv, s.rep0 + uint32_t(rr), pctr, mu, ls, a, lp, &act_draws);
       if (rvalid && i == 0) {
         act[size_t(step) * R + rr] = a;
         logp[size_t(step) * R + rr] = lp;
@@ -990,7 +1007,7 @@ __device__ __forceinline__ void loop_policy_body(const DevView<float> s, const P
       if constexpr (PAIR) {                              // the adversary: the same observation, its own network and stream
         float mu2, ls2, a2, lp2;
         policy_eval<SEG, true>(pv2, &PL2.L, i, o0, o1, 0.0f, mu2, ls2);
-        policy_sample(pv2, s.rep0 + uint32_t(rr), pctr, mu2, ls2, a2, lp2, &act_draws1, 1u);
+        policy_sample<GREEDY>(pv2, s.rep0 + uint32_t(rr), pctr, mu2, ls2, a2, lp2, &act_draws1, 1u);
         if (rvalid && i == 0) {
           act[(size_t(num_steps) + step) * R + rr] = a2;
           logp[(size_t(num_steps) + step) * R + rr] = lp2;
@@ -1133,7 +1150,17 @@ __global__ __launch_bounds__(256) void k_loop_policy(DevView<float> s, PolicyVie
                                                      float* __restrict__ obs, float* __restrict__ act,
                                                      float* __restrict__ logp, float* __restrict__ rew,
                                                      uint8_t* __restrict__ done) {
-  loop_policy_body<HEAD, DELTA4, FASTC, false>(s, pv, pv, 0.0f, num_steps, reset_done, obs, act, logp, rew, done);
+  loop_policy_body<HEAD, DELTA4, FASTC, false, 0>(s, pv, pv, 0.0f, num_steps, reset_done, obs, act, logp, rew, done);
+}
+
+// fs_policy.greedy on this family: the same body with policy_sample<1> (the mean action), a kernel of its own so that the
+// sampling instantiations above keep their names and their code
+template <int HEAD, bool DELTA4, bool FASTC>
+__global__ __launch_bounds__(256) void k_greedy_loop_policy(DevView<float> s, PolicyView pv, int num_steps, int reset_done,
+                                                            float* __restrict__ obs, float* __restrict__ act,
+                                                            float* __restrict__ logp, float* __restrict__ rew,
+                                                            uint8_t* __restrict__ done) {
+  loop_policy_body<HEAD, DELTA4, FASTC, false, 1>(s, pv, pv, 0.0f, num_steps, reset_done, obs, act, logp, rew, done);
 }
 
 // ---- TWO policies on one RL vehicle (AdversarialAccelEnv on the figure eight: the reference's adversarial_figure_eight.py
@@ -1184,7 +1211,8 @@ __global__ __launch_bounds__(256) void k_loop_policy_pair(DevView<float> s, Poli
                                                           int num_steps, int reset_done, float* __restrict__ obs,
                                                           float* __restrict__ act, float* __restrict__ logp,
                                                           float* __restrict__ rew, uint8_t* __restrict__ done) {
-  loop_policy_body<0, DELTA4, FASTC, true>(s, pv, pv2, pw, num_steps, reset_done, obs, act, logp, rew, done);
+  // (the flag per policy, read at run time: the pair kernels keep their registers with it, tests/test_policy_pair_codegen.py)
+  loop_policy_body<0, DELTA4, FASTC, true, -1>(s, pv, pv2, pw, num_steps, reset_done, obs, act, logp, rew, done);
 }
 
 }  // namespace fs

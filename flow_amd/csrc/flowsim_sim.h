@@ -100,6 +100,7 @@ struct SimBase {
   bool no_ring_rl = false;      // FLOWSIM_NO_RING_RL=1: keep the generic k_steps for IDM + RL rings (tests)
   bool no_mask_skip = false;    // FLOWSIM_NO_MASK_SKIP=1: a masked k_steps_open / k_steps_wide launch steps every wave (A/B, tests)
   bool no_queue = false;        // FLOWSIM_NO_QUEUE=1: keep k_steps_open / k_steps_wide for the open networks (tests)
+  double* d_ep_scratch = nullptr;   // k_episode_stats: ticket and partials (flowsim_learn.h), allocated by its first launch
   double* d_adv_scratch = nullptr;  // k_adv_stats: ticket and partial sums (flowsim_learn.h), allocated by its first launch
   unsigned* d_mb_ticket = nullptr;  // k_ppo_minibatch: the ticket its workgroups draw (zero between launches), allocated by its first launch
   int* d_qflag = nullptr;       // k_drop_queue: bit 0 = a path held more than its 64 lanes (the launch's results are invalid)
@@ -915,6 +916,7 @@ struct Sim : SimBase {
     pv.n_out = pol->log_std_dev ? 1 : 2;
     pv.seed_lo = uint32_t(pol->seed & 0xFFFFFFFFull);
     pv.seed_hi = uint32_t(pol->seed >> 32);
+    pv.greedy = pol->greedy != 0 ? 1 : 0;
     return pv;
   }
   int launch_policy(const fs_policy* pol, int num_steps, int reset_done, const float* obs_in, float* obs, float* act,

@@ -502,6 +502,41 @@ class VecFlowEnv(object):
                                          reset_done=reset_done)
         return out
 
+    def episode_stats(self, rew, done, reset=False, accumulate=True):
+        """RLlib's episode statistics of a fragment's ``rew`` / ``done`` ``[K, R]`` (what ``policy_rollout``,
+        ``policy_pair_rollout``, ``rollout`` or a ``StepGraph`` return), in ONE kernel launch (``fs_episode_stats_dev``,
+        k_episode_stats) without a host synchronisation: returns the float64 device tensor ``[8]`` =
+        ``{episodes, sum ret, sum ret^2, min ret, max ret, sum len, min len, max len}`` (the env's buffer: the next call
+        rewrites it), accumulated over the calls since the last ``reset=True``;
+        ``flow_amd.utils.episode_stats.summarize`` turns it into RLlib's names.  The env owns the per-replica carries (the
+        return and length of the episode a replica is in), so an episode that straddles fragments is counted once, in the
+        fragment where it ends: feed the fragments in order.  ``reset=True`` zeroes the carries and the statistics first.
+        ``accumulate=False``: the statistics are those of THIS fragment's episodes alone; the carries go on all the same.
+        Any non-zero ``done`` byte ends an episode, the horizon and a collision alike.
+        On the shared-reward multi-agent heads ``rew`` is the reward every agent shares: the return is that of the shared
+        reward, one episode per replica.  In the two-policy experiment ``rew`` is the av's; the adversary's return is the
+        negation (its mean is ``-mean``, its min ``-max``, its max ``-min``)."""
+        torch, R = self.torch, self.num_envs
+        K = int(rew.shape[0])
+        self._check(rew, (K, R), torch.float32)
+        self._check(done, (K, R), torch.uint8)
+        self.use_current_stream()
+        if getattr(self, "_ep_stats", None) is None:
+            self._ep_ret = torch.zeros(R, dtype=torch.float64, device=self.device)
+            self._ep_len = torch.zeros(R, dtype=torch.int32, device=self.device)
+            self._ep_stats = torch.zeros(8, dtype=torch.float64, device=self.device)
+            self._ep_empty = torch.tensor([0.0, 0.0, 0.0, float("inf"), float("-inf"), 0.0, float("inf"), float("-inf")],
+                                          dtype=torch.float64, device=self.device)
+            reset = True
+        if reset:
+            self._ep_ret.zero_()
+            self._ep_len.zero_()
+            self._ep_stats.copy_(self._ep_empty)
+        L.check(self.sim.lib.fs_episode_stats_dev(self.sim._h, K, rew.data_ptr(), done.data_ptr(), self._ep_ret.data_ptr(),
+                                                  self._ep_len.data_ptr(), self._ep_stats.data_ptr(),
+                                                  1 if accumulate else 0), self.sim.lib)
+        return self._ep_stats
+
     # ---- host-side inspection
     def get_state(self, field):
         return self.sim.get_state(field)

@@ -18,9 +18,14 @@ class DevicePolicy(object):
 
     ``act_dim`` > 1: ONE network with an action vector (MergePOEnv, ``FlowSim.policy_action_dim``): ``head`` has
     ``2 * act_dim`` outputs -- the means, then the log stds: RLlib's DiagGaussian order -- or ``act_dim`` outputs with
-    ``log_std`` of ``act_dim`` elements.  The packed buffer is the same: per layer W [out][in] row-major, then b [out]."""
+    ``log_std`` of ``act_dim`` elements.  The packed buffer is the same: per layer W [out][in] row-major, then b [out].
 
-    def __init__(self, hidden, head, log_std=None, seed=0, act_dim=1):
+    ``greedy`` (``fs_policy.greedy``; also a property that can be set between launches, nothing is repacked): every
+    policy kernel applies the MEAN action -- ``act = mu`` exactly, ``logp`` the density at the mean -- instead of a
+    sample.  The sampling streams advance as they do when sampling, so greedy and sampling calls interleave on one
+    stream.  A captured graph holds the flag's value at capture."""
+
+    def __init__(self, hidden, head, log_std=None, seed=0, act_dim=1, greedy=False):
         import torch
         self.torch = torch
         self.hidden, self.head, self.log_std_param = list(hidden), head, log_std
@@ -38,9 +43,17 @@ class DevicePolicy(object):
         self.ls = torch.zeros(A, dtype=torch.float32, device=dev) if log_std is not None else None
         self.struct = L.fs_policy(struct_size=C.sizeof(L.fs_policy), obs_dim=self.hidden[0].in_features,
                                   num_hidden=len(self.hidden), hidden_width=32, activation=0,
-                                  weights_dev=self.buf.data_ptr(),
+                                  greedy=1 if greedy else 0, weights_dev=self.buf.data_ptr(),
                                   log_std_dev=self.ls.data_ptr() if self.ls is not None else None, seed=int(seed))
         self.sync()
+
+    @property
+    def greedy(self):
+        return bool(self.struct.greedy)
+
+    @greedy.setter
+    def greedy(self, on):
+        self.struct.greedy = 1 if on else 0
 
     def share(self, learner):
         """Run on the storage of ``learner`` (a ``flow_amd.utils.device_ppo.DeviceLearner`` over the same network): the

@@ -76,6 +76,19 @@ def _check_trunk(who, hidden, head, n_out, what):
                                   % (who, head.in_features, head.out_features, what))
 
 
+DESCRIPTOR_NAMES = ("obs_dim D", "act_dim A", "num_hidden", "net_log_std")
+
+
+def check_descriptor(who, theirs, mine):
+    """A checkpoint's model ``(D, A, num_hidden, net_log_std)`` against the one it is loaded into: a mismatch is refused,
+    naming the field."""
+    theirs, mine = list(theirs), list(mine)
+    for name, a, b in zip(DESCRIPTOR_NAMES, theirs, mine):
+        if a != b:
+            raise ValueError("%s: the checkpoint's model has %s = %s, this one %s = %s (checkpoint (D, A, num_hidden, "
+                             "net_log_std) = %s, here %s)" % (who, name, a, name, b, tuple(theirs), tuple(mine)))
+
+
 class DeviceLearner(object):
     """``policy_hidden`` / ``value_hidden``: the ``nn.Linear`` layers of the two trunks (1..3 each, the same number, 32
     units, tanh between them); ``policy_head``: 32 -> A means (1 <= A <= 32) next to the free ``log_std`` [A] -- or, with
@@ -510,6 +523,45 @@ class DeviceLearner(object):
         L.check(self.sim.lib.fs_adam_dev(self.sim._h, self.P, self.weights.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(),
                                          self.v.data_ptr(), self.state.data_ptr(), float(lr), float(betas[0]), float(betas[1]),
                                          float(eps)), self.sim.lib)
+
+    # ---- checkpoints: everything update() carries from one call to the next
+    def descriptor(self):
+        """The model the packed buffers are laid out for: ``(D, A, num_hidden, net_log_std)``."""
+        return (int(self.D), int(self.A), int(self.num_hidden), bool(self.net_log_std))
+
+    def state_dict(self):
+        """Plain CPU tensors and numbers: the packed ``weights``, Adam's ``m`` / ``v`` / ``state`` ({t, beta1^t, beta2^t}),
+        ``kl_state`` ({coefficient, last mean KL}; ``kl_started``: whether an update has set the coefficient yet), the
+        minibatch epoch counter ``mb_epoch`` and the model ``descriptor``.  Synchronises the device (it copies to the
+        host)."""
+        self.sync()
+        self._adam_buffers()
+        cpu = lambda t: t.detach().to("cpu").clone()                               # noqa: E731
+        return dict(descriptor=list(self.descriptor()), weights=cpu(self.weights), m=cpu(self.m), v=cpu(self.v),
+                    state=cpu(self.state), kl_state=cpu(self.kl_state), kl_started=bool(self._kl_started),
+                    mb_epoch=cpu(self.mb_epoch))
+
+    def load_state_dict(self, sd):
+        """Copies a ``state_dict()`` into the learner's buffers IN PLACE: parameters that are views of ``weights``
+        (``adopt_parameters``) and a DevicePolicy that ``share``s the buffer see the loaded values, and a captured graph
+        keeps its addresses.  Parameters that were not adopted are written too.  A state made for another model
+        ``(D, A, num_hidden, net_log_std)`` is refused by name."""
+        torch = self.torch
+        check_descriptor("DeviceLearner.load_state_dict", sd["descriptor"], self.descriptor())
+        if int(sd["weights"].numel()) != self.P:
+            raise ValueError("DeviceLearner.load_state_dict: the checkpoint holds %d packed weights, this learner %d"
+                             % (int(sd["weights"].numel()), self.P))
+        self._adam_buffers()
+        with torch.no_grad():
+            for name in ("weights", "m", "v", "state", "kl_state", "mb_epoch"):
+                getattr(self, name).copy_(sd[name].to(self.device))
+            if not self._adopted:
+                off = 0
+                for p in self.params:
+                    n = p.numel()
+                    p.copy_(self.weights[off:off + n].view_as(p))
+                    off += n
+        self._kl_started = bool(sd.get("kl_started", True))
 
     def _shard_buffers(self, j, K, R):
         """Intermediates of shard ``j`` of ``update()``, allocated once per shape."""

@@ -437,7 +437,7 @@ int fs_add_vehicle(fs_handle h, int replica, int slot, int route, double x, doub
  * "k_ring_policy<POMA>", "k_loop_policy<AccelMA>", "k_merge_policy", "k_merge_policy<PO>", "k_merge_policy<PO,WIDE>",
  * "k_loop_policy<Adversarial>" (fs_policy_pair_rollout_dev; fs_policy_pair_act_dev: "k_policy_pair_act")
  * (fs_policy_act_dev: "k_policy_act", "k_policy_act_vec", "k_policy_act_wide"; the PPO update's entry points: "k_ppo_eval",
- * "k_gae", "k_ppo_grad", "k_adv_stats", "k_adv_finish", "k_adam"),
+ * "k_gae", "k_ppo_grad", "k_adv_stats", "k_adv_finish", "k_adam"; fs_episode_stats_dev: "k_episode_stats"),
  * "k_steps<FAST>", "k_steps<CSET>", "k_steps", "k_steps_ml", "k_steps_open" (also "<mixed>"), "k_steps_wide",
  * "k_merge_queue", "k_drop_queue", "k_obs_mixed"; "" before the first launch).  Diagnostics for tests and bench.py: which
  * configuration class a workload landed in (no reference counterpart).  The string is static.
@@ -517,13 +517,24 @@ const char* fs_last_kernel(fs_handle h);
  * fs_policy_rollout_dev is refused by name on these handles (no fused kernel yet): capture K x (fs_policy_act_dev,
  * fs_step_dev, fs_reset_dev(done)) as one graph instead (VecFlowEnv.capture with a DevicePolicy).  Every refusal on
  * this head -- another precision, obs_dim != fs_obs_dim, num_rl outside 1..64, the model class -- names
- * FS_ENV_BOTTLENECK_DV. */
+ * FS_ENV_BOTTLENECK_DV.
+ * The mean action (greedy != 0; every kernel named above, eager and fused, and fs_policy_pair_* per policy): act = the
+ * head's mean EXACTLY (a select: no std enters it, so it stays finite where exp(log std) overflows) and logp =
+ * (-log_std) - 0.9189385332046727f, the density at the mean -- the sampling expression with a zero draw; the action-vector
+ * heads add their columns in the order they add them when sampling.  The draw counters advance exactly as they do when
+ * sampling (one per call or step, absent agents included; an absent agent still gets NaN and 0), so greedy and sampling
+ * calls interleave on one stream: a sampling call after n greedy calls draws what it draws after n sampling calls.  The
+ * Gaussian head only.  greedy occupies four bytes that were padding before the first pointer: sizeof(fs_policy) and every
+ * other offset are unchanged, and a C caller MUST ZERO the struct (memset, or = {0}) before filling it -- a caller that
+ * left the padding uninitialised would switch the mean action on by accident.  On the k_loop_policy family the flag picks
+ * the kernel's instantiation (the same fs_last_kernel names); every other kernel reads it at run time. */
 typedef struct fs_policy {
   uint32_t struct_size;               /* sizeof(fs_policy) */
   int32_t obs_dim;                    /* must equal fs_obs_dim (FS_ENV_MERGE_PO / BOTTLENECK_DV too); shared agents: fs_obs_dim / num_rl */
   int32_t num_hidden;                 /* 1..3 hidden layers ... */
   int32_t hidden_width;               /* ... of 32 units each */
   int32_t activation;                 /* 0 = tanh */
+  int32_t greedy;                     /* != 0: act = the mean, logp = the density at the mean (see above); 0: sample */
   const float* weights_dev;
   const float* log_std_dev;           /* NULL: the network's second output is the log std (action-vector heads: [num_rl]) */
   uint64_t seed;
@@ -654,6 +665,24 @@ int fs_ppo_grad_n_dev(fs_handle h, const fs_ppo_model* model, int64_t n, const f
  * make it before a stream capture begins. */
 int fs_adv_stats_dev(fs_handle h, int64_t n, const float* adv_dev, const float* act_dev, int act_dim, int accumulate,
                      double* adv64_dev, double* stats_dev);
+/* RLlib's episode statistics from a fragment's rew_dev / done_dev [K, R] (K = num_steps, R = the handle's replicas), ONE
+ * launch ("k_episode_stats") on the handle's stream, no host synchronisation: it can be captured into a graph (after one
+ * eager call, which allocates a few KB of scratch and synchronises the device once).
+ * Replica r is walked k = 0 .. K-1: run_ret[r] += (double)rew[k][r], run_len[r] += 1; where done[k][r] != 0 (any bit: the
+ * horizon and a collision alike) the episode {run_ret, run_len} is emitted and both return to zero.  The carries
+ * run_ret_dev / run_len_dev [R] are read at the start and written at the end (zero them before the first fragment): an
+ * episode that straddles fragments counts once, in the fragment where it ends.
+ *   stats_dev [8] = {episodes, sum ret, sum ret * ret, min ret, max ret, sum len, min len, max len}, in double; with no
+ *   episode min is +inf and max -inf.  accumulate != 0 combines with what stats_dev holds: the sums add, min / max
+ *   combine (several fragments, or several local shards in call order).
+ * G = min(512, ceil(R / 256)) workgroups of 256 lanes: lane t of workgroup b walks replicas 256 b + t + 256 G j, j
+ * ascending, and adds / combines the episodes it meets in that (j, k) order; the lanes of a workgroup meet in a binary
+ * tree (lane t (+)= lane t + half, half = 128 .. 1, a lane without an episode holding {0, 0, 0, +inf, -inf, 0, +inf,
+ * -inf}); the workgroup that finishes last (an integer ticket) combines the G partials: lane t those of workgroups t and
+ * t + 256, then the same tree.  The order depends on (K, R) alone and there are no float atomics: the same inputs give
+ * the same bits.  min / max are fmin / fmax. */
+int fs_episode_stats_dev(fs_handle h, int num_steps, const float* rew_dev, const uint8_t* done_dev, double* run_ret_dev,
+                         int32_t* run_len_dev, double* stats_dev, int accumulate);
 /* One thread, in double, exactly (no contraction; division and square root correctly rounded)
  *   n = stats[2];  mean = stats[0] / n;  var = (stats[1] - (n * mean) * mean) / (n - 1);  std = sqrt(var < 0 ? 0 : var)
  * mean_std_n_dev [3] = {mean, std, n}: ppo_update's formula, bit for bit its float64 result.  A launch of its own because
