@@ -142,6 +142,7 @@ __global__ __launch_bounds__(256) void k_rollout_loop(DevView<typename std::cond
   typedef typename std::conditional<MX, double, float>::type X;
   constexpr int SEG = 16, RPW = 4, PERIOD = 4;
   __shared__ X tab_start[FS_MAX_SEGMENTS + 2], tab_fs[FS_MAX_SEGMENTS + 2], tab_sl[FS_MAX_SEGMENTS + 2];
+  __shared__ X tab_cg;                                // (MX without DELTA4) the crash gap in float64
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int seg = lane / SEG;
@@ -157,6 +158,7 @@ __global__ __launch_bounds__(256) void k_rollout_loop(DevView<typename std::cond
   constexpr bool has = true;                          // N > 1 (host-checked)
   const int flags = s.flags;
 
+  if (MX && !DELTA4 && threadIdx.x == 0) tab_cg = X(s.crash_gap);
   if (threadIdx.x < FS_MAX_SEGMENTS + 2) {
     const int q = threadIdx.x, qq = q < FS_MAX_SEGMENTS ? q : 0;
     tab_start[q] = q < s.nseg ? s.seg_start[qq] : X(3.0e38);
@@ -440,7 +442,23 @@ __global__ __launch_bounds__(256) void k_rollout_loop(DevView<typename std::cond
         d = wrap_up(xl - x, Lv);
         h = has ? T(d - len_lead) : T(1000);
         // bit 0 a gap below crash_gap, bits 1 / 2 a body on the crossing point of stream a / b, bit 3 v < -100 (sign masks)
-        unsigned f2 = sm_lt(h, crash_gap) >> 31;
+        unsigned f2 = 0u;
+        if constexpr (!MX) {
+          f2 = sm_lt(h, crash_gap) >> 31;
+        } else if constexpr (DELTA4) {
+          // MX: a decision on positions, so on the float64 gap, not on the float32 one the models read (a gap one float64
+          // ulp below the crash gap rounds to it)
+          f2 = sm_lt(d - len_lead, X(s.crash_gap)) >> 31;
+        } else {
+          // the same decision where pow() is the register peak and a float64 crash gap held through the step costs two
+          // VGPRs: h = RN32(d - len_lead) and crash_gap = RN32(crash gap) order as the float64 values do unless they are
+          // EQUAL (rounding is monotone) -- then, and that is rare, the float64 values decide, the crash gap read from LDS
+          f2 = sm_lt(h, crash_gap) >> 31;
+          if (__ballot(h == crash_gap) != 0ull) {
+            const X cg = *(const volatile X*)&tab_cg;
+            f2 = (h == crash_gap) ? ((d - len_lead) < cg ? 1u : 0u) : f2;
+          }
+        }
         if (junction_on) {
           f2 |= (sm_in(x, za_lo, za_hi) >> 31) << 1;
           f2 |= (sm_in(x, zb_lo, zb_hi) >> 31) << 2;

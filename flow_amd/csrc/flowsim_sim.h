@@ -886,7 +886,7 @@ struct Sim : SimBase {
   const char* policy_loop_why(const fs_policy* pol, bool po_ok, bool fragment_resets) const {
     const bool po = po_ok && dv.env == FS_ENV_WAVE_ATTENUATION_PO, accel = dv.env == FS_ENV_ACCEL && !dv.evaluate;
     if (!std::is_same<T, float>::value || mixed) return "precision (f32 on segment-table loops)";
-    if (seg != 16 || dv.N < 2) return "num_vehicles (2..16: a row of 16 lanes per replica)";
+    if (seg != 16 || dv.N < 2) return "num_vehicles (9..16: a row of 16 lanes per replica; up to 8 vehicles a replica is laid out in 8 lanes)";
     if (!(po || accel) || dv.num_rl != 1)
       return po_ok ? "env (WaveAttenuationPOEnv or AccelEnv with one RL vehicle)" : "env (AccelEnv with one RL vehicle)";
     if (pol->obs_dim != (po ? 3 : 2 * dv.N)) return "fs_policy.obs_dim (the environment's observation)";
@@ -983,7 +983,7 @@ struct Sim : SimBase {
         why = "env (FS_ENV_WAVE_ATTENUATION_PO_MA on a segment-table loop: loops take MultiAgentAccelPOEnv)";
       else if (dv.num_rl < 1 || pol->obs_dim * dv.num_rl != obs_dim)
         why = "fs_policy.obs_dim (one agent's block: fs_obs_dim / num_rl)";
-      else if (loop && (seg != 16 || dv.N < 2)) why = "num_vehicles (2..16: a row of 16 lanes per replica)";
+      else if (loop && (seg != 16 || dv.N < 2)) why = "num_vehicles (9..16: a row of 16 lanes per replica; up to 8 vehicles a replica is laid out in 8 lanes)";
       else if (loop && (!(dv.flags & fs::FLAG_IDM_SET) || (dv.flags & fs::FLAG_HAS_FAILSAFE) || dv.sims_per_step != 1 ||
                         dv.integrator != FS_EULER || dv.track_aux || dv.sort_vehicles || dv.obs_perm != nullptr ||
                         !loop_div_ok || (obs != nullptr && reset_done && cfg.warmup_steps != 0)))

@@ -575,7 +575,7 @@ int fs_policy_rollout_dev(fs_handle h, const fs_policy* pol, int num_steps, int 
  * K x (fs_policy_pair_act_dev, fs_step_dev(cmd), fs_reset_dev(done)) bit for bit, and with perturb_weight = 0 its obs,
  * plane 0, rew and done are fs_policy_rollout_dev(av)'s.
  * Accepted: what fs_policy_rollout_dev takes for the AccelEnv head on a segment-table loop -- FS_F32, FS_ENV_ACCEL without
- * evaluate, num_rl = 1, 2..16 vehicles, the configuration k_rollout_loop steps, warmup_steps = 0 when a fragment resets --
+ * evaluate, num_rl = 1, 9..16 vehicles, the configuration k_rollout_loop steps, warmup_steps = 0 when a fragment resets --
  * with obs_dim = 2 N for BOTH policies.  Everything else -- rings and open networks, other heads, other precisions -- is
  * FS_ERR_UNSUPPORTED, refused before anything launches, with a message that names fs_policy_pair; a perturb_weight that
  * is not finite is FS_ERR_INVALID. */

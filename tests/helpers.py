@@ -584,3 +584,421 @@ def fig8_fixture_case():
 # leaving vehicle (0.84 / 1.76 / 2.75 m/s), S-J holds it until the tail has left the box; idm_7 behind it feels that
 # from the third step on
 FIG8_FIXTURE_DEVIATIONS = {(8, 2.0), (8, 3.0), (8, 4.0), (7, 4.0)}
+
+
+# ------------------------------------------------------------------ constructed edge layouts of the figure-eight step
+# (k_rollout_loop, flowsim_fig8.h, and loop_policy_body, flowsim_policy.h; tests/test_loop_edges_cpu.py proves on the oracle
+# that every layout reaches the event it is named for, tests/test_loop_edges_gpu.py runs them on the kernels).  Everything
+# is dyadic: sim_step 1/8, slowdown_ramp 1, loop lengths and table entries on multiples of 1/8.  Three kinds of vehicle
+# move EXACTLY, in float32 and float64 alike:
+#   * an RL vehicle with speed_mode 0 and a dyadic action keeps a dyadic speed (action 0: x advances by v / 8 per step);
+#   * a `parked` IDM vehicle (s0 = minGap = 512 m > every headway of these loops) has a negative acceleration whatever its
+#     leader does and stays at v = 0, noise 0.2 included (a - 3 + 0.2 g < 0 for |g| < 15);
+#   * a `waiting` IDM vehicle (default parameters, v = 0, obey_safe_speed) stays where it is while the crossing holds it --
+#     the stop speed towards a line less than 2 m ahead is 0 -- and accelerates as soon as it is released.
+LOOP_DT = 0.125
+LOOP_CRASH_GAP = 0.5
+
+
+def rl_mover(rl_index=0, speed_mode=0):
+    return idm_vehicle(controller=S.CTRL_RL, rl_index=rl_index, speed_mode=speed_mode)
+
+
+def parked(noise=0.0, delta=4):
+    return idm_vehicle(p=[30, 1, 1, 1.5, delta, 512, 0, 0], sumo_min_gap=512.0, noise=noise, speed_mode=1)
+
+
+def waiting(noise=0.0, delta=4):
+    return idm_vehicle(p=[30, 1, 1, 1.5, delta, 2, 0, 0], noise=noise, speed_mode=1)
+
+
+def ulps(x, n, dtype=np.float32):
+    """x as `dtype`, moved n representable numbers up (n < 0: down)."""
+    T = np.dtype(dtype).type
+    x = T(x)
+    for _ in range(abs(n)):
+        x = np.nextafter(x, T(np.inf) if n > 0 else T(-np.inf))
+    return x
+
+
+def start_for(target, v, steps, dtype=np.float32):
+    """init_pos from which `steps` steps of x <- x + v / 8 (rounded to `dtype` each time, as the step does) end EXACTLY on
+    `target` (itself a `dtype` number, possibly one ulp off a table entry)."""
+    T = np.dtype(dtype).type
+    target, inc = T(target), T(v) * T(LOOP_DT)
+    x0 = T(np.float64(target) - steps * np.float64(inc))
+    for _ in range(16):
+        x = x0
+        for _ in range(steps):
+            x = T(x + inc)
+        if x == target:
+            return x0
+        x0 = np.nextafter(x0, T(np.inf) if x < target else T(-np.inf))
+    raise AssertionError("no %s start reaches %r in %d steps" % (np.dtype(dtype).name, target, steps))
+
+
+def loop_edge_spec(L, segs, junction, vehicles, X, V, **kw):
+    """The spec of a constructed loop: X, V [R, N] initial positions and speeds."""
+    X, V = np.asarray(X, dtype=np.float64), np.asarray(V, dtype=np.float64)
+    R, N = X.shape
+    assert V.shape == X.shape and len(vehicles) == N and (X >= 0).all() and (X < L).all()
+    spec = dict(num_replicas=R, num_vehicles=N, num_rl=sum(v["controller"] == S.CTRL_RL for v in vehicles),
+                sim_step=LOOP_DT, slowdown_ramp=1.0, junction_length=0.0, ring_length=np.full(R, float(L)), max_speed=32.0,
+                env=S.ENV_ACCEL, target_velocity=8.0, action_low=-1.0, action_high=1.0, horizon=10 ** 6, warmup_steps=0,
+                sims_per_step=1, vehicles=vehicles, init_pos=X, init_vel=V, junction_mode=1, segments=segs,
+                junction=junction, crash_gap=LOOP_CRASH_GAP, seed=12345, noise_math="exact", track_aux=False)
+    spec.update(kw)
+    return spec
+
+
+def with_form(spec, form):
+    """-> (spec, environment, last_kernel) of one of the four forms the figure-eight rollout step exists in.  'full' wants a
+    noisy IDM slot in the spec; 'delta2' gives the first IDM slot the exponent 2 (pow_delta's x * x: still exact)."""
+    if form == "full":
+        return spec, {}, "k_rollout_loop<FULL>"
+    if form == "flags":
+        return spec, {"FLOWSIM_NO_LOOP_FULL": "1"}, "k_rollout_loop"
+    if form == "k_steps":
+        return spec, {"FLOWSIM_NO_LOOP_KERNEL": "1"}, "k_steps"
+    assert form == "delta2"
+    veh, first = [], True
+    for v in spec["vehicles"]:
+        if v["controller"] == S.CTRL_IDM and first:
+            v, first = dict(v, p=list(v["p"][:4]) + [2] + list(v["p"][5:])), False
+        veh.append(v)
+    assert not first
+    return dict(spec, vehicles=veh), {}, "k_rollout_loop"
+
+
+LOOP_FORMS = ("full", "flags", "delta2", "k_steps")
+
+
+# ---- case 1: the segment cursor
+def cursor_table(L=64.0, full16=True):
+    """Starts in clusters 1/8 m apart: three right after 0, four mid-loop, three right before L and (full16: 16 rows =
+    FS_MAX_SEGMENTS) three at L / 4 and 3 L / 4.  Every row has its own flow_start; odd rows are internal (slope 0)."""
+    starts = [0.0, 0.125, 0.25]
+    if full16:
+        starts += [L / 4, L / 4 + 0.125, L / 4 + 0.25]
+    starts += [L / 2, L / 2 + 0.125, L / 2 + 0.25, L / 2 + 0.375]
+    if full16:
+        starts += [3 * L / 4, 3 * L / 4 + 0.125, 3 * L / 4 + 0.25]
+    starts += [L - 0.375, L - 0.25, L - 0.125]
+    assert len(starts) == (16 if full16 else 10)
+    return [(st, k % 2, 1000.0 + 64.0 * k, 0.0 if k % 2 else 1.0) for k, st in enumerate(starts)]
+
+
+def cursor_junction(L=64.0):
+    """A small crossing off the clusters (the FULL form needs one): lines at 5 L / 16 and 7 L / 8 - 3 (no multiple of the
+    16 m, or the 32 m, between the vehicles of these layouts apart: no two of them in the two conflict zones at once)."""
+    a, b = 5 * L / 16, 7 * L / 8 - 3
+    return dict(a_in=a, a_out=a + 1, b_in=b, b_out=b + 1, lookahead=0.0, time_gap=0.125,      # (nobody is ever held)
+                za_lo=a + 0.25, za_hi=a + 0.5, zb_lo=b + 0.25, zb_hi=b + 0.5)
+
+
+# (speed, fraction of a metre) of a replica's vehicles, which start an integer number of metres before the clusters; at
+# v = 8 a step is 1 m, at v = 4 half a metre.  With C a cluster's first start (the mid-loop one has four starts):
+#   .25 @ 8: C - .75 -> C + .25 passes 3 starts and lands on the third; L - .75 -> .25 passes the last three, wraps, passes 2
+#   .375 @ 8: -> C + .375 passes 4 mid-loop and lands on the fourth      .5 @ 8: -> C + .5 passes 4
+#   .125 @ 8 and @ 4: -> .125 wraps and passes 1                          0 @ 4: L - .5 -> 0.0 lands on L = 0
+#   .25 @ 4: C - .25 -> C + .25 passes 3; L - .25 -> .25 passes the last start, wraps, passes 2
+#   .375 @ 4: C - .125 -> C + .375 passes 4; L - .625 -> L - .125 passes 3 and lands on the last start
+CURSOR_REPLICAS = ((8.0, 0.25), (8.0, 0.375), (8.0, 0.125), (8.0, 0.5), (4.0, 0.0), (4.0, 0.25), (4.0, 0.375), (4.0, 0.125))
+CURSOR_N = 12
+
+
+def cursor_spec(full16=True, replicas=CURSOR_REPLICAS, one_rl=False, lead=8.0, **kw):
+    """12 vehicles 16 m apart all round a loop of 192 m (the rollout kernels take rows of 9 to 16), all at the replica's
+    speed, vehicle 0 `lead` m (one value, or one per replica) minus the replica's fraction before the mid-loop cluster --
+    and so vehicles 3, 6 and 9 before the clusters at 3 L / 4, L and L / 4.  RL vehicles (they keep their speed exactly)
+    but for slot 10, a noisy IDM vehicle: the one whose commands the internal rows switch off.  one_rl (the policy
+    kernels take ONE RL vehicle): slot 11 is the RL vehicle, the others are IDM vehicles."""
+    N, L = CURSOR_N, 16.0 * CURSOR_N
+    veh, n_rl = [], 0
+    for i in range(N):
+        if i == N - 2 or (one_rl and i != N - 1):
+            veh.append(waiting(noise=0.2 if i == N - 2 else 0.0))
+        else:
+            veh.append(rl_mover(n_rl))
+            n_rl += 1
+    lead = np.broadcast_to(np.asarray(lead, dtype=np.float64), (len(replicas),))
+    X = np.array([[(L / 2 - d + f + 16.0 * i) % L for i in range(N)] for d, (_, f) in zip(lead, replicas)])
+    V = np.array([[v] * N for v, _ in replicas])
+    return loop_edge_spec(L, cursor_table(L, full16), cursor_junction(L), veh, X, V, **kw)
+
+
+class LoopLog:
+    """What an oracle run reached, per sub-step (hooks RingOracle._substep and _yield_speed_cap): positions before and
+    after, the vehicles the crossing held (a finite yield speed), the collisions."""
+
+    def __init__(self, ora):
+        self.ora, self.x0, self.x1, self.v0, self.v1, self.held, self.crash = ora, [], [], [], [], [], []
+        step, cap = ora._substep, ora._yield_speed_cap
+
+        def capped(v):
+            c = cap(v)
+            self.held.append(c < ora.dt_.type(1.0e38))
+            return c
+
+        def substep(actions, active):
+            self.x0.append(ora.x.copy())
+            self.v0.append(ora.v.copy())
+            crash = step(actions, active)
+            self.x1.append(ora.x.copy())
+            self.v1.append(ora.v.copy())
+            self.crash.append(crash.copy())
+            return crash
+        ora._substep, ora._yield_speed_cap = substep, capped
+
+    def arrays(self):
+        return tuple(np.array(a) for a in (self.x0, self.x1, self.v0, self.held))     # each [K, R, N]
+
+    def cursor_events(self):
+        """{event: count [R]} over the run."""
+        x0, x1, _, _ = self.arrays()
+        starts = np.array([s[0] for s in self.ora.segments], dtype=self.ora.dt_)
+        k0 = (x0[..., None] >= starts).sum(axis=-1) - 1
+        k1 = (x1[..., None] >= starts).sum(axis=-1) - 1
+        wrapped = x1 < x0
+        last = len(starts) - 1
+        ev = dict(pass3=~wrapped & (k1 - k0 == 3), pass4=~wrapped & (k1 - k0 == 4), wrap1=wrapped & (k1 == 1),
+                  wrap2=wrapped & (k1 == 2), last_wrap=wrapped & (k0 < last),
+                  exact=(x1 != x0) & (x1[..., None] == starts).any(axis=-1), changed=(k1 != k0))
+        return {name: m.sum(axis=(0, 2)) for name, m in ev.items()}
+
+
+    def changed_rows(self):
+        """[K, R]: some vehicle of the replica is on another segment after the step."""
+        x0, x1, _, _ = self.arrays()
+        starts = np.array([s[0] for s in self.ora.segments], dtype=self.ora.dt_)
+        return ((x0[..., None] >= starts).sum(axis=-1) != (x1[..., None] >= starts).sum(axis=-1)).any(axis=2)
+
+
+CURSOR_EVENTS = ("pass3", "pass4", "wrap1", "wrap2", "last_wrap", "exact")
+POLICY_HORIZON = 3
+
+
+def policy_cursor_spec(**kw):
+    """The cursor layout for the fused policy kernels: ONE RL vehicle, episodes of 3 steps, everybody at 8 m/s.  Vehicles
+    0, 3, 6 and 9 start 3, 2 or 1 m (the replica number modulo 3) before a cluster: replicas 0, 3 and 6 pass the clusters
+    and wrap in the LAST step of every episode, so the reset that follows finds the cursor advanced; the others carry it
+    on for a step or two."""
+    reps = tuple((8.0, f) for _, f in CURSOR_REPLICAS)
+    return cursor_spec(one_rl=True, replicas=reps, lead=[3.0 - r % 3 for r in range(len(reps))], horizon=POLICY_HORIZON, **kw)
+
+
+def assert_policy_cursor_events(log, dones):
+    """dones [K, R] of the replayed fragment: episodes end on steps that change the segment, steps pass three starts and
+    more, wrap and advance -- also in steps that do not end an episode."""
+    ev, changed = log.cursor_events(), log.changed_rows()
+    ends = int((dones & changed).sum())
+    inside = int((~dones & changed).sum())
+    assert ends >= 3 and inside >= 3 and ev["pass3"].sum() + ev["pass4"].sum() >= 3 and \
+        ev["wrap1"].sum() + ev["wrap2"].sum() >= 3, (ends, inside, ev)
+
+
+def assert_cursor_events(log, names=CURSOR_EVENTS, total=3, replicas=2):
+    ev = log.cursor_events()
+    for name in names:
+        assert ev[name].sum() >= total and (ev[name] > 0).sum() >= replicas, (name, ev[name])
+    return ev
+
+
+# ---- case 2: ties at the crossing
+TIE_L = 256.0
+TIE_SEGS = [(0.0, 0, 0.0, 1.0), (128.0, 0, 128.0, 1.0)]
+TIE_J = dict(a_in=32.0, a_out=40.0, b_in=160.0, b_out=168.0, lookahead=2.0, time_gap=2.0,
+             za_lo=35.0, za_hi=42.0, zb_lo=163.0, zb_hi=170.0)
+# name -> (kind, the boundary, closed: does x == boundary count as inside, where the other vehicle stands)
+#   'approach': a waiting IDM vehicle (slot 1) ON the boundary of an approach window, the box held busy by the RL vehicle
+#               at rest in the other stream (slot 0); inside: it is held for the whole run, outside: it drives off
+#   'busy':     the RL vehicle (slot 0, 4 m/s) reaches the boundary of its stream's busy window at step `at`; a waiting IDM
+#               vehicle 1 m before the other stream's line is held while the window is occupied
+#   'zone':     the RL vehicle reaches the boundary of its conflict zone at step `at` with a parked vehicle inside the
+#               other zone: a collision inside, none outside
+TIES = {
+    "jb_in-look": ("approach", 158.0, True, 36.0), "jb_in": ("approach", 160.0, False, 36.0),
+    "ja_in-look": ("approach", 30.0, True, 164.0), "ja_in": ("approach", 32.0, False, 164.0),
+    "ja_in-tgap*v": ("busy", 24.0, True, 159.0), "ja_out+len": ("busy", 45.0, False, 159.0),
+    "jb_out+len": ("busy", 173.0, False, 31.0),
+    "za_lo": ("zone", 35.0, True, 165.0), "za_hi": ("zone", 42.0, False, 165.0),
+    "zb_lo": ("zone", 163.0, True, 37.0), "zb_hi": ("zone", 170.0, False, 37.0),
+}
+TIE_OFFSETS = (-1, 0, 1, -1, 0, 1)          # replica r stands TIE_OFFSETS[r] ulps off the boundary ...
+TIE_AT = {"approach": (0, 0, 0, 0, 0, 0), "busy": (0, 0, 0, 5, 5, 5), "zone": (1, 1, 1, 5, 5, 5),
+          "gap": (2, 2, 2, 5, 5, 5)}        # ... at this step (0: the first snapshot of a launch)
+TIE_PROP = (220.0, 220.0, 220.0, 216.5, 216.5, 216.5)     # the parked noisy vehicle (the last slot): the replicas differ in it
+TIE_PARKED = (180.0, 186.0, 192.0, 198.0, 204.0, 210.0)   # parked vehicles that fill the row (the rollout kernels take 9 to 16)
+
+
+def padded(veh, X, V, last=None, extra=TIE_PARKED):
+    """The vehicles, positions and speeds with parked vehicles at `extra` appended and then `last` = (vehicle, x [R], v)."""
+    veh = list(veh) + [parked() for _ in extra]
+    X = [list(x) + list(extra) for x in X]
+    V = [list(v) + [0.0] * len(extra) for v in V]
+    if last is not None:
+        veh.append(last[0])
+        X = [x + [xl] for x, xl in zip(X, last[1])]
+        V = [v + [last[2]] for v in V]
+    return veh, X, V
+
+
+def tie_inside(name):
+    """[R] does replica r count as inside (held / busy / colliding) at its step."""
+    closed = TIES[name][2]
+    return np.array([(o >= 0) if closed else (o < 0) for o in TIE_OFFSETS])
+
+
+def tie_spec(name, dtype=np.float32, **kw):
+    """dtype: the type the ulps are counted in (float32 kernels and their oracle twin; float64 for FS_MIXED)."""
+    kind, bound, _, other = TIES[name]
+    X, V = [], []
+    for off, at, prop in zip(TIE_OFFSETS, TIE_AT[kind], TIE_PROP):
+        edge = ulps(bound, off, dtype)
+        if kind == "approach":
+            X.append([other, edge])
+            V.append([0.0, 0.0])
+        else:
+            X.append([start_for(edge, 4.0, at, dtype), other])
+            V.append([4.0, 0.0])
+    veh, X, V = padded([rl_mover(0), parked() if kind == "zone" else waiting()], X, V, (parked(noise=0.2), TIE_PROP, 0.0))
+    return loop_edge_spec(TIE_L, TIE_SEGS, TIE_J, veh, X, V, **kw)
+
+
+def gap_tie_spec(dtype=np.float32, **kw):
+    """h == crash_gap: the RL vehicle (4 m/s) is 5.5 m behind the front of a parked vehicle of 5 m at its step: no collision
+    on the boundary or an ulp before it, one an ulp past it -- and for everyone one step later."""
+    X, V = [], []
+    for off, at, prop in zip(TIE_OFFSETS, TIE_AT["gap"], TIE_PROP):
+        X.append([start_for(ulps(94.5, off, dtype), 4.0, at, dtype), 100.0])
+        V.append([4.0, 0.0])
+    veh, X, V = padded([rl_mover(0), parked()], X, V, (parked(noise=0.2), TIE_PROP, 0.0))
+    return loop_edge_spec(TIE_L, TIE_SEGS, TIE_J, veh, X, V, **kw)
+
+
+def assert_tie(name, log, dones, K, dtype=None):
+    """The oracle's side of a tie run of K steps (dones [K, R]; the horizon is out of reach: done = collision); dtype:
+    the type the layout's ulps were counted in (the oracle's own unless given)."""
+    x0, x1, v0, held = log.arrays()
+    dtype = log.ora.dt_ if dtype is None else dtype
+    kind = TIES[name][0] if name != "gap" else "gap"
+    at = np.array(TIE_AT[kind])
+    rows = np.arange(len(at))
+    if kind == "gap":
+        assert (x1[at - 1, rows, 0] == np.array([ulps(94.5, o, dtype) for o in TIE_OFFSETS])).all()
+        np.testing.assert_array_equal(dones[at - 1, rows], np.array(TIE_OFFSETS) > 0)
+        assert dones[at, rows].all() and not dones[:at.min() - 1].any()
+        return
+    inside = tie_inside(name)
+    edge = np.array([ulps(TIES[name][1], o, dtype) for o in TIE_OFFSETS])
+    if kind == "approach":                                   # held for the whole run / gone with the first step
+        assert (x0[0, :, 1] == edge).all()
+        np.testing.assert_array_equal(held[0, :, 1], inside)
+        assert held[:, inside, 1].all() and (x1[-1, inside, 1] == edge[inside]).all()
+        assert (x1[0, ~inside, 1] > edge[~inside]).all()
+    elif kind == "busy":                                     # the snapshot of step `at` decides step `at`
+        assert (x0[at, rows, 0] == edge).all()
+        np.testing.assert_array_equal(held[at, rows, 1], inside)
+    else:                                                    # the state AFTER step `at - 1` is the one judged
+        assert (x1[at - 1, rows, 0] == edge).all()
+        np.testing.assert_array_equal(dones[at - 1, rows], inside)
+    assert K > at.max()
+
+
+# ---- case 3: both lines within one look-ahead
+def degenerate_spec(a_first=True, **kw):
+    """ja_in and jb_in 4 m apart with a look-ahead of 16 m, ONE vehicle at rest (the RL vehicle, slot 0, at 46) inside both
+    boxes: an IDM vehicle (slot 1, obey_safe_speed) drives up to the lines on both approaches at once and stops at the
+    nearer one -- stream a's (a_first) or stream b's.  The stop speed grows with the gap, so the nearer line is the one
+    that binds; the two tables are there so that each STREAM's line is that one once."""
+    near, far = (40.0, 48.0), (44.0, 52.0)
+    (a_in, a_out), (b_in, b_out) = (near, far) if a_first else (far, near)
+    J = dict(a_in=a_in, a_out=a_out, b_in=b_in, b_out=b_out, lookahead=16.0, time_gap=2.0,
+             za_lo=a_in + 5.0, za_hi=a_in + 5.5, zb_lo=b_in + 5.0, zb_hi=b_in + 5.5)
+    X = [[46.0, 20.0], [46.0, 22.5], [46.0, 18.25], [46.0, 25.0]]
+    V = [[0.0, 6.0], [0.0, 4.0], [0.0, 8.0], [0.0, 5.0]]
+    veh, X, V = padded([rl_mover(0), waiting()], X, V, (parked(noise=0.2), TIE_PROP[1:5], 0.0))
+    return loop_edge_spec(TIE_L, TIE_SEGS, J, veh, X, V, **kw)
+
+
+def degenerate_winners(log):
+    """(steps in which stream a's stop speed is the smaller of the two, steps in which stream b's is, replicas with a
+    vehicle on both approaches and both boxes blocked) -- restated from the oracle's snapshot with its own model function."""
+    from oracle import controllers as C
+    ora = log.ora
+    x0, _, v0, held = log.arrays()
+    T, J = ora.dt_.type, ora.junction
+    x, v = x0[:, :, 1], v0[:, :, 1]
+    both = held[:, :, 1] & (x >= T(J["a_in"]) - T(J["lookahead"])) & (x < T(J["a_in"])) & \
+        (x >= T(J["b_in"]) - T(J["lookahead"])) & (x < T(J["b_in"]))
+    vs = ora.veh[1]
+    stop = [C.sumo_idm_speed(v, np.zeros_like(v), T(J[line]) - x, np.ones(v.shape, bool), ora.dt, accel=vs["max_accel"],
+                             decel=vs["max_decel"], tau=vs["sumo_tau"], min_gap=vs["sumo_min_gap"],
+                             max_speed=vs["sumo_max_speed"]) for line in ("a_in", "b_in")]
+    return int((both & (stop[0] < stop[1])).sum()), int((both & (stop[1] < stop[0])).sum()), int(both.any(axis=0).sum())
+
+
+# ---- case 4: the tail of a launch and the time limit
+TAIL_K = 11
+TAIL_FIRST_CRASH = (4, 5, 6, 7, 8, 9, 10, None)      # replica r: the step of its first collision (a launch of 11 steps:
+                                                     # every slot of the second block of four, every slot of the tail)
+
+
+def tail_spec(follower=True, horizon=10 ** 6, **kw):
+    """The RL vehicle (slot 0, 4 m/s) runs into a parked one (slot 1, front at 100, 5 m long): the gap is below 0.5 m after
+    step TAIL_FIRST_CRASH[r].  follower: a noisy IDM vehicle (the last slot) follows the RL vehicle -- visible noise;
+    without it every vehicle moves exactly.  Parked vehicles fill the row."""
+    X, V = [], []
+    for r, c in enumerate(TAIL_FIRST_CRASH):
+        X.append([20.0 if c is None else 94.75 - 0.5 * (c + 1), 100.0])
+        V.append([4.0, 0.0])
+    last = (waiting(noise=0.2), [(x[0] - 30.0 - 0.25 * r) % TIE_L for r, x in enumerate(X)], 4.0) if follower else None
+    veh, X, V = padded([rl_mover(0), parked()], X, V, last, TIE_PARKED + (() if follower else (216.0,)))
+    return loop_edge_spec(TIE_L, TIE_SEGS, TIE_J, veh, X, V, horizon=horizon, **kw)
+
+
+def fragments_of(K, cycle):
+    """K cut into launches of cycle[0], cycle[1], ... steps, cyclically."""
+    out = []
+    while sum(out) < K:
+        out.append(min(cycle[len(out) % len(cycle)], K - sum(out)))
+    return out
+
+
+ODD_CYCLE = (1, 7, 3, 16, 5)           # (tests/test_queue_edges_gpu.py odd_fragments)
+SHORT_CYCLE = (2, 3, 1, 4, 6)          # launches of 1, 2 and 3 steps; starts two steps into a block of four
+
+
+def start_phases(fragments):
+    """{launch start mod 4}: where in Philox's block of four draws the launches begin."""
+    return {int(s) % 4 for s in np.cumsum([0] + list(fragments[:-1]))}
+
+
+# ---- case 5: shapes
+def shape_spec(N, R, env=None, rl_slots=None, **kw):
+    """N vehicles 16 m apart on the cursor table of a loop of max(64, 16 N) m, 8 m/s (RL vehicles keep it exactly), the
+    replicas 1/8 m apart; IDM vehicles (noisy) at slot N - 2 or wherever rl_slots leaves one."""
+    L = float(max(64, 16 * N))
+    rl_slots = [i for i in range(N) if i != N - 2] if rl_slots is None else list(rl_slots)
+    veh = [rl_mover(rl_slots.index(i)) if i in rl_slots else waiting(noise=0.2) for i in range(N)]
+    X = np.array([[(L / 2 - 8.75 + 0.125 * r + 16.0 * i) % L for i in range(N)] for r in range(R)])
+    spec = loop_edge_spec(L, cursor_table(L, True), cursor_junction(L), veh, X, np.full((R, N), 8.0), **kw)
+    if env is not None:
+        spec["env"] = env
+    return spec
+
+
+def oracle_rows(spec, acts, K, dtype=np.float32, log=True):
+    """K oracle steps -> (oracle, LoopLog, obs [K, R, D], rew [K, R], done [K, R] bool, limit [K, R] bool)."""
+    ora = S.RingOracle(spec, dtype)
+    lg = LoopLog(ora) if log else None
+    ora.reset()
+    o, r, d, lim = [], [], [], []
+    for k in range(K):
+        ok, rk, dk = ora.step(None if acts is None else acts[k])
+        o.append(ok), r.append(rk), d.append(dk.copy()), lim.append(ora.time_counter >= spec["horizon"])
+    return ora, lg, np.array(o), np.array(r), np.array(d), np.array(lim)
+
+
+def zero_actions(spec, K):
+    return np.zeros((K, spec["num_replicas"], max(spec["num_rl"], 1)), dtype=np.float32)
