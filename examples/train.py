@@ -53,7 +53,8 @@ def parse_args(args):
                              'rollout per fragment, one update per policy; without it such an experiment is refused')
     parser.add_argument('--epochs', type=int, default=4, help='device: passes over a rollout fragment per update')
     from train_vec import add_checkpoint_flags, add_model_flags, add_ppo_loss_flags
-    add_checkpoint_flags(parser)            # --checkpoint_dir --checkpoint_freq --restore --episode_stats: all off by default
+    add_checkpoint_flags(parser)            # --checkpoint_dir --checkpoint_freq --restore --episode_stats --checkpoint_env_state
+                                            # --evaluation_interval --evaluation_steps: all off by default
     add_ppo_loss_flags(parser)              # --kl_target --kl_coeff --entropy_coeff --vf_clip --sgd_minibatch_size: all off by default
     add_model_flags(parser)                 # --net_log_std: off by default
     parser.add_argument('--reference_ppo', action='store_true',
@@ -84,6 +85,12 @@ def checkpoint_settings(flags):
     """train_on_device's checkpoint and log keywords from the flags (all off by default)."""
     return dict(checkpoint_dir=flags.checkpoint_dir, checkpoint_freq=flags.checkpoint_freq, restore=flags.restore,
                 episode_stats=flags.episode_stats)
+
+
+def env_state_settings(flags):
+    """--checkpoint_env_state (both trainers) and --evaluation_interval / --evaluation_steps (train_on_device), off by default."""
+    return dict(checkpoint_env_state=flags.checkpoint_env_state, evaluation_interval=flags.evaluation_interval,
+                evaluation_steps=flags.evaluation_steps)
 
 
 def load_experiment(name):
@@ -139,7 +146,8 @@ def train_device(submodule, flags, multiagent=False):
     return train_on_device(fp, replicas=flags.replicas, fragment=flags.rollout_size, iterations=flags.num_steps,
                            shared_agents=multiagent, fuse_action_vector=flags.fuse_policy and not multiagent,
                            device_update=flags.device_update or flags.device_adam, device_adam=flags.device_adam,
-                           net_log_std=flags.net_log_std, **checkpoint_settings(flags), **ppo_loss_settings(flags))
+                           net_log_std=flags.net_log_std, **checkpoint_settings(flags), **env_state_settings(flags),
+                           **ppo_loss_settings(flags))
 
 
 def train_adversary(submodule, flags):
@@ -150,6 +158,7 @@ def train_adversary(submodule, flags):
     return train_adversarial_on_device(fp, replicas=flags.replicas, fragment=flags.rollout_size, iterations=flags.num_steps,
                                        device_update=flags.device_update or flags.device_adam,
                                        device_adam=flags.device_adam, net_log_std=flags.net_log_std,
+                                       checkpoint_env_state=flags.checkpoint_env_state,
                                        **checkpoint_settings(flags), **ppo_loss_settings(flags))
 
 

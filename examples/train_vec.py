@@ -421,21 +421,76 @@ def restore_policy(entry, pi, opt=None, kl=None, learner=None, log=print, name="
     return False
 
 
-def save_checkpoint(directory, iteration, flow_params, policies, seed=0, update_path="torch", model=None):
+def save_checkpoint(directory, iteration, flow_params, policies, seed=0, update_path="torch", model=None, env=None):
     """``directory/checkpoint_<iteration>/``: ``state.pt`` -- a ``torch.save`` of plain tensors and numbers:
     ``policies`` ({name: policy_state(...)}: one entry, 'av', or the adversarial trainer's two), ``iteration``, ``seed``,
     ``update_path`` ('torch', 'device_update' or 'device_adam') and ``model`` (how the trainer was called: shared_agents,
     fuse_action_vector, adversarial) -- and ``params.json``, the flow params through FlowParamsEncoder, as the reference
-    puts next to its checkpoints.  Returns the checkpoint's path."""
+    puts next to its checkpoints.  ``env`` (``env_state``: --checkpoint_env_state) adds the entry ``env``, the environments'
+    state; without it the file is what it was.  Returns the checkpoint's path."""
     import json
     from flow_amd.utils.rllib import FlowParamsEncoder
     path = os.path.join(str(directory), "checkpoint_%d" % int(iteration))
     os.makedirs(path, exist_ok=True)
     with open(os.path.join(path, "params.json"), "w") as f:
         json.dump(flow_params, f, cls=FlowParamsEncoder, sort_keys=True, indent=4)
-    torch.save(dict(iteration=int(iteration), seed=int(seed), update_path=str(update_path), model=dict(model or {}),
-                    policies=policies), os.path.join(path, "state.pt"))
+    state = dict(iteration=int(iteration), seed=int(seed), update_path=str(update_path), model=dict(model or {}),
+                 policies=policies)
+    if env is not None:
+        state["env"] = env
+    torch.save(state, os.path.join(path, "state.pt"))
     return path
+
+
+def env_state(vec, graph=None, torch_sampling=False, world=1):
+    """The ``env`` entry of a checkpoint (--checkpoint_env_state): ``VecFlowEnv.snapshot().state_dict()`` -- the simulator's
+    host blob, the observation, the generator that draws ring lengths and inflows, the episode-statistics carries --, the
+    rollout graph's carry where there is a graph, and torch's CUDA generator state where the graph samples from it (the
+    torch module's ``pi.act``) -- and ``handle_seed``, the Philox key of the handle: a constant of the handle, not part of its
+    state, which an experiment with ``SumoParams(seed=None)`` draws anew per process (``checkpoint_handle_seed``).  Plain
+    tensors, ints and strings: ``load_checkpoint`` reads it with ``weights_only=True``."""
+    out = dict(snapshot=vec.snapshot().state_dict(), world=int(world), handle_seed=int(vec.env._spec["seed"]))
+    if graph is not None:
+        out["carry"] = graph.carry().cpu()
+    if torch_sampling:
+        out["torch_cuda_rng"] = torch.cuda.get_rng_state(vec.device).clone()
+    return out
+
+
+def checkpoint_handle_seed(ck):
+    """The handle seed the environments of checkpoint ``ck`` ran on (None: the checkpoint holds no environment state): the
+    trainer creates its ``VecFlowEnv`` with it, so that the continued Philox streams are the interrupted run's."""
+    env = None if ck is None else ck.get("env")
+    return None if env is None or "handle_seed" not in env else int(env["handle_seed"])
+
+
+def restore_env_state(entry, vec, graph=None, torch_sampling=False, world=1, log=print):
+    """Continue the environments of a checkpoint instead of starting them from a reset: True if done.  An entry of another
+    layout (another --replicas, another experiment) or of a data-parallel run is not an error: the log names the
+    difference and the caller's reset stands."""
+    if entry is None:
+        log("restore: the checkpoint holds no environment state (written without --checkpoint_env_state): the environments "
+            "start from a reset, the sampling streams from their seeds")
+        return False
+    snap = entry["snapshot"]
+    here = int(vec.sim.snapshot_info().layout)
+    if world > 1 or int(entry.get("world", 1)) > 1:
+        log("restore: the checkpoint's environment state is one rank's shard (data-parallel runs keep rank 0's only): the "
+            "environments start from a reset")
+        return False
+    if int(snap["layout"]) != here or (graph is not None) != ("carry" in entry):
+        log("restore: the checkpoint's environment state has another layout (%s; this run: %s%s): the environments start from "
+            "a reset, the sampling streams from their seeds"
+            % (snap.get("shape", "?"), vec._shape_tag(), "" if (graph is not None) == ("carry" in entry) else "; another rollout path"))
+        return False
+    vec.load_snapshot(snap)
+    if graph is not None:
+        graph.set_carry(entry["carry"])
+    if torch_sampling and "torch_cuda_rng" in entry:
+        torch.cuda.set_rng_state(entry["torch_cuda_rng"], vec.device)
+    log("restore: the environments continue from the checkpoint's state (simulator, draw counters, observation%s)"
+        % ("; the torch-sampled graph: torch's CUDA generator state too" if torch_sampling else ""))
+    return True
 
 
 def load_checkpoint(path):
@@ -454,7 +509,19 @@ def add_checkpoint_flags(ap):
     ap.add_argument("--checkpoint_freq", type=int, default=None, help="iterations between checkpoints (with --checkpoint_dir)")
     ap.add_argument("--restore", type=str, default=None,
                     help="a checkpoint_<iteration> directory: continue at iteration + 1 with its weights, optimiser state, KL "
-                         "coefficient and epoch counter (the environments start from a reset, the sampling streams from their seeds)")
+                         "coefficient and epoch counter (the environments start from a reset, the sampling streams from their seeds, "
+                         "unless the checkpoint was written with --checkpoint_env_state: then they continue)")
+    ap.add_argument("--checkpoint_env_state", action="store_true",
+                    help="checkpoints also hold the environments' state (VecFlowEnv.snapshot: simulator, Philox counters, "
+                         "observation, the rollout graph's carry); --restore of such a checkpoint continues the environments "
+                         "instead of resetting them: where the library draws the samples, the run is the uninterrupted run's "
+                         "bit for bit")
+    ap.add_argument("--evaluation_interval", type=int, default=None,
+                    help="after every N-th update, evaluate the MEAN action for --evaluation_steps steps on the trainer's own "
+                         "handle, inside a snapshot / restore bracket (training is bit for bit what it is without); the "
+                         "iteration line gains evaluation/episode_reward_mean|min|max, evaluation/episode_len_mean, "
+                         "evaluation/episodes")
+    ap.add_argument("--evaluation_steps", type=int, default=None, help="steps per evaluation (default: the experiment's horizon)")
     ap.add_argument("--episode_stats", action="store_true",
                     help="append RLlib's episode_reward_mean / min / max, episode_len_mean and episodes (of the episodes that "
                          "ended in the iteration's fragment) to the iteration line (k_episode_stats)")
@@ -525,11 +592,72 @@ def choose_rollout(vec, pi, fragment, seed, log, shared_agents=False, fuse_actio
     return fused, graph, graph_policy
 
 
+class Evaluator(object):
+    """In-training evaluation on the trainer's own handle (train_on_device(evaluation_interval=)): ``run()`` = snapshot,
+    reset, S steps of the MEAN action, episode statistics, restore.  The greedy policy or graph is ``choose_rollout(...,
+    greedy=True)``'s, built ONCE here inside a bracket of its own (its probe and warm-up steps move the simulator, and the
+    torch generator is put back too); a DevicePolicy shares the learner's buffer under device_adam and is repacked from the
+    module otherwise.  The statistics use carries of their own, not training's.  ``graphs``: the trainer's StepGraphs -- their
+    carries live outside the environment and are left alone."""
+
+    def __init__(self, vec, pi, steps, seed, log, shared_agents=False, fuse_action_vector=False, learner=None, world=1, rank=0,
+                 graphs=()):
+        self.vec, self.S, self.world = vec, int(steps), world
+        dev, R = vec.device, vec.num_envs
+        rng, rng_host = torch.cuda.get_rng_state(dev), torch.get_rng_state()
+        self.snap = vec.snapshot()
+        self.fused, self.graph, self.graph_policy = choose_rollout(
+            vec, pi, self.S, seed, lambda m: log("evaluation: " + m), shared_agents=shared_agents,
+            fuse_action_vector=fuse_action_vector, learner=learner, world=world, rank=rank, greedy=True)
+        vec.restore(self.snap)
+        torch.cuda.set_rng_state(rng, dev)
+        torch.set_rng_state(rng_host)
+        self.ret = torch.zeros(R, dtype=torch.float64, device=dev)
+        self.len = torch.zeros(R, dtype=torch.int32, device=dev)
+        self.stats = torch.zeros(8, dtype=torch.float64, device=dev)
+        self.empty = torch.tensor([0.0, 0.0, 0.0, float("inf"), float("-inf"), 0.0, float("inf"), float("-inf")],
+                                  dtype=torch.float64, device=dev)
+
+    def run(self):
+        from flow_amd import _lib as L
+        from flow_amd.utils import episode_stats as es
+        vec, S = self.vec, self.S
+        vec.snapshot(out=self.snap)
+        obs0 = vec.reset()                                      # every replica evaluates whole episodes
+        if self.fused is not None:
+            self.fused.sync()
+            _, _, _, rew, done = vec.policy_rollout(self.fused, S, reset_done=True)
+        else:
+            if self.graph_policy is not None:
+                self.graph_policy.sync()
+            self.graph.begin(obs0)
+            _, _, rew, done = self.graph.replay()
+        vec.use_current_stream()
+        self.ret.zero_()
+        self.len.zero_()
+        self.stats.copy_(self.empty)
+        L.check(vec.sim.lib.fs_episode_stats_dev(vec.sim._h, S, rew.data_ptr(), done.data_ptr(), self.ret.data_ptr(),
+                                                 self.len.data_ptr(), self.stats.data_ptr(), 0), vec.sim.lib)
+        summary = es.summarize(es.allreduce(self.stats))
+        vec.restore(self.snap)
+        return summary
+
+    @staticmethod
+    def log_suffix(summary):
+        if not summary["episodes"]:
+            return "  evaluation/episodes 0"
+        return ("  evaluation/episode_reward_mean %.4f  evaluation/episode_reward_min %.4f  evaluation/episode_reward_max %.4f"
+                "  evaluation/episode_len_mean %.1f  evaluation/episodes %d"
+                % (summary["episode_reward_mean"], summary["episode_reward_min"], summary["episode_reward_max"],
+                   summary["episode_len_mean"], summary["episodes"]))
+
+
 def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epochs=4, lr=3e-4, seed=0, log=print,
                     rank=0, world=1, shared_agents=False, fuse_action_vector=False, device_update=False, device_adam=False,
                     kl_target=None, kl_coeff=0.2, entropy_coeff=0.0, vf_clip=None, vf_coef=0.5, clip=0.2,
                     sgd_minibatch_size=None, net_log_std=False, checkpoint_dir=None, checkpoint_freq=None, restore=None,
-                    episode_stats=False, on_episodes=None):
+                    episode_stats=False, on_episodes=None, checkpoint_env_state=False, evaluation_interval=None,
+                    evaluation_steps=None, on_evaluation=None):
     """PPO on R replicas of ``flow_params`` with everything in HBM: returns the mean step reward per iteration.
     ``world`` > 1: this process is rank ``rank`` of a data-parallel run (torch.distributed is initialised): it steps its
     block of the R replicas on its own GPU.
@@ -572,7 +700,20 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     not the uninterrupted run's bit for bit -- the update is.  ``episode_stats``: the iteration line ends with RLlib's
     ``episode_reward_mean / min / max``, ``episode_len_mean`` and ``episodes`` over the episodes that ended in the
     iteration's fragment (``VecFlowEnv.episode_stats``: one launch per fragment; the shared reward on the multi-agent
-    heads); ``on_episodes`` (a callable) then receives ``(iteration, summary dict)`` of every iteration.  All off by
+    heads); ``on_episodes`` (a callable) then receives ``(iteration, summary dict)`` of every iteration.
+    ``checkpoint_env_state``: the checkpoints also hold the environments' state (``env_state``); ``restore`` of such a
+    checkpoint continues the environments instead of resetting them (``restore_env_state``; the log says which it did).
+    Where the LIBRARY draws the samples -- the fused kernels, and the graph around a DevicePolicy (``fuse_action_vector``) --
+    iterations k + 1 .. n after a restore are then the uninterrupted run's bit for bit: weights, optimiser state, history,
+    episode statistics.  The graph around the torch module samples from torch's CUDA generator, whose state is saved and set
+    back as well (DESIGN.md 4.3 says what was shown for that path).  Single process only: a data-parallel run keeps no
+    environment state.
+    ``evaluation_interval`` N (RLlib's name) with ``evaluation_steps`` S (default: the horizon): after every N-th update the
+    environments are snapshot (``VecFlowEnv.snapshot``), reset, stepped S times with the MEAN action (``choose_rollout(...,
+    greedy=True)``'s policy or graph, built once, on the learner's weights), and restored; the episodes that ended are
+    summarised (k_episode_stats with carries of their own) into ``evaluation/episode_reward_mean|min|max``,
+    ``evaluation/episode_len_mean`` and ``evaluation/episodes`` on the iteration line, and ``on_evaluation(iteration,
+    summary)`` receives them.  Training with any N is training without it, bit for bit.  All off by
     default: the line, the history and every launch are then what they were."""
     from flow_amd.dist import allreduce_sum, shard_range
     if net_log_std and device_update and not device_adam:
@@ -585,7 +726,9 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     torch.cuda.set_device(dev)
     torch.manual_seed(seed)                                   # the same initial policy on every rank
     lo, hi = shard_range(replicas, rank, world)
-    vec = VecFlowEnv(flow_params, num_replicas=hi - lo, device=local, replica_offset=lo)
+    ck = load_checkpoint(restore) if restore is not None else None
+    vec = VecFlowEnv(flow_params, num_replicas=hi - lo, device=local, replica_offset=lo,
+                     seed=checkpoint_handle_seed(ck) if world == 1 else None)
     n_ag = vec.act_dim if shared_agents else 1
     if shared_agents and (vec.act_dim < 1 or vec.obs_dim % vec.act_dim):
         raise ValueError("shared_agents: the observation (%d) is not one block per action column (%d)" % (vec.obs_dim, vec.act_dim))
@@ -614,12 +757,21 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     kl = AdaptiveKL(kl_target, kl_coeff) if kl_target is not None and not device_adam else None
     update_path = "device_adam" if device_adam else "device_update" if device_update else "torch"
     start = 0
+    torch_sampling = fused is None and graph_policy is None      # the graph's samples come from torch's CUDA generator
+    env_continues = False
     if restore is not None:
-        ck = load_checkpoint(restore)
         restore_policy(ck["policies"]["av"], pi, opt, kl, learner, log=log if rank == 0 else (lambda *a: None), name="av")
         start = int(ck["iteration"]) + 1
         if rank == 0:
             log("restore: %s (iteration %d, written on %s): continuing at iteration %d" % (restore, ck["iteration"], ck["update_path"], start))
+        if "env" in ck or checkpoint_env_state:
+            env_continues = restore_env_state(ck.get("env"), vec, graph, torch_sampling, world,
+                                              log=log if rank == 0 else (lambda *a: None))
+    evaluator = None
+    if evaluation_interval:
+        evaluator = Evaluator(vec, pi, int(evaluation_steps or flow_params["env"].horizon), seed, log if rank == 0 else (lambda *a: None),
+                              shared_agents=shared_agents, fuse_action_vector=fuse_action_vector,
+                              learner=learner if device_adam else None, world=world, rank=rank, graphs=(graph,))
     history = []
     for it in range(start, start + iterations):
         vec.redraw_ring_lengths()                              # pending ring length per replica for its next in-graph reset
@@ -659,10 +811,16 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
         ep_log = ""
         if episode_stats:                                      # (the episodes that ended in this fragment; carries kept)
             from flow_amd.utils import episode_stats as es
-            summary = es.summarize(es.allreduce(vec.episode_stats(rew, done, reset=it == start, accumulate=False)))
+            summary = es.summarize(es.allreduce(vec.episode_stats(rew, done, reset=it == start and not env_continues,
+                                                                   accumulate=False)))
             if on_episodes is not None:
                 on_episodes(it, summary)
             ep_log = es.log_suffix(summary)
+        if evaluator is not None and (it + 1) % int(evaluation_interval) == 0:
+            ev = evaluator.run()
+            if on_evaluation is not None:
+                on_evaluation(it, ev)
+            ep_log += evaluator.log_suffix(ev)
         if rank == 0:
             log("iteration %3d  mean step reward %8.4f  rollout %.1f ms (%.2f M env-steps/s per GPU, %d GPU%s)  episodes ended %d%s%s"
                 % (it, mean_rew, t_roll * 1e3, K * R / t_roll / 1e6, world, "s" if world > 1 else "", int(tot[2]), kl_log, ep_log))
@@ -670,7 +828,8 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
                 path = save_checkpoint(checkpoint_dir, it, flow_params, dict(av=policy_state(pi, opt, kl, learner)), seed=seed,
                                        update_path=update_path,
                                        model=dict(shared_agents=bool(shared_agents), fuse_action_vector=bool(fuse_action_vector),
-                                                  adversarial=False))
+                                                  adversarial=False),
+                                       env=env_state(vec, graph, torch_sampling, world) if checkpoint_env_state else None)
                 log("checkpoint: %s" % path)
     vec.close()
     return history
@@ -691,7 +850,7 @@ def train_adversarial_on_device(flow_params, replicas=1024, fragment=100, iterat
                                 device_update=False, device_adam=False, kl_target=None, kl_coeff=0.2, entropy_coeff=0.0,
                                 vf_clip=None, vf_coef=0.5, clip=0.2, sgd_minibatch_size=None, net_log_std=False,
                                 checkpoint_dir=None, checkpoint_freq=None, restore=None, episode_stats=False,
-                                on_episodes=None):
+                                on_episodes=None, checkpoint_env_state=False):
     """PPO on TWO policies with opposite rewards (the reference's adversarial_figure_eight.py: POLICY_GRAPHS 'av' and
     'adversary', policy_mapping_fn the identity): both read AccelEnv's observation, each draws an action, the RL vehicle
     receives ``av + perturb_weight * adversary``.  One fragment is ONE launch (``VecFlowEnv.policy_pair_rollout``:
@@ -705,7 +864,9 @@ def train_adversarial_on_device(flow_params, replicas=1024, fragment=100, iterat
     The observation row is the kernel's AccelEnv order ``[v..., x...]``, where the reference's adversarial state
     interleaves ``[v_i, x_i]``: a fixed permutation of the first layer's inputs, irrelevant to training from scratch.
     ``checkpoint_dir`` / ``checkpoint_freq`` / ``restore`` / ``episode_stats`` / ``on_episodes``: ``train_on_device``'s; a checkpoint holds
-    both policies ('av' and 'adversary'), and the episode statistics are the av's (the adversary's return is the negation)."""
+    both policies ('av' and 'adversary'), and the episode statistics are the av's (the adversary's return is the negation).
+    ``checkpoint_env_state``: ``train_on_device``'s -- both policies sample in the library, so a restored run is the
+    uninterrupted run's bit for bit.  In-training evaluation is not built for two policies."""
     if net_log_std and device_update and not device_adam:
         raise NotImplementedError("train_adversarial_on_device(net_log_std=True, device_update=True): the 2A-output head is "
                                   "not built for the device update around torch's Adam (fs_ppo_grad_dev); add device_adam "
@@ -715,7 +876,8 @@ def train_adversarial_on_device(flow_params, replicas=1024, fragment=100, iterat
     from flow_amd.utils.device_ppo import DeviceLearner
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    vec = VecFlowEnv(flow_params, num_replicas=replicas, device=0)
+    ck = load_checkpoint(restore) if restore is not None else None
+    vec = VecFlowEnv(flow_params, num_replicas=replicas, device=0, seed=checkpoint_handle_seed(ck))
     if vec.act_dim != 1:
         raise ValueError("train_adversarial_on_device: two policies drive ONE action column; this environment has %d" % vec.act_dim)
 
@@ -758,12 +920,14 @@ def train_adversarial_on_device(flow_params, replicas=1024, fragment=100, iterat
     K, R = fragment, replicas
     update_path = "device_adam" if device_adam else "device_update" if device_update else "torch"
     start = 0
+    env_continues = False
     if restore is not None:
-        ck = load_checkpoint(restore)
         for sd in sides:
             restore_policy(ck["policies"][sd.name], sd.pi, sd.opt, sd.kl, sd.learner, log=log, name=sd.name)
         start = int(ck["iteration"]) + 1
         log("restore: %s (iteration %d, written on %s): continuing at iteration %d" % (restore, ck["iteration"], ck["update_path"], start))
+        if "env" in ck or checkpoint_env_state:
+            env_continues = restore_env_state(ck.get("env"), vec, log=log)
     history = []
     for it in range(start, start + iterations):
         def updater(sd):
@@ -792,7 +956,7 @@ def train_adversarial_on_device(flow_params, replicas=1024, fragment=100, iterat
         ep_log = ""
         if episode_stats:                                      # (the av's return; the adversary's is its negation)
             from flow_amd.utils import episode_stats as es
-            summary = es.summarize(vec.episode_stats(rew, done, reset=it == start, accumulate=False))
+            summary = es.summarize(vec.episode_stats(rew, done, reset=it == start and not env_continues, accumulate=False))
             if on_episodes is not None:
                 on_episodes(it, summary)
             ep_log = es.log_suffix(summary)
@@ -802,7 +966,8 @@ def train_adversarial_on_device(flow_params, replicas=1024, fragment=100, iterat
             path = save_checkpoint(checkpoint_dir, it, flow_params,
                                    {sd.name: policy_state(sd.pi, sd.opt, sd.kl, sd.learner) for sd in sides}, seed=seed,
                                    update_path=update_path,
-                                   model=dict(shared_agents=False, fuse_action_vector=False, adversarial=True))
+                                   model=dict(shared_agents=False, fuse_action_vector=False, adversarial=True),
+                                   env=env_state(vec) if checkpoint_env_state else None)
             log("checkpoint: %s" % path)
     vec.close()
     return history
@@ -888,7 +1053,9 @@ def main(argv=None):
                                kl_target=args.kl_target, kl_coeff=args.kl_coeff, entropy_coeff=args.entropy_coeff,
                                vf_clip=args.vf_clip, sgd_minibatch_size=args.sgd_minibatch_size,
                                net_log_std=args.net_log_std, checkpoint_dir=args.checkpoint_dir,
-                               checkpoint_freq=args.checkpoint_freq, restore=args.restore, episode_stats=args.episode_stats)
+                               checkpoint_freq=args.checkpoint_freq, restore=args.restore, episode_stats=args.episode_stats,
+                               checkpoint_env_state=args.checkpoint_env_state, evaluation_interval=args.evaluation_interval,
+                               evaluation_steps=args.evaluation_steps)
     finally:
         if world > 1 or force:
             import torch.distributed as dist

@@ -49,7 +49,8 @@ EXPORTS = ["fs_create", "fs_destroy", "fs_last_error", "fs_abi_version", "fs_obs
            "fs_ppo_grad_n_dev", "fs_adv_stats_dev", "fs_adv_finish_dev", "fs_adam_dev", "fs_ppo_eval_dist_dev",
            "fs_ppo_loss_workspace", "fs_ppo_grad_loss_dev", "fs_kl_adapt_dev", "fs_ppo_perm_host",
            "fs_ppo_minibatch_workspace", "fs_ppo_minibatch_dev", "fs_ppo_mb_finish_dev", "fs_policy_pair_act_dev",
-           "fs_policy_pair_rollout_dev", "fs_episode_stats_dev"]
+           "fs_policy_pair_rollout_dev", "fs_episode_stats_dev", "fs_snapshot_info", "fs_snapshot_dev", "fs_restore_dev",
+           "fs_snapshot", "fs_restore"]
 # fs_ppo_minibatch.mode / .flags
 FS_MB_STEP, FS_MB_PARTIAL = 0, 1
 FS_MB_ACCUMULATE, FS_MB_FIRST, FS_MB_LAST = 1, 2, 4
@@ -140,6 +141,11 @@ class fs_ppo_minibatch(C.Structure):
                 ("count_dev", C.c_void_p), ("weights_dev", C.c_void_p), ("m_dev", C.c_void_p), ("v_dev", C.c_void_p),
                 ("state_dev", C.c_void_p), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
                 ("eps", C.c_double)]
+
+
+class fs_snapshot_info(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("host_bytes", C.c_uint64), ("layout", C.c_uint64), ("nonce", C.c_uint64),
+                ("num_fields", C.c_int32), ("reserved", C.c_int32)]
 
 
 _libs = {}
@@ -250,6 +256,16 @@ def load(path=None):
     lib.fs_ppo_mb_finish_dev.argtypes = [h, C.c_int64, f32p, f32p, f32p, f32p, f64p, f64p, C.c_void_p, C.c_int, C.c_double,
                                          C.c_double, C.c_double, C.c_double]
     lib.fs_ppo_mb_finish_dev.restype = C.c_int
+    lib.fs_snapshot_info.argtypes = [h, C.POINTER(fs_snapshot_info)]
+    lib.fs_snapshot_info.restype = C.c_int
+    lib.fs_snapshot_dev.argtypes = [h, C.c_void_p, C.c_size_t, u8p]
+    lib.fs_snapshot_dev.restype = C.c_int
+    lib.fs_restore_dev.argtypes = [h, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, u8p]
+    lib.fs_restore_dev.restype = C.c_int
+    lib.fs_snapshot.argtypes = [h, C.c_void_p, C.c_size_t]
+    lib.fs_snapshot.restype = C.c_int
+    lib.fs_restore.argtypes = [h, C.c_void_p, C.c_size_t, C.c_uint64]
+    lib.fs_restore.restype = C.c_int
     if lib.fs_abi_version() != FS_ABI_VERSION:
         raise FatalFlowError("libflowsim.so ABI %d != binding ABI %d" % (lib.fs_abi_version(), FS_ABI_VERSION))
     _libs[path] = lib

@@ -285,7 +285,8 @@ int create_typed(const fs_config* cfg, fs_handle* out) {
         {"FLOWSIM_FORCE_GENERIC", &SimBase::force_generic}, {"FLOWSIM_NO_FASTDIV", &SimBase::no_fastdiv},
         {"FLOWSIM_NO_LOOP_KERNEL", &SimBase::no_loop_kernel}, {"FLOWSIM_NO_LOOP_FULL", &SimBase::no_loop_full},
         {"FLOWSIM_NO_RING_RL", &SimBase::no_ring_rl}, {"FLOWSIM_NO_QUEUE", &SimBase::no_queue},
-        {"FLOWSIM_NO_PAIR", &SimBase::no_pair}, {"FLOWSIM_NO_MASK_SKIP", &SimBase::no_mask_skip}};
+        {"FLOWSIM_NO_PAIR", &SimBase::no_pair}, {"FLOWSIM_NO_MASK_SKIP", &SimBase::no_mask_skip},
+        {"FLOWSIM_SNAPSHOT_COPIES", &SimBase::snap_copies}};
     for (const auto& sw : switches) {
       const char* v = std::getenv(sw.first);
       s->*sw.second = v && v[0] == '1';
@@ -839,6 +840,120 @@ int fs_ppo_mb_finish_dev(fs_handle h, int64_t num_params, float* weights_dev, fl
   S(h)->last_kernel = "k_mb_finish";
   return launch_mb_finish(S(h)->stream, int(num_params), weights_dev, grad_dev, m_dev, v_dev, state_dev, count_dev,
                           reinterpret_cast<unsigned long long*>(epoch_dev), flags, lr, beta1, beta2, eps);
+}
+
+// ---- snapshots (flowsim_snap.h): every refusal is decided from the arguments and the handle's host fields, before any HIP call
+// the sequence of copies k_snapshot replaces (FLOWSIM_SNAPSHOT_COPIES=1, unmasked): one stream-ordered copy per field
+static int snapshot_copies(SimBase* s, char* blob, bool restore) {
+  for (int k = 0; k < s->snap.n; ++k) {
+    const fs::SnapEntry& en = s->snap.e[k];
+    const size_t n = size_t(s->cfg.num_replicas) * en.row;
+    HIP_TRY(hipMemcpyAsync(restore ? en.ptr : blob + en.off, restore ? blob + en.off : en.ptr, n, hipMemcpyDeviceToDevice, s->stream));
+  }
+  return FS_OK;
+}
+
+int fs_snapshot_info(fs_handle h, struct fs_snapshot_info* out) {
+  if (!out) return fail(FS_ERR_INVALID, "fs_snapshot_info: out is NULL");
+  if (!h) return fail(FS_ERR_INVALID, "fs_snapshot_info: NULL handle");
+  const SimBase* s = S(h);
+  out->bytes = uint64_t(s->snap_bytes);
+  out->host_bytes = uint64_t(s->snap_bytes + sizeof(fs::SnapHostHeader));
+  out->layout = s->snap_layout;
+  out->nonce = s->snap_nonce;
+  out->num_fields = s->snap.n;
+  out->reserved = 0;
+  return FS_OK;
+}
+
+int fs_snapshot_dev(fs_handle h, void* dst_dev, size_t bytes, const uint8_t* mask_dev) {
+  if (!dst_dev) return fail(FS_ERR_INVALID, "fs_snapshot_dev: dst_dev is NULL");
+  if (bytes == 0) return fail(FS_ERR_INVALID, "fs_snapshot_dev: wrong bytes (0; fs_snapshot_info.bytes)");
+  if (!h) return fail(FS_ERR_INVALID, "fs_snapshot_dev: NULL handle");
+  SimBase* s = S(h);
+  if (bytes != s->snap_bytes)
+    return fail(FS_ERR_INVALID, "fs_snapshot_dev: wrong bytes (" + std::to_string(bytes) + "; fs_snapshot_info.bytes is " +
+                                    std::to_string(s->snap_bytes) + ")");
+  DeviceGuard guard(s->cfg.device);
+  s->snap_mirrors_out();
+  if (s->snap_copies && !mask_dev) return snapshot_copies(s, static_cast<char*>(dst_dev), false);
+  HIP_TRY(fs::launch_snapshot(s->stream, s->snap, false, static_cast<char*>(dst_dev), mask_dev));
+  return FS_OK;
+}
+
+int fs_restore_dev(fs_handle h, const void* src_dev, size_t bytes, uint64_t layout, uint64_t nonce, const uint8_t* mask_dev) {
+  if (!src_dev) return fail(FS_ERR_INVALID, "fs_restore_dev: src_dev is NULL");
+  if (bytes == 0) return fail(FS_ERR_INVALID, "fs_restore_dev: wrong bytes (0; fs_snapshot_info.bytes)");
+  if (!h) return fail(FS_ERR_INVALID, "fs_restore_dev: NULL handle");
+  SimBase* s = S(h);
+  if (layout != s->snap_layout)
+    return fail(FS_ERR_INVALID, "fs_restore_dev: wrong layout (the blob is of a handle with another precision, shape, network "
+                                "or environment: fs_snapshot_info.layout)");
+  if (bytes != s->snap_bytes)
+    return fail(FS_ERR_INVALID, "fs_restore_dev: wrong bytes (" + std::to_string(bytes) + "; fs_snapshot_info.bytes is " +
+                                    std::to_string(s->snap_bytes) + ")");
+  if (nonce != s->snap_nonce)
+    return fail(FS_ERR_INVALID, "fs_restore_dev: foreign nonce (a device blob goes back into the handle it was taken from; "
+                                "fs_snapshot / fs_restore carry state between handles)");
+  DeviceGuard guard(s->cfg.device);
+  s->snap_mirrors_in();
+  if (s->snap_copies && !mask_dev) return snapshot_copies(s, static_cast<char*>(const_cast<void*>(src_dev)), true);
+  HIP_TRY(fs::launch_snapshot(s->stream, s->snap, true, static_cast<char*>(const_cast<void*>(src_dev)), mask_dev));
+  return FS_OK;
+}
+
+int fs_snapshot(fs_handle h, void* host_dst, size_t bytes) {
+  if (!host_dst) return fail(FS_ERR_INVALID, "fs_snapshot: host_dst is NULL");
+  if (bytes == 0) return fail(FS_ERR_INVALID, "fs_snapshot: wrong bytes (0; fs_snapshot_info.host_bytes)");
+  if (!h) return fail(FS_ERR_INVALID, "fs_snapshot: NULL handle");
+  SimBase* s = S(h);
+  if (bytes != s->snap_bytes + sizeof(fs::SnapHostHeader))
+    return fail(FS_ERR_INVALID, "fs_snapshot: wrong bytes (" + std::to_string(bytes) + "; fs_snapshot_info.host_bytes is " +
+                                    std::to_string(s->snap_bytes + sizeof(fs::SnapHostHeader)) + ")");
+  DeviceGuard guard(s->cfg.device);
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  if (int qrc = s->check_qflag()) return qrc;
+  char* out = static_cast<char*>(host_dst);
+  std::memset(out, 0, bytes);                             // (the padding between fields too: equal states, equal blobs)
+  fs::SnapHostHeader hd{};
+  hd.magic = fs::SNAP_MAGIC;
+  hd.layout = s->snap_layout;
+  hd.dev_bytes = uint64_t(s->snap_bytes);
+  hd.after_reset = s->after_reset;
+  std::memcpy(out, &hd, sizeof(hd));
+  for (int k = 0; k < s->snap.n; ++k) {
+    const fs::SnapEntry& en = s->snap.e[k];
+    HIP_TRY(hipMemcpy(out + sizeof(hd) + en.off, en.ptr, size_t(s->cfg.num_replicas) * en.row, hipMemcpyDeviceToHost));
+  }
+  return FS_OK;
+}
+
+int fs_restore(fs_handle h, const void* host_src, size_t bytes, uint64_t layout) {
+  if (!host_src) return fail(FS_ERR_INVALID, "fs_restore: host_src is NULL");
+  if (bytes == 0) return fail(FS_ERR_INVALID, "fs_restore: wrong bytes (0; fs_snapshot_info.host_bytes)");
+  if (!h) return fail(FS_ERR_INVALID, "fs_restore: NULL handle");
+  SimBase* s = S(h);
+  if (layout != s->snap_layout)
+    return fail(FS_ERR_INVALID, "fs_restore: wrong layout (the blob is of a handle with another precision, shape, network or "
+                                "environment: fs_snapshot_info.layout)");
+  if (bytes != s->snap_bytes + sizeof(fs::SnapHostHeader))
+    return fail(FS_ERR_INVALID, "fs_restore: wrong bytes (" + std::to_string(bytes) + "; fs_snapshot_info.host_bytes is " +
+                                    std::to_string(s->snap_bytes + sizeof(fs::SnapHostHeader)) + ")");
+  const char* in = static_cast<const char*>(host_src);
+  fs::SnapHostHeader hd;
+  std::memcpy(&hd, in, sizeof(hd));
+  if (hd.magic != fs::SNAP_MAGIC || hd.layout != layout || hd.dev_bytes != uint64_t(s->snap_bytes))
+    return fail(FS_ERR_INVALID, "fs_restore: wrong layout (the blob's own header does not name this layout: not a blob of "
+                                "fs_snapshot, or of another handle shape)");
+  DeviceGuard guard(s->cfg.device);
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  for (int k = 0; k < s->snap.n; ++k) {
+    const fs::SnapEntry& en = s->snap.e[k];
+    HIP_TRY(hipMemcpy(en.ptr, in + sizeof(hd) + en.off, size_t(s->cfg.num_replicas) * en.row, hipMemcpyHostToDevice));
+  }
+  s->snap_mirrors_blob(in + sizeof(hd));
+  s->after_reset = hd.after_reset;
+  return FS_OK;
 }
 
 const char* fs_last_kernel(fs_handle h) { return h ? reinterpret_cast<SimBase*>(h)->last_kernel : ""; }

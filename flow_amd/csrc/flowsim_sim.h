@@ -28,6 +28,7 @@
 #include "flowsim_policy.h"
 #include "flowsim_wide.h"
 #include "flowsim_queue_consts.h"
+#include "flowsim_snap.h"
 
 
 namespace fsim {
@@ -100,6 +101,7 @@ struct SimBase {
   bool no_ring_rl = false;      // FLOWSIM_NO_RING_RL=1: keep the generic k_steps for IDM + RL rings (tests)
   bool no_mask_skip = false;    // FLOWSIM_NO_MASK_SKIP=1: a masked k_steps_open / k_steps_wide launch steps every wave (A/B, tests)
   bool no_queue = false;        // FLOWSIM_NO_QUEUE=1: keep k_steps_open / k_steps_wide for the open networks (tests)
+  bool snap_copies = false;     // FLOWSIM_SNAPSHOT_COPIES=1: an unmasked fs_snapshot_dev / fs_restore_dev is one hipMemcpyAsync per field (A/B)
   double* d_ep_scratch = nullptr;   // k_episode_stats: ticket and partials (flowsim_learn.h), allocated by its first launch
   double* d_adv_scratch = nullptr;  // k_adv_stats: ticket and partial sums (flowsim_learn.h), allocated by its first launch
   unsigned* d_mb_ticket = nullptr;  // k_ppo_minibatch: the ticket its workgroups draw (zero between launches), allocated by its first launch
@@ -136,6 +138,18 @@ struct SimBase {
                                  const float* obs_in, float* obs, float* act, float* logp, float* cmd, float* rew,
                                  uint8_t* done) = 0;
   uint32_t* d_pol_ctr = nullptr;   // [R] actions sampled so far per replica (the policy's draw counters)
+  // ---- snapshots (flowsim_snap.h; include/flowsim.h fs_snapshot_info): the table Sim<T>::init builds once
+  fs::SnapTable snap{};
+  size_t snap_bytes = 0;           // the device blob
+  uint64_t snap_layout = 0;        // fingerprint of everything the blob's layout depends on
+  uint64_t snap_nonce = 0;         // this handle's: fs_restore_dev takes blobs of this handle only (snap_mirrors_out says why)
+  // The host mirrors of device state (h_ring_len behind the divisor proofs, neg_speed_possible, init_vel_negative) must
+  // cover whatever a restore brings back.  fs_snapshot_dev notes them (out), fs_restore_dev widens the handle's by what
+  // was noted (in): host work only, no HIP call.  A blob of ANOTHER handle has no note here, hence the nonce; fs_restore
+  // (host blob) rebuilds the mirrors from the blob's contents instead (blob).
+  virtual void snap_mirrors_out() = 0;
+  virtual void snap_mirrors_in() = 0;
+  virtual void snap_mirrors_blob(const char* dev_part) = 0;
   virtual int get_state(int field, void* dst, size_t bytes) = 0;
   virtual int set_state(int field, const void* src, size_t bytes) = 0;
   virtual int add_vehicle(int replica, int slot, int route, double x, double speed) = 0;
@@ -385,7 +399,146 @@ struct Sim : SimBase {
     if ((rc = dev_alloc(&d_dump, size_t(256)))) return rc;
     if ((rc = launch_reset(nullptr))) return rc;
     if (open_net) HIP_TRY(hipMemsetAsync(ov.episode, 0xFF, size_t(R) * sizeof(int32_t), stream));
+    if ((rc = policy_counters())) return rc;      // (allocated here, not by the first policy launch: the table holds its address)
+    return build_snapshot_table();
+  }
+
+  // ---- snapshots: every device array a kernel or an fs_* call writes after fs_create (DESIGN.md 4.3 lists what is in,
+  // what is out and why); [R][row] each, in the blob at multiples of 16 bytes
+  int build_snapshot_table() {
+    const size_t R = size_t(dv.R), N = size_t(dv.N), t = sizeof(T), F = FS_MAX_INFLOWS;
+    snap.n = 0;
+    snap.R = dv.R;
+    size_t off = 0;
+    bool fits = true;
+    auto add = [&](unsigned tag, const void* p, size_t row) {
+      if (!p || row == 0) return;
+      if (snap.n >= fs::SNAP_MAX_FIELDS || row > 0xFFFFFFFFull) { fits = false; return; }
+      snap.e[snap.n++] = fs::SnapEntry{static_cast<char*>(const_cast<void*>(p)), (unsigned long long)off, unsigned(row), tag};
+      off = (off + R * row + 15) & ~size_t(15);
+    };
+    add(fs::SNAP_POS, dv.pos, N * t);
+    add(fs::SNAP_VEL, dv.vel, N * t);
+    add(fs::SNAP_PREV_VEL, dv.prev_vel, N * t);
+    add(fs::SNAP_ACCEL, dv.accel, N * t);
+    add(fs::SNAP_CTRL_STATE, dv.ctrl_state, N * t);
+    add(fs::SNAP_LANE, dv.lane, N * 4);
+    add(fs::SNAP_LAST_LC, dv.last_lc, N * 4);
+    add(fs::SNAP_TIME, dv.time, 4);
+    add(fs::SNAP_SORT_KEY, dv.sort_key, N * t);
+    add(fs::SNAP_NOISE_CTR, dv.noise_ctr, 4);
+    add(fs::SNAP_RING_LEN, dv.ring_len, t);
+    add(fs::SNAP_INIT_RING_LEN, dv.init_ring_len, t);
+    if (dv.st16) {                                   // FS_F16S: three planes [R,N] of halves
+      add(fs::SNAP_ST16_HI, dv.st16, N * 2);
+      add(fs::SNAP_ST16_LO, dv.st16 + R * N, N * 2);
+      add(fs::SNAP_ST16_VEL, dv.st16 + 2 * R * N, N * 2);
+    }
+    if (dv.n_pis > 0) {
+      add(fs::SNAP_PIS_HIST, dv.pis_hist, size_t(dv.n_pis) * dv.pis_H * t);
+      add(fs::SNAP_PIS_N, dv.pis_n, size_t(dv.n_pis) * 4);
+    }
+    add(fs::SNAP_INIT_POS, dv.init_pos, N * t);
+    add(fs::SNAP_INIT_VEL, dv.init_vel, N * t);
+    add(fs::SNAP_INIT_LANE, dv.init_lane, N * 4);
+    if (open_net) {
+      add(fs::SNAP_SEQ, ov.seq, N * 4);
+      add(fs::SNAP_ORIGIN, ov.origin, N * 4);
+      add(fs::SNAP_FOLL, ov.foll, N * 4);
+      add(fs::SNAP_FOLL_H, ov.foll_h, N * t);
+      add(fs::SNAP_CTL_SEQ, ov.ctl_seq, N * 4);
+      add(fs::SNAP_LEAD, ov.lead, N * 4);
+      add(fs::SNAP_HEADWAY, ov.headway, N * t);
+      add(fs::SNAP_VMAX, ov.vmax, N * t);
+      add(fs::SNAP_ARRIVED_RL, ov.arrived_rl, N * 4);
+      add(fs::SNAP_ARR_HIST, ov.arr_hist, 20 * 4);
+      add(fs::SNAP_COUNTERS, ov.counters, 8 * 4);
+      add(fs::SNAP_EMITTED, ov.emitted, F * 4);
+      add(fs::SNAP_GENERATED, ov.generated, F * 4);
+      add(fs::SNAP_FLOW_PER, ov.flow_per(dv.R), F * 8);
+      add(fs::SNAP_INIT_FLOW_PER, ov.init_flow_per(dv.R), F * 8);
+      add(fs::SNAP_EPISODE, ov.episode, 4);
+    }
+    add(fs::SNAP_POL_CTR, d_pol_ctr, 4);
+    add(fs::SNAP_OBS, d_obs, size_t(obs_dim) * 4);
+    if (!fits) return fail(FS_ERR_UNSUPPORTED, "fs_create: the snapshot table does not hold this handle's fields");
+    snap_bytes = off;
+    uint64_t h = 0xCBF29CE484222325ull;
+    for (uint64_t v : {uint64_t(FS_ABI_VERSION), uint64_t(cfg.precision), uint64_t(dv.R), uint64_t(dv.N), uint64_t(cfg.network),
+                       uint64_t(cfg.env), uint64_t(obs_dim), uint64_t(act_dim), uint64_t(snap.n)})
+      h = fs::snap_hash(h, v);
+    for (int k = 0; k < snap.n; ++k) h = fs::snap_hash(fs::snap_hash(h, snap.e[k].tag), snap.e[k].row);
+    snap_layout = h;
+    static std::mutex mu;
+    static uint64_t serial = 0;
+    {
+      std::lock_guard<std::mutex> lock(mu);
+      ++serial;
+      uint64_t z = serial * 0x9E3779B97F4A7C15ull + uint64_t(reinterpret_cast<uintptr_t>(this));     // splitmix64
+      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+      z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+      snap_nonce = (z ^ (z >> 31)) | 1ull;           // never 0
+    }
     return FS_OK;
+  }
+
+  std::vector<T> snap_ring_len;       // the distinct ring lengths (current and pending) of every snapshot taken so far
+  bool snap_out_stale = true;         // h_ring_len changed since snap_ring_len last took it in
+  bool snap_in_stale = false;         // snap_ring_len may hold a length h_ring_len lacks
+  bool snap_neg = false, snap_init_neg = false;
+  static void sorted_union(std::vector<T>& into, const std::vector<T>& more) {
+    into.insert(into.end(), more.begin(), more.end());
+    std::sort(into.begin(), into.end());
+    into.erase(std::unique(into.begin(), into.end()), into.end());
+  }
+  void ring_mirror_changed() {
+    fastdiv_state = -1;
+    ringrl_fast_state = -1;
+    snap_out_stale = true;
+    snap_in_stale = true;
+  }
+  void snap_mirrors_out() override {
+    if (snap_out_stale) {
+      sorted_union(snap_ring_len, h_ring_len);
+      snap_out_stale = false;
+    }
+    snap_neg = snap_neg || neg_speed_possible;
+    snap_init_neg = snap_init_neg || init_vel_negative;
+  }
+  void snap_mirrors_in() override {
+    if (snap_in_stale) {
+      std::vector<T> have = h_ring_len;
+      sorted_union(have, {});
+      std::vector<T> all = have;
+      sorted_union(all, snap_ring_len);
+      if (all.size() != have.size()) {             // a snapshot holds a length set_state has since replaced
+        h_ring_len = all;
+        fastdiv_state = -1;
+        ringrl_fast_state = -1;
+        snap_out_stale = true;
+      }
+      snap_in_stale = false;
+    }
+    neg_speed_possible = neg_speed_possible || snap_neg;
+    init_vel_negative = init_vel_negative || snap_init_neg;
+  }
+  // fs_restore: the device part of a host blob of this layout, whatever handle it came from
+  void snap_mirrors_blob(const char* dev_part) override {
+    const size_t R = size_t(dv.R);
+    for (int k = 0; k < snap.n; ++k) {
+      const fs::SnapEntry& en = snap.e[k];
+      const T* vals = reinterpret_cast<const T*>(dev_part + en.off);
+      const size_t count = R * en.row / sizeof(T);
+      if (en.tag == fs::SNAP_RING_LEN || en.tag == fs::SNAP_INIT_RING_LEN) {
+        sorted_union(h_ring_len, std::vector<T>(vals, vals + count));
+        ring_mirror_changed();
+      } else if (en.tag == fs::SNAP_VEL || en.tag == fs::SNAP_INIT_VEL) {
+        bool neg = false;
+        for (size_t e = 0; e < count; ++e) neg = neg || !(vals[e] >= T(-100));
+        neg_speed_possible = neg_speed_possible || neg;
+        if (en.tag == fs::SNAP_INIT_VEL) init_vel_negative = init_vel_negative || neg;
+      }
+    }
   }
 
   // ---- open networks: per-slot bookkeeping arrays, route tables, inflow table ------------------
@@ -1307,8 +1460,7 @@ struct Sim : SimBase {
     if (field == FS_FIELD_RING_LENGTH) {            // sets the pending lengths too
       HIP_TRY(hipMemcpy(const_cast<T*>(dv.init_ring_len), src, bytes, hipMemcpyHostToDevice));
       h_ring_len.assign(static_cast<const T*>(src), static_cast<const T*>(src) + count);
-      fastdiv_state = -1;
-      ringrl_fast_state = -1;
+      ring_mirror_changed();
     }
     if (field == FS_FIELD_INIT_RING_LENGTH) {
       // the host copy the divisor proofs walk holds every length a replica may be running on: the current ones and,
@@ -1317,8 +1469,7 @@ struct Sim : SimBase {
       h_ring_len.insert(h_ring_len.end(), vals, vals + count);
       std::sort(h_ring_len.begin(), h_ring_len.end());             // the distinct lengths only: the proofs walk this list
       h_ring_len.erase(std::unique(h_ring_len.begin(), h_ring_len.end()), h_ring_len.end());
-      fastdiv_state = -1;
-      ringrl_fast_state = -1;
+      ring_mirror_changed();
     }
     return FS_OK;
   }

@@ -537,6 +537,130 @@ class VecFlowEnv(object):
                                                   1 if accumulate else 0), self.sim.lib)
         return self._ep_stats
 
+    # ---- snapshots: the state of the whole vectorised environment, handed out and taken back -----------------------
+    _WARN_FLAGS = ("_warned_generic", "_warned_pending_inflow", "_warned_pending_length")
+
+    def _host_part(self):
+        host = {"rng": rng_state_to_plain(self._rng.bit_generator.state),
+                "warned": {k: int(bool(getattr(self, k, False))) for k in self._WARN_FLAGS}}
+        return host
+
+    def snapshot(self, mask=None, out=None):
+        """Everything the next step, reset or policy call of this environment depends on, as a ``VecSnapshot``: the
+        simulator's device blob (``fs_snapshot_dev``: ONE kernel launch on the current stream, no host synchronisation),
+        clones of the current observation and done flags, the episode-statistics carries, and the host part -- the state of
+        the generator that draws ring lengths and inflows at resets and the one-time warning flags.  ``mask`` [R]: only
+        those replicas' rows are written (into ``out``, a snapshot taken earlier from this environment, which is reused
+        and returned; without ``out`` the other rows are zero).  ``restore`` puts it back: a restored replica reproduces
+        its future exactly, the simulator's noise and the policy kernels' samples included."""
+        torch = self.torch
+        self.use_current_stream()
+        if mask is not None:
+            mask = self._check(mask.to(torch.uint8), (self.num_envs,), torch.uint8)
+        info = self.sim.snapshot_info()
+        if out is None:
+            out = VecSnapshot(self, torch.zeros(int(info.bytes), dtype=torch.uint8, device=self.device),
+                              torch.zeros_like(self._obs), torch.zeros_like(self._done), None, None)
+        elif out.owner is not self or out.blob is None:
+            raise ValueError("VecFlowEnv.snapshot: `out` must be a snapshot taken from this environment")
+        self.sim.snapshot_dev(out.blob, mask)
+        have_ep = getattr(self, "_ep_stats", None) is not None
+        if have_ep and out.ep is None:
+            out.ep = (torch.zeros_like(self._ep_ret), torch.zeros_like(self._ep_len), torch.zeros_like(self._ep_stats))
+        if not have_ep:
+            out.ep = None
+        if mask is None:
+            out.obs.copy_(self._obs)
+            out.done.copy_(self._done)
+            if have_ep:
+                for dst, src in zip(out.ep, (self._ep_ret, self._ep_len, self._ep_stats)):
+                    dst.copy_(src)
+        else:
+            m = mask != 0
+            out.obs.copy_(torch.where(m[:, None], self._obs, out.obs))
+            out.done.copy_(torch.where(m, self._done, out.done))
+            if have_ep:
+                out.ep[0].copy_(torch.where(m, self._ep_ret, out.ep[0]))
+                out.ep[1].copy_(torch.where(m, self._ep_len, out.ep[1]))
+                out.ep[2].copy_(self._ep_stats)
+        out.host = self._host_part()
+        return out
+
+    def restore(self, snap, mask=None):
+        """Put a ``VecSnapshot`` of THIS environment back (``fs_restore_dev``: one launch, no host synchronisation) and
+        return the observation.  ``mask`` [R]: the device rows of those replicas only -- simulator state, observation, done
+        flag, episode carries; the host generator, the accumulated episode statistics and the warning flags are left as
+        they are, since they are not per replica (so resets after a masked restore draw new lengths / inflows, not the
+        ones they drew the first time)."""
+        torch = self.torch
+        if snap.owner is not self or snap.blob is None:
+            raise ValueError("VecFlowEnv.restore: the snapshot was not taken from this environment "
+                             "(VecFlowEnv.load_snapshot takes a state_dict of any environment of equal layout)")
+        self.use_current_stream()
+        if mask is not None:
+            mask = self._check(mask.to(torch.uint8), (self.num_envs,), torch.uint8)
+        self.sim.restore_dev(snap.blob, mask)
+        self._put_tensors(snap.obs, snap.done, snap.ep, mask)
+        if mask is None:
+            self._put_host(snap.host)
+        return self._obs
+
+    def _put_tensors(self, obs, done, ep, mask):
+        torch = self.torch
+        if ep is not None and getattr(self, "_ep_stats", None) is None:
+            R = self.num_envs
+            self._ep_ret = torch.zeros(R, dtype=torch.float64, device=self.device)
+            self._ep_len = torch.zeros(R, dtype=torch.int32, device=self.device)
+            self._ep_stats = torch.zeros(8, dtype=torch.float64, device=self.device)
+            self._ep_empty = torch.tensor([0.0, 0.0, 0.0, float("inf"), float("-inf"), 0.0, float("inf"), float("-inf")],
+                                          dtype=torch.float64, device=self.device)
+        if mask is None:
+            self._obs.copy_(obs)
+            self._done.copy_(done)
+            if ep is not None:
+                self._ep_ret.copy_(ep[0])
+                self._ep_len.copy_(ep[1])
+                self._ep_stats.copy_(ep[2])
+            elif getattr(self, "_ep_stats", None) is not None:     # taken before the first episode_stats call
+                self._ep_ret.zero_()
+                self._ep_len.zero_()
+                self._ep_stats.copy_(self._ep_empty)
+            return
+        m = mask != 0
+        self._obs.copy_(torch.where(m[:, None], obs.to(self.device), self._obs))
+        self._done.copy_(torch.where(m, done.to(self.device), self._done))
+        if ep is not None:
+            self._ep_ret.copy_(torch.where(m, ep[0].to(self.device), self._ep_ret))
+            self._ep_len.copy_(torch.where(m, ep[1].to(self.device), self._ep_len))
+
+    def _put_host(self, host):
+        self._rng.bit_generator.state = rng_state_from_plain(host["rng"])
+        for k in self._WARN_FLAGS:
+            if host["warned"].get(k):
+                setattr(self, k, True)
+            elif hasattr(self, k):
+                delattr(self, k)
+
+    def load_snapshot(self, state):
+        """Take the ``VecSnapshot.state_dict()`` of ANY environment of equal layout (another process, a checkpoint):
+        ``fs_restore`` rebuilds the handle's host mirrors from the blob.  Raises ValueError naming the layout if the
+        blob is of another shape.  Synchronises the handle's stream.  Returns the observation."""
+        self.use_current_stream()
+        info = self.sim.snapshot_info()
+        if int(state["layout"]) != int(info.layout):
+            raise ValueError("VecFlowEnv.load_snapshot: wrong layout: the snapshot is of %s, this environment is %s"
+                             % (state.get("shape", "another handle"), self._shape_tag()))
+        self.sim.restore(state["blob"], layout=int(state["layout"]))
+        ep = state.get("ep")
+        dev = self.device
+        self._put_tensors(state["obs"].to(dev), state["done"].to(dev),
+                          None if ep is None else tuple(ep[k].to(dev) for k in ("ret", "len", "stats")), None)
+        self._put_host(state["host"])
+        return self._obs
+
+    def _shape_tag(self):
+        return "%s: %d replicas x %d vehicles, obs_dim %d" % (type(self.env).__name__, self.num_envs, self.sim.N, self.obs_dim)
+
     # ---- host-side inspection
     def get_state(self, field):
         return self.sim.get_state(field)
@@ -558,6 +682,54 @@ class VecFlowEnv(object):
         self.env.terminate()
 
     terminate = close
+
+
+def rng_state_to_plain(state):
+    """``np.random.Generator.bit_generator.state`` (PCG64: two 128-bit integers) as strings and small ints, so that it
+    survives ``torch.save`` -> ``torch.load(weights_only=True)``."""
+    inner = state["state"]
+    return {"bit_generator": str(state["bit_generator"]), "state": str(int(inner["state"])), "inc": str(int(inner["inc"])),
+            "has_uint32": int(state["has_uint32"]), "uinteger": int(state["uinteger"])}
+
+
+def rng_state_from_plain(plain):
+    return {"bit_generator": plain["bit_generator"], "state": {"state": int(plain["state"]), "inc": int(plain["inc"])},
+            "has_uint32": int(plain["has_uint32"]), "uinteger": int(plain["uinteger"])}
+
+
+class VecSnapshot(object):
+    """What ``VecFlowEnv.snapshot`` returns.  ``blob``: the simulator's device blob (uint8, ``fs_snapshot_dev``); ``obs`` /
+    ``done``: clones of the environment's current observation and done flags; ``ep``: the episode-statistics carries
+    ``(ret [R], len [R], stats [8])`` or None; ``host``: plain dict -- the generator's state (``rng_state_to_plain``) and
+    the warning flags.  ``state_dict()`` is the form for checkpoints: plain tensors (CPU), ints and strings only, the
+    simulator's part as the HOST blob of ``fs_snapshot``, which ``VecFlowEnv.load_snapshot`` of any environment of equal
+    layout takes.  A snapshot made by hand for a checkpoint (``host_blob``: uint8 CPU tensor, ``layout``) needs no
+    environment."""
+
+    def __init__(self, owner, blob, obs, done, ep, host, host_blob=None, layout=None, shape=""):
+        self.owner, self.blob, self.obs, self.done, self.ep, self.host = owner, blob, obs, done, ep, host
+        self.host_blob, self.layout, self.shape = host_blob, layout, shape
+
+    def state_dict(self):
+        import torch
+        host_blob, layout, shape = self.host_blob, self.layout, self.shape
+        if host_blob is None:
+            # the host ABI pair speaks of the handle's CURRENT state: put this snapshot in, take the host blob, put the
+            # current state back (three launches and one synchronisation: a checkpoint's cost, not a step's)
+            vec = self.owner
+            vec.use_current_stream()
+            now = torch.empty_like(self.blob)
+            vec.sim.snapshot_dev(now)
+            vec.sim.restore_dev(self.blob)
+            host_blob = torch.frombuffer(bytearray(vec.sim.snapshot()), dtype=torch.uint8)
+            vec.sim.restore_dev(now)
+            layout, shape = int(vec.sim.snapshot_info().layout), vec._shape_tag()
+        out = {"version": 1, "layout": int(layout), "shape": str(shape), "blob": host_blob,
+               "obs": self.obs.detach().cpu(), "done": self.done.detach().cpu(),
+               "host": {"rng": dict(self.host["rng"]), "warned": {k: int(v) for k, v in self.host["warned"].items()}}}
+        if self.ep is not None:
+            out["ep"] = {k: t.detach().cpu() for k, t in zip(("ret", "len", "stats"), self.ep)}
+        return out
 
 
 class StepGraph(object):
@@ -635,6 +807,20 @@ class StepGraph(object):
         self._after_caller()
         with self.vec.torch.cuda.stream(self.stream):
             self._carry.copy_(obs0)
+
+    def carry(self):
+        """A clone of the observation the next replay's first policy call will see (what ``begin`` set, then the last
+        observation of each replay): part of the state of a run that is to be resumed exactly."""
+        self._after_caller()
+        with self.vec.torch.cuda.stream(self.stream):
+            out = self._carry.clone()
+        self.vec.torch.cuda.current_stream(self.vec.device).wait_stream(self.stream)
+        return out
+
+    def set_carry(self, obs):
+        """``begin`` under the name that pairs with ``carry``: a restored run replays from the observation the interrupted
+        one would have used."""
+        self.begin(obs.to(self.vec.device))
 
     def replay(self):
         """One fragment: returns (obs [K+1,R,D], actions [K,R,A], rew [K,R], done [K,R]) views, valid until the next

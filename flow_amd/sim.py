@@ -327,6 +327,43 @@ class FlowSim:
         a = np.ascontiguousarray(np.broadcast_to(np.asarray(value, dtype=dt), shape))
         L.check(self.lib.fs_set_state(self._h, int(field), _ptr(a), a.nbytes), self.lib)
 
+    # ------------------------------------------------------------------ snapshots (include/flowsim.h fs_snapshot_info)
+    def snapshot_info(self):
+        """``fs_snapshot_info`` of the handle: .bytes (device blob), .host_bytes, .layout, .nonce, .num_fields."""
+        info = L.fs_snapshot_info()
+        L.check(self.lib.fs_snapshot_info(self._h, C.byref(info)), self.lib)
+        return info
+
+    def snapshot_dev(self, t, mask=None):
+        """The handle's state -> ``t`` (uint8 device tensor of ``snapshot_info().bytes``) in one launch on the handle's
+        stream, for the replicas where ``mask`` [R] uint8 is set (None: all).  No host synchronisation."""
+        L.check(self.lib.fs_snapshot_dev(self._h, _ptr(t), int(t.numel() * t.element_size()), _ptr(mask)), self.lib)
+        return t
+
+    def restore_dev(self, t, mask=None):
+        """``t`` (a blob ``snapshot_dev`` of THIS handle filled) -> the handle, for the replicas ``mask`` selects."""
+        info = self.snapshot_info()
+        L.check(self.lib.fs_restore_dev(self._h, _ptr(t), int(t.numel() * t.element_size()), info.layout, info.nonce,
+                                        _ptr(mask)), self.lib)
+
+    def snapshot(self):
+        """The host blob (``bytes``): synchronises the handle's stream.  ``restore`` of any handle of equal layout takes it."""
+        out = np.empty(int(self.snapshot_info().host_bytes), dtype=np.uint8)
+        L.check(self.lib.fs_snapshot(self._h, _ptr(out), out.nbytes), self.lib)
+        return out.tobytes()
+
+    def restore(self, blob, layout=None):
+        """A host blob (``bytes``, uint8 numpy array or CPU tensor) -> the handle; ``layout``: the blob's (default: this
+        handle's own -- the blob's header is checked against it either way)."""
+        if isinstance(blob, (bytes, bytearray, memoryview)):
+            a = np.frombuffer(blob, dtype=np.uint8)
+        elif isinstance(blob, np.ndarray):
+            a = np.ascontiguousarray(blob.view(np.uint8).reshape(-1))
+        else:
+            a = blob.detach().cpu().contiguous().view(-1).numpy()          # torch tensor
+        L.check(self.lib.fs_restore(self._h, a.ctypes.data, a.nbytes,
+                                    self.snapshot_info().layout if layout is None else int(layout)), self.lib)
+
     @property
     def last_kernel(self):
         """Family of the step kernel the last step / rollout launch chose (fs_last_kernel)."""

@@ -825,6 +825,43 @@ int fs_ppo_mb_finish_dev(fs_handle h, int64_t num_params, float* weights_dev, fl
                          double* state_dev, const double* count_dev, uint64_t* epoch_dev, int flags, double lr, double beta1,
                          double beta2, double eps);
 
+/* ---- Snapshots: a handle hands out its state and takes it back -----------------------------------------------------------
+ * The blob holds every device array a kernel or an fs_* call writes after fs_create -- vehicle state, the arrays a reset
+ * redraws (initial positions, speeds, lanes; pending ring lengths and inflow periods), the open networks' bookkeeping, the
+ * noise counters, the policy draw counters and the handle's own observation buffer -- field after field, each [R][row] as
+ * the handle holds it, every field at a multiple of 16 bytes.  A replica whose Philox streams are keyed by those counters
+ * reproduces its future exactly after a restore.  Constants uploaded once, scratch and staging buffers are not in it.
+ *   bytes       the device blob (fs_snapshot_dev / fs_restore_dev)
+ *   host_bytes  the host blob (fs_snapshot / fs_restore): a 64-byte header, then the device blob
+ *   layout      fingerprint of FS_ABI_VERSION, precision, R, N, network, env head, obs_dim, act_dim and every field's tag
+ *               and row bytes: blobs of equal layout have the same fields at the same offsets
+ *   nonce       this handle's own number (never 0) */
+struct fs_snapshot_info {             /* (a struct tag only: the function below has the name) */
+  uint64_t bytes;
+  uint64_t host_bytes;
+  uint64_t layout;
+  uint64_t nonce;
+  int32_t num_fields;
+  int32_t reserved;
+};
+int fs_snapshot_info(fs_handle h, struct fs_snapshot_info* out);
+/* handle -> dst_dev (fs_snapshot_dev) and src_dev -> handle (fs_restore_dev), all fields in ONE launch (k_snapshot) on the
+ * handle's stream, for the replicas where mask_dev [R] (uint8, device) is not zero (NULL: all; the rows of the others are
+ * left as they are, in the blob and in the handle).  No host synchronisation, no allocation: legal inside a stream capture.
+ * fs_restore_dev takes blobs of THIS handle only, named by `nonce`: the handle keeps host mirrors of device state (the
+ * list of ring lengths behind the exact-division proofs of the ring kernels, "a speed below -100 is possible") that must
+ * cover whatever a restore brings back; fs_snapshot_dev notes them on the host and fs_restore_dev widens the handle's by
+ * the notes, which a blob of another handle does not have.  Refused by name before any HIP call: a NULL buffer, wrong
+ * bytes, wrong layout, a foreign nonce. */
+int fs_snapshot_dev(fs_handle h, void* dst_dev, size_t bytes, const uint8_t* mask_dev);
+int fs_restore_dev(fs_handle h, const void* src_dev, size_t bytes, uint64_t layout, uint64_t nonce, const uint8_t* mask_dev);
+/* The synchronous host pair, for persistence: fs_snapshot synchronises the handle's stream and fills host_dst
+ * [host_bytes]; fs_restore takes a blob of ANY handle of equal layout and rebuilds the host mirrors from its contents (its
+ * ring lengths and pending ring lengths join the list the division proofs walk, its speeds are scanned for values below
+ * -100; the header carries the rest).  Equal states give equal blobs byte for byte. */
+int fs_snapshot(fs_handle h, void* host_dst, size_t bytes);
+int fs_restore(fs_handle h, const void* host_src, size_t bytes, uint64_t layout);
+
 /* Append the CURRENT state of one replica to a CSV file (header `time,id,x,speed,lane_number` when the file is new;
  * one row per vehicle, id = slot index, free slots of open networks skipped): the trajectory ("emission") dump of
  * flow/core/kernel/simulation/traci.py:95-101 (SUMO's --emission-output) for callers without the Python layer;
