@@ -38,7 +38,7 @@ def parse_args(args):
                         help='rllib: checkpoint to restore (device: --checkpoint_dir / --restore)')
     parser.add_argument('--replicas', type=int, default=1024, help='device: environment replicas in the handle')
     parser.add_argument('--fuse_policy', action='store_true',
-                        help='device: roll an action-vector policy (singleagent_merge) out through the fused policy + '
+                        help='device: roll an action-vector policy (singleagent_merge, lord_of_the_rings) out through the fused policy + '
                              'step kernel instead of the captured graph; where there is none (singleagent_bottleneck), '
                              'capture the graph around the policy kernel instead of the torch module')
     parser.add_argument('--device_update', action='store_true',
@@ -143,6 +143,13 @@ def train_device(submodule, flags, multiagent=False):
     from train_vec import train_on_device
     fp = submodule.flow_params
     fp['sim'].render = False
+    # lord_of_the_rings (MultiWaveAttenuationPOEnv on MultiRingNetwork): every ring is a row of the handle with ONE agent,
+    # so the rows are the sample streams of the shared policy -- RLlib's treatment of agents that share a policy -- and the
+    # experiment takes singleagent_ring's flags and paths (n_ag = 1).  --episode_stats then reports per RING: RLlib's
+    # policy_reward_mean/av, not its per-environment episode_reward_mean (the sum over an environment's rings)
+    from flow_amd import _lib
+    if getattr(fp['env_name'], 'FS_ENV', None) == _lib.FS_ENV_MULTI_WAVE_ATTENUATION_PO:
+        multiagent = False
     return train_on_device(fp, replicas=flags.replicas, fragment=flags.rollout_size, iterations=flags.num_steps,
                            shared_agents=multiagent, fuse_action_vector=flags.fuse_policy and not multiagent,
                            device_update=flags.device_update or flags.device_adam, device_adam=flags.device_adam,

@@ -582,7 +582,7 @@ def choose_rollout(vec, pi, fragment, seed, log, shared_agents=False, fuse_actio
         log("rollout: HIP graph of %d single steps around the torch policy (%s)%s" % (fragment, why, shared))
         if world > 1:
             torch.manual_seed(seed + 1000 * (rank + 1))       # the graph's torch.randn: another stream per rank
-        R_ = vec.num_envs
+        R_ = getattr(vec, "num_rows", vec.num_envs)
 
         def act_shared(obs):                                   # [R, agents * k] -> [R, agents]: every agent its own sample
             return pi.act(obs.view(R_ * n_ag, k_ag), explore=not greedy).view(R_, n_ag)
@@ -603,7 +603,7 @@ class Evaluator(object):
     def __init__(self, vec, pi, steps, seed, log, shared_agents=False, fuse_action_vector=False, learner=None, world=1, rank=0,
                  graphs=()):
         self.vec, self.S, self.world = vec, int(steps), world
-        dev, R = vec.device, vec.num_envs
+        dev, R = vec.device, getattr(vec, "num_rows", vec.num_envs)
         rng, rng_host = torch.cuda.get_rng_state(dev), torch.get_rng_state()
         self.snap = vec.snapshot()
         self.fused, self.graph, self.graph_policy = choose_rollout(
@@ -747,7 +747,7 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     fused, graph, graph_policy = choose_rollout(vec, pi, fragment, seed, log, shared_agents=shared_agents,
                                                 fuse_action_vector=fuse_action_vector, learner=learner if device_adam else None,
                                                 world=world, rank=rank)
-    K, R = fragment, hi - lo
+    K, R = fragment, getattr(vec, "num_rows", hi - lo)                              # (rows: hi - lo environments x num_rings)
     if device_adam:
         log("update: on the device, Adam included (k_ppo_eval, k_gae, k_adv_stats, k_adv_finish, k_ppo_grad, k_adam)")
     elif device_update:

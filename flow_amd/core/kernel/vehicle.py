@@ -19,6 +19,7 @@ class VehicleKernel(object):
         self.sim_step = sim_params.sim_step
         self.sim = None
         self.replica = 0
+        self._rows = 1                # rows of the handle that make up this environment (MultiRingNetwork: one per ring)
         self.__ids, self.__human_ids, self.__controlled_ids = [], [], []
         self.__controlled_lc_ids, self.__rl_ids = [], []
         self.__vehicles = {}
@@ -80,8 +81,10 @@ class VehicleKernel(object):
         self._order = list(order)
         self._slot = {v: i for i, v in enumerate(order)}
 
-    def attach(self, sim, replica=0):
-        self.sim, self.replica = sim, replica
+    def attach(self, sim, replica=0, rows=1):
+        """``rows`` > 1 (MultiRingNetwork): the environment is the handle's rows ``replica * rows ..``, one ring each; the
+        slot of a vehicle is its place in those rows laid end to end (ring g's vehicles: slots g N .. g N + N - 1)."""
+        self.sim, self.replica, self._rows = sim, replica, int(rows)
         self._cache = {}
         self._open = bool(getattr(sim, "open_net", False))
         if self._open:
@@ -224,12 +227,17 @@ class VehicleKernel(object):
     def _field(self, field):
         if field not in self._cache:
             a = self.sim.get_state(field)
-            self._cache[field] = a[self.replica]
+            if self._rows > 1:
+                a = a[self.replica * self._rows:(self.replica + 1) * self._rows]
+                self._cache[field] = a.reshape(-1) if a.ndim > 1 else a
+            else:
+                self._cache[field] = a[self.replica]
         return self._cache[field]
 
     def _ring_neighbour(self, i, step):
         """Slot ``step`` places ahead of slot i (closed single-lane loops keep their order)."""
-        return (i + step) % self.num_vehicles
+        n = self.num_vehicles // self._rows                       # (rows > 1: the neighbour on the vehicle's own ring)
+        return i - i % n + (i % n + step) % n
 
     def _vec(self, veh_id, fn, error=-1001):
         if isinstance(veh_id, (list, np.ndarray)):
@@ -281,7 +289,7 @@ class VehicleKernel(object):
         """Flow's absolute position: edge start of the network's table + position on the edge
         (vehicle/traci.py:1011-1017)."""
         net = self.master_kernel.network
-        if net.loop_starts is None and not self._open:
+        if net.loop_starts is None and not self._open and self._rows == 1:
             return self._vec(veh_id, lambda i: float(self._field(L.FS_FIELD_POS)[i]), 0.)
         return self._vec(veh_id, lambda i: float(net.get_x(*self._edge_pos(i))), 0.)
 
@@ -289,6 +297,10 @@ class VehicleKernel(object):
         if self._open:
             return self.master_kernel.network.open_locate(int(self._field(L.FS_FIELD_ROUTE)[i]),
                                                           float(self._field(L.FS_FIELD_POS)[i]))
+        if self._rows > 1:
+            net = self.master_kernel.network
+            return net.network.ring_locate(i // (self.num_vehicles // self._rows), float(self._field(L.FS_FIELD_POS)[i]),
+                                           net.junction_length)
         return self.master_kernel.network.locate(float(self._field(L.FS_FIELD_POS)[i]))
 
     def get_route(self, veh_id, error=None):
@@ -351,7 +363,7 @@ class VehicleKernel(object):
     def get_max_speed(self, veh_id, error=-1001):
         """maxSpeed of the SUMO car-following model of the vehicle (vehicle/traci.py get_max_speed)."""
         if not self._open:
-            return self._vec(veh_id, lambda i: float(self.sim.spec["vehicles"][i].get("sumo_max_speed", 30.0)), error)
+            return self._vec(veh_id, lambda i: float(self.sim.spec["vehicles"][i % self.sim.N].get("sumo_max_speed", 30.0)), error)
         return self._vec(veh_id, lambda i: float(self._field(L.FS_FIELD_MAX_SPEED)[i]), error)
 
     def set_max_speed(self, veh_id, max_speed):

@@ -31,6 +31,8 @@ int validate(const fs_config* c) {
     const bool fig8 = c->network == FS_NET_FIGURE_EIGHT;
     const char* why = nullptr;
     if ((c->network != FS_NET_RING && !fig8) || c->num_lanes > 1) why = "network (single-lane ring or figure eight)";
+    else if (c->env == FS_ENV_MULTI_WAVE_ATTENUATION_PO)
+      why = "env (FS_ENV_MULTI_WAVE_ATTENUATION_PO is built for FS_F32, and for FS_F64 on the generic kernel)";
     else if (c->env != FS_ENV_ACCEL && c->env != FS_ENV_WAVE_ATTENUATION_PO) why = "env (AccelEnv or WaveAttenuationPOEnv)";
     else if (c->evaluate) why = "evaluate";
     else if (c->sims_per_step != 1) why = "sims_per_step (1)";
@@ -134,7 +136,7 @@ int validate(const fs_config* c) {
       if (!(c->segments[k].start > c->segments[k - 1].start))
         return fail(FS_ERR_INVALID, "fs_create: segment starts must increase");
   }
-  if (c->env < FS_ENV_ACCEL || c->env > FS_ENV_LANE_CHANGE_ACCEL_PO) return fail(FS_ERR_INVALID, "fs_create: bad env");
+  if (c->env < FS_ENV_ACCEL || c->env > FS_ENV_MULTI_WAVE_ATTENUATION_PO) return fail(FS_ERR_INVALID, "fs_create: bad env");
   const bool lc_env = c->env == FS_ENV_LANE_CHANGE_ACCEL || c->env == FS_ENV_LANE_CHANGE_ACCEL_PO;
   if (lc_env && c->network != FS_NET_RING)
     return fail(FS_ERR_UNSUPPORTED, "fs_create: the lane-change envs are built for rings (k_steps_ml)");
@@ -144,6 +146,17 @@ int validate(const fs_config* c) {
     if (open_net || c->num_lanes > 1)
       return fail(FS_ERR_UNSUPPORTED, "fs_create: the multi-agent ring heads are built for single-lane closed loops");
     if (c->num_rl < 1) return fail(FS_ERR_INVALID, "fs_create: a multi-agent ring env needs an RL vehicle");
+    if (c->sort_vehicles || c->obs_perm) return fail(FS_ERR_INVALID, "fs_create: sort_vehicles / shuffled ids belong to AccelEnv");
+  }
+  if (c->env == FS_ENV_MULTI_WAVE_ATTENUATION_PO) {      // one ring of MultiRingNetwork per replica row, one agent per ring
+    if (c->network != FS_NET_RING)
+      return fail(FS_ERR_UNSUPPORTED, "fs_create: FS_ENV_MULTI_WAVE_ATTENUATION_PO on a segment-table loop or an open network "
+                                      "is not built (MultiRingNetwork's rings are plain rings)");
+    if (c->num_lanes > 1)
+      return fail(FS_ERR_UNSUPPORTED, "fs_create: FS_ENV_MULTI_WAVE_ATTENUATION_PO on a multi-lane ring is not built");
+    if (c->num_rl != 1)
+      return fail(FS_ERR_UNSUPPORTED, "fs_create: FS_ENV_MULTI_WAVE_ATTENUATION_PO needs num_rl = 1 (one RL vehicle per ring: "
+                                      "the reference's environment works with nothing else)");
     if (c->sort_vehicles || c->obs_perm) return fail(FS_ERR_INVALID, "fs_create: sort_vehicles / shuffled ids belong to AccelEnv");
   }
   if (c->num_lanes > 1 && c->env == FS_ENV_WAVE_ATTENUATION_PO)
@@ -260,6 +273,7 @@ int create_typed(const fs_config* cfg, fs_handle* out) {
   }
   s->obs_dim = (cfg->env == FS_ENV_WAVE_ATTENUATION_PO) ? 3
                : (cfg->env == FS_ENV_WAVE_ATTENUATION_PO_MA) ? 3 * cfg->num_rl
+               : (cfg->env == FS_ENV_MULTI_WAVE_ATTENUATION_PO) ? 3
                : (cfg->env == FS_ENV_ACCEL_PO_MA) ? 6 * cfg->num_rl
                : (cfg->env == FS_ENV_BOTTLENECK_DV) ? 4 * cfg->num_obs_cells + 1
                : (cfg->env == FS_ENV_BOTTLENECK) ? 1

@@ -94,6 +94,9 @@ struct DevView {
   unsigned seg_internal;                 // bit k: segment k is a junction-internal edge
   T seg_start[FS_MAX_SEGMENTS], seg_flow_start[FS_MAX_SEGMENTS], seg_flow_slope[FS_MAX_SEGMENTS];
   T ja_in, ja_out, jb_in, jb_out, j_lookahead, j_time_gap, za_lo, za_hi, zb_lo, zb_hi;
+  // FS_ENV_MULTI_WAVE_ATTENUATION_PO: max_cost_tab[n] = ||[target_velocity] * n||, n = 0 .. N (float64 on the host, rounded
+  // to T); NULL for every other head.  (Last: the fields above keep their kernel-argument offsets)
+  const T* max_cost_tab;
 };
 
 // FS_F16S: a position as two halves (hi = RN16(x), lo = RN16(x - hi): 22 significant bits), a speed as one
@@ -1086,7 +1089,10 @@ __global__ __launch_bounds__(64) void k_steps(DevView<T> s, int num_steps_arg, c
 
   const T dt = s.dt;
   const int env = FAST ? int(FS_ENV_ACCEL) : s.env;
-  const bool ma_wa = !FAST && env == FS_ENV_WAVE_ATTENUATION_PO_MA, ma_acc = !FAST && env == FS_ENV_ACCEL_PO_MA;
+  // (FS_ENV_MULTI_WAVE_ATTENUATION_PO, `mring`: MultiAgentWaveAttenuationPOEnv's observation with its one column, a reward
+  // of its own below)
+  const bool mring = !FAST && env == FS_ENV_MULTI_WAVE_ATTENUATION_PO;
+  const bool ma_wa = !FAST && (env == FS_ENV_WAVE_ATTENUATION_PO_MA || mring), ma_acc = !FAST && env == FS_ENV_ACCEL_PO_MA;
   const int obs_dim = (env == FS_ENV_WAVE_ATTENUATION_PO) ? 3 : (ma_wa ? 3 * s.num_rl : (ma_acc ? 6 * s.num_rl : 2 * N));
   const int sims_per_step = FAST ? 1 : s.sims_per_step;
   // the multi-agent ring heads (flow/envs/multiagent/ring/*): one block per RL vehicle at column rl_index; `xo` = Flow's
@@ -1255,7 +1261,21 @@ __global__ __launch_bounds__(64) void k_steps(DevView<T> s, int num_steps_arg, c
       // reward
       T reward;
       const bool bad = seg_any<SEG>(valid && (v < T(-100)), seg) || crashed;
-      if (env == FS_ENV_ACCEL || ma_acc) {
+      if (mring) {                               // multiagent/ring/wave_attenuation.py:101-127 (MultiWaveAttenuationPOEnv)
+        if (act == nullptr) {                    // the warm-up steps
+          reward = T(0);
+        } else {
+          // vehs_on_edge: the ring's vehicles whose front is on none of its internal edges (control_accel's arithmetic)
+          const T u = x - tfloor(x / qj) * qj;
+          const bool on = valid && !(u >= quarter);
+          const T dv = on ? v - s.target_velocity : T(0);
+          const T cost = tsqrt(seg_sum<SEG>(dv * dv));
+          const int n_on = int(seg_sum<SEG>(on ? T(1) : T(0)));           // (at most 64: exact in any order)
+          const T mc = s.max_cost_tab[n_on];
+          reward = tmax(mc - cost, T(0)) / mc;                             // no epsilon: n_on = 0 gives 0 / 0 = NaN
+          reward = seg_any<SEG>(on && (v < T(-100)), seg) ? T(0) : reward;
+        }
+      } else if (env == FS_ENV_ACCEL || ma_acc) {
         if (!FAST && s.evaluate) {
           reward = seg_sum<SEG>(valid ? v : T(0)) / T(N);                    // accel.py:111-112
         } else {                                                            // rewards.py:6-59

@@ -191,7 +191,10 @@ namespace fsim {
     } else {
       k = single(std::false_type());
     }
-    last_kernel = ma_head ? (dv.env == FS_ENV_ACCEL_PO_MA ? "k_ring_pair<AccelMA>" : "k_ring_pair<POMA>")
+    if constexpr (std::is_same<T, float>::value) {
+      if (dv.env == FS_ENV_MULTI_WAVE_ATTENUATION_PO) k = kernel(Int<4>(), std::false_type());   // one action column: never MC
+    }
+    last_kernel = dv.env == FS_ENV_MULTI_WAVE_ATTENUATION_PO ? "k_ring_pair<MultiRing>" : ma_head ? (dv.env == FS_ENV_ACCEL_PO_MA ? "k_ring_pair<AccelMA>" : "k_ring_pair<POMA>")
                           : (po ? "k_ring_pair<PO>" : "k_ring_pair<Accel>");
     const int waves = (dv.R + (64 / ROW) - 1) / (64 / ROW);
     hipLaunchKernelGGL(k, dim3((waves + 3) / 4), dim3(256), 0, stream, dv, a.num_steps, a.mask, a.actions, a.act_stride,
@@ -302,6 +305,10 @@ namespace fsim {
       if (dv.env == FS_ENV_WAVE_ATTENUATION_PO_MA) {                // MultiAgentWaveAttenuationPOEnv (float32 only)
         k = kernel(Int<2>());
         last_kernel = "k_ring_policy<POMA>";
+      }
+      if (dv.env == FS_ENV_MULTI_WAVE_ATTENUATION_PO) {             // MultiWaveAttenuationPOEnv (float32 only)
+        k = kernel(Int<4>());
+        last_kernel = "k_ring_policy<MultiRing>";
       }
     }
     const int waves = (dv.R + 3) / 4;

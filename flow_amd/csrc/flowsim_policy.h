@@ -591,6 +591,9 @@ __global__ __launch_bounds__(256) void k_policy_act_wide(PolicyView pv, int R, i
 // collision ends nothing (multiagent/base.py:188-190).  Per step the row evaluates the agents in turn (the observation of
 // agent c, the network, the draw of column 0x40000000 + c); each lane keeps the actions of its own slots' columns and of
 // its places in the reward's sum by selects.
+// HEAD 4: MultiWaveAttenuationPOEnv (float32; a row is ONE ring of MultiRingNetwork, one agent): HEAD 1 with the
+// bumper-to-bumper headway as third value, the on-edge desired-velocity reward (multi_ring_terms / multi_ring_reward,
+// flowsim_ringrl.h) and no crash; the shapes are HEAD 1's.
 // The simulator part is RingPairCore (flowsim_ringrl.h): the ONE definition of the ring step, which k_ring_pair runs too.
 template <typename T, int HEAD, bool NOISE, bool FAST>
 __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv, int num_steps, int reset_done,
@@ -600,8 +603,9 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
   constexpr int ROW = 16;
   constexpr bool MIXED = sizeof(T) == 8;
   constexpr bool MA = HEAD == 2;
-  static_assert(HEAD == 1 || HEAD == 2, "k_ring_policy: the PO heads");
-  static_assert(!(MA && MIXED), "the multi-agent head exists in float32 only");
+  constexpr bool MR = HEAD == 4;
+  static_assert(HEAD == 1 || HEAD == 2 || HEAD == 4, "k_ring_policy: the PO heads");
+  static_assert(!((MA || MR) && MIXED), "the multi-agent heads exist in float32 only");
   __shared__ PolicyLds PL;
   policy_load(pv, &PL, threadIdx.x, blockDim.x);
   RingPairCore<T, ROW, NOISE, FAST> core(s);
@@ -612,6 +616,12 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
   core.load_state(s.pos, s.vel);
   core.snapshot();
   const f2 &v = core.v, &vl = core.vl, &h = core.h, &dgap = core.dgap;                  // (the core's state, by its names)
+  MultiRingGeom mrg = {0.0f, 0.0f, 0.0f};
+  if constexpr (MR) {
+    mrg.quarter = float(s.ring_len[rr]) / 4.0f;
+    mrg.qj = mrg.quarter + float(s.jlen);
+    mrg.target = float(s.target_velocity);
+  }
 
   // WaveAttenuationPOEnv.get_state of the current snapshot (k_ring_pair's write_obs): computed by the RL vehicle's
   // lane, handed to the row through LDS (the policy's input), stored by that lane
@@ -638,7 +648,8 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
   const int src0 = (lane - k) + k_po;
   auto observe = [&](float* orow) {
     if constexpr (!MIXED && ROW == 16) {
-      observe_po(k_po, poB, poB ? dgap.y : dgap.x, orow);
+      // (MR: the third value is the bumper-to-bumper headway, k_ring_pair<MultiRing>'s write_obs)
+      observe_po(k_po, poB, MR ? (poB ? h.y : h.x) : (poB ? dgap.y : dgap.x), orow);
     } else {
       // (hand-off to the row through the LDS crossbar, ds_bpermute: one round trip and no memory, where the first version
       // wrote the three values to LDS and read them back between two wave barriers)
@@ -721,19 +732,27 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
     pctr += 1u;
     // ---- Env.step ------------------------------------------------------------------------------------------------
     core.template advance<false>(true, true, aA, aB);
-    const unsigned fany = seg_or<ROW>(core.step_flags());
-    const bool crashed = !MA && (fany & 1u) != 0u;          // (multiagent/base.py:188-190: crash = 0)
+    unsigned fl_step;
+    float mr_t0 = 0.0f, mr_t1 = 0.0f;
+    if constexpr (MR) multi_ring_terms(mrg, valid, core.x, v, fl_step, mr_t0, mr_t1);
+    else fl_step = core.step_flags();
+    const unsigned fany = seg_or<ROW>(fl_step);
+    const bool crashed = !MA && !MR && (fany & 1u) != 0u;   // (multiagent/base.py:188-190: crash = 0)
     const bool bad = (fany & 2u) != 0u || crashed;
-    const float sv = seg_sum<ROW>(valid ? v.x + v.y : 0.0f);
+    const float sv = seg_sum<ROW>(MR ? mr_t0 : (valid ? v.x + v.y : 0.0f));
     float mean_a;
-    if constexpr (MA) {                                     // k_ring_pair's terms / finish: column i summed where slot i stands
+    if constexpr (MR) {                                     // k_ring_pair<MultiRing>'s terms / finish
+      mean_a = seg_sum<ROW>(mr_t1);                         // (the number of on-edge vehicles)
+    } else if constexpr (MA) {                              // k_ring_pair's terms / finish: column i summed where slot i stands
       const float caA = tabs(core.clip(arA)), caB = tabs(core.clip(arB));
       const float sa = seg_sum<ROW>((redA ? caA : 0.0f) + (redB ? caB : 0.0f));
       mean_a = div_via_f64(sa, double(s.num_rl), 1.0 / double(s.num_rl));
     } else {
       mean_a = tabs(core.clip(a));                              // (one column: the sum is the value, / 1)
     }
-    const float reward = wave_reward(sv, N, mean_a, bad);
+    float reward;
+    if constexpr (MR) reward = multi_ring_reward(reinterpret_cast<const float*>(s.max_cost_tab), sv, mean_a, bad);
+    else reward = wave_reward(sv, N, mean_a, bad);
     const uint8_t dflag = done_flag(core.tcount >= s.step_limit, crashed);
     if (rvalid && k == 0) {
       rew[size_t(step) * R + rr] = reward;
@@ -747,6 +766,10 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
         core.load_state(s.init_pos, s.init_vel);
         core.set_length(s.init_ring_len[rr] + T(4) * s.jlen);
         core.tcount = 0;
+        if constexpr (MR) {
+          mrg.quarter = float(s.init_ring_len[rr]) / 4.0f;
+          mrg.qj = mrg.quarter + float(s.jlen);
+        }
       }
       core.snapshot();
 #pragma unroll 1

@@ -11,7 +11,9 @@
 //     SUMO's car-following model (S5/S7), like in k_steps;
 //   * the heads: HEAD 0 AccelEnv (accel.py:109-123), HEAD 1 WaveAttenuationPOEnv (wave_attenuation.py:113-139, 248-269),
 //     HEAD 2 MultiAgentWaveAttenuationPOEnv (multiagent/ring/wave_attenuation.py:128-252: the reference's
-//     examples/exp_configs/rl/multiagent/multiagent_ring.py), HEAD 3 MultiAgentAccelPOEnv (multiagent/ring/accel.py:84-227);
+//     examples/exp_configs/rl/multiagent/multiagent_ring.py), HEAD 3 MultiAgentAccelPOEnv (multiagent/ring/accel.py:84-227),
+//     HEAD 4 MultiWaveAttenuationPOEnv (multiagent/ring/wave_attenuation.py:34-140: lord_of_the_rings.py; a row is one
+//     ring of MultiRingNetwork: HEAD 2's observation with one column, a reward over the vehicles outside the junctions);
 //     the multi-agent heads (float32 only) see no crash (multiagent/base.py:188-190);
 //   * MC: several action columns in the 16-step group form (every lane reads the columns of its own slots and of its
 //     places in the reward's reduction four steps ahead, into the register the step four steps earlier has consumed);
@@ -324,6 +326,32 @@ __device__ __forceinline__ float wave_reward(float sum_v, int N, float mean_a, b
   return bad ? 0.0f : reward;
 }
 
+// MultiWaveAttenuationPOEnv's reward (multiagent/ring/wave_attenuation.py:101-127; k_steps' `mring` branch is the
+// definition), shared by k_ring_pair HEAD 4 and k_ring_policy HEAD 4.  The lane's terms after a step: `vehs_on_edge` are
+// the vehicles whose front is on none of the ring's internal edges (u = x - floor(x / qj) qj < quarter, both divisions
+// IEEE); t0 = the squared deviations of the lane's on-edge vehicles (A + B first: tree_sum's first level), t1 = how many
+// of its two are on an edge, fl bit 1 = one of THOSE speeds is below -100.
+struct MultiRingGeom {
+  float quarter, qj, target;
+};
+__device__ __forceinline__ void multi_ring_terms(const MultiRingGeom& g, bool valid, f2 x, f2 v, unsigned& fl, float& t0,
+                                                 float& t1) {
+  const float uA = x.x - tfloor(x.x / g.qj) * g.qj, uB = x.y - tfloor(x.y / g.qj) * g.qj;
+  const bool onA = valid && !(uA >= g.quarter), onB = valid && !(uB >= g.quarter);
+  const float dA = onA ? v.x - g.target : 0.0f, dB = onB ? v.y - g.target : 0.0f;
+  t0 = dA * dA + dB * dB;
+  t1 = (onA ? 1.0f : 0.0f) + (onB ? 1.0f : 0.0f);
+  fl = ((onA && v.x < -100.0f) || (onB && v.y < -100.0f)) ? 2u : 0u;
+}
+// ... and the reward from the row's sums: s0 = sum of t0 (tree order), s1 = n, the number of on-edge vehicles (0 .. N: the
+// table's range); one sqrt, one table read, one IEEE division; no epsilon, so n = 0 gives 0 / 0 = NaN as numpy does
+__device__ __forceinline__ float multi_ring_reward(const float* __restrict__ max_cost_tab, float s0, float s1, bool bad) {
+  const float cost = tsqrt(s0);
+  const float mc = max_cost_tab[int(s1)];
+  const float reward = tmax(mc - cost, 0.0f) / mc;
+  return bad ? 0.0f : reward;
+}
+
 template <typename T, int ROW, int HEAD, bool NOISE, bool FAST, bool MC = false>
 __global__ __launch_bounds__(256) void k_ring_pair(DevView<T> s, int num_steps_arg, const uint8_t* __restrict__ mask,
                                                    const float* __restrict__ actions, size_t act_stride,
@@ -332,6 +360,8 @@ __global__ __launch_bounds__(256) void k_ring_pair(DevView<T> s, int num_steps_a
   constexpr bool MIXED = sizeof(T) == 8;
   constexpr bool WA = HEAD == 1 || HEAD == 2;       // WaveAttenuationEnv's reward (the single- and the multi-agent head)
   constexpr bool MA = HEAD >= 2;                    // per-agent observation blocks, crash = 0
+  constexpr bool MR = HEAD == 4;                    // MultiWaveAttenuationPOEnv: HEAD 2's observation (one column), its own reward
+  constexpr bool TWO_SUMS = WA || MR;               // the reward reduces two per-lane terms
   static_assert(!(MA && MIXED), "the multi-agent heads exist in float32 only");
   // (FS_MIXED with noise: the float32 controller output + sigma g in float32, as in the float32 kernel; the C twin cannot
   // reproduce the hardware's log / cos, so this form is held against the float64 kernel with the same Philox streams at
@@ -359,7 +389,7 @@ __global__ __launch_bounds__(256) void k_ring_pair(DevView<T> s, int num_steps_a
   // read one step ahead so that no step waits for HBM.  One RL vehicle (the reference's ring experiments): the
   // replica's single action is one broadcast load per lane and step.
   const int num_rl = s.num_rl;
-  const bool single_rl = num_rl == 1;                                            // wave-uniform
+  const bool single_rl = MR || num_rl == 1;                                      // wave-uniform (MR: fs_create's num_rl = 1)
   const bool redA = WA && valid && iA < num_rl, redB = WA && valid && iB < num_rl;
   float ownA_n = 0.0f, ownB_n = 0.0f, redA_n = 0.0f, redB_n = 0.0f;
   auto load_actions = [&](int step) {
@@ -376,7 +406,7 @@ __global__ __launch_bounds__(256) void k_ring_pair(DevView<T> s, int num_steps_a
   if (have_act && num_steps > 0) load_actions(0);
 
   // ---- heads -------------------------------------------------------------------------------------------------
-  const int obs_dim = HEAD == 1 ? 3 : (HEAD == 2 ? 3 * num_rl : (HEAD == 3 ? 6 * num_rl : 2 * N));
+  const int obs_dim = HEAD == 1 ? 3 : ((HEAD == 2 || MR) ? 3 * num_rl : (HEAD == 3 ? 6 * num_rl : 2 * N));
   const size_t step_rows = obs_every_step ? size_t(s.R) : 0;
   float* orow = obs + size_t(rr) * obs_dim;
   float* rrow = rew + rr;
@@ -392,7 +422,7 @@ __global__ __launch_bounds__(256) void k_ring_pair(DevView<T> s, int num_steps_a
   const double Lq64 = double(Lf), rc_Lq64 = 1.0 / Lq64;
   const float len_meA = float(s.length[iA]), len_meB = float(core.lenB);
   auto write_obs = [&]() {
-    if constexpr (HEAD == 2) {
+    if constexpr (HEAD == 2 || MR) {
       // MultiAgentWaveAttenuationPOEnv.get_state (multiagent/ring/wave_attenuation.py:188-208): per RL vehicle, at column
       // rl_index, [v / 15, (v_lead - v) / 15, headway / max_length] (get_headway: bumper to bumper).  The lane's RL
       // half is selected first; a lane with two RL vehicles writes A's block in a second region
@@ -470,7 +500,17 @@ __global__ __launch_bounds__(256) void k_ring_pair(DevView<T> s, int num_steps_a
 
   // the lane's terms of the replica's reductions after a step: flags (bit 0 a gap below crash_gap, bit 1 a speed below
   // -100, rewards.py:46), first sum (PO: speeds; Accel: squared deviations), second sum (PO: |actions|)
+  MultiRingGeom mrg = {0.0f, 0.0f, 0.0f};
+  if constexpr (MR) {
+    mrg.quarter = float(s.ring_len[rr]) / 4.0f;
+    mrg.qj = mrg.quarter + float(s.jlen);
+    mrg.target = float(s.target_velocity);
+  }
   auto terms = [&](float aredA, float aredB, unsigned& fl, float& t0, float& t1) {
+    if constexpr (MR) {
+      multi_ring_terms(mrg, valid, x, v, fl, t0, t1);
+      return;
+    }
     fl = core.step_flags();
     if (WA) {
       t0 = valid ? v.x + v.y : 0.0f;
@@ -487,7 +527,10 @@ __global__ __launch_bounds__(256) void k_ring_pair(DevView<T> s, int num_steps_a
   auto finish = [&](unsigned fany, float s0, float s1, bool live, int t_after, float& reward, uint8_t& dflag) {
     const bool crashed = !MA && live && (fany & 1u) != 0u;          // (multiagent/base.py:188-190: crash = 0)
     const bool bad = (fany & 2u) != 0u || crashed;
-    if (WA) {                                           // wave_attenuation.py:113-139
+    if constexpr (MR) {                                 // multiagent/ring/wave_attenuation.py:101-127
+      reward = multi_ring_reward(reinterpret_cast<const float*>(s.max_cost_tab), s0, s1, bad);
+      reward = have_act ? reward : 0.0f;
+    } else if (WA) {                                    // wave_attenuation.py:113-139
       reward = wave_reward(s0, N, div_via_f64(s1, double(num_rl), 1.0 / double(num_rl)), bad);
       reward = have_act ? reward : 0.0f;
     } else {                                                   // rewards.desired_velocity (rewards.py:6-59)
@@ -512,7 +555,7 @@ __global__ __launch_bounds__(256) void k_ring_pair(DevView<T> s, int num_steps_a
       terms(aredA, aredB, fl, t0, t1);
       const unsigned fany = seg_or<ROW>(fl);
       write_obs();
-      const float s0 = seg_sum<ROW>(t0), s1 = WA ? seg_sum<ROW>(t1) : 0.0f;
+      const float s0 = seg_sum<ROW>(t0), s1 = TWO_SUMS ? seg_sum<ROW>(t1) : 0.0f;
       float reward;
       uint8_t dflag;
       finish(fany, s0, s1, live_replica, core.tcount, reward, dflag);
@@ -641,7 +684,7 @@ __global__ __launch_bounds__(256) void k_ring_pair(DevView<T> s, int num_steps_a
           orow += size_t(4) * step_rows * obs_dim;
         }
         const float s0 = transposed_sum<ROW, 4>(t0, lane);
-        const float s1 = WA ? transposed_sum<ROW, 4>(t1, lane) : 0.0f;
+        const float s1 = TWO_SUMS ? transposed_sum<ROW, 4>(t1, lane) : 0.0f;
         const unsigned crash_any = seg_or<ROW>(crash_bits), bad_any = seg_or<ROW>(bad_bits);
         if (k < 4) {                                           // lane k finishes step k of the block
           const unsigned fany = ((crash_any >> (3 - k)) & 1u) | (((bad_any >> (3 - k)) & 1u) << 1);

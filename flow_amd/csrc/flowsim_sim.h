@@ -383,6 +383,17 @@ struct Sim : SimBase {
       for (int i = 0; i < N; ++i) ss += cfg.target_velocity * cfg.target_velocity;
       dv.max_cost = T(std::sqrt(ss));
     }
+    dv.max_cost_tab = nullptr;
+    if (cfg.env == FS_ENV_MULTI_WAVE_ATTENUATION_PO) {
+      // the reward's vehicle count changes from step to step: np.linalg.norm([target_velocity] * n) for n = 0 .. N
+      std::vector<T> tab(size_t(N) + 1);
+      double ss = 0.0;
+      for (int n = 0; n <= N; ++n) {
+        tab[n] = T(std::sqrt(ss));
+        ss += cfg.target_velocity * cfg.target_velocity;
+      }
+      if ((rc = upload(&dv.max_cost_tab, tab))) return rc;
+    }
     dv.act_lo = T(cfg.action_low);
     dv.act_hi = T(cfg.action_high);
     dv.po_max_length = T(cfg.po_max_length);
@@ -933,7 +944,8 @@ struct Sim : SimBase {
   // k_rollout_pair (pair_ok)
   bool ring_rl_ok(const StepArgs& a) const {
     const int f = dv.flags;
-    const bool ma_head = dv.env == FS_ENV_WAVE_ATTENUATION_PO_MA || dv.env == FS_ENV_ACCEL_PO_MA;   // float32 only
+    const bool ma_head = dv.env == FS_ENV_WAVE_ATTENUATION_PO_MA || dv.env == FS_ENV_ACCEL_PO_MA ||
+                         dv.env == FS_ENV_MULTI_WAVE_ATTENUATION_PO;                                 // float32 only
     return (std::is_same<T, float>::value || mixed) && dv.nseg == 0 && !dv.junction_on && (f & fs::FLAG_IDM_SET) &&
            !any_sim && !(f & fs::FLAG_HAS_FAILSAFE) && dv.sims_per_step == 1 && dv.integrator == FS_EULER &&
            !dv.junction_mode && !dv.track_aux && !dv.sort_vehicles && dv.obs_perm == nullptr && !dv.evaluate &&
@@ -1152,7 +1164,10 @@ struct Sim : SimBase {
     else if (loop) why = policy_loop_why(pol, true, obs != nullptr && reset_done);
     else if (!f32_or_mixed) why = "precision (f32 or mixed)";
     else if (seg != 32) why = "num_vehicles (18..32: a row of 16 lanes per replica)";
-    else if (dv.env != FS_ENV_WAVE_ATTENUATION_PO || dv.num_rl != 1) why = "env (WaveAttenuationPOEnv with one RL vehicle)";
+    else if (dv.env == FS_ENV_MULTI_WAVE_ATTENUATION_PO && (!std::is_same<T, float>::value || mixed))
+      why = "precision (FS_ENV_MULTI_WAVE_ATTENUATION_PO: the policy kernels are float32 only)";
+    else if ((dv.env != FS_ENV_WAVE_ATTENUATION_PO && dv.env != FS_ENV_MULTI_WAVE_ATTENUATION_PO) || dv.num_rl != 1)
+      why = "env (WaveAttenuationPOEnv or MultiWaveAttenuationPOEnv with one RL vehicle)";
     else if (pol->obs_dim != 3) why = "fs_policy.obs_dim (3)";
     else if (dv.nseg != 0 || dv.junction_on || dv.num_lanes > 1 || !(dv.flags & fs::FLAG_IDM_SET) || any_sim ||
              (dv.flags & fs::FLAG_HAS_FAILSAFE) || dv.sims_per_step != 1 || dv.integrator != FS_EULER || dv.junction_mode ||

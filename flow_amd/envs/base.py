@@ -96,14 +96,17 @@ class Env(_Base):
             spec["env"] = L.FS_ENV_ACCEL
         self._spec = spec
         self.sim = FlowSim(spec, precision=self._precision(), device=getattr(self, "_device_index", 0))
-        self.k.vehicle.attach(self.sim, 0)
-        x0 = spec["init_pos"][0]
+        rings = int(spec.get("num_rings", 1))               # MultiRingNetwork: an environment is `rings` rows of the handle
+        self.k.vehicle.attach(self.sim, 0, rows=rings)
+        x0 = np.asarray(spec["init_pos"])[:rings].reshape(-1) if rings > 1 else spec["init_pos"][0]
         open_net = spec.get("network") in ("merge", "bottleneck")
         # closed loops: slot i of the simulator holds k.vehicle._order[i] (id order unless shuffled / re-ordered)
         for i, veh_id in enumerate(self.initial_ids if open_net else self.k.vehicle._order):
             if open_net:
                 slot = spec["init_slot"][veh_id]
                 edge, pos = self.k.network.open_locate(int(spec["init_route"][0][slot]), float(x0[slot]))
+            elif hasattr(self.network, "ring_locate"):      # slot i of the flattened rows: ring i // N
+                edge, pos = self.network.ring_locate(i // spec["num_vehicles"], float(x0[i]), self.k.network.junction_length)
             else:
                 edge, pos = self.k.network.get_edge(float(x0[i]))
             self.initial_state[veh_id] = (self.k.vehicle.get_type(veh_id), edge, 0, pos,

@@ -36,6 +36,7 @@ class MultiEnv(_MA, Env):
         self.k.update(reset=False)
         self.time_counter = int(self.sim.time_counter[0])
         self._last_obs, self._last_reward = obs[0], float(rew[0])
+        self._obs_rows, self._rew_rows = obs, rew        # (every row: an environment of several rings, MultiRingNetwork)
         self.k.simulation.crashed = False
         crash = 0                                                    # multiagent/base.py:188-190
         states = self.get_state()
@@ -63,6 +64,7 @@ class MultiEnv(_MA, Env):
         self.k.update(reset=True)
         self.time_counter = int(self.sim.time_counter[0])
         self._last_obs, self._last_reward = obs[0], 0.0
+        self._obs_rows, self._rew_rows = obs, np.zeros(len(obs))
         return self.get_state()
 
     def clip_actions(self, rl_actions=None):

@@ -5,6 +5,7 @@ import numpy as np
 from flow_amd import _lib as L
 from flow_amd.controllers import RLController
 from flow_amd.networks.figure_eight import FigureEightNetwork
+from flow_amd.networks.multi_ring import MultiRingNetwork
 from flow_amd.networks.ring import RingNetwork
 from flow_amd.utils.exceptions import FatalFlowError
 
@@ -327,6 +328,75 @@ def build_open_spec(env, num_replicas, rng=None):
     return spec
 
 
+def build_multi_ring_spec(env, num_replicas):
+    """MultiRingNetwork: the rings share only the step counter (and this fork's MultiEnv sees no crash), so ring ``g`` of
+    environment ``e`` is ROW ``e * num_rings + g`` of a handle of ``num_replicas * num_rings`` rows and ``N`` = vehicles
+    per ring; FS_FIELD_INIT_POS differs per row (the custom start positions).  The per-slot constants are shared by all
+    rows, so every ring must hold the same vehicles in the same slot order.  (``perturbation`` is ignored, as by the
+    reference's gen_custom_start_pos, whose perturbation code is commented out.)"""
+    network, net_k, veh_k = env.network, env.k.network, env.k.vehicle
+    sp, ep = env.sim_params, env.env_params
+    ap = network.net_params.additional_params
+    G, R = int(ap["num_rings"]), int(num_replicas)
+    if int(ap["lanes"]) != 1:
+        raise NotImplementedError("multi-lane MultiRingNetwork is not built in the HIP step loop yet")
+    if len(network.net_params.inflows.get()) > 0:
+        raise NotImplementedError("inflows are not built in the HIP step loop yet")
+    if network.initial_config.shuffle:
+        raise NotImplementedError("InitialConfig(shuffle=True) on MultiRingNetwork is not built")
+    total = veh_k.num_vehicles
+    if G < 1 or total % G != 0:
+        raise NotImplementedError("MultiRingNetwork: %d vehicles do not divide into %d rings" % (total, G))
+    N = total // G
+    ids = veh_k.get_ids()
+    rl_ids = env._rl_action_order()
+    slots = vehicle_slots(veh_k, rl_ids)
+
+    def constants(d):
+        return {k: (0 if (k == "rl_index" and v >= 0) else v) for k, v in d.items()}
+    ring0 = [constants(d) for d in slots[:N]]
+    for g in range(1, G):
+        if [constants(d) for d in slots[g * N:(g + 1) * N]] != ring0:
+            raise NotImplementedError("MultiRingNetwork: all rings must hold the same vehicles in the same slot order (ring "
+                                      "%d differs from ring 0; the slot constants are shared by all rows)" % g)
+    if sum(1 for d in ring0 if d["rl_index"] >= 0) != 1:
+        raise NotImplementedError("MultiWaveAttenuationPOEnv needs exactly one RL vehicle on each ring (ring 0 has %d)"
+                                  % sum(1 for d in ring0 if d["rl_index"] >= 0))
+    jl = float(net_k.junction_length)
+    pos, lanes = net_k.generate_starting_positions(network.initial_config, total)
+    X = np.zeros((G, N))
+    for n, (edge, p) in enumerate(pos):
+        ring, x = network.ring_coordinate(edge, p, jl)
+        if ring != n // N:
+            raise FatalFlowError("MultiRingNetwork: vehicle %s starts on ring %d, not on ring %d" % (ids[n], ring, n // N))
+        X[ring, n % N] = x
+    for v in rl_ids:                                       # the agent's ring is read from its id (rl_id.split('_')[1])
+        if int(v.split('_')[1]) != ids.index(v) // N:
+            raise NotImplementedError("MultiWaveAttenuationPOEnv: RL vehicle %r is not on the ring its id names" % v)
+    check_placement(X, np.array([d["length"] for d in ring0]), float(ap["length"]) + 4 * jl)
+    dt = sp.sim_step
+    ramp = getattr(sp, "slowdown_ramp", None)
+    space = env.action_space
+    return dict(
+        num_replicas=R * G, num_vehicles=N, num_rl=1, num_rings=G, num_envs=R, vehicles=ring0,
+        user_controller_source=user_controller_source(ring0),
+        ring_length=np.full(R * G, float(ap["length"])), init_pos=np.tile(X, (R, 1)), segments=None, junction=None,
+        sim_step=dt, slowdown_ramp=dt / (dt + 1e-3) if ramp is None else float(ramp),
+        integrator="ballistic" if getattr(sp, "use_ballistic", False) else "euler",
+        junction_mode=int(0 if getattr(sp, "junction_mode", None) is None else sp.junction_mode),
+        junction_length=jl, crash_gap=float(getattr(sp, "crash_gap", 0.0)), max_speed=float(net_k.max_speed()),
+        env=env.FS_ENV, target_velocity=float(ep.additional_params["target_velocity"]),
+        action_low=float(space.low[0]), action_high=float(space.high[0]),
+        clip_actions=bool(ep.clip_actions) and not getattr(env, "UNCLIPPED_ACTIONS", False), evaluate=False,
+        po_max_length=float(env._po_max_length()), horizon=ep.horizon, warmup_steps=int(ep.warmup_steps),
+        sims_per_step=int(ep.sims_per_step), seed=handle_seed(sp), noise_math=getattr(sp, "noise_math", "hw"),
+        track_aux=bool(getattr(env, "_track_aux", True)) and getattr(sp, "precision", "f32") != "mixed",
+        replica_offset=int(getattr(env, "_replica_offset", 0)) * G, num_lanes=1,
+        init_lane=np.zeros((R * G, N), dtype=np.int32), lane_change_duration=0.0, lane_change_mode=512,
+        lane_change_cooldown_steps=max(1, int(round(float(getattr(sp, "lane_change_cooldown", 5.0)) / dt))),
+        lane_change_min_gain=float(getattr(sp, "lane_change_min_gain", 10.0)), last_lc_quirk=True, sort_vehicles=False)
+
+
 def build_spec(env, num_replicas, rng=None):
     """The spec of ``env`` (a flow_amd Env under construction) replicated ``num_replicas`` times."""
     network, net_k, veh_k = env.network, env.k.network, env.k.vehicle
@@ -339,6 +409,11 @@ def build_spec(env, num_replicas, rng=None):
         return build_open_spec(env, num_replicas, rng)
     if env.FS_ENV in (L.FS_ENV_MERGE_PO, L.FS_ENV_MERGE_MA, L.FS_ENV_BOTTLENECK_DV, L.FS_ENV_BOTTLENECK):
         raise NotImplementedError("%s needs its open network (MergeNetwork / BottleneckNetwork)" % type(env).__name__)
+    if isinstance(network, MultiRingNetwork) != (env.FS_ENV == L.FS_ENV_MULTI_WAVE_ATTENUATION_PO):
+        raise NotImplementedError("MultiRingNetwork and MultiWaveAttenuationPOEnv go together (%s on %s is not built)"
+                                  % (type(env).__name__, type(network).__name__))
+    if isinstance(network, MultiRingNetwork):
+        return build_multi_ring_spec(env, num_replicas)
     if not isinstance(network, (RingNetwork, FigureEightNetwork)):
         raise NotImplementedError("network %s is not built in the HIP step loop yet" % type(network).__name__)
     num_lanes = int(network.net_params.additional_params["lanes"])

@@ -18,7 +18,11 @@ class VecFlowEnv(object):
     sim_params, network``.  ``device`` is the HIP ordinal of this process' GPU; ``replica_offset`` the global index
     of this process' first replica when a job is sharded over GPUs (noise streams follow global replica ids).
     ``track_aux=True`` keeps ``k.vehicle.get_previous_speed`` / ``get_accel`` of the wrapped env current (fields the
-    specialised rollout kernels do not write: such a handle steps on the generic kernels)."""
+    specialised rollout kernels do not write: such a handle steps on the generic kernels).
+
+    Attributes: ``num_envs`` environments; ``num_rows`` = ``num_envs * num_rings`` rows of the handle, the leading axis
+    of every observation / reward / done / action / mask tensor (``num_rings`` is 1 except on MultiRingNetwork, where row
+    ``env * num_rings + ring`` is one ring with its own agent: MultiWaveAttenuationPOEnv)."""
 
     def __init__(self, flow_params=None, num_replicas=4096, device=0, env_class=None, env_params=None,
                  sim_params=None, network=None, seed=None, replica_offset=0, track_aux=False):
@@ -55,11 +59,15 @@ class VecFlowEnv(object):
                                       "reward on the host: scalar Env only")
         self.env = env
         self.sim = env.sim
+        # MultiRingNetwork: an environment is `num_rings` rows of the handle (row = env * num_rings + ring), and every
+        # tensor leads with ROWS; everything else has one row per environment
+        self.num_rings = int(env._spec.get("num_rings", 1))
+        self.num_rows = self.num_envs * self.num_rings
         self.k = env.k
         self.observation_space = env.observation_space
         self.action_space = env.action_space
         self.obs_dim, self.num_rl, self.act_dim = self.sim.obs_dim, self.sim.num_rl, self.sim.act_dim
-        R = self.num_envs
+        R = self.num_rows
         self._obs = torch.empty((R, self.obs_dim), dtype=torch.float32, device=self.device)
         self._rew = torch.empty((R,), dtype=torch.float32, device=self.device)
         self._done = torch.zeros((R,), dtype=torch.uint8, device=self.device)
@@ -146,7 +154,7 @@ class VecFlowEnv(object):
             return
         lengths = self.sim.get_state(L.FS_FIELD_INIT_RING_LENGTH).astype(np.float64)
         init = self.sim.get_state(L.FS_FIELD_INIT_POS).astype(np.float64)
-        self._draw_placements(np.arange(self.num_envs), lengths, init)
+        self._draw_placements(np.arange(self.num_rows), lengths, init)
         self.sim.set_state(L.FS_FIELD_INIT_RING_LENGTH, lengths)
         self.sim.set_state(L.FS_FIELD_INIT_POS, init)
 
@@ -168,7 +176,7 @@ class VecFlowEnv(object):
         from flow_amd.envs.spec import inflow_periods
         base = self._base_inflow_rates()
         rates = np.asarray(vehs_per_hour, dtype=np.float64)
-        R, nf = self.num_envs, len(base)
+        R, nf = self.num_rows, len(base)
         if rates.shape == (R,):
             per = inflow_periods(rates, base)
         elif rates.shape == (R, nf):
@@ -219,7 +227,7 @@ class VecFlowEnv(object):
         import numpy as np
         if not self._reset_inflow:
             return
-        self._resample_inflow_rates(np.ones(self.num_envs, bool))
+        self._resample_inflow_rates(np.ones(self.num_rows, bool))
 
     def reset(self, mask=None):
         """Reset all replicas (or those where ``mask`` [R] uint8/bool tensor is set); returns obs [R, obs_dim].
@@ -227,10 +235,10 @@ class VecFlowEnv(object):
         first (_resample_inflow_rates; its docstring states how this differs from the reference's rebuilt network)."""
         self.use_current_stream()
         if mask is not None:
-            mask = self._check(mask.to(self.torch.uint8), (self.num_envs,), self.torch.uint8)
+            mask = self._check(mask.to(self.torch.uint8), (self.num_rows,), self.torch.uint8)
         if self._resample or self._reset_inflow:
             import numpy as np
-            mask_host = np.ones(self.num_envs, bool) if mask is None else mask.cpu().numpy() != 0
+            mask_host = np.ones(self.num_rows, bool) if mask is None else mask.cpu().numpy() != 0
             if self._resample:
                 self._resample_ring_lengths(mask_host)
             if self._reset_inflow:
@@ -293,7 +301,7 @@ class VecFlowEnv(object):
         return why
 
     def _warn_if_generic(self):
-        if getattr(self, "_warned_generic", False) or self.num_envs < 1024:
+        if getattr(self, "_warned_generic", False) or self.num_rows < 1024:
             return
         if self.sim.last_kernel in self.GENERIC_KERNELS:
             import warnings
@@ -301,13 +309,13 @@ class VecFlowEnv(object):
             why = self.why_generic()
             warnings.warn("VecFlowEnv: %d replicas step on the generic kernel %s (several times slower than the rollout "
                           "kernels of this network) because of: %s" %
-                          (self.num_envs, self.sim.last_kernel, "; ".join(why) if why else "this configuration"),
+                          (self.num_rows, self.sim.last_kernel, "; ".join(why) if why else "this configuration"),
                           stacklevel=3)
 
     def step(self, actions=None):
         """One Env.step of every replica.  ``actions``: float32 [R, action_dim] device tensor or None."""
         self.use_current_stream()
-        a = self._check(actions, (self.num_envs, self.act_dim), self.torch.float32) if self.act_dim else None
+        a = self._check(actions, (self.num_rows, self.act_dim), self.torch.float32) if self.act_dim else None
         self.sim.step_dev(self._obs, self._rew, self._done, a)
         self._warn_if_generic()
         return self._obs, self._rew, self._done
@@ -316,7 +324,7 @@ class VecFlowEnv(object):
         """``num_steps`` consecutive steps in one launch.  ``actions``: None, [R, num_rl] (held) or
         [K, R, num_rl] (one per step).  Returns (obs, rew, done) with a leading K axis when
         ``obs_every_step``."""
-        torch, R, K = self.torch, self.num_envs, int(num_steps)
+        torch, R, K = self.torch, self.num_rows, int(num_steps)
         self.use_current_stream()
         if out is None:
             lead = (K,) if obs_every_step else ()
@@ -379,7 +387,7 @@ class VecFlowEnv(object):
         on the action-vector heads (MergePOEnv, BottleneckDesiredVelocityEnv: ``A = sim.policy_action_dim`` columns,
         one joint log-probability), ``(act [R, n], logp [R, n])`` for ``n = sim.policy_agents`` agents sharing the
         policy.  Every call advances the replicas' draw counters by one."""
-        torch, R = self.torch, self.num_envs
+        torch, R = self.torch, self.num_rows
         self.use_current_stream()
         A, n_ag = self.sim.policy_action_dim, self.sim.policy_agents
         if policy.act_dim != A:
@@ -415,7 +423,7 @@ class VecFlowEnv(object):
         ``[K, R, num_rl]`` -- every column sampled every step, the environment ignores those beyond its list of controlled
         vehicles -- and ``logp [K, R]`` the joint log-probability; with ``reset_done`` a replica is reset when its
         ``done`` byte is not zero, collisions included.  ``capture`` serves every other environment / model."""
-        torch, R, K = self.torch, self.num_envs, int(num_steps)
+        torch, R, K = self.torch, self.num_rows, int(num_steps)
         self.use_current_stream()
         if reset_done and self._resample and not getattr(self, "_warned_pending_length", False):
             import warnings
@@ -459,7 +467,7 @@ class VecFlowEnv(object):
         receives, ``cmd = av + weight * adversary`` (one float32 fma) -- what ``step(cmd.unsqueeze(-1))`` takes.
         ``weight=None`` reads ``env_params.additional_params['perturb_weight']``.  Every call advances the replicas' draw
         counters by one."""
-        torch, R = self.torch, self.num_envs
+        torch, R = self.torch, self.num_rows
         self.use_current_stream()
         weight = self._pair_weight("policy_pair_act", av, adversary, weight)
         obs = self._obs if obs is None else self._check(obs, (R, self.obs_dim), torch.float32)
@@ -483,7 +491,7 @@ class VecFlowEnv(object):
         (AdversarialAccelEnv); any other handle raises NotImplementedError naming fs_policy_pair.  The observation row is
         the kernel's AccelEnv order ``[v..., x...]``; the reference's adversarial state interleaves ``[v_i, x_i]`` -- a
         fixed permutation of the first layer's inputs."""
-        torch, R, K = self.torch, self.num_envs, int(num_steps)
+        torch, R, K = self.torch, self.num_rows, int(num_steps)
         self.use_current_stream()
         weight = self._pair_weight("policy_pair_rollout", av, adversary, weight)
         if out is None:
@@ -516,7 +524,7 @@ class VecFlowEnv(object):
         On the shared-reward multi-agent heads ``rew`` is the reward every agent shares: the return is that of the shared
         reward, one episode per replica.  In the two-policy experiment ``rew`` is the av's; the adversary's return is the
         negation (its mean is ``-mean``, its min ``-max``, its max ``-min``)."""
-        torch, R = self.torch, self.num_envs
+        torch, R = self.torch, self.num_rows
         K = int(rew.shape[0])
         self._check(rew, (K, R), torch.float32)
         self._check(done, (K, R), torch.uint8)
@@ -556,7 +564,7 @@ class VecFlowEnv(object):
         torch = self.torch
         self.use_current_stream()
         if mask is not None:
-            mask = self._check(mask.to(torch.uint8), (self.num_envs,), torch.uint8)
+            mask = self._check(mask.to(torch.uint8), (self.num_rows,), torch.uint8)
         info = self.sim.snapshot_info()
         if out is None:
             out = VecSnapshot(self, torch.zeros(int(info.bytes), dtype=torch.uint8, device=self.device),
@@ -598,7 +606,7 @@ class VecFlowEnv(object):
                              "(VecFlowEnv.load_snapshot takes a state_dict of any environment of equal layout)")
         self.use_current_stream()
         if mask is not None:
-            mask = self._check(mask.to(torch.uint8), (self.num_envs,), torch.uint8)
+            mask = self._check(mask.to(torch.uint8), (self.num_rows,), torch.uint8)
         self.sim.restore_dev(snap.blob, mask)
         self._put_tensors(snap.obs, snap.done, snap.ep, mask)
         if mask is None:
@@ -608,7 +616,7 @@ class VecFlowEnv(object):
     def _put_tensors(self, obs, done, ep, mask):
         torch = self.torch
         if ep is not None and getattr(self, "_ep_stats", None) is None:
-            R = self.num_envs
+            R = self.num_rows
             self._ep_ret = torch.zeros(R, dtype=torch.float64, device=self.device)
             self._ep_len = torch.zeros(R, dtype=torch.int32, device=self.device)
             self._ep_stats = torch.zeros(8, dtype=torch.float64, device=self.device)
@@ -659,7 +667,7 @@ class VecFlowEnv(object):
         return self._obs
 
     def _shape_tag(self):
-        return "%s: %d replicas x %d vehicles, obs_dim %d" % (type(self.env).__name__, self.num_envs, self.sim.N, self.obs_dim)
+        return "%s: %d replicas x %d vehicles, obs_dim %d" % (type(self.env).__name__, self.num_rows, self.sim.N, self.obs_dim)
 
     # ---- host-side inspection
     def get_state(self, field):
@@ -674,8 +682,8 @@ class VecFlowEnv(object):
         return self.sim.get_state(L.FS_FIELD_VEL)
 
     def vehicle_view(self, replica):
-        """The k.vehicle accessor object looking at ``replica``."""
-        self.k.vehicle.attach(self.sim, int(replica))
+        """The k.vehicle accessor object looking at environment ``replica`` (all ``num_rings`` rows of it)."""
+        self.k.vehicle.attach(self.sim, int(replica), rows=self.num_rings)
         return self.k.vehicle
 
     def close(self):
@@ -751,7 +759,7 @@ class StepGraph(object):
     def __init__(self, vec, num_steps, policy=None, reset_done=False):
         torch = vec.torch
         self.vec, self.K, self.policy, self.reset_done = vec, int(num_steps), policy, bool(reset_done)
-        R, K = vec.num_envs, self.K
+        R, K = getattr(vec, "num_rows", vec.num_envs), self.K      # (rows; a stand-in without rings has num_envs)
         dev = vec.device
         self.obs = torch.zeros((K + 1, R, vec.obs_dim), dtype=torch.float32, device=dev)
         self.rew = torch.zeros((K, R), dtype=torch.float32, device=dev)

@@ -23,6 +23,11 @@ class FlowVectorEnv(_Base):
         from flow_amd.envs.vec import VecFlowEnv
         self.torch = torch
         self.vec = VecFlowEnv(flow_params, num_replicas=int(num_envs), device=device, seed=seed)
+        if self.vec.num_rings != 1:
+            self.vec.close()
+            raise NotImplementedError("FlowVectorEnv is RLlib's single-agent VectorEnv: an environment of %d rings "
+                                      "(MultiWaveAttenuationPOEnv) has an agent per ring; use VecFlowEnv, whose tensors "
+                                      "lead with rows" % self.vec.num_rings)
         self.observation_space = self.vec.observation_space
         self.action_space = self.vec.action_space
         self.num_envs = int(num_envs)

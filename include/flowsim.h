@@ -115,10 +115,18 @@ enum fs_env {
                                        [m], leader speed / v_max, follower speed / v_max (1000, 1000, 0, 0 for an empty lane; a
                                        vehicle alone in its lane is its own leader and follower, one lap away), then
                                        obs[4 * lanes * num_rl + c] = own speed [m/s]; obs 4 * lanes * num_rl + num_rl */
-  FS_ENV_ACCEL_PO_MA = 9            /* MultiAgentAccelPOEnv     flow/envs/multiagent/ring/accel.py:84-227: per RL vehicle
+  FS_ENV_ACCEL_PO_MA = 9,           /* MultiAgentAccelPOEnv     flow/envs/multiagent/ring/accel.py:84-227: per RL vehicle
                                        [x / L, v / v_max, (v_lead - v) / v_max, (x_lead - x - len_ego) / L,
                                        (v - v_follow) / v_max, headway(follower) / L], obs 6 * num_rl; desired_velocity
                                        reward shared by the agents; crash = 0 (multiagent/base.py:188-190) */
+  FS_ENV_MULTI_WAVE_ATTENUATION_PO = 11 /* MultiWaveAttenuationPOEnv  flow/envs/multiagent/ring/wave_attenuation.py:34-140
+                                       on MultiRingNetwork: a replica ROW is ONE ring with one RL vehicle (num_rl = 1); obs 3 =
+                                       [v / 15, (v_lead - v) / 15, headway / max_length] (bumper to bumper); the reward is a
+                                       desired-velocity norm over the n vehicles whose front is on one of the ring's four
+                                       edges (not inside a junction): max(max_cost[n] - cost, 0) / max_cost[n] with
+                                       max_cost[n] = ||[target] * n|| and NO epsilon (n = 0: NaN, as numpy's 0 / 0), 0 if one
+                                       of those speeds is below -100, 0 without actions (warm-up); crash = 0.  FS_F32 (every
+                                       ring kernel) and FS_F64 (the generic kernel); FS_MIXED is refused */
 };
 
 enum fs_network {
