@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Runner for RL experiments on the GPU step loop -- the command line of the reference's examples/train.py:34-71.
 
-    python examples/train.py singleagent_ring [--rl_trainer device|rllib] [--num_steps N] [--rollout_size K]
+    python examples/train.py singleagent_ring [--rl_trainer device|es|ars|rllib] [--num_steps N] [--rollout_size K]
                                               [--num_cpus C] [--replicas R]
+
+``--rl_trainer es`` / ``ars``: the reference's other two trainers (flow/benchmarks/rllib/es_runner.py, ars_runner.py) on
+the device: ``replicas / 16`` perturbed policies roll out whole episodes in one launch per fragment, a workgroup per
+member (train_vec.train_es_on_device; ``--es_sigma --es_stepsize --es_l2 --es_top --es_eval_members``).
 
 ``--rl_trainer device`` (default here): PPO with the rollout on the device -- R replicas of the experiment in one
 handle, a fragment of ``rollout_size`` closed-loop steps (policy, Env.step, reset of finished episodes) replayed as one
@@ -30,7 +34,10 @@ def parse_args(args):
                                      epilog="python train.py EXP_CONFIG")
     parser.add_argument('exp_config', type=str,
                         help='module in exp_configs/rl/singleagent or exp_configs/rl/multiagent')
-    parser.add_argument('--rl_trainer', type=str, default="device", help='device (on-GPU PPO) or rllib')
+    parser.add_argument('--rl_trainer', type=str, default="device",
+                        help='device (on-GPU PPO), es or ars (evolution strategies / augmented random search on the device: '
+                             'one perturbed policy per workgroup) or rllib')
+    parser.add_argument('--gpus', type=int, default=1, help='es / ars: GPUs (more than one is refused: not built)')
     parser.add_argument('--num_cpus', type=int, default=1, help='rollout workers (rllib only)')
     parser.add_argument('--num_steps', type=int, default=20, help='training iterations')
     parser.add_argument('--rollout_size', type=int, default=100, help='env steps per rollout fragment')
@@ -52,7 +59,8 @@ def parse_args(args):
                              'and the adversary that perturbs its accelerations, opposite rewards) -- one fused two-policy '
                              'rollout per fragment, one update per policy; without it such an experiment is refused')
     parser.add_argument('--epochs', type=int, default=4, help='device: passes over a rollout fragment per update')
-    from train_vec import add_checkpoint_flags, add_model_flags, add_ppo_loss_flags
+    from train_vec import add_checkpoint_flags, add_es_flags, add_model_flags, add_ppo_loss_flags
+    add_es_flags(parser)                    # --es_sigma --es_stepsize --es_l2 --es_top --es_eval_members
     add_checkpoint_flags(parser)            # --checkpoint_dir --checkpoint_freq --restore --episode_stats --checkpoint_env_state
                                             # --evaluation_interval --evaluation_steps: all off by default
     add_ppo_loss_flags(parser)              # --kl_target --kl_coeff --entropy_coeff --vf_clip --sgd_minibatch_size: all off by default
@@ -157,6 +165,20 @@ def train_device(submodule, flags, multiagent=False):
                            **ppo_loss_settings(flags))
 
 
+def train_es(submodule, flags, multiagent=False):
+    """--rl_trainer es | ars: train_es_on_device (a population of perturbed policies, no backward pass)."""
+    from train_vec import train_es_on_device
+    from flow_amd import _lib
+    fp = submodule.flow_params
+    fp['sim'].render = False
+    if getattr(fp['env_name'], 'FS_ENV', None) == _lib.FS_ENV_MULTI_WAVE_ATTENUATION_PO:
+        multiagent = False                                  # (lord_of_the_rings: a ring per row, one agent each)
+    return train_es_on_device(fp, mode=flags.rl_trainer.lower(), replicas=flags.replicas, fragment=flags.rollout_size,
+                              iterations=flags.num_steps, sigma=flags.es_sigma, stepsize=flags.es_stepsize, l2=flags.es_l2,
+                              top=flags.es_top, eval_members=flags.es_eval_members, shared_agents=multiagent, gpus=flags.gpus,
+                              checkpoint_dir=flags.checkpoint_dir, checkpoint_freq=flags.checkpoint_freq, restore=flags.restore)
+
+
 def train_adversary(submodule, flags):
     """--train_adversary: the two policies of an adversarial experiment ('av' and 'adversary', opposite rewards)."""
     from train_vec import train_adversarial_on_device
@@ -174,6 +196,11 @@ def main(args):
     submodule, multiagent = load_experiment(flags.exp_config)
     if flags.rl_trainer.lower() == "rllib":
         return train_rllib(submodule, flags)
+    if flags.rl_trainer.lower() in ("es", "ars"):
+        if multiagent and (len(getattr(submodule, "POLICIES_TO_TRAIN", ["av"])) > 1 or flags.exp_config.startswith("adversarial")):
+            raise NotImplementedError("--rl_trainer %s trains one policy; there is no population form of fs_policy_pair (%s "
+                                      "trains two)" % (flags.rl_trainer, flags.exp_config))
+        return train_es(submodule, flags, multiagent)
     if flags.rl_trainer.lower() == "device":
         # multi-agent experiments whose agents share the policy 'av' (multiagent_ring / _figure_eight / _merge: one
         # observation block and one action column per agent) train that ONE policy; adversarial_figure_eight has two
@@ -190,7 +217,7 @@ def main(args):
                              "both (one fused two-policy rollout, one update per policy)"
                              % (flags.exp_config, getattr(submodule, "POLICIES_TO_TRAIN", "two")))
         return train_device(submodule, flags, multiagent)
-    raise ValueError("rl_trainer should be either 'device' or 'rllib'.")
+    raise ValueError("rl_trainer should be 'device', 'es', 'ars' or 'rllib'.")
 
 
 if __name__ == "__main__":

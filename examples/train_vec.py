@@ -835,6 +835,122 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     return history
 
 
+ES_DEFAULTS = {"es": dict(sigma=0.02, stepsize=0.02, l2=0.005),       # es_runner.py: noise_stdev, stepsize; RLlib ES l2_coeff
+               "ars": dict(sigma=0.2, stepsize=0.2, l2=0.0)}             # ars_runner.py: noise_stdev 0.2, sgd_stepsize 0.2
+
+
+def es_refusal(flow_params, gpus=1):
+    """What ``train_es_on_device`` refuses from the experiment's parameters alone, before anything touches a device: the
+    message, or None."""
+    from flow_amd import _lib as L
+    if int(gpus) > 1:
+        return ("--rl_trainer es|ars: --gpus %d is not built: data-parallel ES (members sharded over GPUs, returns gathered "
+                "before the ranking) -- run on one GPU" % int(gpus))
+    head = getattr(flow_params["env_name"], "FS_ENV", None)
+    names = {L.FS_ENV_MERGE_PO: "FS_ENV_MERGE_PO", L.FS_ENV_BOTTLENECK_DV: "FS_ENV_BOTTLENECK_DV", L.FS_ENV_MERGE_MA: "FS_ENV_MERGE_MA"}
+    if head in names:
+        return ("fs_population: not built for %s (%s): the policy kernels of the merges and the bottleneck give a wave to a "
+                "replica; --rl_trainer device trains this experiment" % (names[head], flow_params["env_name"].__name__))
+    return None
+
+
+def train_es_on_device(flow_params, mode="es", replicas=1024, fragment=100, iterations=20, sigma=None, stepsize=None, l2=None,
+                       top=0, eval_members=0, seed=0, log=print, shared_agents=False, gpus=1, checkpoint_dir=None,
+                       checkpoint_freq=None, restore=None, on_generation=None):
+    """Evolution strategies (``mode='es'``: RLlib's ES, the reference's flow/benchmarks/rllib/es_runner.py) or augmented
+    random search (``'ars'``: ars_runner.py) on R replicas of ``flow_params``: ``flow_amd.utils.device_es.DeviceES``.
+    ``replicas`` divided by the handle's granule (16) is the number of members M; ``eval_members`` E of them run the
+    unperturbed policy, the other M - E are (M - E) / 2 antithetic pairs.  A generation rolls every member out for one
+    whole episode (``horizon`` steps in fragments of ``fragment``) with the mean action, one launch per fragment.
+    ``sigma`` / ``stepsize`` / ``l2`` default to the reference runners' values (``ES_DEFAULTS``); ``top`` (ARS): the
+    directions used, 0 = all.  The iteration line shows ``episode_reward_mean|min|max`` over the perturbed members and,
+    with evaluation members, ``evaluation/episode_reward_mean``.  ``checkpoint_dir`` / ``checkpoint_freq`` / ``restore``:
+    ``save_checkpoint`` / ``load_checkpoint`` with the policy entry examples/evaluate.py reads (the model, in fs_policy's
+    layout), ``es`` = ``DeviceES.state_dict()`` and the environments' state (``env_state``: the simulator's noise
+    streams and the generator that draws ring lengths run on across the generations' resets); a generation depends on
+    nothing else, so a restored run prints the lines the uninterrupted run prints.  Returns the perturbed members' mean
+    return per generation."""
+    why = es_refusal(flow_params, gpus)
+    if why:
+        raise NotImplementedError(why)
+    if mode not in ES_DEFAULTS:
+        raise ValueError("train_es_on_device: mode must be 'es' or 'ars'")
+    from flow_amd.envs import VecFlowEnv
+    from flow_amd.utils.device_es import DeviceES
+    from flow_amd.utils.device_policy import DevicePolicy
+    d = ES_DEFAULTS[mode]
+    sigma, stepsize, l2 = (d["sigma"] if sigma is None else sigma, d["stepsize"] if stepsize is None else stepsize,
+                           d["l2"] if l2 is None else l2)
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    torch.manual_seed(seed)
+    ck = load_checkpoint(restore) if restore is not None else None
+    vec = VecFlowEnv(flow_params, num_replicas=replicas, device=0, seed=checkpoint_handle_seed(ck))
+    n_ag = vec.act_dim if shared_agents else 1
+    if shared_agents and (vec.act_dim < 1 or vec.obs_dim % vec.act_dim):
+        raise ValueError("shared_agents: the observation (%d) is not one block per action column (%d)" % (vec.obs_dim, vec.act_dim))
+    pi = GaussianPolicy(vec.obs_dim // n_ag, 1 if shared_agents else vec.act_dim).to(dev)
+    if pi.act_dim != 1:
+        raise NotImplementedError("fs_population: not built for the action-vector heads (%d action columns per evaluation)" % pi.act_dim)
+    pol = DevicePolicy([pi.mu[0], pi.mu[2]], pi.mu[4], log_std=pi.log_std, seed=seed)
+    granule = vec.sim.population_granule(pol.struct)           # (raises NotImplementedError with the library's message)
+    R = vec.num_rows
+    members = R // granule
+    if R % granule or members - eval_members < 2 or (members - eval_members) % 2:
+        raise ValueError("train_es_on_device: %d rows / %d (fs_population_granule) = %d members; less %d evaluation members "
+                         "they must be an even number of at least 2 (antithetic pairs)" % (R, granule, members, eval_members))
+    es = DeviceES(vec, pol, pairs=(members - eval_members) // 2, eval_members=eval_members, sigma=sigma, mode=mode,
+                  lr=stepsize, stepsize=stepsize, l2=l2, top=top, noise_seed=seed)
+    horizon = int(flow_params["env"].horizon)
+    log("%s: %d pairs + %d evaluation members x %d replicas, sigma %g, stepsize %g%s; kernels %s"
+        % (mode.upper(), es.N, es.E, es.group, sigma, stepsize, ", l2 %g" % l2 if mode == "es" else ", top %d" % (top or es.N),
+           "k_es_perturb, k_es_fitness, k_es_weights, k_es_grad" + (", k_adam" if mode == "es" else "")))
+    start = 0
+    if ck is not None:
+        entry = ck["policies"]["av"]
+        if "es" not in entry or entry["es"].get("mode") != mode:
+            raise ValueError("restore: %s was not written by --rl_trainer %s" % (restore, mode))
+        es.load_state_dict(entry["es"])
+        start = int(ck["iteration"]) + 1
+        log("restore: %s (iteration %d, written on %s): continuing at iteration %d" % (restore, ck["iteration"], ck["update_path"], start))
+        restore_env_state(ck.get("env"), vec, None, False, 1, log=log)
+    history = []
+    for it in range(start, start + iterations):
+        t0 = time.perf_counter()
+        stats = es.generation(horizon, fragment)
+        mean, lo, hi, ev = stats.tolist()                       # (the generation's one host synchronisation)
+        t_gen = time.perf_counter() - t0
+        history.append(mean)
+        if on_generation is not None:
+            on_generation(it, dict(episode_reward_mean=mean, episode_reward_min=lo, episode_reward_max=hi,
+                                   evaluation_episode_reward_mean=ev if es.E else None))
+        log("iteration %3d  episode_reward_mean %.4f  episode_reward_min %.4f  episode_reward_max %.4f%s  generation %.1f ms "
+            "(%.2f M env-steps/s)  kernel %s"
+            % (it, mean, lo, hi, "  evaluation/episode_reward_mean %.4f" % ev if es.E else "", t_gen * 1e3,
+               horizon * R / t_gen / 1e6, es.rollout_kernel))
+        if checkpoint_dir is not None and _checkpoint_due(it, start + iterations - 1, checkpoint_freq):
+            pol.unpack()                                        # (theta -> the modules evaluate.py loads)
+            entry = dict(descriptor=list(model_descriptor(pi)),
+                         pi={k: v.detach().to("cpu").clone() for k, v in pi.state_dict().items()}, es=es.state_dict())
+            path = save_checkpoint(checkpoint_dir, it, flow_params, dict(av=entry), seed=seed, update_path=mode,
+                                   model=dict(shared_agents=bool(shared_agents), fuse_action_vector=False, adversarial=False),
+                                   env=env_state(vec))
+            log("checkpoint: %s" % path)
+    vec.close()
+    return history
+
+
+def add_es_flags(ap):
+    ap.add_argument("--es_sigma", type=float, default=None,
+                    help="es / ars: standard deviation of the parameter noise (default: the reference runners' noise_stdev, 0.02 / 0.2)")
+    ap.add_argument("--es_stepsize", type=float, default=None,
+                    help="es: Adam's step size (default 0.02); ars: sgd_stepsize (default 0.2)")
+    ap.add_argument("--es_l2", type=float, default=None, help="es: l2_coeff of the gradient (default 0.005, RLlib's)")
+    ap.add_argument("--es_top", type=int, default=0, help="ars: directions used per update, the best first (default 0: all)")
+    ap.add_argument("--es_eval_members", type=int, default=0,
+                    help="es / ars: members that run the unperturbed policy (evaluation/episode_reward_mean on the iteration line)")
+
+
 def update_adversarial(rollout, update_av, update_adversary):
     """The update step of train_adversarial_on_device: ``rollout`` is what ``VecFlowEnv.policy_pair_rollout`` returns,
     ``(obs, act [2, K, R], logp, rew, done)``.  The av learns from ``(obs, act[0], rew, done)``, the adversary from

@@ -50,7 +50,11 @@ EXPORTS = ["fs_create", "fs_destroy", "fs_last_error", "fs_abi_version", "fs_obs
            "fs_ppo_loss_workspace", "fs_ppo_grad_loss_dev", "fs_kl_adapt_dev", "fs_ppo_perm_host",
            "fs_ppo_minibatch_workspace", "fs_ppo_minibatch_dev", "fs_ppo_mb_finish_dev", "fs_policy_pair_act_dev",
            "fs_policy_pair_rollout_dev", "fs_episode_stats_dev", "fs_snapshot_info", "fs_snapshot_dev", "fs_restore_dev",
-           "fs_snapshot", "fs_restore"]
+           "fs_snapshot", "fs_restore", "fs_population_granule", "fs_population_act_dev", "fs_population_rollout_dev",
+           "fs_es_perturb_dev", "fs_es_fitness_dev", "fs_es_weights_dev", "fs_es_workspace", "fs_es_grad_dev"]
+# fs_es_weights_dev / fs_es_grad_dev mode
+FS_ES_MODE_ES, FS_ES_MODE_ARS = 0, 1
+FS_ES_MAX_PAIRS = 2048
 # fs_ppo_minibatch.mode / .flags
 FS_MB_STEP, FS_MB_PARTIAL = 0, 1
 FS_MB_ACCUMULATE, FS_MB_FIRST, FS_MB_LAST = 1, 2, 4
@@ -121,6 +125,11 @@ class fs_policy(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("obs_dim", C.c_int32), ("num_hidden", C.c_int32),
                 ("hidden_width", C.c_int32), ("activation", C.c_int32), ("greedy", C.c_int32),
                 ("weights_dev", C.c_void_p), ("log_std_dev", C.c_void_p), ("seed", C.c_uint64)]
+
+
+class fs_population(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("members", C.c_int32), ("group", C.c_int32), ("reserved", C.c_int32),
+                ("stride", C.c_int64)]
 
 
 class fs_ppo_model(C.Structure):
@@ -266,6 +275,24 @@ def load(path=None):
     lib.fs_snapshot.restype = C.c_int
     lib.fs_restore.argtypes = [h, C.c_void_p, C.c_size_t, C.c_uint64]
     lib.fs_restore.restype = C.c_int
+    pol, pop = C.POINTER(fs_policy), C.POINTER(fs_population)
+    lib.fs_population_granule.argtypes = [h, pol]
+    lib.fs_population_granule.restype = C.c_int
+    lib.fs_population_act_dev.argtypes = [h, pol, pop, f32p, f32p, f32p]
+    lib.fs_population_act_dev.restype = C.c_int
+    lib.fs_population_rollout_dev.argtypes = [h, pol, pop, C.c_int, C.c_int, f32p, f32p, f32p, f32p, u8p]
+    lib.fs_population_rollout_dev.restype = C.c_int
+    lib.fs_es_perturb_dev.argtypes = [h, C.c_int64, C.c_int, C.c_int, C.c_int64, f32p, C.c_float, C.c_uint64, C.c_uint32, f32p]
+    lib.fs_es_perturb_dev.restype = C.c_int
+    lib.fs_es_fitness_dev.argtypes = [h, C.c_int, C.c_int, C.c_int, f32p, u8p, C.c_int, f64p, u8p, f64p]
+    lib.fs_es_fitness_dev.restype = C.c_int
+    lib.fs_es_weights_dev.argtypes = [h, C.c_int, C.c_int, C.c_int, C.c_int, f64p, f32p, f64p]
+    lib.fs_es_weights_dev.restype = C.c_int
+    lib.fs_es_workspace.argtypes = [C.c_int64, C.c_int]
+    lib.fs_es_workspace.restype = C.c_size_t
+    lib.fs_es_grad_dev.argtypes = [h, C.c_int, C.c_int64, C.c_int, f32p, C.c_uint64, C.c_uint32, C.c_float, f32p, f32p, f32p,
+                                   C.c_size_t]
+    lib.fs_es_grad_dev.restype = C.c_int
     if lib.fs_abi_version() != FS_ABI_VERSION:
         raise FatalFlowError("libflowsim.so ABI %d != binding ABI %d" % (lib.fs_abi_version(), FS_ABI_VERSION))
     _libs[path] = lib

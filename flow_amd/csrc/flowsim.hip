@@ -5,6 +5,7 @@
 // device fs_create fails with FS_ERR_HIP.
 #include "flowsim_sim.h"
 #include "flowsim_learn.h"
+#include "flowsim_es.h"
 
 #include <cmath>
 
@@ -537,6 +538,109 @@ int fs_policy_pair_rollout_dev(fs_handle h, const fs_policy* av, const fs_policy
   DeviceGuard guard(S(h)->cfg.device);
   return S(h)->launch_policy_pair(av, adversary, perturb_weight, num_steps, reset_done ? 1 : 0, nullptr, obs_dev, act_dev,
                                   logp_dev, nullptr, rew_dev, done_dev);
+}
+
+// ---- policy populations (fs_population; Sim::launch_population)
+int fs_population_granule(fs_handle h, const fs_policy* pol) {
+  if (!h || !pol) {
+    fail(FS_ERR_INVALID, "fs_population_granule: NULL argument");
+    return -1;
+  }
+  DeviceGuard guard(S(h)->cfg.device);
+  if (S(h)->launch_population(pol, nullptr, 1, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) return -1;
+  return 16;
+}
+
+int fs_population_act_dev(fs_handle h, const fs_policy* pol, const fs_population* pop, const float* obs_dev, float* act_dev,
+                          float* logp_dev) {
+  if (!h || !pol || !pop || !obs_dev || !act_dev || !logp_dev)
+    return fail(FS_ERR_INVALID, "fs_population_act_dev: NULL argument");
+  DeviceGuard guard(S(h)->cfg.device);
+  return S(h)->launch_population(pol, pop, 0, 0, 0, obs_dev, nullptr, act_dev, logp_dev, nullptr, nullptr);
+}
+
+int fs_population_rollout_dev(fs_handle h, const fs_policy* pol, const fs_population* pop, int num_steps, int reset_done,
+                              float* obs_dev, float* act_dev, float* logp_dev, float* rew_dev, uint8_t* done_dev) {
+  if (!h || !pol || !pop || !obs_dev || !act_dev || !logp_dev || !rew_dev || !done_dev)
+    return fail(FS_ERR_INVALID, "fs_population_rollout_dev: NULL argument");
+  if (num_steps < 1) return fail(FS_ERR_INVALID, "fs_population_rollout_dev: num_steps < 1");
+  DeviceGuard guard(S(h)->cfg.device);
+  return S(h)->launch_population(pol, pop, 0, num_steps, reset_done ? 1 : 0, nullptr, obs_dev, act_dev, logp_dev, rew_dev,
+                                 done_dev);
+}
+
+// ---- evolution strategies (flowsim_es.h): the handle lends its device, its stream and fs_last_error
+static const char* es_shape_why(int64_t num_params, int pairs, int eval_members) {
+  if (num_params < 1 || num_params > (int64_t(1) << 24)) return "num_params must be 1 .. 2^24";
+  if (pairs < 1 || pairs > fs::ES_MAX_PAIRS) return "pairs must be 1 .. 2048";
+  if (eval_members < 0 || eval_members > 65535 - 2 * pairs) return "eval_members out of range";
+  return nullptr;
+}
+
+int fs_es_perturb_dev(fs_handle h, int64_t num_params, int pairs, int eval_members, int64_t stride, const float* theta_dev,
+                      float sigma, uint64_t noise_seed, uint32_t generation, float* weights_dev) {
+  if (!h || !theta_dev || !weights_dev) return fail(FS_ERR_INVALID, "fs_es_perturb_dev: NULL argument");
+  if (const char* why = es_shape_why(num_params, pairs, eval_members)) return fail(FS_ERR_INVALID, std::string("fs_es_perturb_dev: ") + why);
+  if (stride < num_params) return fail(FS_ERR_INVALID, "fs_es_perturb_dev: stride < num_params");
+  if (generation > 0x1FFFFFFFu) return fail(FS_ERR_INVALID, "fs_es_perturb_dev: generation must be below 2^29");
+  DeviceGuard guard(S(h)->cfg.device);
+  S(h)->last_kernel = "k_es_perturb";
+  return launch_es_perturb(S(h)->stream, num_params, pairs, eval_members, stride, theta_dev, sigma,
+                           uint32_t(noise_seed & 0xFFFFFFFFull), uint32_t(noise_seed >> 32), generation, weights_dev);
+}
+
+int fs_es_fitness_dev(fs_handle h, int num_steps, int members, int group, const float* rew_dev, const uint8_t* done_dev,
+                      int accumulate, double* ret_dev, uint8_t* alive_dev, double* fit_dev) {
+  if (!h || !rew_dev || !done_dev || !ret_dev || !alive_dev || !fit_dev)
+    return fail(FS_ERR_INVALID, "fs_es_fitness_dev: NULL argument");
+  if (num_steps < 1 || members < 1 || group < 1) return fail(FS_ERR_INVALID, "fs_es_fitness_dev: num_steps, members and group must be at least 1");
+  if ((long long)members * group != (long long)S(h)->cfg.num_replicas)
+    return fail(FS_ERR_INVALID, "fs_es_fitness_dev: members * group != num_replicas");
+  DeviceGuard guard(S(h)->cfg.device);
+  S(h)->last_kernel = "k_es_fitness";
+  return launch_es_fitness(S(h)->stream, num_steps, members, group, rew_dev, done_dev, accumulate ? 1 : 0, ret_dev, alive_dev,
+                           fit_dev);
+}
+
+int fs_es_weights_dev(fs_handle h, int mode, int pairs, int eval_members, int top, const double* fit_dev, float* u_dev,
+                      double* stats_dev) {
+  if (!h || !fit_dev || !u_dev || !stats_dev) return fail(FS_ERR_INVALID, "fs_es_weights_dev: NULL argument");
+  if (mode != FS_ES_MODE_ES && mode != FS_ES_MODE_ARS) return fail(FS_ERR_INVALID, "fs_es_weights_dev: mode must be FS_ES_MODE_ES or FS_ES_MODE_ARS");
+  if (const char* why = es_shape_why(1, pairs, eval_members)) return fail(FS_ERR_INVALID, std::string("fs_es_weights_dev: ") + why);
+  DeviceGuard guard(S(h)->cfg.device);
+  S(h)->last_kernel = "k_es_weights";
+  return launch_es_weights(S(h)->stream, mode, pairs, eval_members, top, fit_dev, u_dev, stats_dev);
+}
+
+size_t fs_es_workspace(int64_t num_params, int pairs) {
+  if (es_shape_why(num_params, pairs, 0)) return 0;
+  return fs::es_work_floats(num_params, pairs);
+}
+
+int fs_es_grad_dev(fs_handle h, int mode, int64_t num_params, int pairs, const float* u_dev, uint64_t noise_seed,
+                   uint32_t generation, float l2_or_stepsize, float* theta_dev, float* grad_dev, float* work_dev,
+                   size_t work_floats) {
+  if (!h || !u_dev || !theta_dev || !work_dev || (mode == FS_ES_MODE_ES && !grad_dev))
+    return fail(FS_ERR_INVALID, "fs_es_grad_dev: NULL argument");
+  if (mode != FS_ES_MODE_ES && mode != FS_ES_MODE_ARS) return fail(FS_ERR_INVALID, "fs_es_grad_dev: mode must be FS_ES_MODE_ES or FS_ES_MODE_ARS");
+  if (const char* why = es_shape_why(num_params, pairs, 0)) return fail(FS_ERR_INVALID, std::string("fs_es_grad_dev: ") + why);
+  if (generation > 0x1FFFFFFFu) return fail(FS_ERR_INVALID, "fs_es_grad_dev: generation must be below 2^29");
+  if (work_floats < fs::es_work_floats(num_params, pairs))
+    return fail(FS_ERR_INVALID, "fs_es_grad_dev: work_dev is smaller than fs_es_workspace(num_params, pairs) floats");
+  SimBase* s = S(h);
+  DeviceGuard guard(s->cfg.device);
+  if (!s->d_es_ticket) {
+    // the first call on a handle allocates (and synchronises the device once): make it outside a stream capture
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, fs::ES_MAX_COLS * sizeof(unsigned)));
+    s->allocs.push_back(p);
+    HIP_TRY(hipMemset(p, 0, fs::ES_MAX_COLS * sizeof(unsigned)));
+    HIP_TRY(hipDeviceSynchronize());
+    s->d_es_ticket = static_cast<unsigned*>(p);
+  }
+  s->last_kernel = "k_es_grad";
+  return launch_es_grad(s->stream, mode, num_params, pairs, u_dev, uint32_t(noise_seed & 0xFFFFFFFFull),
+                        uint32_t(noise_seed >> 32), generation, l2_or_stepsize, theta_dev, grad_dev, work_dev, s->d_es_ticket);
 }
 
 // ---- the PPO update on the device (flowsim_learn.h): the handle lends its device, its stream and fs_last_error

@@ -6,6 +6,7 @@
 // so that the step kernels of the pairs compile in parallel and an edit to one kernel family rebuilds few objects.
 #include "flowsim_launch.h"
 #include "flowsim_learn.h"       // (FS_PART_LEARN: defines k_ppo_eval, k_gae, k_ppo_grad, k_adv_stats, k_adv_finish, k_adam and their fsim::launch_*)
+#include "flowsim_es.h"          // (FS_PART_LEARN: defines k_es_perturb, k_es_fitness, k_es_weights, k_es_grad and their fsim::launch_*)
 
 namespace fsim {
 #if defined(FS_PART_LEARN)

@@ -38,6 +38,10 @@ struct PolicyView {
   int in_dim, num_hidden, n_out;
   uint32_t seed_lo, seed_hi;
   int greedy;              // fs_policy.greedy: policy_sample applies the mean (the draw is still made: the streams advance)
+  // fs_population (0, 0: one weight set): the workgroup whose first replica is r0 loads the set at w + (r0 / pop_group) *
+  // pop_stride.  Read once, by policy_load_trunk, before the first barrier of the launch; nothing behind the load sees it.
+  long long pop_stride = 0;
+  int pop_group = 0;
 };
 
 struct alignas(16) PolicyLds {
@@ -70,8 +74,17 @@ __device__ __forceinline__ void policy_wide_inputs(const float* o, int in_dim, i
 // weights -> LDS (once per launch); layout of pv.w: [W1 32 x in_dim][b1 32][W2 32x32][b2][W3 32x32][b3][Wout n_out x 32][bout].
 // policy_load_trunk: layers 1 .. num_hidden and their biases; returns where the output layer starts.  No barrier: the
 // caller loads its output layer and ends with ONE __syncthreads.
+// The weight set of THIS workgroup (fs_population): every kernel that takes a population -- k_policy_act, k_ring_policy,
+// k_loop_policy -- gives a row of 16 lanes to a replica, so a workgroup's first replica is blockIdx.x * (blockDim.x / 16)
+// and its replicas are one member's (Sim::launch_population: pop_group is a multiple of the 16 replicas of a workgroup).
+__device__ __forceinline__ const float* policy_member_weights(const PolicyView& pv) {
+  if (pv.pop_stride == 0) return pv.w;                       // (uniform: one set, or all members share set 0)
+  const unsigned r0 = blockIdx.x * (blockDim.x >> 4);
+  return pv.w + size_t(r0 / unsigned(pv.pop_group)) * size_t(pv.pop_stride);
+}
+
 __device__ __forceinline__ const float* policy_load_trunk(const PolicyView& pv, PolicyLds* L, int tid, int nthreads) {
-  const float* p = pv.w;
+  const float* p = policy_member_weights(pv);
   const bool wide = pv.in_dim > 4;
   for (int e = tid; e < 32 * 4; e += nthreads) L->w_in[e / 4][e % 4] = (!wide && (e % 4) < pv.in_dim) ? p[(e / 4) * pv.in_dim + (e % 4)] : 0.0f;
   {

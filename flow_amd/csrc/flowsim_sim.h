@@ -137,6 +137,11 @@ struct SimBase {
   virtual int launch_policy_pair(const fs_policy* av, const fs_policy* adv, float pw, int num_steps, int reset_done,
                                  const float* obs_in, float* obs, float* act, float* logp, float* cmd, float* rew,
                                  uint8_t* done) = 0;
+  // policy populations (fs_population_*): `probe` != 0 runs the checks alone (fs_population_granule: nothing launches)
+  virtual int launch_population(const fs_policy* pol, const fs_population* pop, int probe, int num_steps, int reset_done,
+                                const float* obs_in, float* obs, float* act, float* logp, float* rew, uint8_t* done) = 0;
+  std::string last_kernel_pop;     // (the storage of a population launch's fs_last_kernel name)
+  unsigned* d_es_ticket = nullptr; // k_es_grad: the tickets its workgroups draw (zero between launches), allocated by its first launch
   uint32_t* d_pol_ctr = nullptr;   // [R] actions sampled so far per replica (the policy's draw counters)
   // ---- snapshots (flowsim_snap.h; include/flowsim.h fs_snapshot_info): the table Sim<T>::init builds once
   fs::SnapTable snap{};
@@ -1082,6 +1087,8 @@ struct Sim : SimBase {
     pv.seed_lo = uint32_t(pol->seed & 0xFFFFFFFFull);
     pv.seed_hi = uint32_t(pol->seed >> 32);
     pv.greedy = pol->greedy != 0 ? 1 : 0;
+    pv.pop_stride = pop_stride;
+    pv.pop_group = pop_group;
     return pv;
   }
   int launch_policy(const fs_policy* pol, int num_steps, int reset_done, const float* obs_in, float* obs, float* act,
@@ -1179,6 +1186,7 @@ struct Sim : SimBase {
         msg += " (FS_ENV_BOTTLENECK_DV)";                // (the checks shared by every head: model class, weights)
       return fail(FS_ERR_UNSUPPORTED, msg);
     }
+    if (pop_probe) return FS_OK;                         // (fs_population_granule: the checks alone)
     if (int rc = policy_counters()) return rc;
     fs::PolicyView pv = policy_view(pol);
     if (dv.env == FS_ENV_MERGE_PO || dv.env == FS_ENV_BOTTLENECK_DV) pv.n_out *= dv.num_rl;  // the action-vector heads: num_rl means [and num_rl log stds]
@@ -1193,6 +1201,60 @@ struct Sim : SimBase {
     if (obs == nullptr) return launch_policy_act(pv, ma ? dv.num_rl : 1, obs_in, act, logp);      // eager: the policy alone
     if (loop) return launch_policy_loop16(pv, num_steps, reset_done, obs, act, logp, rew, done);
     return launch_policy_row16(pv, num_steps, reset_done, obs, act, logp, rew, done);
+  }
+
+  // ---- policy populations (include/flowsim.h fs_population): launch_policy with a stride and a group in the PolicyView.
+  // The kernels that take one -- k_policy_act, k_ring_policy, k_loop_policy -- give a workgroup of 256 lanes to 16 replicas.
+  static constexpr int POP_GRANULE = 16;
+  long long pop_stride = 0;        // (what policy_view hands the kernels: set for the duration of launch_population)
+  int pop_group = 0;
+  bool pop_probe = false;
+  static long long policy_floats(const fs_policy* pol) {
+    const long long n_out = pol->log_std_dev ? 1 : 2;
+    return 32ll * pol->obs_dim + 32 + (pol->num_hidden - 1) * (32ll * 32 + 32) + n_out * 32 + n_out;
+  }
+  int launch_population(const fs_policy* pol, const fs_population* pop, int probe, int num_steps, int reset_done,
+                        const float* obs_in, float* obs, float* act, float* logp, float* rew, uint8_t* done) override {
+    if (!pol || pol->struct_size != sizeof(fs_policy)) return fail(FS_ERR_INVALID, "fs_population: fs_policy struct_size mismatch");
+    if (!probe && (!pop || pop->struct_size != sizeof(fs_population)))
+      return fail(FS_ERR_INVALID, "fs_population: struct_size mismatch");
+    if (dv.env == FS_ENV_MERGE_PO || dv.env == FS_ENV_BOTTLENECK_DV)
+      return fail(FS_ERR_UNSUPPORTED, "fs_population: not built for the action-vector heads (FS_ENV_MERGE_PO, "
+                                      "FS_ENV_BOTTLENECK_DV): their kernels give a wave to a replica and read weights past "
+                                      "the workgroup's LDS copy");
+    if (dv.env == FS_ENV_MERGE_MA)
+      return fail(FS_ERR_UNSUPPORTED, "fs_population: not built for FS_ENV_MERGE_MA (k_merge_queue<POLICY> gives a wave to a replica)");
+    if (!probe) {
+      if (pop->members < 1 || pop->group < 1 || pop->reserved != 0)
+        return fail(FS_ERR_INVALID, "fs_population: members and group must be at least 1, reserved 0");
+      if (pop->group % POP_GRANULE != 0)
+        return fail(FS_ERR_INVALID, "fs_population: group is not a multiple of the granule (fs_population_granule: 16 replicas "
+                                    "share a workgroup's copy of the weights)");
+      if ((long long)pop->members * pop->group != (long long)dv.R)
+        return fail(FS_ERR_INVALID, "fs_population: members * group != num_replicas");
+    }
+    // (what fs_policy_rollout_dev refuses on this handle, with its message, before the stride can be judged: the model class)
+    static float probe_buf;        // (fs_population_granule asks about the fused form; launch_policy only tests obs for NULL)
+    pop_probe = true;
+    int rc = launch_policy(pol, num_steps, reset_done, obs_in, probe ? &probe_buf : obs, act, logp, rew, done);
+    pop_probe = false;
+    if (rc || probe) return rc;
+    if (pop->stride < 0 || (pop->stride != 0 && pop->stride < policy_floats(pol)))
+      return fail(FS_ERR_INVALID, "fs_population: stride is smaller than the policy's own size (" +
+                                  std::to_string(policy_floats(pol)) + " floats; 0: all members share set 0)");
+    pop_stride = pop->stride;
+    pop_group = pop->group;
+    rc = launch_policy(pol, num_steps, reset_done, obs_in, obs, act, logp, rew, done);
+    pop_stride = 0;
+    pop_group = 0;
+    if (rc) return rc;
+    // fs_last_kernel: the family's name with Population among its tags
+    std::string name = last_kernel;
+    if (!name.empty() && name.back() == '>') name = name.substr(0, name.size() - 1) + ",Population>";
+    else name += "<Population>";
+    last_kernel_pop = name;
+    last_kernel = last_kernel_pop.c_str();
+    return FS_OK;
   }
 
   // two policies, one RL vehicle (fs_policy_pair_act_dev / fs_policy_pair_rollout_dev; flowsim_policy.h k_policy_pair_act,

@@ -447,6 +447,43 @@ class VecFlowEnv(object):
         self.sim.policy_rollout_dev(policy.struct, K, out[0], out[1], out[2], out[3], out[4], reset_done=reset_done)
         return out
 
+    def population_act(self, population, obs=None, out=None):
+        """``policy_act`` for a population of weight sets (``DevicePolicy.population(...)``; ``fs_population_act_dev``):
+        replica ``r`` evaluates member ``r // group``.  Shapes, streams and counters are ``policy_act``'s."""
+        torch, R = self.torch, self.num_rows
+        self.use_current_stream()
+        n_ag = self.sim.policy_agents
+        obs = self._obs if obs is None else self._check(obs, (R, self.obs_dim), torch.float32)
+        lp_shape = (R,) if n_ag == 1 else (R, n_ag)
+        if out is None:
+            out = (torch.empty((R, n_ag), dtype=torch.float32, device=self.device),
+                   torch.empty(lp_shape, dtype=torch.float32, device=self.device))
+        else:
+            self._check(out[0], (R, n_ag), torch.float32)
+            self._check(out[1], lp_shape, torch.float32)
+        self.sim.population_act_dev(population.policy_struct(), population.struct, obs, out[0], out[1])
+        return out
+
+    def population_rollout(self, population, num_steps, reset_done=False, out=None):
+        """``policy_rollout`` for a population of weight sets (``fs_population_rollout_dev``): ONE launch in which replica
+        ``r`` runs member ``r // group``'s policy for the whole fragment.  Rows ``[m * group, (m + 1) * group)`` of every
+        returned tensor equal, bit for bit, those of ``policy_rollout`` with member ``m``'s weights.  Built for the heads
+        with one action column per evaluation (the rings, ``lord_of_the_rings``, the figure eights); the merges and the
+        bottleneck raise NotImplementedError naming fs_population."""
+        torch, R, K = self.torch, self.num_rows, int(num_steps)
+        self.use_current_stream()
+        n_ag = self.sim.policy_agents
+        per_agent = (K, R) if n_ag == 1 else (K, R, n_ag)
+        if out is None:
+            out = (torch.empty((K + 1, R, self.obs_dim), dtype=torch.float32, device=self.device),
+                   torch.empty(per_agent, dtype=torch.float32, device=self.device),
+                   torch.empty(per_agent, dtype=torch.float32, device=self.device),
+                   torch.empty((K, R), dtype=torch.float32, device=self.device),
+                   torch.empty((K, R), dtype=torch.uint8, device=self.device))
+        self.sim.population_rollout_dev(population.policy_struct(), population.struct, K, out[0], out[1], out[2], out[3], out[4],
+                                        reset_done=reset_done)
+        return out
+
     def _pair_weight(self, what, av, adversary, weight):
         for name, pol in (("av", av), ("adversary", adversary)):
             if pol.act_dim != 1:

@@ -299,6 +299,24 @@ class FlowSim:
                                                     int(bool(reset_done)), _ptr(obs), _ptr(act), _ptr(logp), _ptr(rew),
                                                     _ptr(done)), self.lib)
 
+    # ------------------------------------------------------------------ policy populations (include/flowsim.h fs_population)
+    def population_granule(self, pol):
+        """Replicas per workgroup of the policy kernel this handle would run: ``group`` of a population is a multiple."""
+        g = self.lib.fs_population_granule(self._h, C.byref(pol))
+        if g < 0:
+            msg = self.lib.fs_last_error().decode("utf-8", "replace")
+            raise (ValueError if "NULL" in msg or "struct_size" in msg else NotImplementedError)(msg)
+        return int(g)
+
+    def population_act_dev(self, pol, pop, obs, act, logp):
+        """fs_policy_act_dev's shapes; replica r evaluates weight set r // pop.group."""
+        L.check(self.lib.fs_population_act_dev(self._h, C.byref(pol), C.byref(pop), _ptr(obs), _ptr(act), _ptr(logp)), self.lib)
+
+    def population_rollout_dev(self, pol, pop, num_steps, obs, act, logp, rew, done, reset_done=False):
+        """fs_policy_rollout_dev's shapes; replica r evaluates weight set r // pop.group."""
+        L.check(self.lib.fs_population_rollout_dev(self._h, C.byref(pol), C.byref(pop), int(num_steps), int(bool(reset_done)),
+                                                   _ptr(obs), _ptr(act), _ptr(logp), _ptr(rew), _ptr(done)), self.lib)
+
     # ------------------------------------------------------------------ state access
     def _field_shape(self, field):
         if field in (L.FS_FIELD_TIME,):

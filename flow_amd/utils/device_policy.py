@@ -89,8 +89,16 @@ class DevicePolicy(object):
         self.struct.log_std_dev = self.ls.data_ptr()
         return self
 
+    def population(self, weights, members, group):
+        """A view of this policy over ``members`` weight sets for ``VecFlowEnv.population_act`` / ``population_rollout``:
+        ``weights`` is a float32 device tensor ``[members, stride]`` (row m: member m's packed buffer, this class's
+        layout, ``stride >= buf.numel()``), or a 1-d tensor of one set that all members share (stride 0); ``group`` replicas
+        in a row run each member, ``members * group == num_replicas``.  The log std, the seed and ``greedy`` stay this
+        policy's.  The view holds ``weights``: write new sets into it between launches, nothing is copied."""
+        return PolicyPopulation(self, weights, members, group)
+
     def sync(self):
-        if getattr(self, "shared", None) is not None:        # (the learner's buffer is the policy's: nothing to repack)
+        if getattr(self, "shared", None) is not None:       # (the learner's buffer is the policy's: nothing to repack)
             return
         torch = self.torch
         with torch.no_grad():
@@ -100,6 +108,17 @@ class DevicePolicy(object):
             self.buf.copy_(torch.cat([p.detach().float() for p in parts]))
             if self.ls is not None:
                 self.ls.copy_(self.log_std_param.detach().float().reshape(self.act_dim))
+
+    def unpack(self):
+        """The inverse of ``sync()``: copy the packed buffer's values into the modules' parameters (a trainer that writes
+        the buffer itself -- ``flow_amd.utils.device_es.DeviceES`` -- calls it before the modules are saved).  The log
+        std is not touched."""
+        torch, at = self.torch, 0
+        with torch.no_grad():
+            for l in self.hidden + [self.head]:
+                for p in (l.weight, l.bias):
+                    p.copy_(self.buf[at:at + p.numel()].reshape(p.shape))
+                    at += p.numel()
 
     def reference(self, obs):
         """(mean, log std) of the same network evaluated by torch (float32): agrees with the kernels to ~1e-6.
@@ -117,3 +136,33 @@ class DevicePolicy(object):
         if self.ls is not None:
             return out[..., 0], self.log_std_param.reshape(1).expand_as(out[..., 0])
         return out[..., 0], out[..., 1]
+
+
+class PolicyPopulation(object):
+    """``DevicePolicy.population``'s view: ``struct`` is the ``fs_population``, ``policy_struct()`` the policy's ``fs_policy``
+    with ``weights_dev`` at the population's weights (built per call: ``greedy`` and the seed are read from the policy)."""
+
+    def __init__(self, policy, weights, members, group):
+        torch = policy.torch
+        if policy.act_dim != 1:
+            raise NotImplementedError("fs_population: not built for the action-vector heads (DevicePolicy(act_dim > 1))")
+        P, M = policy.buf.numel(), int(members)
+        if weights.dtype != torch.float32 or not weights.is_contiguous() or weights.device != policy.buf.device:
+            raise ValueError("DevicePolicy.population: weights must be a contiguous float32 tensor on the policy's device")
+        if weights.dim() == 1:
+            if weights.numel() < P:
+                raise ValueError("DevicePolicy.population: a shared weight set has %d values, the policy %d" % (weights.numel(), P))
+            stride = 0
+        elif weights.dim() == 2 and weights.shape[0] == M:
+            stride = int(weights.shape[1])                  # (the library refuses a stride below the policy's size by name)
+        else:
+            raise ValueError("DevicePolicy.population: weights must be [members, stride] or one shared set")
+        self.policy, self.weights, self.members, self.group, self.stride = policy, weights, M, int(group), stride
+        self.struct = L.fs_population(struct_size=C.sizeof(L.fs_population), members=M, group=int(group), reserved=0,
+                                      stride=stride)
+
+    def policy_struct(self):
+        src = self.policy.struct
+        return L.fs_policy(struct_size=src.struct_size, obs_dim=src.obs_dim, num_hidden=src.num_hidden,
+                           hidden_width=src.hidden_width, activation=src.activation, greedy=src.greedy,
+                           weights_dev=self.weights.data_ptr(), log_std_dev=src.log_std_dev, seed=src.seed)

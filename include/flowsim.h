@@ -445,7 +445,10 @@ int fs_add_vehicle(fs_handle h, int replica, int slot, int route, double x, doub
  * "k_ring_policy<POMA>", "k_loop_policy<AccelMA>", "k_merge_policy", "k_merge_policy<PO>", "k_merge_policy<PO,WIDE>",
  * "k_loop_policy<Adversarial>" (fs_policy_pair_rollout_dev; fs_policy_pair_act_dev: "k_policy_pair_act")
  * (fs_policy_act_dev: "k_policy_act", "k_policy_act_vec", "k_policy_act_wide"; the PPO update's entry points: "k_ppo_eval",
- * "k_gae", "k_ppo_grad", "k_adv_stats", "k_adv_finish", "k_adam"; fs_episode_stats_dev: "k_episode_stats"),
+ * "k_gae", "k_ppo_grad", "k_adv_stats", "k_adv_finish", "k_adam"; fs_episode_stats_dev: "k_episode_stats";
+ * fs_population_*: the policy kernel's name with the tag Population, e.g. "k_ring_policy<Population>",
+ * "k_ring_policy<POMA,Population>" -- that one string lives in the handle and is valid until its next launch; fs_es_*:
+ * "k_es_perturb", "k_es_fitness", "k_es_weights", "k_es_grad"),
  * "k_steps<FAST>", "k_steps<CSET>", "k_steps", "k_steps_ml", "k_steps_open" (also "<mixed>"), "k_steps_wide",
  * "k_merge_queue", "k_drop_queue", "k_obs_mixed"; "" before the first launch).  Diagnostics for tests and bench.py: which
  * configuration class a workload landed in (no reference counterpart).  The string is static.
@@ -593,6 +596,75 @@ int fs_policy_pair_act_dev(fs_handle h, const fs_policy* av, const fs_policy* ad
 int fs_policy_pair_rollout_dev(fs_handle h, const fs_policy* av, const fs_policy* adversary, float perturb_weight,
                                int num_steps, int reset_done, float* obs_dev /*[K+1, R, D]*/, float* act_dev /*[2, K, R]*/,
                                float* logp_dev /*[2, K, R]*/, float* rew_dev /*[K, R]*/, uint8_t* done_dev /*[K, R]*/);
+
+/* ---- policy populations (fs_population) ----------------------------------------
+ * M weight sets in ONE launch of the scalar-head policy kernels: replica r evaluates the set at
+ * pol->weights_dev + (r / group) * stride; everything else -- log_std_dev, the seed, the draw counters, greedy, every
+ * buffer layout -- is fs_policy_act_dev's and fs_policy_rollout_dev's.  A workgroup of those kernels copies the weights
+ * into its LDS once per launch and serves fs_population_granule (16) replicas, so group must be a multiple of the granule:
+ * the member is then the same for a whole workgroup and nothing after the load differs from the single-policy launch.
+ * Rows [m group, (m + 1) group) of a population fragment equal, bit for bit, the same rows of fs_policy_rollout_dev with
+ * weight set m on an identically created handle; stride = 0 (all share set 0) and members = 1 equal it on every row.
+ * fs_last_kernel: the family's name with Population among its tags ("k_ring_policy<Population>",
+ * "k_ring_policy<POMA,Population>", "k_loop_policy<Population>", "k_policy_act<Population>").
+ * Refused before anything launches, FS_ERR_INVALID / FS_ERR_UNSUPPORTED with a message that starts "fs_population: ":
+ * group not a multiple of the granule; members * group != num_replicas; 0 < stride < the policy's own size in floats;
+ * the action-vector heads (FS_ENV_MERGE_PO, FS_ENV_BOTTLENECK_DV) and FS_ENV_MERGE_MA (their kernels give a WAVE to a
+ * replica and read first-layer or output weights past the LDS copy).  There is no population form of fs_policy_pair.
+ * Whatever fs_policy_rollout_dev refuses on the handle is refused here with its message ("fs_policy: ..."). */
+typedef struct fs_population {
+  uint32_t struct_size;               /* sizeof(fs_population) */
+  int32_t members;                    /* M >= 1 */
+  int32_t group;                      /* replicas per member; num_replicas == members * group */
+  int32_t reserved;                   /* 0 */
+  int64_t stride;                     /* floats between consecutive members' weight sets, >= the policy's own size; 0: all share set 0 */
+} fs_population;
+
+/* replicas per workgroup of the kernel that would run for this handle and policy; < 0: a refusal (fs_last_error) */
+int fs_population_granule(fs_handle h, const fs_policy* pol);
+int fs_population_act_dev(fs_handle h, const fs_policy* pol, const fs_population* pop, const float* obs_dev,
+                          float* act_dev, float* logp_dev);
+int fs_population_rollout_dev(fs_handle h, const fs_policy* pol, const fs_population* pop, int num_steps, int reset_done,
+                              float* obs_dev, float* act_dev, float* logp_dev, float* rew_dev, uint8_t* done_dev);
+
+/* ---- evolution strategies on the device (flow_amd/csrc/flowsim_es.h) ------------
+ * ES (Salimans et al. 2017, RLlib's ES) and ARS (Mania et al. 2018, RLlib's ARS) around fs_population_rollout_dev: N
+ * antithetic pairs and E evaluation members, M = 2 N + E weight sets.  Every call is launches on the handle's stream, no
+ * host synchronisation, capturable; no float atomics; every summation order is fixed by the shapes (flowsim_es.h states
+ * each).  The noise is never stored: eps(p, e) = the library's exact Box-Muller draw (fs_config.noise_exact's sequences;
+ * oracle/refsim.py gaussian_noise(exact=True) bit for bit) of Philox key noise_seed, counter (e / 4, 0x60000000 |
+ * generation, p, 0), draw e % 4.
+ *
+ * fs_es_perturb_dev ("k_es_perturb"): weights_dev [M, stride] from theta_dev [P]: member 2 p = theta + t, member 2 p + 1 =
+ *   theta - t, t = sigma * eps(p, e) (one float32 multiply, then one float32 add / subtract); members 2 N .. M - 1 = theta.
+ *   Floats P .. stride - 1 of a row are left alone.
+ * fs_es_fitness_dev ("k_es_fitness"): rew_dev / done_dev [K, R] of a fragment -> ret_dev [R] (double), alive_dev [R],
+ *   fit_dev [M] (double).  A replica adds its rewards in double, k ascending, up to and including its first done != 0;
+ *   after that it is dead (alive = 0).  fit[m] = (sum of ret over the member's replicas, r ascending) / group.
+ *   accumulate != 0 continues from ret_dev / alive_dev as an earlier call left them; 0 starts at ret = 0, alive = 1.
+ * fs_es_weights_dev ("k_es_weights"): fit_dev [0, 2 N) -> u_dev [N] (float32), stats_dev [4] (double) = {mean, min, max
+ *   of the 2 N perturbed returns, mean of the E evaluation members (NaN with E = 0)}.
+ *   FS_ES_MODE_ES: rank = position in the ascending order of (value, index); c = (float)(rank / (2 N - 1) - 0.5), the
+ *     quotient and difference in double; u[p] = (c[2 p] - c[2 p + 1]) / (float)N in float32.
+ *   FS_ES_MODE_ARS: the top directions by max(F+, F-) descending (ties: p ascending) are kept (top <= 0 or > N: all N);
+ *     s = the population standard deviation of the 2 b kept returns, in double (mean and squared deviations summed over
+ *     the kept directions in ascending p, F+ before F-); u[p] = (float)((F+ - F-) / (b s)) kept, 0 otherwise; s == 0: all 0.
+ * fs_es_grad_dev ("k_es_grad"): g[e] = sum over p of u[p] * eps(p, e) in float32 (order: flowsim_es.h), the noise
+ *   regenerated.  FS_ES_MODE_ES: grad_dev[e] = -g[e] + l2 * theta_dev[e] (what fs_adam_dev takes); theta is not written.
+ *   FS_ES_MODE_ARS: theta_dev[e] = theta_dev[e] + stepsize * g[e] in the same launch; grad_dev may be NULL.
+ *   work_dev: fs_es_workspace(num_params, pairs) floats.  pairs <= 2048, num_params <= 2^24. */
+enum { FS_ES_MODE_ES = 0, FS_ES_MODE_ARS = 1 };
+#define FS_ES_MAX_PAIRS 2048
+int fs_es_perturb_dev(fs_handle h, int64_t num_params, int pairs, int eval_members, int64_t stride, const float* theta_dev,
+                      float sigma, uint64_t noise_seed, uint32_t generation, float* weights_dev);
+int fs_es_fitness_dev(fs_handle h, int num_steps, int members, int group, const float* rew_dev, const uint8_t* done_dev,
+                      int accumulate, double* ret_dev, uint8_t* alive_dev, double* fit_dev);
+int fs_es_weights_dev(fs_handle h, int mode, int pairs, int eval_members, int top, const double* fit_dev, float* u_dev,
+                      double* stats_dev);
+size_t fs_es_workspace(int64_t num_params, int pairs);
+int fs_es_grad_dev(fs_handle h, int mode, int64_t num_params, int pairs, const float* u_dev, uint64_t noise_seed,
+                   uint32_t generation, float l2_or_stepsize, float* theta_dev, float* grad_dev, float* work_dev,
+                   size_t work_floats);
 
 /* ---- the PPO update on the device ---------------------------------------------
  * What examples/train_vec.py ppo_update runs in torch between two rollouts -- the no_grad pass, generalised advantage
