@@ -252,35 +252,35 @@ __device__ __forceinline__ void pair_step_asm_b(f2& V, f2& X, f2& H, f2& DVL, f2
 
 // The FS_MIXED step (state float64, controller float32), same construction.  Register map: V32 (float images of
 // the speeds) v[112:113], XA v[114:115], XB v[116:117] (positions, float64), VA v[118:119], VB v[138:139] (speeds,
-// float64), H v[140:141], DVL v[142:143], HH v[120:121], Y v[122:123], A v[124:125], B v[126:127], OV v[128:129],
-// C v[130:131], D v[132:133], E v[134:135], F v[136:137], OXr v[144:145].
+// float64), H v[140:141], DVL v[142:143], v[120:121] (temporaries of the observations), Y v[122:123], A v[124:125], B v[126:127], OV v[128:129],
+// C v[130:131], D v[132:133], E v[134:135], F v[136:137], OXr v[144:145], WA v[156:157], WB v[158:159] (the wrap addends
+// of the gaps: mixed_step_asm_b).
+// H holds the CLAMPED headways (|h| < 1e-3 ? 1e-3 : h): the prologue and the slow step clamp it in place; a fast step
+// has shown that the clamp does not bind.  (The speed-mode part's gap max(h, 1e-3) is the same on the clamped value: a
+// clamped h was below 1e-3 and both give 1e-3; a NaN h is kept by the clamp and dropped by the max either way.)
 struct MixedConsts {
   f2 p0, p1, p2, p5, rc_v0, tsab, rc_ab, one, gap2, vmask, tvm;
   float c1e3;
   double dt, ramp, L, rc_L, rc_ms, len_b, len_next, zero;
+  unsigned L_lo, L_hi, thr;      // the words of L (the slow step's WA / WB selects); min(hi32(L), 0x457CED91): mixed_step_asm_b
   unsigned long long last_mask;
 };
 __device__ __forceinline__ void mixed_step_asm_a(f2& V32, double& XA, double& XB, double& VA, double& VB, f2& H, f2& DVL,
                                                  f2& OV, const MixedConsts& c) {
-  unsigned long long sa, sb;
   asm volatile(
       // ---- IDMController.get_accel in float32 on the rounded speeds / headways (as pair_step_asm)
-      "v_cmp_nlt_f32_e64 %[sa], |v140|, %[c1e3]\n"
-      "v_cmp_nlt_f32_e64 %[sb], |v141|, %[c1e3]\n"
       "v_pk_mul_f32 v[124:125], v[112:113], v[142:143]\n"
       "v_pk_mul_f32 v[126:127], v[124:125], %[rcab]\n"
       "v_pk_fma_f32 v[130:131], v[126:127], %[tsab], v[124:125] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
       "v_pk_fma_f32 v[126:127], v[130:131], %[rcab], v[126:127]\n"
-      "v_cndmask_b32_e64 v120, %[c1e3], v140, %[sa]\n"
-      "v_cndmask_b32_e64 v121, %[c1e3], v141, %[sb]\n"
       "v_pk_mul_f32 v[124:125], v[112:113], %[rcv0]\n"
-      "v_rcp_f32_e32 v122, v120\n"
-      "v_rcp_f32_e32 v123, v121\n"
+      "v_rcp_f32_e32 v122, v140\n"
+      "v_rcp_f32_e32 v123, v141\n"
       "v_pk_fma_f32 v[130:131], v[124:125], %[p0], v[112:113] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
       "v_pk_fma_f32 v[124:125], v[130:131], %[rcv0], v[124:125]\n"
       "v_pk_mul_f32 v[130:131], v[112:113], %[p1]\n"
       "v_pk_add_f32 v[130:131], v[130:131], v[126:127]\n"
-      "v_pk_fma_f32 v[126:127], v[120:121], v[122:123], %[one] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
+      "v_pk_fma_f32 v[126:127], v[140:141], v[122:123], %[one] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
       "v_max_f32_e32 v130, 0, v130\n"
       "v_max_f32_e32 v131, 0, v131\n"
       "v_pk_fma_f32 v[122:123], v[126:127], v[122:123], v[122:123]\n"
@@ -288,10 +288,10 @@ __device__ __forceinline__ void mixed_step_asm_a(f2& V32, double& XA, double& XB
       "v_pk_mul_f32 v[124:125], v[124:125], v[124:125]\n"
       "v_pk_mul_f32 v[126:127], v[130:131], v[122:123]\n"
       "v_pk_mul_f32 v[124:125], v[124:125], v[124:125]\n"
-      "v_pk_fma_f32 v[132:133], v[120:121], v[126:127], v[130:131] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
+      "v_pk_fma_f32 v[132:133], v[140:141], v[126:127], v[130:131] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
       "v_pk_add_f32 v[124:125], %[one], v[124:125] neg_lo:[0,1] neg_hi:[0,1]\n"
       "v_pk_fma_f32 v[126:127], v[132:133], v[122:123], v[126:127]\n"
-      "v_pk_fma_f32 v[132:133], v[120:121], v[126:127], v[130:131] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
+      "v_pk_fma_f32 v[132:133], v[140:141], v[126:127], v[130:131] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
       "v_pk_fma_f32 v[126:127], v[132:133], v[122:123], v[126:127]\n"
       "v_pk_mul_f32 v[126:127], v[126:127], v[126:127]\n"
       "v_pk_add_f32 v[124:125], v[124:125], v[126:127] neg_lo:[0,1] neg_hi:[0,1]\n"
@@ -311,31 +311,21 @@ __device__ __forceinline__ void mixed_step_asm_a(f2& V32, double& XA, double& XB
       "v_mul_f64 v[132:133], v[132:133], %[ramp]\n"
       "v_add_f64 v[118:119], v[118:119], v[130:131]\n"                                      // VA = v'
       "v_add_f64 v[138:139], v[138:139], v[132:133]\n"                                      // VB
-      "v_mul_f64 v[130:131], v[118:119], %[dt]\n"
-      "v_mul_f64 v[132:133], v[138:139], %[dt]\n"
-      "v_add_f64 v[130:131], v[114:115], v[130:131]\n"                                      // x_new
-      "v_add_f64 v[132:133], v[116:117], v[132:133]\n"
-      "v_add_f64 v[134:135], v[130:131], -%[L]\n"                                           // x_new - L
-      "v_add_f64 v[136:137], v[132:133], -%[L]\n"
       "v_cvt_f32_f64_e32 v112, v[118:119]\n"                                                // V32 = float images
       "v_cvt_f32_f64_e32 v113, v[138:139]\n"
-      "v_cmp_gt_i32_e64 %[sa], 0, v135\n"                                                   // x_new - L < 0 (sign)
-      "v_cmp_gt_i32_e64 %[sb], 0, v137\n"
+      "v_mul_f64 v[130:131], v[118:119], %[dt]\n"
+      "v_mul_f64 v[132:133], v[138:139], %[dt]\n"
+      "v_add_f64 v[114:115], v[114:115], v[130:131]\n"                                      // XA = x_new (unwrapped)
+      "v_add_f64 v[116:117], v[116:117], v[132:133]\n"                                      // XB
       "v_mul_f64 v[120:121], v[118:119], %[rcms]\n"                                         // observation v' / max_speed
       "v_mul_f64 v[122:123], v[138:139], %[rcms]\n"
-      "v_cndmask_b32_e64 v114, v134, v130, %[sa]\n"                                         // XA = x'
-      "v_cndmask_b32_e64 v115, v135, v131, %[sa]\n"
-      "v_cndmask_b32_e64 v116, v136, v132, %[sb]\n"                                         // XB
-      "v_cndmask_b32_e64 v117, v137, v133, %[sb]\n"
       "v_cvt_f32_f64_e32 v128, v[120:121]\n"
       "v_cvt_f32_f64_e32 v129, v[122:123]\n"
       : "+{v[112:113]}"(V32), "+{v[114:115]}"(XA), "+{v[116:117]}"(XB), "+{v[118:119]}"(VA), "+{v[138:139]}"(VB),
-        "+{v[140:141]}"(H), "+{v[142:143]}"(DVL), "={v[128:129]}"(OV), [sa] "=&s"(sa), [sb] "=&s"(sb)
-      : [c1e3] "v"(c.c1e3), [rcab] "v"(c.rc_ab), [tsab] "v"(c.tsab), [rcv0] "v"(c.rc_v0), [p0] "v"(c.p0),
-        [p1] "v"(c.p1), [p2] "v"(c.p2), [p5] "v"(c.p5), [one] "v"(c.one), [dt] "v"(c.dt), [ramp] "v"(c.ramp),
-        [L] "v"(c.L), [rcms] "v"(c.rc_ms), [zero] "v"(c.zero)
-      : "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v130", "v131", "v132", "v133", "v134",
-        "v135", "v136", "v137");
+        "+{v[140:141]}"(H), "+{v[142:143]}"(DVL), "={v[128:129]}"(OV)
+      : [rcab] "v"(c.rc_ab), [tsab] "v"(c.tsab), [rcv0] "v"(c.rc_v0), [p0] "v"(c.p0), [p1] "v"(c.p1), [p2] "v"(c.p2),
+        [p5] "v"(c.p5), [one] "v"(c.one), [dt] "v"(c.dt), [ramp] "v"(c.ramp), [rcms] "v"(c.rc_ms), [zero] "v"(c.zero)
+      : "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v130", "v131", "v132", "v133");
 }
 // mixed part A with the speed-mode clamps: SUMO's acceleration in float32 next to the controller's (temporaries G
 // v[146:147], YS v[148:149], S v[150:151], Q v[152:153], R v[154:155], second residual v[134:135]), the clamps in
@@ -344,10 +334,7 @@ struct MixedSumoConsts { double fl0a, fl0b, adta, adtb, ddta, ddtb; };
 __device__ __forceinline__ void mixed_step_asm_a_sm(f2& V32, double& XA, double& XB, double& VA, double& VB, f2& H,
                                                     f2& DVL, f2& OV, const MixedConsts& c, const SumoPair& m,
                                                     const MixedSumoConsts& d) {
-  unsigned long long sa, sb;
   asm volatile(
-      "v_cmp_nlt_f32_e64 %[sa], |v140|, %[c1e3]\n"
-      "v_cmp_nlt_f32_e64 %[sb], |v141|, %[c1e3]\n"
       "v_pk_mul_f32 v[124:125], v[112:113], v[142:143]\n"
       "v_pk_mul_f32 v[126:127], v[124:125], %[rcab]\n"
       "v_pk_mul_f32 v[150:151], v[124:125], %[rcts]\n"
@@ -355,13 +342,11 @@ __device__ __forceinline__ void mixed_step_asm_a_sm(f2& V32, double& XA, double&
       "v_pk_fma_f32 v[152:153], v[150:151], %[ts], v[124:125] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
       "v_pk_fma_f32 v[126:127], v[130:131], %[rcab], v[126:127]\n"
       "v_pk_fma_f32 v[150:151], v[152:153], %[rcts], v[150:151]\n"                          // S = num / ts
-      "v_cndmask_b32_e64 v120, %[c1e3], v140, %[sa]\n"
-      "v_cndmask_b32_e64 v121, %[c1e3], v141, %[sb]\n"
       "v_max_f32_e32 v146, v140, %[c1e3]\n"                                                 // G = max(h, 1e-3)
       "v_max_f32_e32 v147, v141, %[c1e3]\n"
       "v_pk_mul_f32 v[124:125], v[112:113], %[rcv0]\n"
-      "v_rcp_f32_e32 v122, v120\n"
-      "v_rcp_f32_e32 v123, v121\n"
+      "v_rcp_f32_e32 v122, v140\n"
+      "v_rcp_f32_e32 v123, v141\n"
       "v_rcp_f32_e32 v148, v146\n"
       "v_rcp_f32_e32 v149, v147\n"
       "v_pk_fma_f32 v[130:131], v[124:125], %[p0], v[112:113] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
@@ -372,7 +357,7 @@ __device__ __forceinline__ void mixed_step_asm_a_sm(f2& V32, double& XA, double&
       "v_pk_fma_f32 v[154:155], v[152:153], %[rcsm], v[154:155]\n"                          // R = v / maxSpeed
       "v_pk_add_f32 v[130:131], v[130:131], v[126:127]\n"
       "v_pk_mul_f32 v[152:153], v[112:113], %[tau]\n"
-      "v_pk_fma_f32 v[126:127], v[120:121], v[122:123], %[one] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
+      "v_pk_fma_f32 v[126:127], v[140:141], v[122:123], %[one] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
       "v_pk_add_f32 v[150:151], v[152:153], v[150:151]\n"                                   // dyn_s
       "v_pk_fma_f32 v[152:153], v[146:147], v[148:149], %[one] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
       "v_max_f32_e32 v130, 0, v130\n"
@@ -389,13 +374,13 @@ __device__ __forceinline__ void mixed_step_asm_a_sm(f2& V32, double& XA, double&
       "v_pk_mul_f32 v[152:153], v[150:151], v[148:149]\n"                                   // q0_s
       "v_pk_mul_f32 v[124:125], v[124:125], v[124:125]\n"
       "v_pk_mul_f32 v[154:155], v[154:155], v[154:155]\n"
-      "v_pk_fma_f32 v[132:133], v[120:121], v[126:127], v[130:131] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
+      "v_pk_fma_f32 v[132:133], v[140:141], v[126:127], v[130:131] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
       "v_pk_fma_f32 v[134:135], v[146:147], v[152:153], v[150:151] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
       "v_pk_add_f32 v[124:125], %[one], v[124:125] neg_lo:[0,1] neg_hi:[0,1]\n"
       "v_pk_add_f32 v[154:155], %[one], v[154:155] neg_lo:[0,1] neg_hi:[0,1]\n"
       "v_pk_fma_f32 v[126:127], v[132:133], v[122:123], v[126:127]\n"
       "v_pk_fma_f32 v[152:153], v[134:135], v[148:149], v[152:153]\n"
-      "v_pk_fma_f32 v[132:133], v[120:121], v[126:127], v[130:131] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
+      "v_pk_fma_f32 v[132:133], v[140:141], v[126:127], v[130:131] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
       "v_pk_fma_f32 v[134:135], v[146:147], v[152:153], v[150:151] neg_lo:[1,0,0] neg_hi:[1,0,0]\n"
       "v_pk_fma_f32 v[126:127], v[132:133], v[122:123], v[126:127]\n"
       "v_pk_fma_f32 v[152:153], v[134:135], v[148:149], v[152:153]\n"                       // Q = ss / gap
@@ -438,38 +423,69 @@ __device__ __forceinline__ void mixed_step_asm_a_sm(f2& V32, double& XA, double&
       "v_add_f64 v[136:137], v[138:139], -%[ddtb]\n"
       "v_max_f64 v[118:119], v[130:131], v[134:135]\n"                                      // VA = v'
       "v_max_f64 v[138:139], v[132:133], v[136:137]\n"                                      // VB
-      "v_mul_f64 v[130:131], v[118:119], %[dt]\n"
-      "v_mul_f64 v[132:133], v[138:139], %[dt]\n"
-      "v_add_f64 v[130:131], v[114:115], v[130:131]\n"                                      // x_new
-      "v_add_f64 v[132:133], v[116:117], v[132:133]\n"
-      "v_add_f64 v[134:135], v[130:131], -%[L]\n"                                           // x_new - L
-      "v_add_f64 v[136:137], v[132:133], -%[L]\n"
       "v_cvt_f32_f64_e32 v112, v[118:119]\n"                                                // V32 = float images
       "v_cvt_f32_f64_e32 v113, v[138:139]\n"
-      "v_cmp_gt_i32_e64 %[sa], 0, v135\n"                                                   // x_new - L < 0 (sign)
-      "v_cmp_gt_i32_e64 %[sb], 0, v137\n"
+      "v_mul_f64 v[130:131], v[118:119], %[dt]\n"
+      "v_mul_f64 v[132:133], v[138:139], %[dt]\n"
+      "v_add_f64 v[114:115], v[114:115], v[130:131]\n"                                      // XA = x_new (unwrapped)
+      "v_add_f64 v[116:117], v[116:117], v[132:133]\n"                                      // XB
       "v_mul_f64 v[120:121], v[118:119], %[rcms]\n"                                         // observation v' / max_speed
       "v_mul_f64 v[122:123], v[138:139], %[rcms]\n"
-      "v_cndmask_b32_e64 v114, v134, v130, %[sa]\n"                                         // XA = x'
-      "v_cndmask_b32_e64 v115, v135, v131, %[sa]\n"
-      "v_cndmask_b32_e64 v116, v136, v132, %[sb]\n"                                         // XB
-      "v_cndmask_b32_e64 v117, v137, v133, %[sb]\n"
       "v_cvt_f32_f64_e32 v128, v[120:121]\n"
       "v_cvt_f32_f64_e32 v129, v[122:123]\n"
       : "+{v[112:113]}"(V32), "+{v[114:115]}"(XA), "+{v[116:117]}"(XB), "+{v[118:119]}"(VA), "+{v[138:139]}"(VB),
-        "+{v[140:141]}"(H), "+{v[142:143]}"(DVL), "={v[128:129]}"(OV), [sa] "=&s"(sa), [sb] "=&s"(sb)
+        "+{v[140:141]}"(H), "+{v[142:143]}"(DVL), "={v[128:129]}"(OV)
       : [c1e3] "v"(c.c1e3), [rcab] "v"(c.rc_ab), [tsab] "v"(c.tsab), [rcv0] "v"(c.rc_v0), [p0] "v"(c.p0),
         [p1] "v"(c.p1), [p2] "v"(c.p2), [p5] "v"(c.p5), [one] "v"(c.one), [dt] "v"(c.dt), [ramp] "v"(c.ramp),
-        [L] "v"(c.L), [rcms] "v"(c.rc_ms), [zero] "v"(c.zero), [rcts] "v"(m.rc_ts), [ts] "v"(m.ts),
+        [rcms] "v"(c.rc_ms), [zero] "v"(c.zero), [rcts] "v"(m.rc_ts), [ts] "v"(m.ts),
         [rcsm] "v"(m.rc_smax), [smax] "v"(m.smax), [tau] "v"(m.tau), [mgap] "v"(m.min_gap), [maxa] "v"(m.maxa),
         [fl0a] "v"(d.fl0a), [fl0b] "v"(d.fl0b), [adta] "v"(d.adta), [adtb] "v"(d.adtb), [ddta] "v"(d.ddta),
         [ddtb] "v"(d.ddtb)
       : "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v130", "v131", "v132", "v133", "v134",
         "v135", "v136", "v137", "v146", "v147", "v148", "v149", "v150", "v151", "v152", "v153", "v154", "v155");
 }
-__device__ __forceinline__ void mixed_step_asm_b(f2& V32, double& XA, double& XB, f2& H, f2& DVL, f2& OX,
-                                                 unsigned& crash_bits, float& sq, const MixedConsts& c) {
-  unsigned long long sa, sb;
+// part B, the FAST form: new neighbour snapshot, reward term, position observation -- and the wave-wide predicate `need`
+// ("some lane of this wave needs the full form of this step": mixed_step_asm_slow).
+//
+// What the fast step leaves out are the three groups of selects that only rare events need:
+//   wrap of the positions   x' = x_new >= L ? x_new - L : x_new     part A writes x_new into XA / XB;
+//   wrap of the gaps        d' = d < 0 ? d + L : d                  here d' = d + W, W in {0.0, L} per lane and vehicle
+//                                                                   (WA, WB: set from the real compare d < 0 by the
+//                                                                   kernel's prologue and by every slow step);
+//   clamp of the headways   hh = |h| < 1e-3 ? 1e-3 : h              part A reads H itself.
+// A lane raises `need` when u = max(hi32(x_newA), hi32(x_newB), hi32(dA'), hi32(dB'), bits(m) - bits(1e-3f)) >= thr as
+// unsigned integers, m = min(hA, hB) and thr = min(hi32(L), 0x457CED91) (hi32 = upper word of the float64).
+// NO FALSE NEGATIVE -- if no lane of the wave raises it, every value the fast step leaves equals the full form's:
+//   * a float64 y with hi32(y) < hi32(L) has its sign clear, is finite and < L (non-negative doubles order like their
+//     bit patterns; a negative, infinite or NaN y has hi32(y) >= 0x7FF00000 > hi32(L) for the finite positive L).  thr <=
+//     hi32(L), so u < thr gives 0 <= y < L for the four float64 terms.
+//   * positions: 0 <= x_new < L, so x_new - L < 0 and the full form's select takes x_new.  This holds for every lane of
+//     the wave, so the neighbour's position read through DPP is the wrapped one too, and d = x_leader - x is the full form's.
+//   * gaps, W = 0: d' = d + 0.0 >= +0.  A negative d would give d' = d < 0 (and d is never -0: a difference that is zero
+//     rounds to +0), so d >= +0, the full form's select takes d, and d + 0.0 == d bit for bit.
+//     W = L: d' = RN(d + L) < L.  d >= +0 would give RN(d + L) >= RN(0 + L) = L (rounding is monotonic), so d < 0, the
+//     full form's select takes d + L -- the instruction executed here.  So a W that does not agree with the sign of d (after
+//     a wrap, an overtake, or for any other reason) always shows as d' < 0 or d' >= L: the test is made on the result, not
+//     on a belief about W.
+//   * headways: bits(m) - bits(1e-3f) wraps to >= 0xC57CED91 for +0 <= m < 1e-3f and is >= 0x80000000 - 0x3A83126F =
+//     0x457CED91 for every m with the sign bit set; both are >= thr.  So u < thr gives m >= 1e-3f (or m NaN, see below),
+//     both headways are >= 1e-3, |h| < 1e-3 is false and the clamp takes h.  v_min_f32 returns the other operand for a NaN:
+//     a NaN headway is not clamped by the full form either (its compare is "not less than"), and it comes from a NaN d'
+//     whose hi32 raises `need` anyway.
+//   * collision term: sign(m - crash_gap) == sign(min(hA - crash_gap, hB - crash_gap)) for non-NaN headways: both are set
+//     exactly when some h < crash_gap (a non-zero difference never rounds to zero, denormals are kept; a zero one is +0).
+// A false positive costs time only.  There is none on the headline configuration: for m >= 1e-3f the last term is bits(m) -
+// 0x3A83126F, far below hi32(L) for a headway on a ring (m = 200 m: 0x08C4ED91 against hi32(230.4) = 0x406CCCCC), and the
+// predicate fires in exactly the 8.4 % of wave-steps in which a vehicle of the wave passes the seam (tests/
+// test_pair_fastpath_cpu.py).
+// The v_cmp stands 8 instructions before the end of the block: the mask is long written when the scalar compare in front
+// of the branch reads it (read at once, a VALU-written mask costs a lone wave ~35 cycles: flowsim_fig8.h).  The common
+// path falls through; the slow form is out of line (tests/test_pair_fastpath_codegen.py).  Measured in one call
+// (scripts/ubench/pair_bench.hip, 4096 x 22 x 1500): 0.391-0.396 ms before, 0.374-0.379 ms with this, 0.491-0.498 ms
+// with every step slow, 0.345-0.359 ms without the branch (FS_DIAG_NEVER_SLOW); the counters: DESIGN.md section 4.0.
+__device__ __forceinline__ void mixed_step_asm_b(f2& V32, double& XA, double& XB, f2& H, f2& DVL, f2& OX, const double& WA,
+                                                 const double& WB, float& ct, float& sq, unsigned long long& need,
+                                                 const MixedConsts& c) {
   asm volatile(
       // ---- new snapshot: v - v_leader (float32 images), gaps in float64
       "v_sub_f32_e32 v142, v112, v113\n"
@@ -479,40 +495,96 @@ __device__ __forceinline__ void mixed_step_asm_b(f2& V32, double& XA, double& XB
       "v_mov_b32_dpp v131, v115 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
       "v_mov_b32_dpp v132, v114 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
       "v_mov_b32_dpp v133, v115 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
-      "v_cndmask_b32_e64 v143, v143, v124, %[last]\n"
+      "v_add_f64 v[134:135], v[116:117], -v[114:115]\n"                                     // dA = xB - xA
       "v_cndmask_b32_e64 v130, v130, v132, %[last]\n"
       "v_cndmask_b32_e64 v131, v131, v133, %[last]\n"
+      "v_add_f64 v[134:135], v[134:135], %[wa]\n"                                           // dA' = dA + WA
+      "v_add_f64 v[136:137], v[130:131], -v[116:117]\n"                                     // dB = x_next - xB
+      "v_cndmask_b32_e64 v143, v143, v124, %[last]\n"
+      "v_add_f64 v[120:121], v[134:135], -%[lenb]\n"
+      "v_add_f64 v[136:137], v[136:137], %[wb]\n"                                           // dB' = dB + WB
+      "v_max3_u32 v126, v115, v117, v135\n"
+      "v_add_f64 v[122:123], v[136:137], -%[lennext]\n"
+      "v_cvt_f32_f64_e32 v140, v[120:121]\n"                                                // H = new headways (float32)
+      "v_cvt_f32_f64_e32 v141, v[122:123]\n"
+      "v_min_f32_e32 v127, v140, v141\n"                                                    // m
+      "v_sub_u32_e32 v125, v127, %[c1e3]\n"                                                 // bits(m) - bits(1e-3f)
+      "v_max3_u32 v126, v126, v137, v125\n"
+      "v_cmp_le_u32_e64 %[need], %[thr], v126\n"
+      // ---- independent of the predicate: observation x' / L, reward term, collision term (S12)
+      "v_mul_f64 v[120:121], v[114:115], %[rcL]\n"
+      "v_mul_f64 v[122:123], v[116:117], %[rcL]\n"
+      "v_pk_fma_f32 v[124:125], v[112:113], %[vmask], %[tvm]\n"
+      "v_cvt_f32_f64_e32 v144, v[120:121]\n"
+      "v_cvt_f32_f64_e32 v145, v[122:123]\n"
+      "v_pk_mul_f32 v[124:125], v[124:125], v[124:125]\n"
+      "v_sub_f32_e32 %[ct], v127, %[gap]\n"                                                 // sign: some h < crash_gap
+      "v_add_f32_e32 %[sq], v124, v125\n"
+      : "+{v[112:113]}"(V32), "+{v[114:115]}"(XA), "+{v[116:117]}"(XB), "+{v[140:141]}"(H), "+{v[142:143]}"(DVL),
+        "=&{v[144:145]}"(OX), [ct] "=&v"(ct), [sq] "=&v"(sq), [need] "=&s"(need)
+      : [wa] "{v[156:157]}"(WA), [wb] "{v[158:159]}"(WB), [rcL] "v"(c.rc_L), [gap] "v"(c.gap2.x), [vmask] "v"(c.vmask), [tvm] "v"(c.tvm),
+        [lenb] "v"(c.len_b), [lennext] "v"(c.len_next), [c1e3] "v"(c.c1e3), [thr] "v"(c.thr), [last] "s"(c.last_mask)
+      : "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v130", "v131", "v132", "v133", "v134", "v135",
+        "v136", "v137");
+}
+// The SLOW form of the step's tail, out of line: entered by the whole wave when any lane raised `need`, with x_new in
+// XA / XB.  These are the full form's instructions -- positions wrapped by the sign of x_new - L, the neighbour re-read,
+// the gaps selected by the sign of d, WA / WB set from that compare, the headways, the collision term (which reads the
+// unclamped headways), then H clamped in place for the next part A -- and everything part B derived from the unwrapped
+// positions (x' / L, H, the collision term) is formed again.  v - v_leader and the reward term do not depend on positions.
+__device__ __forceinline__ void mixed_step_asm_slow(double& XA, double& XB, f2& H, f2& OX, double& WA, double& WB, float& ct,
+                                                    const MixedConsts& c) {
+  unsigned long long sa, sb;
+  asm volatile(
+      "v_add_f64 v[134:135], v[114:115], -%[L]\n"                                           // x_new - L
+      "v_add_f64 v[136:137], v[116:117], -%[L]\n"
+      "v_cmp_gt_i32_e64 %[sa], 0, v135\n"                                                   // x_new - L < 0 (sign)
+      "v_cmp_gt_i32_e64 %[sb], 0, v137\n"
+      "s_nop 0\n"
+      "v_cndmask_b32_e64 v114, v134, v114, %[sa]\n"                                         // XA = x'
+      "v_cndmask_b32_e64 v115, v135, v115, %[sa]\n"
+      "v_cndmask_b32_e64 v116, v136, v116, %[sb]\n"                                         // XB
+      "v_cndmask_b32_e64 v117, v137, v117, %[sb]\n"
       "v_mul_f64 v[120:121], v[114:115], %[rcL]\n"                                          // observation x' / L
       "v_mul_f64 v[122:123], v[116:117], %[rcL]\n"
       "v_add_f64 v[134:135], v[116:117], -v[114:115]\n"                                     // dA = xB - xA
-      "v_add_f64 v[136:137], v[130:131], -v[116:117]\n"                                     // dB = x_next - xB
       "v_cvt_f32_f64_e32 v144, v[120:121]\n"
       "v_cvt_f32_f64_e32 v145, v[122:123]\n"
-      "v_add_f64 v[130:131], v[134:135], %[L]\n"
+      "v_add_f64 v[126:127], v[134:135], %[L]\n"
+      "v_mov_b32_dpp v130, v114 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"        // position of the next lane's A
+      "v_mov_b32_dpp v131, v115 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
+      "v_mov_b32_dpp v132, v114 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp v133, v115 row_newbcast:0 row_mask:0xf bank_mask:0xf\n"
+      "v_cmp_gt_i32_e64 %[sa], 0, v135\n"                                                   // dA < 0 (d is never -0)
+      "v_cndmask_b32_e64 v130, v130, v132, %[last]\n"
+      "v_cndmask_b32_e64 v131, v131, v133, %[last]\n"
+      "v_add_f64 v[136:137], v[130:131], -v[116:117]\n"                                     // dB = x_next - xB
+      "v_cndmask_b32_e64 v134, v134, v126, %[sa]\n"
+      "v_cndmask_b32_e64 v135, v135, v127, %[sa]\n"
+      "v_cndmask_b32_e64 v156, 0, %[Llo], %[sa]\n"                                          // WA = dA < 0 ? L : 0.0
+      "v_cndmask_b32_e64 v157, 0, %[Lhi], %[sa]\n"
       "v_add_f64 v[132:133], v[136:137], %[L]\n"
-      "v_cmp_gt_i32_e64 %[sa], 0, v135\n"                                                   // d < 0 (d is never -0)
-      "v_cmp_gt_i32_e64 %[sb], 0, v137\n"
-      "v_pk_fma_f32 v[124:125], v[112:113], %[vmask], %[tvm]\n"                             // reward term
-      "v_pk_mul_f32 v[124:125], v[124:125], v[124:125]\n"
-      "v_cndmask_b32_e64 v134, v134, v130, %[sa]\n"
-      "v_cndmask_b32_e64 v135, v135, v131, %[sa]\n"
+      "v_cmp_gt_i32_e64 %[sb], 0, v137\n"                                                   // dB < 0
+      "v_add_f64 v[134:135], v[134:135], -%[lenb]\n"
+      "v_cvt_f32_f64_e32 v140, v[134:135]\n"                                                // H = new headways (float32)
       "v_cndmask_b32_e64 v136, v136, v132, %[sb]\n"
       "v_cndmask_b32_e64 v137, v137, v133, %[sb]\n"
-      "v_add_f32_e32 %[sq], v124, v125\n"
-      "v_add_f64 v[134:135], v[134:135], -%[lenb]\n"
+      "v_cndmask_b32_e64 v158, 0, %[Llo], %[sb]\n"                                          // WB
+      "v_cndmask_b32_e64 v159, 0, %[Lhi], %[sb]\n"
       "v_add_f64 v[136:137], v[136:137], -%[lennext]\n"
-      "v_cvt_f32_f64_e32 v140, v[134:135]\n"                                                // H = new headways (float32)
       "v_cvt_f32_f64_e32 v141, v[136:137]\n"
-      // ---- collision (S12)
+      // ---- collision (S12) on the unclamped headways, then the clamp |h| < 1e-3 ? 1e-3 : h in place
       "v_pk_add_f32 v[126:127], v[140:141], %[gap2] neg_lo:[0,1] neg_hi:[0,1]\n"
-      "v_min_f32_e32 v126, v126, v127\n"
-      "v_alignbit_b32 %[cb], %[cb], v126, 31\n"
-      : "+{v[112:113]}"(V32), "+{v[114:115]}"(XA), "+{v[116:117]}"(XB), "+{v[140:141]}"(H), "+{v[142:143]}"(DVL),
-        "={v[144:145]}"(OX), [cb] "+v"(crash_bits), [sq] "=&v"(sq), [sa] "=&s"(sa), [sb] "=&s"(sb)
-      : [L] "v"(c.L), [rcL] "v"(c.rc_L), [gap2] "v"(c.gap2), [vmask] "v"(c.vmask), [tvm] "v"(c.tvm),
-        [lenb] "v"(c.len_b), [lennext] "v"(c.len_next), [last] "s"(c.last_mask)
-      : "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v130", "v131", "v132", "v133", "v134",
-        "v135", "v136", "v137");
+      "v_cmp_nlt_f32_e64 %[sa], |v140|, %[c1e3]\n"
+      "v_cmp_nlt_f32_e64 %[sb], |v141|, %[c1e3]\n"
+      "v_min_f32_e32 %[ct], v126, v127\n"
+      "v_cndmask_b32_e64 v140, %[c1e3], v140, %[sa]\n"
+      "v_cndmask_b32_e64 v141, %[c1e3], v141, %[sb]\n"
+      : "+{v[114:115]}"(XA), "+{v[116:117]}"(XB), "+{v[140:141]}"(H), "+{v[144:145]}"(OX), "+{v[156:157]}"(WA),
+        "+{v[158:159]}"(WB), [ct] "+v"(ct), [sa] "=&s"(sa), [sb] "=&s"(sb)
+      : [L] "v"(c.L), [Llo] "v"(c.L_lo), [Lhi] "v"(c.L_hi), [rcL] "v"(c.rc_L), [gap2] "v"(c.gap2), [lenb] "v"(c.len_b),
+        [lennext] "v"(c.len_next), [c1e3] "v"(c.c1e3), [last] "s"(c.last_mask)
+      : "v120", "v121", "v122", "v123", "v126", "v127", "v130", "v131", "v132", "v133", "v134", "v135", "v136", "v137");
 }
 
 // T = float: the float32 bit-twin.  T = double: MIXED (see the header).  ROW = lanes per replica (N <= 2 ROW).
@@ -626,6 +698,23 @@ __global__ __launch_bounds__(256) void k_rollout_pair(DevView<T> s, int num_step
   mc.one = one; mc.gap2 = gap2; mc.vmask = vmask; mc.tvm = tvm; mc.c1e3 = 1e-3f; mc.dt = dt64; mc.ramp = ramp64;
   mc.L = L64; mc.rc_L = rc_L64; mc.rc_ms = rc_ms64; mc.len_b = double(lenB); mc.len_next = double(len_nextA);
   mc.zero = 0.0; mc.last_mask = pc.last_mask;
+  {
+    const unsigned long long Lb = __builtin_bit_cast(unsigned long long, L64);
+    mc.L_lo = unsigned(Lb); mc.L_hi = unsigned(Lb >> 32);
+    mc.thr = mc.L_hi < 0x457CED91u ? mc.L_hi : 0x457CED91u;
+  }
+  // hand-written mixed step: the wrap addends of the two gaps from the compare headway() makes, H clamped in place
+  double wA = 0.0, wB = 0.0;
+  if constexpr (ASM && MIXED) {
+    // (launch constants that are uniform would be copied from SGPRs in front of every asm block of a loop body that has
+    // branches in it: as values of an asm statement they stay in the VGPRs they are given once)
+    asm volatile("" : "+v"(mc.dt), "+v"(mc.ramp), "+v"(mc.one), "+v"(mc.zero), "+v"(mc.rc_ms), "+v"(mc.c1e3), "+v"(mc.gap2));
+    const double xn = next_a<ROW>(xdA, last, lane);
+    wA = xdB - xdA < 0.0 ? L64 : 0.0;
+    wB = xn - xdB < 0.0 ? L64 : 0.0;
+    h.x = tabs(h.x) < 1e-3f ? 1e-3f : h.x;
+    h.y = tabs(h.y) < 1e-3f ? 1e-3f : h.y;
+  }
   SumoPair sc{};
   double floor0A = 0, floor0B = 0, adtA = 0, adtB = 0, ddtA = 0, ddtB = 0;      // MIXED: the clamp constants in float64
   if constexpr (SM) {
@@ -717,7 +806,16 @@ __global__ __launch_bounds__(256) void k_rollout_pair(DevView<T> s, int num_step
         if constexpr (SM) mixed_step_asm_a_sm(v, xdA, xdB, vdA, vdB, h, dvl, ov, mc, sc, msc);
         else mixed_step_asm_a(v, xdA, xdB, vdA, vdB, h, dvl, ov, mc);
         if (slot > 0) __builtin_amdgcn_raw_buffer_store_b128(piece, rs, off_16, so - step_b32, 0);
-        mixed_step_asm_b(v, xdA, xdB, h, dvl, ox, crash_bits, sq_out, mc);
+        float ct;
+        unsigned long long need;
+        mixed_step_asm_b(v, xdA, xdB, h, dvl, ox, wA, wB, ct, sq_out, need, mc);
+#if defined(FS_DIAG_ALWAYS_SLOW)   // timing experiments (scripts/ubench/pair_bench.hip): every step takes the slow form,
+        need = ~0ull;
+#elif defined(FS_DIAG_NEVER_SLOW)  // or none does and the branch is gone (wrong results: what the test itself costs)
+        need = 0ull;
+#endif
+        if (__builtin_expect(need != 0ull, 0)) mixed_step_asm_slow(xdA, xdB, h, ox, wA, wB, ct, mc);
+        crash_bits = __builtin_amdgcn_alignbit(crash_bits, __builtin_bit_cast(unsigned, ct), 31);
         transpose_in(ov, ox);
       } else {
 #if defined(FS_DIAG_NOSTORE)   // timing experiment (scripts/dbg/pmc_variants.sh): the results stay in registers

@@ -1,6 +1,11 @@
 // pair_bench.hip -- standalone timing harness of k_rollout_pair (C2 shape) for A/B experiments: compiles in
 // seconds, variants through -D flags (FS_DIAG_* hooks in flowsim_pair.h).  Not a test: no result check.
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -I../../include -I../../flow_amd/csrc -o pair_bench pair_bench.hip
+// The mixed step's fast / slow form (mixed_step_asm_b / mixed_step_asm_slow) in three timings of one call:
+//   -DFS_DIAG_ALWAYS_SLOW   every step takes the slow form (the predicate forced; results unchanged),
+//   (nothing)               the shipped kernel,
+//   -DFS_DIAG_NEVER_SLOW    no step does and the branch is gone (WRONG results: what the test and the slow steps cost);
+// the parent's step for comparison: the same file built with -I to a checkout of the parent's flow_amd/csrc.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
