@@ -33,7 +33,8 @@ def parse_args(args):
     parser = argparse.ArgumentParser(description="Train an RL experiment from exp_configs/rl.",
                                      epilog="python train.py EXP_CONFIG")
     parser.add_argument('exp_config', type=str,
-                        help='module in exp_configs/rl/singleagent or exp_configs/rl/multiagent')
+                        help='module in exp_configs/rl/singleagent or exp_configs/rl/multiagent, or a benchmark '
+                             '(flow.benchmarks: figureeight0, figureeight1, figureeight2)')
     parser.add_argument('--rl_trainer', type=str, default="device",
                         help='device (on-GPU PPO), es or ars (evolution strategies / augmented random search on the device: '
                              'one perturbed policy per workgroup) or rllib')
@@ -45,7 +46,7 @@ def parse_args(args):
                         help='rllib: checkpoint to restore (device: --checkpoint_dir / --restore)')
     parser.add_argument('--replicas', type=int, default=1024, help='device: environment replicas in the handle')
     parser.add_argument('--fuse_policy', action='store_true',
-                        help='device: roll an action-vector policy (singleagent_merge, lord_of_the_rings) out through the fused policy + '
+                        help='device: roll an action-vector policy (singleagent_merge, lord_of_the_rings, figureeight1 / figureeight2) out through the fused policy + '
                              'step kernel instead of the captured graph; where there is none (singleagent_bottleneck), '
                              'capture the graph around the policy kernel instead of the torch module')
     parser.add_argument('--device_update', action='store_true',
@@ -102,13 +103,19 @@ def env_state_settings(flags):
 
 
 def load_experiment(name):
-    """The module of an experiment: exp_configs/rl/singleagent first, then multiagent (train.py:318-330)."""
+    """The module of an experiment: exp_configs/rl/singleagent first, then multiagent (train.py:318-330), then the
+    benchmarks package (flow.benchmarks: figureeight0 / figureeight1 / figureeight2)."""
     for pkg in ("exp_configs.rl.singleagent", "exp_configs.rl.multiagent"):
         try:
             module = __import__(pkg, fromlist=[name])
             return getattr(module, name), pkg.endswith("multiagent")
         except (ImportError, AttributeError):
             continue
+    try:
+        import importlib
+        return importlib.import_module("flow.benchmarks." + name), False
+    except ImportError:
+        pass
     raise ValueError("Unable to find experiment config %r" % name)
 
 

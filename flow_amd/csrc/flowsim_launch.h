@@ -330,6 +330,15 @@ namespace fsim {
         return fastc ? &fs::k_loop_policy<H, true, true>
                      : loop_delta4 ? &fs::k_loop_policy<H, true, false> : &fs::k_loop_policy<H, false, false>;
       };
+      if (dv.env == FS_ENV_ACCEL && dv.num_rl > 1) {      // ONE network, num_rl action columns: k_loop_policy_vec
+        const auto kv = fastc ? &fs::k_loop_policy_vec<true, true>
+                              : loop_delta4 ? &fs::k_loop_policy_vec<true, false> : &fs::k_loop_policy_vec<false, false>;
+        last_kernel = "k_loop_policy<AccelVec>";
+        const int waves_v = (dv.R + 3) / 4;
+        hipLaunchKernelGGL(kv, dim3((waves_v + 3) / 4), dim3(256), 0, stream, dv, pv, num_steps, reset_done, obs, act, logp,
+                           rew, done);
+        return launched();
+      }
       const auto k = dv.env == FS_ENV_WAVE_ATTENUATION_PO ? kernel(Int<1>())
                      : dv.env == FS_ENV_ACCEL_PO_MA ? kernel(Int<2>()) : kernel(Int<0>());
       last_kernel = dv.env == FS_ENV_ACCEL_PO_MA ? "k_loop_policy<AccelMA>" : "k_loop_policy";
@@ -340,6 +349,16 @@ namespace fsim {
     } else {
       return fail(FS_ERR_UNSUPPORTED, "k_loop_policy is a float32 kernel");
     }
+  }
+
+  // the eager form of the row-per-replica action-vector head (AccelEnv with 2 .. 16 RL vehicles on a segment-table loop):
+  // a row of 16 lanes per replica, as in k_loop_policy_vec
+  template <typename T>
+  int Sim<T>::launch_policy_act_row16(const fs::PolicyView& pv, const float* obs_in, float* act, float* logp) {
+    last_kernel = "k_policy_act_row";
+    hipLaunchKernelGGL(fs::k_policy_act_row<16>, dim3((dv.R * 16 + 255) / 256), dim3(256), 0, stream, pv, dv.R, dv.num_rl,
+                       dv.rep0, obs_in, act, logp);
+    return launched();
   }
 
   // two policies on the AccelEnv head's one RL vehicle: k_policy_pair_act (obs == nullptr) or k_loop_policy_pair, in

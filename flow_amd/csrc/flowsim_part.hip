@@ -28,6 +28,7 @@ template int Sim<FS_PART_T>::launch_k_steps<FS_PART_SEG>(const StepArgs&);
 #if FS_PART_SEG == 16
 template int Sim<FS_PART_T>::launch_loop(const StepArgs&);
 template int Sim<FS_PART_T>::launch_policy_loop16(const fs::PolicyView&, int, int, float*, float*, float*, float*, uint8_t*);
+template int Sim<FS_PART_T>::launch_policy_act_row16(const fs::PolicyView&, const float*, float*, float*);
 template int Sim<FS_PART_T>::launch_policy_pair16(const fs::PolicyView&, const fs::PolicyView&, float, int, int, const float*,
                                                   float*, float*, float*, float*, float*, uint8_t*);
 #endif

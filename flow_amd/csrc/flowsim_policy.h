@@ -16,13 +16,14 @@
 // stopped).
 //
 // The network is written ONCE: policy_layer is the 32-input layer, policy_trunk the layer sequence (narrow or WIDE first
-// layer, then the hidden layers), policy_load_trunk its weights' way into LDS.  All ten kernels that evaluate a policy
-// call that trunk -- the eager k_policy_act, k_policy_act_vec and k_policy_act_wide (fs_policy_act_dev; the last with a
-// first layer of more than 32 inputs, policy_wide_layer1, which is policy_layer over chunks), the fused k_ring_policy,
-// k_loop_policy, k_merge_queue<POLICY>, k_merge_policy and k_merge_wide_policy (flowsim_queue.h), and the two-policy
-// pair k_policy_pair_act / k_loop_policy_pair (fs_policy_pair_*: two networks on one RL vehicle) -- through policy_eval
-// (the trunk and the two-output Gaussian head), policy_vec_act (the trunk and the action-vector head) or policy_wide_act
-// (the same head behind a first layer of more than 32 inputs), so a fragment is bit-identical to
+// layer, then the hidden layers), policy_load_trunk its weights' way into LDS.  All twelve kernels that evaluate a policy
+// call that trunk -- the eager k_policy_act, k_policy_act_vec, k_policy_act_wide and k_policy_act_row (fs_policy_act_dev;
+// the third with a first layer of more than 32 inputs, policy_wide_layer1, which is policy_layer over chunks), the fused
+// k_ring_policy, k_loop_policy, k_loop_policy_vec, k_merge_queue<POLICY>, k_merge_policy and k_merge_wide_policy
+// (flowsim_queue.h), and the two-policy pair k_policy_pair_act / k_loop_policy_pair (fs_policy_pair_*: two networks on one
+// RL vehicle) -- through policy_eval (the trunk and the two-output Gaussian head), policy_vec_act (the trunk and the
+// action-vector head, a wave per replica), policy_row_vec_act (that head with a row of 16 lanes per replica) or
+// policy_wide_act (the same head behind a first layer of more than 32 inputs), so a fragment is bit-identical to
 // eager stepping by construction (tests/test_policy_gpu.py and its siblings).  Every operation is an explicit fma /
 // hardware exp2 / rcp: the arithmetic is defined by this file (a torch module with the same weights agrees to ~1e-6, not
 // bit for bit) and its float32 bits are pinned by tests/test_policy_bits_gpu.py.
@@ -596,6 +597,135 @@ __global__ __launch_bounds__(256) void k_policy_act_wide(PolicyView pv, int R, i
   }
 }
 
+// ---- the ROW-per-replica action-vector head (FS_ENV_ACCEL with num_rl = 2 .. 16 on a segment-table loop: the reference's
+// flow/benchmarks/figureeight1.py, 28 -> 7, and figureeight2.py, 28 -> 14) -------------------------------------------
+// ONE network maps the whole observation (in_dim <= 32 values in policy_wide_inputs' layout) to A = num_rl action
+// columns, with a ROW of 16 lanes per replica -- k_loop_policy's mapping, where a lane already holds the vehicle a column
+// belongs to -- instead of policy_vec_act's wave.  policy_trunk<true>, then an output layer of n_out = 2 A rows (rows
+// 0 .. A-1 the means, A .. 2A-1 the log stds: RLlib's DiagGaussian order) or of A rows next to A free log stds; output
+// row c is policy_vec_act's expression, the row's tree sum of the lanes' two products plus the bias.  Every lane is
+// told which column it samples (`col`, -1: none): the eager k_policy_act_row gives column j to lane j, the fused
+// k_loop_policy_vec gives column rl_index to the lane of that RL vehicle; a column's mean and log std are computed alike
+// whichever lane keeps them, its draw is Philox column 0x40000000 + c at the replica's counter (agent c's stream of the
+// shared-policy heads), and the joint log-probability is the columns' values added in ascending column order, so the
+// two kernels agree bit for bit by construction (tests/test_policy_loop_vec_gpu.py).
+constexpr int FS_POLICY_ROW_VEC_MAX = 16;                  // one column per lane of a row
+
+struct alignas(16) PolicyRowVecLds {
+  // the output rows in groups of four columns: [group g][half][lane j][t] = W[4 g + t][j + 16 half] -- a lane reads its two
+  // weights of four columns with two b128 reads, the 16 lanes of a row 256 consecutive bytes (w_hid's reason).  w_ls: rows
+  // A + 4 g + t (the 2 A head; zero next to free log stds).  Columns from A on: zero.
+  float w_mu[4][2][16][4];
+  float w_ls[4][2][16][4];
+  float b_mu[16];
+  float b_ls[16];                                          // the bias of row A + c, or the free log std of column c
+  float lp[16][16];                                        // [row of the workgroup][column]: the log-probabilities of a step
+};
+
+// weights -> LDS, once per launch: policy_load_trunk, then the output layer and the free log stds; one barrier
+__device__ __forceinline__ void policy_row_vec_load(const PolicyView& pv, int A, PolicyLds* L, PolicyRowVecLds* V, int tid,
+                                                    int nthreads) {
+  const float* p = policy_load_trunk(pv, L, tid, nthreads);
+  const bool free_ls = pv.log_std != nullptr;
+  const float* b = p + size_t(pv.n_out) * 32;
+  for (int e = tid; e < 16 * 32; e += nthreads) {
+    const int c = e / 32, u = e % 32;
+    V->w_mu[c >> 2][u >> 4][u & 15][c & 3] = c < A ? p[c * 32 + u] : 0.0f;
+    V->w_ls[c >> 2][u >> 4][u & 15][c & 3] = (c < A && !free_ls) ? p[(A + c) * 32 + u] : 0.0f;
+  }
+  for (int c = tid; c < 16; c += nthreads) {
+    V->b_mu[c] = c < A ? b[c] : 0.0f;
+    V->b_ls[c] = c < A ? (free_ls ? pv.log_std[c] : b[A + c]) : 0.0f;
+  }
+  __syncthreads();
+}
+
+// The action of THIS lane's column `col` (-1: none, action 0) and the joint log-probability of the row's replica (the
+// return value, the same in every lane of the row).  j: the lane within its row; (ia, ib): its two inputs in
+// policy_wide_inputs' layout; lp_row: 16 floats of LDS of THIS row (PolicyRowVecLds::lp).  Every column 0 .. A-1 must be
+// some lane's.  nzb (a fragment): this lane's Philox block kept over four steps (NoiseBlock::draw is gauss() bit for bit).
+// pv.greedy is read at run time (policy_sample<-1>).
+__device__ __forceinline__ float policy_row_vec_act(const PolicyView& pv, int A, const PolicyLds* L,
+                                                    const PolicyRowVecLds* V, float* lp_row, uint32_t replica, uint32_t ctr,
+                                                    int j, float ia, float ib, int col, float& action,
+                                                    NoiseBlock<float>* nzb = nullptr) {
+  float ha, hb;
+  policy_trunk<true>(pv, L, j, ia, ib, 0.0f, ha, hb);
+  const bool free_ls = pv.log_std != nullptr;
+  float mu = 0.0f, ls = 0.0f;
+#pragma unroll 1
+  for (int g = 0; 4 * g < A; ++g) {                        // four columns at a time (a column >= A: zeros, kept by no lane)
+    const float4 wa = *reinterpret_cast<const float4*>(V->w_mu[g][0][j]), wb = *reinterpret_cast<const float4*>(V->w_mu[g][1][j]);
+    const float4 bm = *reinterpret_cast<const float4*>(&V->b_mu[4 * g]), bl = *reinterpret_cast<const float4*>(&V->b_ls[4 * g]);
+    const float was[4] = {wa.x, wa.y, wa.z, wa.w}, wbs[4] = {wb.x, wb.y, wb.z, wb.w};
+    const float bms[4] = {bm.x, bm.y, bm.z, bm.w}, bls[4] = {bl.x, bl.y, bl.z, bl.w};
+    float m[4], l[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      float p0 = was[t] * ha;
+      p0 = __builtin_fmaf(wbs[t], hb, p0);
+      m[t] = seg_sum<16>(p0) + bms[t];
+      l[t] = bls[t];
+    }
+    if (!free_ls) {                                        // (wave-uniform)
+      const float4 la = *reinterpret_cast<const float4*>(V->w_ls[g][0][j]), lb = *reinterpret_cast<const float4*>(V->w_ls[g][1][j]);
+      const float las[4] = {la.x, la.y, la.z, la.w}, lbs[4] = {lb.x, lb.y, lb.z, lb.w};
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        float p1 = las[t] * ha;
+        p1 = __builtin_fmaf(lbs[t], hb, p1);
+        l[t] = seg_sum<16>(p1) + bls[t];
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      mu = col == 4 * g + t ? m[t] : mu;
+      ls = col == 4 * g + t ? l[t] : ls;
+    }
+  }
+  float a, lp;
+  policy_sample(pv, replica, ctr, mu, ls, a, lp, nzb, uint32_t(col < 0 ? 0 : col));
+  action = col >= 0 ? a : 0.0f;
+  if (col >= 0) lp_row[col & 15] = lp;
+  asm volatile("" ::: "memory");                           // (one wave: the hardware keeps its DS instructions in order)
+  float4 q[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) q[t] = *reinterpret_cast<const float4*>(lp_row + 4 * t);
+  asm volatile("" ::: "memory");
+  const float lps[16] = {q[0].x, q[0].y, q[0].z, q[0].w, q[1].x, q[1].y, q[1].z, q[1].w,
+                         q[2].x, q[2].y, q[2].z, q[2].w, q[3].x, q[3].y, q[3].z, q[3].w};
+  float logp = lps[0];
+#pragma unroll
+  for (int c = 1; c < 16; ++c) logp = c < A ? logp + lps[c] : logp;      // ((lp0 + lp1) + lp2) + ...
+  return logp;
+}
+
+// eager form of the row-per-replica action-vector head: obs [R, in_dim] -> act [R, A], logp [R]; a row of 16 lanes per
+// replica and 256 threads per workgroup, as in k_policy_act; lane j samples column j; the replica's counter advances by
+// ONE per call
+template <int ROW>     // (a template so that every object of the library may include this header)
+__global__ __launch_bounds__(256) void k_policy_act_row(PolicyView pv, int R, int A, uint32_t rep0,
+                                                        const float* __restrict__ obs, float* __restrict__ act,
+                                                        float* __restrict__ logp) {
+  static_assert(ROW == 16, "k_policy_act_row: a row of 16 lanes holds the 32 units of a layer");
+  __shared__ PolicyLds L;
+  __shared__ PolicyRowVecLds V;
+  policy_row_vec_load(pv, A, &L, &V, threadIdx.x, blockDim.x);
+  const int j = threadIdx.x & 15;
+  const int r = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+  const int rr = r < R ? r : R - 1;
+  const uint32_t c0 = pv.ctr[rr];
+  float ia, ib, a;
+  policy_wide_inputs(obs + size_t(rr) * pv.in_dim, pv.in_dim, j, ia, ib);
+  const float lp = policy_row_vec_act(pv, A, &L, &V, V.lp[threadIdx.x >> 4], rep0 + uint32_t(rr), c0, j, ia, ib,
+                                      j < A ? j : -1, a);
+  if (r < R && j < A) act[size_t(r) * A + j] = a;
+  if (r < R && j == 0) {
+    logp[r] = lp;
+    pv.ctr[r] = c0 + 1u;
+  }
+}
+
 // K x (policy -> action -> Env.step [-> reset of a finished episode]) for rings of IDM vehicles and RL vehicles.
 // HEAD 1: WaveAttenuationPOEnv, ONE RL vehicle: obs [K+1, R, 3] (obs[0]: the observation of the state the fragment starts
 // from), act [K, R], logp [K, R], rew [K, R], done [K, R].
@@ -817,6 +947,11 @@ __global__ __launch_bounds__(256) void k_ring_policy(DevView<T> s, PolicyView pv
 // (tests/test_policy_ma_gpu.py).  Agent c's six values sit on two lanes -- its RL vehicle's (four) and its follower's (two,
 // k_rollout_loop's flush_obs) -- and are gathered from registers into policy_wide_inputs' layout for in_dim = 6.
 //
+// VEC (HEAD 0 with num_rl = 2 .. 16 RL vehicles: the reference's figureeight1 / figureeight2 benchmarks): ONE network, the
+// 2 N observations in, num_rl action columns out -- policy_row_vec_act above; the lane of the RL vehicle with rl_index c
+// samples and applies column c; act [K, R, num_rl], logp [K, R] (FS_ENV_MERGE_PO's layouts).  Observation, step, reward,
+// done and reset are HEAD 0's statements (the desired-velocity reward does not read the action).
+//
 // The body is written ONCE, loop_policy_body: k_loop_policy calls it with PAIR = false, k_loop_policy_pair (below) with
 // HEAD 0 and PAIR = true.  PAIR (two policies, one RL vehicle: AdversarialAccelEnv on the figure eight) adds, all of it
 // under `if constexpr (PAIR)`: the adversary's PolicyView pv2 with its LDS copy PL2 and the weight pw; its evaluation on
@@ -831,8 +966,14 @@ struct PairLds {           // the adversary's LDS copy (PAIR), or nothing
 };
 template <>
 struct PairLds<false> {};
+template <bool VEC>
+struct RowVecLds {         // the action-vector head's output rows (VEC), or nothing
+  PolicyRowVecLds V;
+};
+template <>
+struct RowVecLds<false> {};
 
-template <int HEAD, bool DELTA4, bool FASTC, bool PAIR, int GREEDY>
+template <int HEAD, bool DELTA4, bool FASTC, bool PAIR, int GREEDY, bool VEC = false>
 __device__ __forceinline__ void loop_policy_body(const DevView<float> s, const PolicyView pv, const PolicyView pv2,
                                                  float pw, int num_steps, int reset_done, float* __restrict__ obs,
                                                  float* __restrict__ act, float* __restrict__ logp,
@@ -841,11 +982,14 @@ __device__ __forceinline__ void loop_policy_body(const DevView<float> s, const P
   typedef float X;
   constexpr int SEG = 16, RPW = 4;
   static_assert(!PAIR || HEAD == 0, "loop_policy_body: two policies drive the AccelEnv head's one RL vehicle");
+  static_assert(!VEC || (HEAD == 0 && !PAIR && GREEDY == -1), "loop_policy_body: the action-vector head is AccelEnv's, one policy");
   // (the LDS of the kernel this body is inlined into: every instantiation has ONE caller)
   __shared__ X tab_start[FS_MAX_SEGMENTS + 2], tab_fs[FS_MAX_SEGMENTS + 2], tab_sl[FS_MAX_SEGMENTS + 2];
   __shared__ PolicyLds PL;
   __shared__ PairLds<PAIR> PL2;
-  policy_load(pv, &PL, threadIdx.x, blockDim.x);
+  __shared__ RowVecLds<VEC> PV;
+  if constexpr (VEC) policy_row_vec_load(pv, s.num_rl, &PL, &PV.V, threadIdx.x, blockDim.x);
+  else policy_load(pv, &PL, threadIdx.x, blockDim.x);
   if constexpr (PAIR) policy_load(pv2, &PL2.L, threadIdx.x, blockDim.x);
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -1005,6 +1149,8 @@ __device__ __forceinline__ void loop_policy_body(const DevView<float> s, const P
   NoiseBlock<float> act_draws, act_draws1;
   act_draws.init();
   act_draws1.init();
+  // VEC: the column this lane samples and applies -- its RL vehicle's rl_index
+  const int vec_col = (VEC && valid && rl_lane) ? sl.rl_index : -1;
   observe(obs + size_t(rr) * obs_dim);
   for (int step = 0; step < num_steps; ++step) {
     // ---- policy -> action --------------------------------------------------------------------------------------
@@ -1032,6 +1178,12 @@ __device__ __forceinline__ void loop_policy_body(const DevView<float> s, const P
         }
         a = (rl_lane && own_col == c) ? ac : a;
       }
+    } else if constexpr (VEC) {
+      // ONE evaluation, num_rl columns (policy_row_vec_act: what k_policy_act_row runs); act [K, R, A], logp [K, R]
+      lp = policy_row_vec_act(pv, num_rl, &PL, &PV.V, PV.V.lp[threadIdx.x >> 4], s.rep0 + uint32_t(rr), pctr, i, o0, o1,
+                              vec_col, a, &act_draws);
+      if (rvalid && vec_col >= 0) act[(size_t(step) * R + rr) * num_rl + vec_col] = a;
+      if (rvalid && i == 0) logp[size_t(step) * R + rr] = lp;
     } else {
       if (HEAD == 1) policy_eval<SEG>(pv, &PL, i, o0, o1, o2, mu, ls);
       else policy_eval<SEG, true>(pv, &PL, i, o0, o1, 0.0f, mu, ls);
@@ -1249,6 +1401,16 @@ __global__ __launch_bounds__(256) void k_loop_policy_pair(DevView<float> s, Poli
                                                           float* __restrict__ rew, uint8_t* __restrict__ done) {
   // (the flag per policy, read at run time: the pair kernels keep their registers with it, tests/test_policy_pair_codegen.py)
   loop_policy_body<0, DELTA4, FASTC, true, -1>(s, pv, pv2, pw, num_steps, reset_done, obs, act, logp, rew, done);
+}
+
+// the action-vector AccelEnv head in the loop (fs_last_kernel "k_loop_policy<AccelVec>"): loop_policy_body<0, ., ., ., ., VEC>;
+// obs [K+1, R, 2 N], act [K, R, num_rl], logp / rew / done [K, R].  fs_policy.greedy is read at run time.
+template <bool DELTA4, bool FASTC>
+__global__ __launch_bounds__(256) void k_loop_policy_vec(DevView<float> s, PolicyView pv, int num_steps, int reset_done,
+                                                         float* __restrict__ obs, float* __restrict__ act,
+                                                         float* __restrict__ logp, float* __restrict__ rew,
+                                                         uint8_t* __restrict__ done) {
+  loop_policy_body<0, DELTA4, FASTC, false, -1, true>(s, pv, pv, 0.0f, num_steps, reset_done, obs, act, logp, rew, done);
 }
 
 }  // namespace fs

@@ -1037,12 +1037,14 @@ struct Sim : SimBase {
   // MultiAgentMergePOEnv with its actions applied on the merge's queue kernel: k_merge_queue<POLICY>); MergePOEnv's ONE
   // network with num_rl action columns: k_policy_act_vec (eager) and k_merge_policy (fused) up to 6 places, k_policy_act_wide
   // and k_merge_wide_policy with 7 .. 32; BottleneckDesiredVelocityEnv's (more than 32 inputs, up to 64 columns):
-  // k_policy_act_wide, eager only
+  // k_policy_act_wide, eager only; AccelEnv's on a segment-table loop with 2 .. 16 RL vehicles (the figure-eight
+  // benchmarks: 2 N inputs, num_rl columns, a row of 16 lanes per replica): k_policy_act_row and k_loop_policy_vec
   int launch_policy_act(const fs::PolicyView& pv, int n_ag, const float* obs_in, float* act, float* logp);
   int launch_policy_row16(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act, float* logp,
                           float* rew, uint8_t* done);
   int launch_policy_loop16(const fs::PolicyView& pv, int num_steps, int reset_done, float* obs, float* act, float* logp,
                            float* rew, uint8_t* done);
+  int launch_policy_act_row16(const fs::PolicyView& pv, const float* obs_in, float* act, float* logp);
   // ---- launch_policy's checks and set-up that fs_policy_pair shares (launch_policy_pair below) ----
   // the model class every policy kernel evaluates
   const char* policy_model_why(const fs_policy* pol) const {
@@ -1051,13 +1053,27 @@ struct Sim : SimBase {
     if (!pol->weights_dev) return "fs_policy.weights_dev (NULL)";
     return nullptr;
   }
+  // AccelEnv with several RL vehicles on a segment-table loop: the handles of the row-per-replica action-vector head
+  bool accel_vec() const { return dv.nseg > 0 && dv.env == FS_ENV_ACCEL && dv.num_rl > 1; }
   // ONE RL vehicle on a segment-table loop (k_loop_policy): why this handle / policy is not built, or nullptr.  po_ok:
-  // the WaveAttenuationPOEnv head counts (not for two policies); fragment_resets: a fused launch that resets in place
-  const char* policy_loop_why(const fs_policy* pol, bool po_ok, bool fragment_resets) const {
+  // the WaveAttenuationPOEnv head counts (not for two policies); fragment_resets: a fused launch that resets in place;
+  // vec_ok: an accel_vec() handle counts too -- ONE network with num_rl = 2 .. 16 action columns (k_policy_act_row,
+  // k_loop_policy_vec; not for two policies).  Every refusal of such a handle names FS_ENV_ACCEL and num_rl
+  const char* policy_loop_why(const fs_policy* pol, bool po_ok, bool fragment_resets, bool vec_ok = false) const {
     const bool po = po_ok && dv.env == FS_ENV_WAVE_ATTENUATION_PO, accel = dv.env == FS_ENV_ACCEL && !dv.evaluate;
+    const bool vec = accel_vec();
+    if (vec && (!std::is_same<T, float>::value || mixed))
+      return "precision (FS_ENV_ACCEL with num_rl > 1 is FS_F32 only: FS_MIXED / FS_F64 handles are not built)";
     if (!std::is_same<T, float>::value || mixed) return "precision (f32 on segment-table loops)";
     if (seg != 16 || dv.N < 2) return "num_vehicles (9..16: a row of 16 lanes per replica; up to 8 vehicles a replica is laid out in 8 lanes)";
-    if (!(po || accel) || dv.num_rl != 1)
+    if (vec && !vec_ok)
+      return "env (FS_ENV_ACCEL with num_rl > 1 takes ONE policy with num_rl action columns, fs_policy_act_dev / "
+             "fs_policy_rollout_dev: two policies drive AccelEnv with one RL vehicle)";
+    if (dv.env == FS_ENV_WAVE_ATTENUATION_PO && dv.num_rl > 1)
+      return "env (WaveAttenuationPOEnv with num_rl > 1: the PO head observes one RL vehicle; the action-vector head is "
+             "FS_ENV_ACCEL's, num_rl = 2..16)";
+    const bool vec_head = vec && accel && dv.num_rl <= fs::FS_POLICY_ROW_VEC_MAX;      // (the action-vector head)
+    if (!vec_head && (!(po || accel) || dv.num_rl != 1))
       return po_ok ? "env (WaveAttenuationPOEnv or AccelEnv with one RL vehicle)" : "env (AccelEnv with one RL vehicle)";
     if (pol->obs_dim != (po ? 3 : 2 * dv.N)) return "fs_policy.obs_dim (the environment's observation)";
     if (!(dv.flags & fs::FLAG_IDM_SET) || (dv.flags & fs::FLAG_HAS_FAILSAFE) || dv.sims_per_step != 1 ||
@@ -1168,7 +1184,7 @@ struct Sim : SimBase {
                          (dv.N % 2) != 0))
         why = "configuration (what k_ring_pair steps: single-lane ring of IDM / RL vehicles, Euler, track_aux = 0)";
     }
-    else if (loop) why = policy_loop_why(pol, true, obs != nullptr && reset_done);
+    else if (loop) why = policy_loop_why(pol, true, obs != nullptr && reset_done, true);
     else if (!f32_or_mixed) why = "precision (f32 or mixed)";
     else if (seg != 32) why = "num_vehicles (18..32: a row of 16 lanes per replica)";
     else if (dv.env == FS_ENV_MULTI_WAVE_ATTENUATION_PO && (!std::is_same<T, float>::value || mixed))
@@ -1189,7 +1205,7 @@ struct Sim : SimBase {
     if (pop_probe) return FS_OK;                         // (fs_population_granule: the checks alone)
     if (int rc = policy_counters()) return rc;
     fs::PolicyView pv = policy_view(pol);
-    if (dv.env == FS_ENV_MERGE_PO || dv.env == FS_ENV_BOTTLENECK_DV) pv.n_out *= dv.num_rl;  // the action-vector heads: num_rl means [and num_rl log stds]
+    if (dv.env == FS_ENV_MERGE_PO || dv.env == FS_ENV_BOTTLENECK_DV || accel_vec()) pv.n_out *= dv.num_rl;  // the action-vector heads: num_rl means [and num_rl log stds]
     if constexpr (std::is_same<T, float>::value) {
       const bool po_wide = dv.env == FS_ENV_MERGE_PO && dv.num_rl > fs::FS_POLICY_VEC_MAX;   // 35 .. 160 inputs
       if (dv.env == FS_ENV_MERGE_PO && obs == nullptr && !po_wide) return launch_policy_act_vec(pv, obs_in, act, logp);
@@ -1198,6 +1214,7 @@ struct Sim : SimBase {
         if (obs != nullptr) return launch_policy_queue(pv, num_steps, reset_done, obs, act, logp, rew, done);
       }
     }
+    if (obs == nullptr && accel_vec()) return launch_policy_act_row16(pv, obs_in, act, logp);     // (launch_policy_loop16 takes the fused form)
     if (obs == nullptr) return launch_policy_act(pv, ma ? dv.num_rl : 1, obs_in, act, logp);      // eager: the policy alone
     if (loop) return launch_policy_loop16(pv, num_steps, reset_done, obs, act, logp, rew, done);
     return launch_policy_row16(pv, num_steps, reset_done, obs, act, logp, rew, done);
@@ -1224,6 +1241,10 @@ struct Sim : SimBase {
                                       "the workgroup's LDS copy");
     if (dv.env == FS_ENV_MERGE_MA)
       return fail(FS_ERR_UNSUPPORTED, "fs_population: not built for FS_ENV_MERGE_MA (k_merge_queue<POLICY> gives a wave to a replica)");
+    if (accel_vec())
+      return fail(FS_ERR_UNSUPPORTED, "fs_population: not built for FS_ENV_ACCEL with num_rl > 1 (the action-vector head of "
+                                      "k_policy_act_row / k_loop_policy<AccelVec>: policy_floats and the members' stride "
+                                      "count one action column)");
     if (!probe) {
       if (pop->members < 1 || pop->group < 1 || pop->reserved != 0)
         return fail(FS_ERR_INVALID, "fs_population: members and group must be at least 1, reserved 0");

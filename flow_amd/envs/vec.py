@@ -384,8 +384,9 @@ class VecFlowEnv(object):
         """ONE evaluation of ``policy`` (a ``DevicePolicy``) for every replica in one kernel launch
         (``fs_policy_act_dev``): actions sampled from the policy's Philox streams and their log-probabilities, for the
         observations ``obs [R, obs_dim]`` (default: those of the last reset / step).  Returns ``(act [R, A], logp [R])``
-        on the action-vector heads (MergePOEnv, BottleneckDesiredVelocityEnv: ``A = sim.policy_action_dim`` columns,
-        one joint log-probability), ``(act [R, n], logp [R, n])`` for ``n = sim.policy_agents`` agents sharing the
+        on the action-vector heads (MergePOEnv, BottleneckDesiredVelocityEnv, AccelEnv with several RL vehicles on the
+        figure eight -- flow_amd.benchmarks.figureeight1 / figureeight2 --: ``A = sim.policy_action_dim`` columns, one joint
+        log-probability), ``(act [R, n], logp [R, n])`` for ``n = sim.policy_agents`` agents sharing the
         policy.  Every call advances the replicas' draw counters by one."""
         torch, R = self.torch, self.num_rows
         self.use_current_stream()
@@ -422,7 +423,11 @@ class VecFlowEnv(object):
         (``DevicePolicy(..., act_dim=num_rl)``: the whole observation in, ``num_rl`` accelerations out): ``actions`` is
         ``[K, R, num_rl]`` -- every column sampled every step, the environment ignores those beyond its list of controlled
         vehicles -- and ``logp [K, R]`` the joint log-probability; with ``reset_done`` a replica is reset when its
-        ``done`` byte is not zero, collisions included.  ``capture`` serves every other environment / model."""
+        ``done`` byte is not zero, collisions included.  AccelEnv on the figure eight with ``num_rl`` = 2..16 RL vehicles
+        (flow_amd.benchmarks.figureeight1 / figureeight2: k_loop_policy<AccelVec>) takes the same kind of policy
+        (``DevicePolicy(..., act_dim=num_rl)``: the 2 N observations in, ``num_rl`` accelerations out) with the same
+        layouts, ``actions [K, R, num_rl]`` and ``logp [K, R]``; column c is the RL vehicle with rl_index c.  ``capture``
+        serves every other environment / model."""
         torch, R, K = self.torch, self.num_rows, int(num_steps)
         self.use_current_stream()
         if reset_done and self._resample and not getattr(self, "_warned_pending_length", False):

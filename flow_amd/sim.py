@@ -271,9 +271,13 @@ class FlowSim:
     def policy_action_dim(self):
         """Action columns of ONE policy evaluation: num_rl on MergePOEnv (FS_ENV_MERGE_PO: one network maps the whole
         observation to num_rl accelerations, with one joint log-probability) and on BottleneckDesiredVelocityEnv
-        (FS_ENV_BOTTLENECK_DV: one column per action cell), 1 otherwise."""
+        (FS_ENV_BOTTLENECK_DV: one column per action cell), and on AccelEnv with several RL vehicles on a segment-table
+        loop (FS_ENV_ACCEL on the figure eight: the reference's figureeight1 / figureeight2 benchmarks, 2 N observations
+        in, num_rl accelerations out); 1 otherwise."""
         vec_heads = (L.FS_ENV_MERGE_PO, L.FS_ENV_BOTTLENECK_DV)
-        return max(self.num_rl, 1) if int(self.spec.get("env", L.FS_ENV_ACCEL)) in vec_heads else 1
+        env = int(self.spec.get("env", L.FS_ENV_ACCEL))
+        loop_vec = env == L.FS_ENV_ACCEL and not self.open_net and bool(self.spec.get("segments")) and self.num_rl > 1
+        return max(self.num_rl, 1) if env in vec_heads or loop_vec else 1
 
     def policy_act_dev(self, pol, obs, act, logp):
         """act / logp [R] (one agent) or [R, policy_agents] for the observations obs [R, obs_dim]; MergePOEnv and

@@ -443,8 +443,9 @@ int fs_add_vehicle(fs_handle h, int replica, int slot, int route, double x, doub
  * "+speed_mode" and / or "+noise", "k_rollout_idm", "k_ring_pair<Accel | PO | POMA | AccelMA>", "k_rollout_loop",
  * "k_rollout_loop<FULL>", "k_rollout_loop<AccelMA>", "k_rollout_loop<FULL,AccelMA>", "k_ring_policy", "k_loop_policy",
  * "k_ring_policy<POMA>", "k_loop_policy<AccelMA>", "k_merge_policy", "k_merge_policy<PO>", "k_merge_policy<PO,WIDE>",
- * "k_loop_policy<Adversarial>" (fs_policy_pair_rollout_dev; fs_policy_pair_act_dev: "k_policy_pair_act")
- * (fs_policy_act_dev: "k_policy_act", "k_policy_act_vec", "k_policy_act_wide"; the PPO update's entry points: "k_ppo_eval",
+ * "k_loop_policy<AccelVec>", "k_loop_policy<Adversarial>" (fs_policy_pair_rollout_dev; fs_policy_pair_act_dev:
+ * "k_policy_pair_act")
+ * (fs_policy_act_dev: "k_policy_act", "k_policy_act_vec", "k_policy_act_wide", "k_policy_act_row"; the PPO update's entry points: "k_ppo_eval",
  * "k_gae", "k_ppo_grad", "k_adv_stats", "k_adv_finish", "k_adam"; fs_episode_stats_dev: "k_episode_stats";
  * fs_population_*: the policy kernel's name with the tag Population, e.g. "k_ring_policy<Population>",
  * "k_ring_policy<POMA,Population>" -- that one string lives in the handle and is valid until its next launch; fs_es_*:
@@ -529,6 +530,20 @@ const char* fs_last_kernel(fs_handle h);
  * fs_step_dev, fs_reset_dev(done)) as one graph instead (VecFlowEnv.capture with a DevicePolicy).  Every refusal on
  * this head -- another precision, obs_dim != fs_obs_dim, num_rl outside 1..64, the model class -- names
  * FS_ENV_BOTTLENECK_DV.
+ * AccelEnv with SEVERAL RL vehicles on a segment-table loop (FS_ENV_ACCEL without evaluate, num_rl = 2..16 among 9..16
+ * vehicles: the reference's flow/benchmarks/figureeight1.py, 7 IDM + 7 RL vehicles, 28 -> 7, and figureeight2.py, 14 RL
+ * vehicles, 28 -> 14) takes the same ACTION-VECTOR head with a ROW of 16 lanes per replica ("k_policy_act_row" /
+ * "k_loop_policy<AccelVec>"; flowsim_policy.h policy_row_vec_act): obs_dim = fs_obs_dim = 2 N (at most 32: the first layer
+ * of the AccelEnv head with one RL vehicle), the last layer 2 A rows (means, then log stds) or A rows next to A free log
+ * stds at log_std_dev, A = num_rl.  Column c belongs to the RL vehicle with rl_index c, whatever its slot; it draws from
+ * Philox column 0x40000000 + c at the replica's counter, which advances by one per call / step, and logp is the float32
+ * sum of the columns' values in ascending column order.  fs_policy_act_dev takes obs [R, 2 N] and writes act [R, A] and
+ * logp [R]; fs_policy_rollout_dev takes obs [K+1, R, 2 N], act [K, R, A] and logp / rew / done [K, R] (FS_ENV_MERGE_PO's
+ * layouts); a fragment equals K x (fs_policy_act_dev, fs_step_dev, fs_reset_dev(done)) bit for bit.  The conditions are
+ * those of the head with one RL vehicle -- FS_F32, a row of 16 lanes, IDM / RL / Sim vehicles, no fail-safes, Euler,
+ * track_aux = 0, no sorting, warmup_steps = 0 when a fragment resets --, and num_rl = 1 keeps its path and kernel names.
+ * Refused by name, each message naming FS_ENV_ACCEL and num_rl: FS_MIXED / FS_F64; the WaveAttenuationPOEnv head with
+ * num_rl > 1; fs_policy_pair_* (two policies drive ONE RL vehicle); fs_population_* ("fs_population: ...").
  * The mean action (greedy != 0; every kernel named above, eager and fused, and fs_policy_pair_* per policy): act = the
  * head's mean EXACTLY (a select: no std enters it, so it stays finite where exp(log std) overflows) and logp =
  * (-log_std) - 0.9189385332046727f, the density at the mean -- the sampling expression with a zero draw; the action-vector
@@ -538,7 +553,7 @@ const char* fs_last_kernel(fs_handle h);
  * Gaussian head only.  greedy occupies four bytes that were padding before the first pointer: sizeof(fs_policy) and every
  * other offset are unchanged, and a C caller MUST ZERO the struct (memset, or = {0}) before filling it -- a caller that
  * left the padding uninitialised would switch the mean action on by accident.  On the k_loop_policy family the flag picks
- * the kernel's instantiation (the same fs_last_kernel names); every other kernel reads it at run time. */
+ * the kernel's instantiation (the same fs_last_kernel names; "k_loop_policy<AccelVec>" reads it at run time); every other kernel reads it at run time. */
 typedef struct fs_policy {
   uint32_t struct_size;               /* sizeof(fs_policy) */
   int32_t obs_dim;                    /* must equal fs_obs_dim (FS_ENV_MERGE_PO / BOTTLENECK_DV too); shared agents: fs_obs_dim / num_rl */
@@ -610,7 +625,8 @@ int fs_policy_pair_rollout_dev(fs_handle h, const fs_policy* av, const fs_policy
  * Refused before anything launches, FS_ERR_INVALID / FS_ERR_UNSUPPORTED with a message that starts "fs_population: ":
  * group not a multiple of the granule; members * group != num_replicas; 0 < stride < the policy's own size in floats;
  * the action-vector heads (FS_ENV_MERGE_PO, FS_ENV_BOTTLENECK_DV) and FS_ENV_MERGE_MA (their kernels give a WAVE to a
- * replica and read first-layer or output weights past the LDS copy).  There is no population form of fs_policy_pair.
+ * replica and read first-layer or output weights past the LDS copy) and FS_ENV_ACCEL with num_rl > 1 (the row-per-replica
+ * action-vector head: a member's size and stride count one action column).  There is no population form of fs_policy_pair.
  * Whatever fs_policy_rollout_dev refuses on the handle is refused here with its message ("fs_policy: ..."). */
 typedef struct fs_population {
   uint32_t struct_size;               /* sizeof(fs_population) */
