@@ -300,7 +300,9 @@ int create_typed(const fs_config* cfg, fs_handle* out) {
         {"FLOWSIM_FORCE_GENERIC", &SimBase::force_generic}, {"FLOWSIM_NO_FASTDIV", &SimBase::no_fastdiv},
         {"FLOWSIM_NO_LOOP_KERNEL", &SimBase::no_loop_kernel}, {"FLOWSIM_NO_LOOP_FULL", &SimBase::no_loop_full},
         {"FLOWSIM_NO_RING_RL", &SimBase::no_ring_rl}, {"FLOWSIM_NO_QUEUE", &SimBase::no_queue},
-        {"FLOWSIM_NO_PAIR", &SimBase::no_pair}, {"FLOWSIM_NO_MASK_SKIP", &SimBase::no_mask_skip},
+        {"FLOWSIM_NO_PAIR", &SimBase::no_pair}, {"FLOWSIM_PAIR_GENERIC_N", &SimBase::pair_generic_n},
+        {"FLOWSIM_KERNEL_DETAIL", &SimBase::kernel_detail}, {"FLOWSIM_PAIR_N_ALWAYS", &SimBase::pair_n_always},
+        {"FLOWSIM_NO_MASK_SKIP", &SimBase::no_mask_skip},
         {"FLOWSIM_SNAPSHOT_COPIES", &SimBase::snap_copies}};
     for (const auto& sw : switches) {
       const char* v = std::getenv(sw.first);

@@ -241,6 +241,25 @@ namespace fsim {
     last_kernel = noise ? (sm ? "k_rollout_pair+speed_mode+noise" : "k_rollout_pair+noise")
                         : (sm ? "k_rollout_pair+speed_mode" : "k_rollout_pair");
     const int waves = (dv.R + (64 / ROW) - 1) / (64 / ROW);
+    // the reference's ring of 22 vehicles in the hand-written class: k_rollout_pair_n<T, 11, speed mode, noise> -- for
+    // launches long enough to pay for it.  The image of the launch's last full block leaves after the loop with nothing
+    // to hide behind (11 KB per wave): a launch of 20 steps was 2-7 us (4-20 %) slower on this entry, a step of a long
+    // one gains 0.013 us, so the entry pays from a few hundred steps on.
+    if constexpr (SEG == 32) {
+      if (dv.N == 22 && delta4 && fd && !bc && !pair_generic_n && (a.num_steps >= PAIR_N_MIN_STEPS || pair_n_always)) {
+        decltype(&fs::k_rollout_pair_n<T, 11>) kn = nullptr;
+        if constexpr (std::is_same<T, float>::value) {
+          kn = pick(sm, [&](auto SM) { return pick(noise, [&](auto NZ) { return &fs::k_rollout_pair_n<T, 11, SM, NZ>; }); });
+        } else {
+          kn = pick(sm, [&](auto SM) { return &fs::k_rollout_pair_n<T, 11, SM>; });
+        }
+        if (kernel_detail)
+          last_kernel = noise ? (sm ? "k_rollout_pair+speed_mode+noise[n11]" : "k_rollout_pair+noise[n11]")
+                              : (sm ? "k_rollout_pair+speed_mode[n11]" : "k_rollout_pair[n11]");
+        hipLaunchKernelGGL(kn, dim3((waves + 3) / 4), dim3(256), 0, stream, dv, a.num_steps, a.obs, a.rew, a.done);
+        return launched();
+      }
+    }
     hipLaunchKernelGGL(k, dim3((waves + 3) / 4), dim3(256), 0, stream, dv, a.num_steps, a.obs, a.rew, a.done);
     return launched();
   }

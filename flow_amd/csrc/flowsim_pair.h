@@ -587,13 +587,21 @@ __device__ __forceinline__ void mixed_step_asm_slow(double& XA, double& XB, f2& 
       : "v120", "v121", "v122", "v123", "v126", "v127", "v130", "v131", "v132", "v133", "v134", "v135", "v136", "v137");
 }
 
+template <typename F, int... S>
+__device__ __forceinline__ void each_slot(F&& f, std::integer_sequence<int, S...>) {
+  (f(std::integral_constant<int, S>()), ...);
+}
+
 // T = float: the float32 bit-twin.  T = double: MIXED (see the header).  ROW = lanes per replica (N <= 2 ROW).
 // SM: some slot carries a speed-mode clamp (bits 0-2): the C++ step with sumo_acc_pair.
 // NOISE (float32 only): IDMController(noise = sigma) slots -- acc + sigma * g with the generic kernel's draws (gauss4 keyed
 // by seed, global replica, vehicle, draw counter / 4; base_controller.py:109-110), the C++ step.
-template <typename T, int ROW, bool DELTA4, bool FASTDIV, bool BADCHK, bool SM = false, bool NOISE = false>
-__global__ __launch_bounds__(256) void k_rollout_pair(DevView<T> s, int num_steps, float* __restrict__ obs,
-                                                      float* __restrict__ rew, uint8_t* __restrict__ done) {
+//
+// NH: 0 = the number of vehicles is the handle's (s.N), the observation row goes through transpose_in; > 0 = N is 2 NH at
+// compile time and the hand-written step keeps a 16-step image of the wave's rows in LDS (k_rollout_pair_n below).
+template <typename T, int ROW, bool DELTA4, bool FASTDIV, bool BADCHK, bool SM, bool NOISE, int NH>
+__device__ __forceinline__ void rollout_pair_body(const DevView<T>& s, int num_steps, float* __restrict__ obs,
+                                                  float* __restrict__ rew, uint8_t* __restrict__ done) {
   constexpr bool MIXED = sizeof(T) == 8;
   static_assert(!(NOISE && MIXED), "FS_MIXED has no noise form (its C twin cannot reproduce the hardware's log / cos)");
   // the hand-written steps: pair_step_asm_a / _a_sm + _b (float32, without / with the speed-mode clamps), mixed_step_asm
@@ -605,7 +613,7 @@ __global__ __launch_bounds__(256) void k_rollout_pair(DevView<T> s, int num_step
   const int row = lane / ROW;
   const int k = lane % ROW;
   const int r = wave * RPW + row;
-  const int N = s.N;
+  const int N = NH > 0 ? 2 * NH : s.N;
   const int LP = N >> 1;                            // occupied lanes of a row (N is even: host-checked)
   const bool rvalid = r < s.R;
   const bool valid = rvalid && k < LP;
@@ -764,8 +772,46 @@ __global__ __launch_bounds__(256) void k_rollout_pair(DevView<T> s, int num_step
   // removed) gained nothing: two ds_write_b64 per step cost the stepping wave what the stores did.
   typedef unsigned u4v __attribute__((__vector_size__(16)));
   constexpr bool XPOSE = ASM;
-  __shared__ float row_img[XPOSE ? 4 : 1][XPOSE ? RPW * 64 : 1];          // [wave of the block][row * 2 N floats], N <= 32
-  float* const my_img = row_img[XPOSE ? (threadIdx.x >> 6) & 3 : 0] + (XPOSE ? row * 2 * N : 0);
+  // RING (NH > 0): the wave keeps the image of a whole 16-step block, [16][4 rows x 8 N bytes] -- the layout of the
+  // block in HBM but for the stride between steps.  A step is ONE ds_write2_b64 (speeds and positions are N / 2 qwords
+  // apart: an immediate now that N is one), and the block leaves as NPIECE = N / 2 full-wave dwordx4 stores: piece j is
+  // the KB at byte 1024 j of the image, lane l's 16 bytes of it belong to step g / WSTEP at byte g % WSTEP of the wave's
+  // rows, g = 1024 j + 16 l (doff[j]: its offset in the HBM block, rows past R redirected to replica R - 1 like rr).
+  // IN PLACE: step s <= NPIECE - 1 of the NEXT block first reads piece s of this one, then writes its own row at byte
+  // WSTEP s -- LDS operations of a wave execute in order and reads 0..s have freed bytes [0, 1024 (s + 1)), which hold
+  // [WSTEP s, WSTEP (s + 1)) because WSTEP = 32 N <= 1024.  The piece is stored one step later, as before.  The last
+  // block of a launch is drained after the loop (Sim::launch_pair: why short launches stay on k_rollout_pair); the first
+  // block's reads find nothing: their stores go through a descriptor of zero bytes, which drops them.
+  // Measured in one call (scripts/ubench/pair_bench.hip, 4096 x 22 x 1500): mixed 0.380-0.385 ms on k_rollout_pair,
+  // 0.342-0.346 ms with this; the merged write alone 0.357-0.363, the ring alone 0.364-0.368, the burst form 0.346-0.352;
+  // f32 0.372-0.390 -> 0.325-0.337 ms.  The counters: DESIGN.md section 4.0.
+  constexpr bool RING = ASM && NH > 0
+#if defined(FS_DIAG_PAIRN_NO_RING)     // timing experiments (scripts/ubench/pair_bench.hip): N at compile time only,
+      && false
+#endif
+      ;
+#if defined(FS_DIAG_PAIRN_BURST)       // the block drained in one burst at its end instead of in place,
+  constexpr bool BURST = true;
+#else
+  constexpr bool BURST = false;
+#endif
+  constexpr int WSTEP = RPW * 8 * (NH > 0 ? 2 * NH : 1);                    // bytes of a wave's rows of one step
+  constexpr int NPIECE = NH > 0 ? NH : 1;                                   // PERIOD * WSTEP / 1024
+  static_assert(!RING || (PERIOD * WSTEP == NPIECE * 1024 && WSTEP <= 1024), "the 16-step image is NPIECE full-wave pieces");
+  // [wave of the block][row * 2 N floats], N <= 32; RING: [wave of the block][step][row * 2 N floats]
+  __shared__ __attribute__((aligned(16))) float row_img[XPOSE ? 4 : 1][RING ? PERIOD * WSTEP / 4 : XPOSE ? RPW * 64 : 1];
+  float* const my_wave_img = row_img[XPOSE ? (threadIdx.x >> 6) & 3 : 0];
+  float* const my_img = my_wave_img + (XPOSE ? row * 2 * N : 0);
+  unsigned doff[NPIECE];
+  if constexpr (RING) {
+#pragma unroll
+    for (int j = 0; j < NPIECE; ++j) {
+      const unsigned g = unsigned(j) * 1024u + 16u * unsigned(lane);
+      const unsigned st = g / unsigned(WSTEP), in_step = g % unsigned(WSTEP);
+      const int rp = wave * RPW + int(in_step / rowb);                      // the replica whose row holds these 16 bytes
+      doff[j] = st * step_b32 + unsigned(rp < s.R ? rp : s.R - 1) * rowb + in_step % rowb;
+    }
+  }
   const unsigned off_16 = unsigned(rr) * rowb + unsigned(kk) * 16u;         // byte offset of piece kk of my replica's row
   u4v piece = {0u, 0u, 0u, 0u};
   auto transpose_in = [&](f2 ov, f2 ox) {
@@ -775,6 +821,42 @@ __global__ __launch_bounds__(256) void k_rollout_pair(DevView<T> s, int num_step
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     piece = *reinterpret_cast<const u4v*>(my_img + 4 * kk);
+  };
+  // RING: the lane's two qwords of step `slot` of the block; in place, the read of the previous block's piece first
+  // (ds_write2_b64 reaches 255 qwords from its address: one address per three steps, formed once and kept -- as values
+  // of an asm statement they are not formed again inside the loop)
+  typedef __attribute__((address_space(3))) char lds_char;
+  typedef __attribute__((address_space(3))) f2 lds_f2;
+  constexpr int WR_SPAN = RING ? (255 * 8 - 4 * 2 * NH) / WSTEP + 1 : PERIOD;  // steps one address serves
+  constexpr int WR_BASES = (PERIOD + WR_SPAN - 1) / WR_SPAN;
+  lds_char* ring_wr[WR_BASES] = {};
+  if constexpr (RING) {
+#pragma unroll
+    for (int q = 0; q < WR_BASES; ++q) {
+      ring_wr[q] = (lds_char*)(reinterpret_cast<char*>(my_img + 2 * kk)) + q * WR_SPAN * WSTEP;
+      asm volatile("" : "+v"(ring_wr[q]));
+    }
+  }
+  const char* const ring_rd = reinterpret_cast<const char*>(my_wave_img + 4 * lane);
+#if defined(FS_DIAG_PAIRN_NO_MERGE)    // or the ring with two ds_write_b64 (their distance read from the handle).
+  const int wr_dist = 4 * s.N;
+#else
+  constexpr int wr_dist = 4 * (NH > 0 ? 2 * NH : 1);
+#endif
+  auto ring_piece = [&](int j) { return *reinterpret_cast<const u4v*>(ring_rd + j * 1024); };
+  auto ring_in = [&](int slot, f2 ov, f2 ox) {
+    if (!BURST && slot < NPIECE) {
+      piece = ring_piece(slot);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");             // same wave: LDS operations execute in order
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    lds_char* const at = ring_wr[slot / WR_SPAN] + (slot % WR_SPAN) * WSTEP;
+    *(lds_f2*)at = ov;
+    *(lds_f2*)(at + wr_dist) = ox;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   };
 
   // sigma * g of this step for the lane's two vehicles (-0.0 for a slot without noise: x + (-0) keeps every bit of x)
@@ -798,14 +880,28 @@ __global__ __launch_bounds__(256) void k_rollout_pair(DevView<T> s, int num_step
     return nz;
   };
 
-  auto one_step = [&](int slot, __amdgpu_buffer_rsrc_t rs, float& sq_out) {
+  // IN_RING: a step of a full block of the RING form (rs_prev: the block before, whose pieces leave during this one)
+  auto one_step = [&](int slot, __amdgpu_buffer_rsrc_t rs, float& sq_out, auto IN_RING, __amdgpu_buffer_rsrc_t rs_prev)
+                      __attribute__((always_inline)) {
     if constexpr (ASM) {
       f2 ov, ox;
       const unsigned so = unsigned(slot) * step_b32;
+      // the piece read during the step before, stored between the two parts of this one
+      auto store_late = [&]() {
+        if constexpr (decltype(IN_RING)::value) {
+          if (!BURST && slot >= 1 && slot <= NPIECE) __builtin_amdgcn_raw_buffer_store_b128(piece, rs_prev, doff[slot - 1], 0, 0);
+        } else {
+          if (slot > 0) __builtin_amdgcn_raw_buffer_store_b128(piece, rs, off_16, so - step_b32, 0);
+        }
+      };
+      auto rows_in = [&]() {
+        if constexpr (decltype(IN_RING)::value) ring_in(slot, ov, ox);
+        else transpose_in(ov, ox);
+      };
       if constexpr (MIXED) {
         if constexpr (SM) mixed_step_asm_a_sm(v, xdA, xdB, vdA, vdB, h, dvl, ov, mc, sc, msc);
         else mixed_step_asm_a(v, xdA, xdB, vdA, vdB, h, dvl, ov, mc);
-        if (slot > 0) __builtin_amdgcn_raw_buffer_store_b128(piece, rs, off_16, so - step_b32, 0);
+        store_late();
         float ct;
         unsigned long long need;
         mixed_step_asm_b(v, xdA, xdB, h, dvl, ox, wA, wB, ct, sq_out, need, mc);
@@ -816,7 +912,7 @@ __global__ __launch_bounds__(256) void k_rollout_pair(DevView<T> s, int num_step
 #endif
         if (__builtin_expect(need != 0ull, 0)) mixed_step_asm_slow(xdA, xdB, h, ox, wA, wB, ct, mc);
         crash_bits = __builtin_amdgcn_alignbit(crash_bits, __builtin_bit_cast(unsigned, ct), 31);
-        transpose_in(ov, ox);
+        rows_in();
       } else {
 #if defined(FS_DIAG_NOSTORE)   // timing experiment (scripts/dbg/pmc_variants.sh): the results stay in registers
         pair_step_asm_a(v, x, h, dvl, ox, pc);
@@ -836,9 +932,9 @@ __global__ __launch_bounds__(256) void k_rollout_pair(DevView<T> s, int num_step
           if constexpr (SM) pair_step_asm_a_sm(v, x, h, dvl, ox, pc, sc);
           else pair_step_asm_a(v, x, h, dvl, ox, pc);
         }
-        if (slot > 0) __builtin_amdgcn_raw_buffer_store_b128(piece, rs, off_16, so - step_b32, 0);
+        store_late();
         pair_step_asm_b(v, x, h, dvl, ov, crash_bits, sq_out, pc);
-        transpose_in(ov, ox);
+        rows_in();
 #endif
       }
       return;
@@ -916,15 +1012,39 @@ __global__ __launch_bounds__(256) void k_rollout_pair(DevView<T> s, int num_step
 
   // full blocks of PERIOD steps: straight-line code, rewards finished PERIOD at a time
   int base = 0;
+  char* ob_prev = ob;                  // RING: the block whose image is in LDS, and its bytes (none before the first block)
+  unsigned prev_bytes = 0u;
+  const std::integral_constant<bool, RING> in_ring{};
   for (; base + PERIOD <= num_steps; base += PERIOD) {
     float sq[PERIOD];
     const size_t remain = size_t(num_steps - base) * step_bytes;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
         ob, 0, remain > 0xFFFFFFFFull ? 0xFFFFFFFFu : unsigned(remain), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_prev = __builtin_amdgcn_make_buffer_rsrc(ob_prev, 0, prev_bytes, 0x00020000);
+    if constexpr (RING) {
+      // (written out through a pack expansion: the slot of a RING step must be a constant, and the unroller gives up on
+      // sixteen steps with the noise draws and the speed-mode clamps in them)
+      each_slot([&](auto S) __attribute__((always_inline)) { one_step(S.value, rs, sq[S.value], in_ring, rs_prev); },
+                std::make_integer_sequence<int, PERIOD>());
+    } else {
 #pragma unroll
-    for (int slot = 0; slot < PERIOD; ++slot) one_step(slot, rs, sq[slot]);
+      for (int slot = 0; slot < PERIOD; ++slot) one_step(slot, rs, sq[slot], in_ring, rs_prev);
+    }
 #if !defined(FS_DIAG_NOSTORE) && !defined(FS_DIAG_NOXPOSE)
-    if (XPOSE) __builtin_amdgcn_raw_buffer_store_b128(piece, rs, off_16, unsigned(PERIOD - 1) * step_b32, 0);
+    if constexpr (RING) {
+      if constexpr (BURST) {
+#pragma unroll
+        for (int j = 0; j < NPIECE; ++j) __builtin_amdgcn_raw_buffer_store_b128(ring_piece(j), rs, doff[j], 0, 0);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      } else {
+        ob_prev = ob;
+        prev_bytes = unsigned(PERIOD) * step_b32;
+      }
+    } else if (XPOSE) {
+      __builtin_amdgcn_raw_buffer_store_b128(piece, rs, off_16, unsigned(PERIOD - 1) * step_b32, 0);
+    }
 #endif
     ob += size_t(PERIOD) * step_bytes;
     tcount += PERIOD;
@@ -946,12 +1066,22 @@ __global__ __launch_bounds__(256) void k_rollout_pair(DevView<T> s, int num_step
       done[o] = done_flag(t_k >= s.step_limit, my_crash);                                // envs/base.py:398-400
     }
   }
+  // RING: the last block's image leaves now, with nothing to hide behind (11 KB per wave: what a SHORT launch pays for
+  // the ring -- Sim::launch_pair takes this entry for long launches only)
+  if (RING && !BURST && prev_bytes != 0u) {
+    const __amdgpu_buffer_rsrc_t rs_prev = __builtin_amdgcn_make_buffer_rsrc(ob_prev, 0, prev_bytes, 0x00020000);
+#pragma unroll
+    for (int j = 0; j < NPIECE; ++j) __builtin_amdgcn_raw_buffer_store_b128(ring_piece(j), rs_prev, doff[j], 0, 0);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
   // the remaining num_steps % PERIOD steps one at a time (same tree: seg_sum is transposed_sum's order)
 #pragma unroll 1
   for (; base < num_steps; ++base) {
     float sq1;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(ob, 0, unsigned(step_bytes), 0x00020000);
-    one_step(0, rs, sq1);
+    one_step(0, rs, sq1, std::false_type(), rs);
 #if !defined(FS_DIAG_NOSTORE) && !defined(FS_DIAG_NOXPOSE)
     if (XPOSE) __builtin_amdgcn_raw_buffer_store_b128(piece, rs, off_16, 0u, 0);
 #endif
@@ -983,6 +1113,20 @@ __global__ __launch_bounds__(256) void k_rollout_pair(DevView<T> s, int num_step
     if (kk == 0) s.time[rr] = tcount;
     if (NOISE && kk == 0) s.noise_ctr[rr] = nctr;
   }
+}
+
+template <typename T, int ROW, bool DELTA4, bool FASTDIV, bool BADCHK, bool SM = false, bool NOISE = false>
+__global__ __launch_bounds__(256) void k_rollout_pair(DevView<T> s, int num_steps, float* __restrict__ obs,
+                                                      float* __restrict__ rew, uint8_t* __restrict__ done) {
+  rollout_pair_body<T, ROW, DELTA4, FASTDIV, BADCHK, SM, NOISE, 0>(s, num_steps, obs, rew, done);
+}
+// The hand-written class (ROW = 16, delta = 4, the proven divisions, no v < -100 check) for 2 NH vehicles: same step, same
+// results, the observation rows through the wave's 16-step LDS image (rollout_pair_body: RING).
+template <typename T, int NH, bool SM = false, bool NOISE = false>
+__global__ __launch_bounds__(256) void k_rollout_pair_n(DevView<T> s, int num_steps, float* __restrict__ obs,
+                                                        float* __restrict__ rew, uint8_t* __restrict__ done) {
+  static_assert(NH >= 1 && NH <= 16, "a row of 16 lanes holds up to 32 vehicles");
+  rollout_pair_body<T, 16, true, true, false, SM, NOISE, NH>(s, num_steps, obs, rew, done);
 }
 
 // observation of the current state of a FS_MIXED handle (Env.reset): the mixed head's own form (reciprocal

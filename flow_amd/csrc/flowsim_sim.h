@@ -96,6 +96,10 @@ struct SimBase {
   bool f16s = false;            // FS_F16S: the state between launches is kept as halves (DevView::st16)
   bool mixed = false;           // FS_MIXED: float64 state, float32 controller arithmetic (k_rollout_pair<double>)
   bool no_pair = false;         // FLOWSIM_NO_PAIR=1: keep k_rollout_idm (one vehicle per lane) for the float rollout
+  bool pair_generic_n = false;  // FLOWSIM_PAIR_GENERIC_N=1: keep k_rollout_pair where k_rollout_pair_n would run (A/B, tests)
+  bool pair_n_always = false;   // FLOWSIM_PAIR_N_ALWAYS=1: k_rollout_pair_n also for launches shorter than PAIR_N_MIN_STEPS (tests)
+  static constexpr int PAIR_N_MIN_STEPS = 512;
+  bool kernel_detail = false;   // FLOWSIM_KERNEL_DETAIL=1: fs_last_kernel names the vehicle-count-specialised entry ("[n11]")
   bool no_loop_kernel = false;  // FLOWSIM_NO_LOOP_KERNEL=1: keep the generic k_steps for segment-table loops (tests)
   bool no_loop_full = false;    // FLOWSIM_NO_LOOP_FULL=1: keep the run-time-flag instantiation of k_rollout_loop (tests)
   bool no_ring_rl = false;      // FLOWSIM_NO_RING_RL=1: keep the generic k_steps for IDM + RL rings (tests)

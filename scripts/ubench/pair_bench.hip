@@ -6,6 +6,13 @@
 //   (nothing)               the shipped kernel,
 //   -DFS_DIAG_NEVER_SLOW    no step does and the branch is gone (WRONG results: what the test and the slow steps cost);
 // the parent's step for comparison: the same file built with -I to a checkout of the parent's flow_amd/csrc.
+// The vehicle-count-specialised entry k_rollout_pair_n<T, 11> (the observation rows through a 16-step LDS image) is timed
+// next to k_rollout_pair in every call; its forms, one binary each:
+//   (nothing)                     the shipped form: one ds_write2_b64 per step, the block drained in place,
+//   -DFS_DIAG_PAIRN_NO_RING       N at compile time only: today's per-step path, its two writes merged by the compiler,
+//   -DFS_DIAG_PAIRN_NO_MERGE      the ring with two ds_write_b64 (their distance read from the handle),
+//   -DFS_DIAG_PAIRN_BURST         the block drained in one burst at its end;
+//   -DFS_BENCH_NO_PAIRN           k_rollout_pair alone (a parent whose flowsim_pair.h has no such entry).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -14,7 +21,7 @@
 #include "flowsim_pair.h"
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s line %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
 
-template <typename T>
+template <typename T, bool PAIRN>
 double run(int R, int N, int K, int block, int reps) {
   fs::DevView<T> s{};
   std::vector<T> pos(size_t(R) * N), vel(size_t(R) * N, T(0)), rl(R, T(230.0)), p(6 * N), len(N, T(5));
@@ -40,6 +47,10 @@ double run(int R, int N, int K, int block, int reps) {
     CK(hipMemcpy(dpos, pos.data(), pos.size() * sizeof(T), hipMemcpyHostToDevice));
     CK(hipMemcpy(dvel, vel.data(), vel.size() * sizeof(T), hipMemcpyHostToDevice));
     CK(hipEventRecord(e0, 0));
+#if !defined(FS_BENCH_NO_PAIRN)
+    if (PAIRN) hipLaunchKernelGGL((fs::k_rollout_pair_n<T, 11>), dim3((waves + wpb - 1) / wpb), dim3(block), 0, 0, s, K, obs, rew, done);
+    else
+#endif
     hipLaunchKernelGGL((fs::k_rollout_pair<T, 16, true, true, false>), dim3((waves + wpb - 1) / wpb), dim3(block), 0, 0, s, K, obs, rew, done);
     CK(hipEventRecord(e1, 0));
     CK(hipDeviceSynchronize());
@@ -51,8 +62,13 @@ double run(int R, int N, int K, int block, int reps) {
 }
 int main(int argc, char** argv) {
   const int R = argc > 1 ? atoi(argv[1]) : 4096, K = argc > 2 ? atoi(argv[2]) : 1500, block = argc > 3 ? atoi(argv[3]) : 256;
-  const double f = run<float>(R, 22, K, block, 8);
-  const double m = run<double>(R, 22, K, block, 8);
+  const double f = run<float, false>(R, 22, K, block, 8);
+  const double m = run<double, false>(R, 22, K, block, 8);
   printf("R=%d K=%d block=%d  f32 %.4f ms (%.2f G)  mixed %.4f ms (%.2f G)\n", R, K, block, f, R * double(K) / f / 1e6, m, R * double(K) / m / 1e6);
+#if !defined(FS_BENCH_NO_PAIRN)
+  const double fn = run<float, true>(R, 22, K, block, 8);
+  const double mn = run<double, true>(R, 22, K, block, 8);
+  printf("R=%d K=%d block=%d  pair_n: f32 %.4f ms (%.2f G)  mixed %.4f ms (%.2f G)\n", R, K, block, fn, R * double(K) / fn / 1e6, mn, R * double(K) / mn / 1e6);
+#endif
   return 0;
 }
