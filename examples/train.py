@@ -47,7 +47,7 @@ def parse_args(args):
     parser.add_argument('--replicas', type=int, default=1024, help='device: environment replicas in the handle')
     parser.add_argument('--fuse_policy', action='store_true',
                         help='device: roll an action-vector policy (singleagent_merge, lord_of_the_rings, figureeight1 / figureeight2) out through the fused policy + '
-                             'step kernel instead of the captured graph; where there is none (singleagent_bottleneck), '
+                             'step kernel instead of the captured graph; where there is none (singleagent_bottleneck, compiled_highway_ring), '
                              'capture the graph around the policy kernel instead of the torch module')
     parser.add_argument('--device_update', action='store_true',
                         help='device: run the PPO update on the library\'s kernels (fs_ppo_eval_dev, fs_gae_dev, '
@@ -165,8 +165,12 @@ def train_device(submodule, flags, multiagent=False):
     from flow_amd import _lib
     if getattr(fp['env_name'], 'FS_ENV', None) == _lib.FS_ENV_MULTI_WAVE_ATTENUATION_PO:
         multiagent = False
+    # a CompiledEnv (FS_ENV_USER) has no fused policy + step kernel: --fuse_policy captures the graph around the eager policy
+    # kernel, for its shared agents (OBSERVE = "rl") as for one RL vehicle
+    user_head = getattr(fp['env_name'], 'FS_ENV', None) == _lib.FS_ENV_USER
     return train_on_device(fp, replicas=flags.replicas, fragment=flags.rollout_size, iterations=flags.num_steps,
                            shared_agents=multiagent, fuse_action_vector=flags.fuse_policy and not multiagent,
+                           fuse_shared_agents=flags.fuse_policy and multiagent and user_head,
                            device_update=flags.device_update or flags.device_adam, device_adam=flags.device_adam,
                            net_log_std=flags.net_log_std, **checkpoint_settings(flags), **env_state_settings(flags),
                            **ppo_loss_settings(flags))

@@ -532,12 +532,13 @@ def _checkpoint_due(it, last, freq):
 
 
 def choose_rollout(vec, pi, fragment, seed, log, shared_agents=False, fuse_action_vector=False, learner=None, world=1,
-                   rank=0, greedy=False):
+                   rank=0, greedy=False, fuse_shared_agents=False):
     """How a fragment of ``fragment`` closed-loop steps runs for this environment and model -- train_on_device's choice,
     which examples/evaluate.py shares: ``(fused, graph, graph_policy)``, exactly one of ``fused`` (a DevicePolicy for
     ``vec.policy_rollout``) and ``graph`` (a StepGraph, begun after a reset) set.  ``learner``: a DeviceLearner whose
     buffer a DevicePolicy shares (device_adam).  ``greedy``: the mean action instead of a sample -- ``fs_policy.greedy`` in
-    the kernels, ``pi.act(obs, explore=False)`` around the torch module."""
+    the kernels, ``pi.act(obs, explore=False)`` around the torch module.  ``fuse_shared_agents``: shared agents on a head
+    without a fused kernel (a CompiledEnv with OBSERVE = "rl") take the graph around the eager policy kernel too."""
     n_ag = vec.act_dim if shared_agents else 1
     k_ag = vec.obs_dim // n_ag
     free_log_std = None if pi.net_log_std else pi.log_std
@@ -565,9 +566,10 @@ def choose_rollout(vec, pi, fragment, seed, log, shared_agents=False, fuse_actio
         log("rollout: fused policy + step kernel (%s)%s" % (kernel, shared))
     except NotImplementedError as e:
         why = e
-        graph_policy, fused = (fused if fuse_action_vector and not shared_agents else None), None
+        in_graph = (fuse_action_vector and not shared_agents) or (fuse_shared_agents and shared_agents)
+        graph_policy, fused = (fused if in_graph else None), None
         if graph_policy is not None:
-            # no fused kernel for this head (BottleneckDesiredVelocityEnv): the library's eager policy kernel, where it is
+            # no fused kernel for this head (BottleneckDesiredVelocityEnv, a CompiledEnv): the library's eager policy kernel, where it is
             # built, goes into the captured fragment in the torch module's place -- one launch per step instead of ten-odd
             try:
                 vec.reset()
@@ -653,7 +655,8 @@ class Evaluator(object):
 
 
 def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epochs=4, lr=3e-4, seed=0, log=print,
-                    rank=0, world=1, shared_agents=False, fuse_action_vector=False, device_update=False, device_adam=False,
+                    rank=0, world=1, shared_agents=False, fuse_action_vector=False, fuse_shared_agents=False,
+                    device_update=False, device_adam=False,
                     kl_target=None, kl_coeff=0.2, entropy_coeff=0.0, vf_clip=None, vf_coef=0.5, clip=0.2,
                     sgd_minibatch_size=None, net_log_std=False, checkpoint_dir=None, checkpoint_freq=None, restore=None,
                     episode_stats=False, on_episodes=None, checkpoint_env_state=False, evaluation_interval=None,
@@ -672,6 +675,9 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
     k_policy_act_wide), the captured graph holds that kernel instead of the torch module.  Off by default: the library's
     kernels draw their samples from its Philox streams, the torch policy from torch.randn, so the two are different
     (equally valid) trajectories.
+    ``fuse_shared_agents``: the same for shared agents on a head without a fused kernel (a flow_amd.envs.CompiledEnv with
+    OBSERVE = "rl": compiled_highway_ring.py): the captured graph holds k_policy_act, which runs the replica's agents
+    through the shared policy, instead of the torch module.  Off by default.
     ``device_update``: the PPO update runs on the library's kernels (DeviceLearner: fs_ppo_eval_dev, fs_gae_dev,
     fs_ppo_grad_dev) instead of torch forward passes, the Python loop of gae() and autograd.  Off by default.
     ``device_adam``: the WHOLE update runs on the device (DeviceLearner.update: the statistics, the gradient and Adam
@@ -746,7 +752,7 @@ def train_on_device(flow_params, replicas=1024, fragment=100, iterations=20, epo
         opt = torch.optim.Adam(pi.parameters(), lr=lr)
     fused, graph, graph_policy = choose_rollout(vec, pi, fragment, seed, log, shared_agents=shared_agents,
                                                 fuse_action_vector=fuse_action_vector, learner=learner if device_adam else None,
-                                                world=world, rank=rank)
+                                                world=world, rank=rank, fuse_shared_agents=fuse_shared_agents)
     K, R = fragment, getattr(vec, "num_rows", hi - lo)                              # (rows: hi - lo environments x num_rings)
     if device_adam:
         log("update: on the device, Adam included (k_ppo_eval, k_gae, k_adv_stats, k_adv_finish, k_ppo_grad, k_adam)")

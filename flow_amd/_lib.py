@@ -30,6 +30,8 @@ FS_FAILSAFE_NONE, FS_FAILSAFE_INSTANTANEOUS, FS_FAILSAFE_SAFE_VELOCITY = range(3
 (FS_ENV_ACCEL, FS_ENV_WAVE_ATTENUATION, FS_ENV_WAVE_ATTENUATION_PO, FS_ENV_LANE_CHANGE_ACCEL, FS_ENV_MERGE_PO,
  FS_ENV_MERGE_MA, FS_ENV_BOTTLENECK_DV, FS_ENV_BOTTLENECK, FS_ENV_WAVE_ATTENUATION_PO_MA,
  FS_ENV_ACCEL_PO_MA, FS_ENV_LANE_CHANGE_ACCEL_PO, FS_ENV_MULTI_WAVE_ATTENUATION_PO) = range(12)
+FS_ENV_USER = 12                 # a head compiled from the user's text (flow_amd.envs.CompiledEnv)
+FS_MAX_USER_ENV_PARAMS = 8
 # enum fs_network / fs_integrator
 FS_NET_RING, FS_NET_FIGURE_EIGHT, FS_NET_MERGE, FS_NET_BOTTLENECK = 0, 1, 2, 3
 FS_MAX_SEGMENTS = 16
@@ -118,7 +120,8 @@ class fs_config(C.Structure):
                 ("track_followers", C.c_int32), ("num_paths", C.c_int32),
                 ("lane_change_cooldown_steps", C.c_int32), ("reserved6", C.c_int32), ("lane_change_min_gain", C.c_double),
                 ("sort_vehicles", C.c_int32),
-                ("noise_exact", C.c_int32), ("obs_perm", C.POINTER(C.c_int32)), ("replica_offset", C.c_int64)]
+                ("noise_exact", C.c_int32), ("obs_perm", C.POINTER(C.c_int32)), ("replica_offset", C.c_int64),
+                ("user_env_p", C.c_double * 8)]
 
 
 class fs_policy(C.Structure):

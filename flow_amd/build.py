@@ -176,13 +176,68 @@ def user_header(body):
             "%s {\n%s\n}\n" % (USER_SIGNATURE, body))
 
 
-def build_user(body, verbose=False):
-    """A copy of the library whose FS_CTRL_USER slots run the user's controller: flow_amd/_user/<hash>/libflowsim.so.
-    Every part but the queue kernels' and the learner's is recompiled with -DFS_USER_CONTROLLER_HEADER (in parallel; the C ABI object too:
-    its Sim::launch_steps refuses FS_CTRL_USER slots without the header); cached by the hash of the body and of the
-    sources."""
-    text = user_header(body)
-    tag = hashlib.sha256((text + _stamp([])).encode()).hexdigest()[:16]
+USER_ENV_VEHICLE_ARGS = ("T v, T v_lead, T h, bool has_lead, T v_follow, T h_follow, T length, T x, T L, bool is_rl, "
+                         "int rl_index, T action, bool has_action, T max_speed, T target_velocity, T dt, T N, T num_rl, "
+                         "const T* p")
+USER_ENV_SIGNATURES = {
+    "obs": "template <typename T>\n__device__ __forceinline__ void fs_user_obs(" + USER_ENV_VEHICLE_ARGS + ", T* o)",
+    "terms": "template <typename T>\n__device__ __forceinline__ void fs_user_terms(" + USER_ENV_VEHICLE_ARGS + ", T* %s)",
+    "reward": ("template <typename T>\n__device__ __forceinline__ T fs_user_reward(const T* %s, bool fail, bool has_action, "
+               "T N, T num_rl, T max_speed, T target_velocity, T dt, const T* p)"),
+}
+
+
+def _norm_body(body):
+    return "\n".join("  " + ln.strip() for ln in str(body).strip().splitlines())    # (the text is the cache key: normalised)
+
+
+def user_env_header(env):
+    """The header a user environment head is compiled from (include/flowsim.h FS_ENV_USER).  ``env``: a dict with the C++
+    statement bodies ``obs`` and ``terms`` (per vehicle; they write ``o[0 .. obs_per_vehicle-1]`` / ``t[0 ..
+    reward_terms-1]``) and ``reward`` (per replica, ending in a return; it reads ``sum[0 .. reward_terms-1]``), and the
+    shapes ``obs_per_vehicle`` (1..8), ``rl_only`` (one block per RL vehicle, else AccelEnv's layout) and ``reward_terms``
+    (0..4).  flow_amd.envs.CompiledEnv lists the names in scope.  With ``reward_terms = 0`` neither ``t`` nor ``sum`` is
+    declared: a body that uses one does not compile.  flowsim_kernels.h includes the header inside namespace fs, after
+    the helper functions (tmin / tmax / tabs / tsqrt)."""
+    k, terms = int(env["obs_per_vehicle"]), int(env["reward_terms"])
+    if not 1 <= k <= 8:
+        raise ValueError("user environment head: obs_per_vehicle (OBS_PER_VEHICLE) must be 1..8, got %d" % k)
+    if not 0 <= terms <= 4:
+        raise ValueError("user environment head: reward_terms (REWARD_TERMS) must be 0..4, got %d" % terms)
+    for name in ("obs", "reward") + (("terms",) if terms else ()):
+        if not env.get(name) or not str(env[name]).strip():
+            raise ValueError("user environment head: the %s body is empty" % name)
+    return ("// generated by flow_amd.build.build_user -- the head of a flow_amd.envs.CompiledEnv\n"
+            "constexpr int kUserObsPerVehicle = %d;\nconstexpr bool kUserObsRlOnly = %s;\nconstexpr int kUserRewardTerms = %d;\n"
+            "%s {\n%s\n}\n%s {\n%s\n}\n%s {\n%s\n}\n"
+            % (k, "true" if env["rl_only"] else "false", terms,
+               USER_ENV_SIGNATURES["obs"], _norm_body(env["obs"]),
+               USER_ENV_SIGNATURES["terms"] % ("t" if terms else "/* no terms */"), _norm_body(env.get("terms") or "") if terms else "",
+               USER_ENV_SIGNATURES["reward"] % ("sum" if terms else "/* no sums */"), _norm_body(env["reward"])))
+
+
+def user_tag(body=None, env=None):
+    """The cache key of a user library: the generated header texts (controller, environment head) and the sources."""
+    text = user_header(body) if body is not None else ""       # (a controller alone keeps the key it always had)
+    if env is not None:
+        text += "\0" + user_env_header(env)
+    return hashlib.sha256((text + _stamp([])).encode()).hexdigest()[:16]
+
+
+def build_user(body=None, verbose=False, env=None):
+    """A copy of the library with the user's code in it: flow_amd/_user/<hash>/libflowsim.so.  ``body``: the get_accel of a
+    CompiledController (its FS_CTRL_USER slots run it, -DFS_USER_CONTROLLER_HEADER); ``env``: the head of a CompiledEnv
+    (user_env_header's dict; FS_ENV_USER handles run it, -DFS_USER_ENV_HEADER); either or both.
+    Every part but the queue kernels' and the learner's is recompiled (in parallel; the C ABI object too: it refuses
+    FS_CTRL_USER slots and FS_ENV_USER handles without the headers); cached by the hash of the texts and of the sources."""
+    if body is None and env is None:
+        raise ValueError("build_user: give the controller body, the environment head, or both")
+    texts = {}
+    if body is not None:
+        texts["user_controller.h"] = ("FS_USER_CONTROLLER_HEADER", user_header(body))
+    if env is not None:
+        texts["user_env.h"] = ("FS_USER_ENV_HEADER", user_env_header(env))
+    tag = user_tag(body, env)
     out_dir = os.path.join(USER_DIR, tag)
     lib = os.path.join(out_dir, "libflowsim.so")
     if os.path.exists(lib):
@@ -197,17 +252,20 @@ def build_user(body, verbose=False):
             shutil.rmtree(os.path.join(USER_DIR, stale), ignore_errors=True)
     with open(os.path.join(out_dir, "sources.stamp"), "w") as f:
         f.write(_stamp([]))
-    hdr = os.path.join(out_dir, "user_controller.h")
-    with open(hdr, "w") as f:
-        f.write(text)
+    defines = []
+    for fname, (macro, text) in texts.items():
+        hdr = os.path.join(out_dir, fname)
+        with open(hdr, "w") as f:
+            f.write(text)
+        defines.append('-D%s="%s"' % (macro, hdr))
     objs, todo = [], []
     for name, src, extra in parts():
-        if name.startswith(("queue", "learn")):           # (no controller in them: the plain build's objects)
+        if name.startswith(("queue", "learn")):           # (no controller or head in them: the plain build's objects)
             objs.append(os.path.join(OBJ, name + ".o"))
             continue
         out = os.path.join(out_dir, name + ".o")
         objs.append(out)
-        todo.append((name, src, extra + ['-DFS_USER_CONTROLLER_HEADER="%s"' % hdr], out, verbose))
+        todo.append((name, src, extra + defines, out, verbose))
     with concurrent.futures.ThreadPoolExecutor(_jobs()) as pool:
         list(pool.map(_compile, todo))
     res = subprocess.run([find_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib + ".tmp"] + objs,

@@ -137,7 +137,18 @@ int validate(const fs_config* c) {
       if (!(c->segments[k].start > c->segments[k - 1].start))
         return fail(FS_ERR_INVALID, "fs_create: segment starts must increase");
   }
-  if (c->env < FS_ENV_ACCEL || c->env > FS_ENV_MULTI_WAVE_ATTENUATION_PO) return fail(FS_ERR_INVALID, "fs_create: bad env");
+  if (c->env < FS_ENV_ACCEL || c->env > FS_ENV_USER) return fail(FS_ERR_INVALID, "fs_create: bad env");
+  if (c->env == FS_ENV_USER) {          // a user head (flow_amd.envs.CompiledEnv): k_steps of a library that holds it
+    if (!fs::kHasUserEnv)
+      return fail(FS_ERR_UNSUPPORTED, "fs_create: FS_ENV_USER: this library was built without a user environment head "
+                                      "(flow_amd.build.build_user / flow_amd.envs.CompiledEnv)");
+    if (open_net) return fail(FS_ERR_UNSUPPORTED, "fs_create: FS_ENV_USER on an open network is not built");
+    if (c->num_lanes > 1) return fail(FS_ERR_UNSUPPORTED, "fs_create: FS_ENV_USER on a multi-lane ring is not built");
+    if (c->precision != FS_F32 && c->precision != FS_F64)
+      return fail(FS_ERR_UNSUPPORTED, "fs_create: FS_ENV_USER is built for FS_F32 and FS_F64");
+    if (c->sort_vehicles) return fail(FS_ERR_UNSUPPORTED, "fs_create: FS_ENV_USER with sort_vehicles is not built");
+    if (c->num_vehicles > 64) return fail(FS_ERR_UNSUPPORTED, "fs_create: FS_ENV_USER with more than 64 vehicles is not built");
+  }
   const bool lc_env = c->env == FS_ENV_LANE_CHANGE_ACCEL || c->env == FS_ENV_LANE_CHANGE_ACCEL_PO;
   if (lc_env && c->network != FS_NET_RING)
     return fail(FS_ERR_UNSUPPORTED, "fs_create: the lane-change envs are built for rings (k_steps_ml)");
@@ -273,6 +284,8 @@ int create_typed(const fs_config* cfg, fs_handle* out) {
     }
   }
   s->obs_dim = (cfg->env == FS_ENV_WAVE_ATTENUATION_PO) ? 3
+               : (cfg->env == FS_ENV_USER)                  // (the shapes of the head this library was compiled with)
+                     ? fs::kUserObsPerVehicle * (fs::kUserObsRlOnly ? cfg->num_rl : cfg->num_vehicles)
                : (cfg->env == FS_ENV_WAVE_ATTENUATION_PO_MA) ? 3 * cfg->num_rl
                : (cfg->env == FS_ENV_MULTI_WAVE_ATTENUATION_PO) ? 3
                : (cfg->env == FS_ENV_ACCEL_PO_MA) ? 6 * cfg->num_rl

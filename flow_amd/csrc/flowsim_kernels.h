@@ -890,6 +890,33 @@ constexpr bool kHasUserController = false;
 #endif
 
 // ---------------------------------------------------------------------------
+// FS_ENV_USER: the observation / reward head of a user-defined environment (the reference's extension point: an Env
+// subclass with get_state / compute_reward, flow/envs/base.py).  flow_amd.build.build_user generates the header from the
+// three bodies flow_amd.envs.CompiledEnv carries -- fs_user_obs and fs_user_terms per vehicle, fs_user_reward per replica,
+// next to the shapes kUserObsPerVehicle / kUserObsRlOnly / kUserRewardTerms -- and compiles the parts with
+// -DFS_USER_ENV_HEADER.  The head sits in k_steps where the built-in heads sit (include/flowsim.h FS_ENV_USER states the
+// contract); its parameters p[0..7] travel as one more kernel argument of that library's k_steps (UserEnvParams), so the
+// stock library's kernels and DevView are what they are without it.
+// ---------------------------------------------------------------------------
+#ifdef FS_USER_ENV_HEADER
+#include FS_USER_ENV_HEADER
+constexpr bool kHasUserEnv = true;
+static_assert(kUserObsPerVehicle >= 1 && kUserObsPerVehicle <= 8, "FS_ENV_USER: 1..8 observations per vehicle");
+static_assert(kUserRewardTerms >= 0 && kUserRewardTerms <= 4, "FS_ENV_USER: 0..4 reward terms");
+template <typename T>
+struct UserEnvParams {
+  T p[8];
+};
+#define FS_USER_ENV_KARG(T) , UserEnvParams<T> user_env
+#else
+constexpr bool kHasUserEnv = false;
+constexpr int kUserObsPerVehicle = 1;
+constexpr bool kUserObsRlOnly = false;
+constexpr int kUserRewardTerms = 0;
+#define FS_USER_ENV_KARG(T)
+#endif
+
+// ---------------------------------------------------------------------------
 // BaseController.get_action for one vehicle (base_controller.py:70-118) + the RL command
 // (envs/base.py:599-615): shared by the single-lane and the multi-lane step kernels.
 // Returns the commanded acceleration; `commanded` = false means "no command this step" (S5).
@@ -1000,7 +1027,7 @@ template <typename T, int SEG, int FAST, int CSET = 0>
 __global__ __launch_bounds__(64) void k_steps(DevView<T> s, int num_steps_arg, const uint8_t* __restrict__ mask,
                                               const float* __restrict__ actions, size_t act_stride,
                                               float* __restrict__ obs, float* __restrict__ rew,
-                                              uint8_t* __restrict__ done, int obs_every_step) {
+                                              uint8_t* __restrict__ done, int obs_every_step FS_USER_ENV_KARG(T)) {
   constexpr int RPW = 64 / SEG;
   const int lane = threadIdx.x;
   const int seg = lane / SEG;
@@ -1093,7 +1120,13 @@ __global__ __launch_bounds__(64) void k_steps(DevView<T> s, int num_steps_arg, c
   // of its own below)
   const bool mring = !FAST && env == FS_ENV_MULTI_WAVE_ATTENUATION_PO;
   const bool ma_wa = !FAST && (env == FS_ENV_WAVE_ATTENUATION_PO_MA || mring), ma_acc = !FAST && env == FS_ENV_ACCEL_PO_MA;
+#ifdef FS_USER_ENV_HEADER
+  const bool uenv = !FAST && env == FS_ENV_USER;
+  const int obs_dim = uenv ? kUserObsPerVehicle * (kUserObsRlOnly ? s.num_rl : N)
+                           : (env == FS_ENV_WAVE_ATTENUATION_PO) ? 3 : (ma_wa ? 3 * s.num_rl : (ma_acc ? 6 * s.num_rl : 2 * N));
+#else
   const int obs_dim = (env == FS_ENV_WAVE_ATTENUATION_PO) ? 3 : (ma_wa ? 3 * s.num_rl : (ma_acc ? 6 * s.num_rl : 2 * N));
+#endif
   const int sims_per_step = FAST ? 1 : s.sims_per_step;
   // the multi-agent ring heads (flow/envs/multiagent/ring/*): one block per RL vehicle at column rl_index; `xo` = Flow's
   // coordinate of x, `hh` the headway of the snapshot (written by the RL vehicle's lane; every lane makes the follower reads)
@@ -1123,6 +1156,48 @@ __global__ __launch_bounds__(64) void k_steps(DevView<T> s, int num_steps_arg, c
       }
     }
   };
+#ifdef FS_USER_ENV_HEADER
+  // FS_ENV_USER (include/flowsim.h states the contract): the user's observation of this lane's vehicle, and -- `score` --
+  // the replica's reward from the sums of the user's per-vehicle terms.  Every lane makes the follower reads and the sums;
+  // `xo` = Flow's coordinate of x, `a_cmd` / `has_act` the lane's command of the step just taken
+  auto user_head = [&](float* orow_, T xo, bool has_act, float a_cmd, bool fail, bool score) -> T {
+    const T vf_ = foll_read<SEG>(v, seg, wrap_foll, N), hf_ = foll_read<SEG>(h, seg, wrap_foll, N);
+    const bool is_rl = sl.ctrl == FS_CTRL_RL;
+    T a_ = T(0);
+    if (has_act && is_rl) {
+      a_ = T(a_cmd);
+      if (s.clip_actions) a_ = tmin(tmax(a_, s.act_lo), s.act_hi);
+    }
+    T o_[kUserObsPerVehicle];
+#pragma unroll
+    for (int k = 0; k < kUserObsPerVehicle; ++k) o_[k] = T(0);
+    fs_user_obs<T>(v, vl, h, has, vf_, hf_, sl.length, xo, L, is_rl, sl.rl_index, a_, has_act, s.max_speed,
+                   s.target_velocity, dt, T(N), T(s.num_rl), user_env.p, o_);
+    if (kUserObsRlOnly) {
+      if (valid && is_rl) {
+#pragma unroll
+        for (int k = 0; k < kUserObsPerVehicle; ++k) orow_[kUserObsPerVehicle * sl.rl_index + k] = float(o_[k]);
+      }
+    } else if (valid) {
+#pragma unroll
+      for (int k = 0; k < kUserObsPerVehicle; ++k) orow_[k * N + perm_i] = float(o_[k]);
+    }
+    if (!score) return T(0);
+    T sum_[kUserRewardTerms > 0 ? kUserRewardTerms : 1];
+    if constexpr (kUserRewardTerms > 0) {
+      T t_[kUserRewardTerms];
+#pragma unroll
+      for (int m = 0; m < kUserRewardTerms; ++m) t_[m] = T(0);
+      fs_user_terms<T>(v, vl, h, has, vf_, hf_, sl.length, xo, L, is_rl, sl.rl_index, a_, has_act, s.max_speed,
+                       s.target_velocity, dt, T(N), T(s.num_rl), user_env.p, t_);
+#pragma unroll
+      for (int m = 0; m < kUserRewardTerms; ++m) sum_[m] = seg_sum<SEG>(valid ? t_[m] : T(0));
+    } else {
+      sum_[0] = T(0);
+    }
+    return fs_user_reward<T>(sum_, fail, has_act, T(N), T(s.num_rl), s.max_speed, s.target_velocity, dt, user_env.p);
+  };
+#endif
   const size_t step_rows = obs_every_step ? size_t(s.R) : 0;     // rows to advance per step
   float* orow = obs + size_t(rr) * obs_dim;
   float* rrow = rew + rr;
@@ -1245,6 +1320,12 @@ __global__ __launch_bounds__(64) void k_steps(DevView<T> s, int num_steps_arg, c
     if (emit) {
       const int oi = FAST ? ii : (sorted ? order_rank(false) : perm_i);
       const T xo = use_seg ? cur.flow_x(x) : x;
+#ifdef FS_USER_ENV_HEADER
+      const bool bad_u = uenv && (seg_any<SEG>(valid && (v < T(-100)), seg) || crashed);
+      const T reward_u = uenv ? user_head(orow, xo, act != nullptr, a_own, bad_u, true) : T(0);
+      if (uenv) {
+      } else
+#endif
       if (ma_wa || ma_acc) {
         write_ma(orow, xo, h, d);
       } else if (env == FS_ENV_WAVE_ATTENUATION_PO) {
@@ -1261,6 +1342,11 @@ __global__ __launch_bounds__(64) void k_steps(DevView<T> s, int num_steps_arg, c
       // reward
       T reward;
       const bool bad = seg_any<SEG>(valid && (v < T(-100)), seg) || crashed;
+#ifdef FS_USER_ENV_HEADER
+      if (uenv) {
+        reward = reward_u;
+      } else
+#endif
       if (mring) {                               // multiagent/ring/wave_attenuation.py:101-127 (MultiWaveAttenuationPOEnv)
         if (act == nullptr) {                    // the warm-up steps
           reward = T(0);
@@ -1314,6 +1400,11 @@ __global__ __launch_bounds__(64) void k_steps(DevView<T> s, int num_steps_arg, c
   if (num_steps == 0) {   // observation of the current state only (Env.reset, envs/base.py:544-551)
     const int oi = FAST ? ii : (sorted ? order_rank(false) : perm_i);
     const T xo = use_seg ? cur.flow_x(x) : x;
+#ifdef FS_USER_ENV_HEADER
+    if (uenv) {
+      (void)user_head(orow, xo, false, 0.0f, false, false);
+    } else
+#endif
     if (ma_wa || ma_acc) {
       write_ma(orow, xo, h, d);
     } else if (env == FS_ENV_WAVE_ATTENUATION_PO) {

@@ -293,8 +293,16 @@ namespace fsim {
       k = &fs::k_steps<T, SEG, 0, 1>;
       last_kernel = "k_steps<CSET>";
     }
+#ifdef FS_USER_ENV_HEADER
+    // (a library with a user head: its k_steps takes the head's parameters as one more argument, FS_ENV_USER or not)
+    fs::UserEnvParams<T> up;
+    for (int k = 0; k < 8; ++k) up.p[k] = T(cfg.user_env_p[k]);
+    hipLaunchKernelGGL(k, dim3((dv.R + RPW - 1) / RPW), dim3(64), 0, stream, dv, a.num_steps, a.mask, a.actions,
+                       a.act_stride, a.obs, a.rew, a.done, a.obs_every_step, up);
+#else
     hipLaunchKernelGGL(k, dim3((dv.R + RPW - 1) / RPW), dim3(64), 0, stream, dv, a.num_steps, a.mask, a.actions,
                        a.act_stride, a.obs, a.rew, a.done, a.obs_every_step);
+#endif
     return launched();
   }
 

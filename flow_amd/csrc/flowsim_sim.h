@@ -1015,6 +1015,9 @@ struct Sim : SimBase {
     if (has_user_ctrl && !fs::kHasUserController)
       return fail(FS_ERR_UNSUPPORTED, "FS_CTRL_USER: this library was built without a user controller "
                                       "(flow_amd.build.build_user / flow_amd.controllers.CompiledController)");
+    // a user head (FS_ENV_USER; fs_create has refused it on a library without one) lives in k_steps alone: none of the
+    // conditions below admits it, and this line keeps that true when one of them changes
+    if (dv.env == FS_ENV_USER) return per_seg([&](auto S) { return launch_k_steps<S>(a); });
     if constexpr (std::is_same<T, float>::value) {
       if (queue_ok(a)) return launch_queue(a);
       if (dropq_ok(a)) return launch_dropq(a);
@@ -1119,7 +1122,24 @@ struct Sim : SimBase {
     const bool ma = dv.env == FS_ENV_WAVE_ATTENUATION_PO_MA || dv.env == FS_ENV_ACCEL_PO_MA || dv.env == FS_ENV_MERGE_MA;
     const char* why = policy_model_why(pol);
     if (why) {}                                          // (the model class: every head's first check)
-    else if (dv.env == FS_ENV_MERGE_PO) {                // ONE network: the whole observation -> num_rl action columns
+    else if (dv.env == FS_ENV_USER) {                    // a user head: the eager k_policy_act only
+      const bool shared = fs::kUserObsRlOnly;            // num_rl agents share the policy, one block each
+      if (obs != nullptr)
+        why = "fs_policy_rollout_dev (FS_ENV_USER: the policy is not fused into a user head's step; the eager "
+              "fs_policy_act_dev is built (k_policy_act) -- capture it around the step: VecFlowEnv.capture with a "
+              "DevicePolicy)";
+      else if (!std::is_same<T, float>::value || mixed)
+        why = "precision (FS_ENV_USER: the policy kernels serve float32 handles; FS_F64 handles are not built)";
+      else if (dv.num_rl < 1) why = "num_rl (FS_ENV_USER: an RL vehicle)";
+      else if (!shared && dv.num_rl != 1)
+        why = "num_rl (FS_ENV_USER with OBSERVE = \"all\": one RL vehicle; several RL vehicles share a policy with "
+              "OBSERVE = \"rl\")";
+      else if (shared && pol->obs_dim != fs::kUserObsPerVehicle)
+        why = "fs_policy.obs_dim (FS_ENV_USER with OBSERVE = \"rl\": one agent's block, OBS_PER_VEHICLE)";
+      else if (!shared && (pol->obs_dim != obs_dim || obs_dim > 32))
+        why = "fs_policy.obs_dim (FS_ENV_USER with OBSERVE = \"all\": the whole observation, fs_obs_dim <= 32)";
+    }
+    else if (dv.env == FS_ENV_MERGE_PO) {              // ONE network: the whole observation -> num_rl action columns
       if (!std::is_same<T, float>::value || mixed)
         why = "precision (FS_ENV_MERGE_PO is FS_F32 / FS_F16S only: FS_MIXED / FS_F64 handles are not built)";
       else if (dv.num_rl < 1 || dv.num_rl > 32)
@@ -1219,7 +1239,8 @@ struct Sim : SimBase {
       }
     }
     if (obs == nullptr && accel_vec()) return launch_policy_act_row16(pv, obs_in, act, logp);     // (launch_policy_loop16 takes the fused form)
-    if (obs == nullptr) return launch_policy_act(pv, ma ? dv.num_rl : 1, obs_in, act, logp);      // eager: the policy alone
+    const bool user_shared = dv.env == FS_ENV_USER && fs::kUserObsRlOnly;
+    if (obs == nullptr) return launch_policy_act(pv, (ma || user_shared) ? dv.num_rl : 1, obs_in, act, logp);   // eager: the policy alone
     if (loop) return launch_policy_loop16(pv, num_steps, reset_done, obs, act, logp, rew, done);
     return launch_policy_row16(pv, num_steps, reset_done, obs, act, logp, rew, done);
   }
@@ -1239,6 +1260,9 @@ struct Sim : SimBase {
     if (!pol || pol->struct_size != sizeof(fs_policy)) return fail(FS_ERR_INVALID, "fs_population: fs_policy struct_size mismatch");
     if (!probe && (!pop || pop->struct_size != sizeof(fs_population)))
       return fail(FS_ERR_INVALID, "fs_population: struct_size mismatch");
+    if (dv.env == FS_ENV_USER)
+      return fail(FS_ERR_UNSUPPORTED, "fs_population: not built for FS_ENV_USER (a user head takes one policy through the eager "
+                                      "fs_policy_act_dev)");
     if (dv.env == FS_ENV_MERGE_PO || dv.env == FS_ENV_BOTTLENECK_DV)
       return fail(FS_ERR_UNSUPPORTED, "fs_population: not built for the action-vector heads (FS_ENV_MERGE_PO, "
                                       "FS_ENV_BOTTLENECK_DV): their kernels give a wave to a replica and read weights past "
@@ -1295,7 +1319,8 @@ struct Sim : SimBase {
     if (!std::isfinite(pw)) return fail(FS_ERR_INVALID, "fs_policy_pair: perturb_weight is not finite");
     const bool resets = obs != nullptr && reset_done;
     const char *why = nullptr, *who = "";
-    if (dv.nseg == 0) why = "network (a segment-table loop: the figure eight; rings and the open networks take one policy)";
+    if (dv.env == FS_ENV_USER) why = "env (FS_ENV_USER: two policies on a user head are not built)";
+    else if (dv.nseg == 0) why ="network (a segment-table loop: the figure eight; rings and the open networks take one policy)";
     for (const fs_policy* pol : {av, adv}) {
       if (why) break;
       who = pol == av ? "av: " : "adversary: ";

@@ -484,4 +484,6 @@ def build_spec(env, num_replicas, rng=None):
         last_lc_quirk=bool(getattr(env, "LAST_LC_QUIRK", True)), sort_vehicles=sort_vehicles)
     if obs_perm is not None:
         spec["obs_perm"] = obs_perm
+    if env.FS_ENV == L.FS_ENV_USER:                        # a CompiledEnv: the head's text and parameters
+        spec.update(env.fs_user_env())
     return spec

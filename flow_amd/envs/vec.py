@@ -73,7 +73,8 @@ class VecFlowEnv(object):
         self._done = torch.zeros((R,), dtype=torch.uint8, device=self.device)
         import numpy as np
         self._resample = env.env_params.additional_params.get('ring_length', None) is not None \
-            and env.FS_ENV in (L.FS_ENV_WAVE_ATTENUATION, L.FS_ENV_WAVE_ATTENUATION_PO, L.FS_ENV_WAVE_ATTENUATION_PO_MA)
+            and env.FS_ENV in (L.FS_ENV_WAVE_ATTENUATION, L.FS_ENV_WAVE_ATTENUATION_PO, L.FS_ENV_WAVE_ATTENUATION_PO_MA,
+                               L.FS_ENV_USER)
         # BottleneckDesiredVelocityEnv(reset_inflow=True): a new total inflow per episode (_draw_inflow_totals)
         self._reset_inflow = env.FS_ENV == L.FS_ENV_BOTTLENECK_DV \
             and bool(env.env_params.additional_params.get("reset_inflow"))

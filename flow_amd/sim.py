@@ -43,11 +43,12 @@ class FlowSim:
     """
 
     def __init__(self, spec, precision="f32", device=0):
-        # a population with a CompiledController steps on a copy of the library that holds its get_accel (FS_CTRL_USER)
-        src = spec.get("user_controller_source")
-        if src is not None:
+        # a population with a CompiledController steps on a copy of the library that holds its get_accel (FS_CTRL_USER), a
+        # CompiledEnv on one that holds its head (FS_ENV_USER): one copy with both when the spec carries both
+        src, head = spec.get("user_controller_source"), spec.get("user_env_source")
+        if src is not None or head is not None:
             from flow_amd import build as _build
-            self.lib = L.load(_build.build_user(src))
+            self.lib = L.load(_build.build_user(src, env=head))
         else:
             self.lib = L.load()
         self.spec = spec
@@ -190,6 +191,11 @@ class FlowSim:
             sort_vehicles=int(bool(spec.get("sort_vehicles", False))), noise_exact=int(spec.get("noise_math", "hw") == "exact"),
             obs_perm=obs_perm.ctypes.data_as(C.POINTER(C.c_int32)) if obs_perm is not None else None,
             replica_offset=int(spec.get("replica_offset", 0)))
+        user_p = [float(x) for x in spec.get("user_env_p", ())]
+        if len(user_p) > L.FS_MAX_USER_ENV_PARAMS:
+            raise ValueError("spec['user_env_p'] holds more than %d values" % L.FS_MAX_USER_ENV_PARAMS)
+        for k, x in enumerate(user_p):
+            cfg.user_env_p[k] = x
         if self.open_net:
             cfg.route_start[0] = float(spec["routes"][0]["start"])
             cfg.route_start[1] = float(spec["routes"][min(1, len(spec["routes"]) - 1)]["start"])
@@ -265,6 +271,8 @@ class FlowSim:
         c are agent c's), 1 otherwise.  fs_policy.obs_dim is one agent's block: obs_dim / policy_agents."""
         env = int(self.spec.get("env", L.FS_ENV_ACCEL))
         ma = env in (L.FS_ENV_WAVE_ATTENUATION_PO_MA, L.FS_ENV_ACCEL_PO_MA, L.FS_ENV_MERGE_MA)
+        if env == L.FS_ENV_USER:             # OBSERVE = "rl": the RL vehicles share the policy, one block each
+            ma = bool((self.spec.get("user_env_source") or {}).get("rl_only"))
         return max(self.num_rl, 1) if ma else 1
 
     @property

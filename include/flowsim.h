@@ -119,7 +119,7 @@ enum fs_env {
                                        [x / L, v / v_max, (v_lead - v) / v_max, (x_lead - x - len_ego) / L,
                                        (v - v_follow) / v_max, headway(follower) / L], obs 6 * num_rl; desired_velocity
                                        reward shared by the agents; crash = 0 (multiagent/base.py:188-190) */
-  FS_ENV_MULTI_WAVE_ATTENUATION_PO = 11 /* MultiWaveAttenuationPOEnv  flow/envs/multiagent/ring/wave_attenuation.py:34-140
+  FS_ENV_MULTI_WAVE_ATTENUATION_PO = 11, /* MultiWaveAttenuationPOEnv flow/envs/multiagent/ring/wave_attenuation.py:34-140
                                        on MultiRingNetwork: a replica ROW is ONE ring with one RL vehicle (num_rl = 1); obs 3 =
                                        [v / 15, (v_lead - v) / 15, headway / max_length] (bumper to bumper); the reward is a
                                        desired-velocity norm over the n vehicles whose front is on one of the ring's four
@@ -127,6 +127,31 @@ enum fs_env {
                                        max_cost[n] = ||[target] * n|| and NO epsilon (n = 0: NaN, as numpy's 0 / 0), 0 if one
                                        of those speeds is below -100, 0 without actions (warm-up); crash = 0.  FS_F32 (every
                                        ring kernel) and FS_F64 (the generic kernel); FS_MIXED is refused */
+  FS_ENV_USER = 12                  /* an observation / reward head of the USER's (the reference lets user code subclass Env
+                                       and write get_state / compute_reward, flow/envs/base.py): three device functions
+                                       compiled INTO a copy of this library with -DFS_USER_ENV_HEADER, see
+                                       flow_amd.envs.CompiledEnv and flow_amd.build.build_user.  The header also fixes the
+                                       shapes: kUserObsPerVehicle (1..8), kUserObsRlOnly, kUserRewardTerms (0..4).  Contract:
+                                       - per vehicle, fs_user_obs writes o[0 .. kUserObsPerVehicle-1]; the lane stores float(o[k]).
+                                         kUserObsRlOnly: only an RL vehicle's lane writes, at kUserObsPerVehicle * rl_index + k,
+                                         fs_obs_dim = kUserObsPerVehicle * num_rl; else obs[k * N + i] with i the vehicle's
+                                         place in get_ids() (AccelEnv's index without sort_vehicles: obs_perm or the slot),
+                                         fs_obs_dim = kUserObsPerVehicle * N;
+                                       - per vehicle, fs_user_terms writes t[0 .. kUserRewardTerms-1]; sum[m] is the replica's
+                                         sum of (valid ? t[m] : 0) over its lanes in the built-in heads' tree order
+                                         (seg_sum; oracle.rewards.tree_sum);
+                                       - per replica, fs_user_reward(sum, fail, ...) returns the reward; fail = a collision in
+                                         this step or a speed below -100 (the built-in heads' condition); the replica's first
+                                         vehicle stores it;
+                                       - actions are accelerations of the RL vehicles in rl_index order, clipped as
+                                         clip_actions says (FS_ENV_ACCEL's); `action` is the vehicle's clipped command of the
+                                         step just taken (0 for a non-RL vehicle or a step without actions);
+                                       - done is the built-in flag byte (horizon, collision);
+                                       - p[0..7] = fs_config.user_env_p in the handle's precision.
+                                       Single-lane rings and segment-table loops, at most 64 vehicles, FS_F32 / FS_F64, no
+                                       sort_vehicles; always on k_steps.  The stock library refuses such a handle at fs_create
+                                       (FS_ERR_UNSUPPORTED); fs_policy_rollout_dev, fs_policy_pair_* and fs_population_* refuse
+                                       it by name, fs_policy_act_dev takes it (see there) */
 };
 
 enum fs_network {
@@ -364,6 +389,9 @@ typedef struct fs_config {
                                          block of the job's replicas): the Philox streams (acceleration noise, random
                                          entry lanes) are keyed by offset + local index, so a replica's trajectory does
                                          not depend on how the job is sharded */
+  /* ---- FS_ENV_USER ---- */
+  double user_env_p[8];               /* the user head's parameters p[0..7] (flow_amd.envs.CompiledEnv(params=...)); read by
+                                         FS_ENV_USER handles only */
 } fs_config;
 
 typedef struct fs_sim* fs_handle;
@@ -569,7 +597,10 @@ typedef struct fs_policy {
 /* actions [R] and log-probabilities [R] for the observations obs_dev [R, obs_dim] ([R, n_ag] for [R, n_ag * obs_dim] with
  * shared agents; FS_ENV_MERGE_PO and FS_ENV_BOTTLENECK_DV: actions [R, num_rl], log-probabilities [R]); advances the
  * sampling streams by one draw per replica.  One kernel launch on the handle's stream, no host synchronisation: it can be
- * captured into a graph between fs_step_dev launches (after one eager call, which allocates the draw counters). */
+ * captured into a graph between fs_step_dev launches (after one eager call, which allocates the draw counters).
+ * FS_ENV_USER (FS_F32 handles, "k_policy_act"): with kUserObsRlOnly, n_ag = num_rl agents share the policy, obs_dim =
+ * kUserObsPerVehicle, the shared agents' layouts; without it and with num_rl = 1, one agent with obs_dim = fs_obs_dim
+ * <= 32.  Every other form is refused by a message that names FS_ENV_USER. */
 int fs_policy_act_dev(fs_handle h, const fs_policy* pol, const float* obs_dev, float* act_dev, float* logp_dev);
 /* K x (policy -> action -> Env.step), with reset_done != 0 followed by Env.reset of the replicas whose episode ended
  * (placement, FS_FIELD_INIT_RING_LENGTH, warm-up steps).  obs_dev [K+1, R, obs_dim]: obs[0] = observation of the state
